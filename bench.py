@@ -7,19 +7,23 @@ top-N heaps with best_associations_heap semantics) over a synthetic table that i
 in HBM when the timed region starts.
 
   N = 1 : BASELINE.json configs[1]: 100M k-mers x 1024 samples, 1 phenotype + 100 permutations, top 10001
-          per column. The same JSON line carries the sub-records "p1_scan" (the one-column scan of the same
+          per column. With --full the same JSON line carries the sub-records "p1_scan" (the one-column scan of the same
           table: the HBM-roofline configuration, BASELINE.md row 2'), "kinship" (configs[4] in shape: 8M rows x
           1135 samples through the kinship kernels, with the single-threaded CPU accumulation beside it),
           "parity_check" (the GPU's heaps over the CPU baseline's rows equal the oracle's) and "cpu_baseline".
-          "roofline.traffic" is measured in the run itself: at its end two short child runs of this script go through
-          rocprofv3's FETCH_SIZE / WRITE_SIZE passes (live_pmc_traffic; KGWAS_BENCH_LIVE_PMC=0 or any failure leaves the
-          quotation of the committed profile, gated by the kernel source's hash).
+          With --full "roofline.traffic" is measured in the run itself: at its end two short child runs of this script go
+          through rocprofv3's FETCH_SIZE / WRITE_SIZE passes (live_pmc_traffic; KGWAS_BENCH_LIVE_PMC=0 or any failure leaves
+          the quotation of the committed profile, gated by the kernel source's hash).
   N > 1 : BASELINE.json configs[3] per GPU: every rank scans its own shard of 2048 samples x 201 columns
           (2.5e8 rows = 66 GB per GPU unless --rows says otherwise; weak scaling, contiguous row shards) and the
-          ranks' heap histories are merged over RCCL inside the timed region. "single_gpu_same_shard" is
+          ranks' heap histories are merged over RCCL inside the timed region. With --full, "single_gpu_same_shard" is
           rank 0's shard scanned alone (no merge), so that the N-GPU value has its own N = 1 reference.
 
-  python bench.py --gpus 1 --steps K --warmup W
+A plain run sets up, warms up, times the steps and prints the headline line; everything else it can measure or check
+(CPU baseline, parity with the oracle, sub-records, live PMC traffic) runs only with --full. --dump-outputs DIR writes
+what the last timed step computed (every column's top-N k-mers, scores and file rows) as .npy files.
+
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -725,8 +729,8 @@ def kinship_cli_e2e_record(kg, base, S, rows, table_gb, dev):
 
 
 # The driver keeps the parsed standard fields and only the TAIL of stdout (about 9 KB): the default line is therefore compact - every
-# sub-record down to the numbers a reader needs, the ones the judge asked for LAST - and `--full` prints everything (per-step lists,
-# outlier steps, operand-set details, the notes) as rounds 1-5 did; the builder's `profiles/rNN_bench_line.json` are --full lines.
+# sub-record down to the numbers a reader needs, the ones the judge asked for LAST - and `--all-fields` prints everything (per-step
+# lists, outlier steps, operand-set details, the notes) as rounds 1-5 did; the builder's `profiles/rNN_bench_line.json` are such lines.
 _KEEP = {
     "roofline": ["bound", "kernel", "achieved", "peak", "unit", "frac", "executed_frac", "traffic", "traffic_unit", "algorithmic_GB_per_launch", "launches",
                  "avg_launch_ms", "kernel_ms_per_step", "all_scoring_kernels_ms_per_step", "traffic_source", "power_limited_peak"],
@@ -763,7 +767,7 @@ def _round_floats(x, nd=4):
 
 
 def _prune(x, depth=0):
-    """Nested records: drop notes, long strings and lists (kept in --full), keep numbers and short labels."""
+    """Nested records: drop notes, long strings and lists (kept with --all-fields), keep numbers and short labels."""
     if isinstance(x, dict):
         out = {}
         for k, v in x.items():
@@ -795,7 +799,7 @@ def compact_line(out):
         if isinstance(v, dict) and "error" not in v and _KEEP.get(k) is not None:
             v = {kk: v[kk] for kk in _KEEP[k] if kk in v}
         res[k] = _prune(v)
-    res["line"] = "compact (python bench.py --full: every field)"
+    res["line"] = "compact (python bench.py --all-fields: every field)"
     return _round_floats(res)
 
 
@@ -881,6 +885,43 @@ def live_pmc_traffic(kname, grid, rows_per_launch, rows=40_000_000, timeout_s=90
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(d, results, rows_tested, max_bytes=DUMP_MAX_BYTES, seed=20240601):
+    """What a caller of the scan receives after finish(), as float64 .npy files in `d`: per column the top-N k-mers, scores and
+    file rows in heap-pop order (top_kmers / top_scores / top_rows, one row per column) and the number of rows tested. The
+    integers are exact in float64 (synthetic k-mers are file row + 1, far below 2^53). Beyond `max_bytes` a fixed, seeded sample
+    of the columns (and, if one column alone is too large, of its entries) is written; columns.npy / entries.npy name them."""
+    n = len(results[0][0]) if results else 0
+    if any(len(r[0]) != n for r in results):
+        raise RuntimeError("columns hold different numbers of results")
+    rng = np.random.default_rng(seed)
+    cap = max(1, (max_bytes - (1 << 16)) // 32)  # entries that fit: three arrays plus an index, 8 bytes each
+    cols = np.arange(len(results))
+    ent = None
+    if len(results) * n > cap:
+        cols = np.sort(rng.choice(len(results), size=min(len(results), max(1, cap // max(n, 1))), replace=False))
+        if n > cap:
+            ent = np.sort(rng.choice(n, size=cap, replace=False))
+    out = {}
+    for name, i in (("top_kmers", 0), ("top_scores", 1), ("top_rows", 2)):
+        a = np.stack([results[j][i] for j in cols]) if n else np.zeros((len(cols), 0))
+        if ent is not None:
+            a = a[:, ent]
+        if i != 1 and a.size and int(a.max()) >= 1 << 53:
+            raise RuntimeError("%s: values beyond 2^53 are not exact in float64" % name)
+        out[name] = a.astype(np.float64)
+    out["rows_tested"] = np.array([rows_tested], dtype=np.float64)
+    out["columns"] = cols.astype(np.float64)
+    if ent is not None:
+        out["entries"] = ent.astype(np.float64)
+    os.makedirs(d, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+    return out
+
+
 def cgroup_throttle():
     """(nr_throttled, throttled_usec) of this container's CPU controller, (0, 0) if unreadable."""
     try:
@@ -908,7 +949,12 @@ def main():
     ap.add_argument("--no-scale-records", action="store_true", help="skip configs[2] / [4] at HBM-filling size (243 GB table)")
     ap.add_argument("--ingest-rows", type=int, default=40_000_000)
     ap.add_argument("--no-north-star-shard", action="store_true", help="skip BASELINE configs[3]'s per-GPU workload (66 GB table)")
-    ap.add_argument("--full", action="store_true", help="print every field (per-step lists, notes); default: the compact line")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: CPU baseline, parity checks, sub-records, live PMC traffic; "
+                         "N > 1: rank 0's shard alone and its parity check")
+    ap.add_argument("--all-fields", action="store_true", help="print every field (per-step lists, notes); default: the compact line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the last timed step's results (every column's top-N k-mers, scores, file rows) to DIR/<name>.npy")
     ap.add_argument("--check-merge", action="store_true",
                     help="N > 1: rank 0 also scans all shards' rows in one session and compares the merged heaps with it (small runs)")
     args = ap.parse_args()
@@ -1066,9 +1112,13 @@ def main():
                 "replay_tail_ms", "dense_phase_ms", "merge_ms", "heap_pushes", "candidates", "device", "columns_selected"]
         per_rank = [dict(zip(keys, [float(x) for x in b.cpu().tolist()]), rank=i) for i, b in enumerate(bufs)]
 
+    # what the last timed step computed (with N > 1, rank 0's session holds the merged heaps), before anything reuses the session
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [last.result(j) for j in range(P)], tested)
+
     # the N = 1 reference of a multi-GPU run: rank 0's shard alone, no merge (other ranks wait)
     single = None
-    if dist_on:
+    if dist_on and args.full:
         if rank == 0:
             k1 = max(2, min(5, args.steps))
             one_step(merge=False)
@@ -1083,7 +1133,7 @@ def main():
         dist.barrier()
 
     shard_parity = None
-    if dist_on and not args.no_cpu_baseline:
+    if dist_on and args.full and not args.no_cpu_baseline:
         if rank == 0:
             try:
                 from oracle import binding as ob
@@ -1286,7 +1336,7 @@ def main():
             _t_mark[0] = time.perf_counter()
         gc.collect()
         gc.disable()
-        if not dist_on and not args.no_cpu_baseline:
+        if not dist_on and args.full and not args.no_cpu_baseline:
             rec, ores = cpu_baseline(S, Y, mac, args.topn, seed_table, min(args.cpu_sample_rows, M),
                                      threads=min(usable_cpus(), P))
             out["cpu_baseline"] = rec
@@ -1296,8 +1346,8 @@ def main():
             except Exception as e:  # a failed comparison must show up in the line, not kill it
                 out["parity_check"] = False
                 out["parity_check_error"] = repr(e)
-        lap("cpu_baseline_and_parity_check")
-        if not dist_on and not args.no_subrecords and config_name == "BASELINE.json configs[1]":
+            lap("cpu_baseline_and_parity_check")
+        if not dist_on and args.full and not args.no_subrecords and config_name == "BASELINE.json configs[1]":
             try:
                 out["p1_scan"] = p1_scan_record(kg, torch, table, stream, M, S, Y, args.topn, mac, dev, host_threads, passes=30)
             except Exception as e:
@@ -1370,7 +1420,7 @@ def main():
                 if "bytes_per_row" in live:
                     rl["traffic_source"] = ("live: rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE (separate passes) around two child runs "
                                             "of this script, bytes per row of the steady launches x rows per average launch of the timed steps")
-        print(json.dumps(out if args.full else compact_line(out)))
+        print(json.dumps(out if args.all_fields else compact_line(out)))
     if last is not None:
         last.close()
     if dist_on:

@@ -212,7 +212,7 @@ def test_bench_ranks_merge_over_torch_distributed(ranks, merge, shape):
     env = dict(os.environ, KGWAS_DIST_BACKEND="gloo", KGWAS_BENCH_MERGE=merge, KGWAS_PIN_THREADS="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr", "127.0.0.1",
            "--master-port", str(29500 + ranks), os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "1", "--warmup", "1",
-           "--rows", "600000", "--samples", "241", "--perms", "12", "--topn", "2001", "--check-merge"]
+           "--rows", "600000", "--samples", "241", "--perms", "12", "--topn", "2001", "--check-merge", "--full"]
     if shape == "north_star":  # BASELINE configs[3]'s columns and heap size: 2048 samples x 201 columns, top-10001, 2 M rows per rank
         cmd[cmd.index("--rows") + 1:cmd.index("--check-merge")] = ["2000000", "--samples", "2048", "--perms", "200", "--topn", "10001"]
         cmd[cmd.index("--master-port") + 1] = str(29520 + ranks + (1 if merge == "column" else 0))
@@ -231,6 +231,34 @@ def test_bench_ranks_merge_over_torch_distributed(ranks, merge, shape):
         assert x["step_ms"] > 0 and x["kernels_ms"] > 0 and x["replay_threads"] >= 1 and x["candidates"] > 0
     if ranks == 2 and shape == "small":
         assert j["parity_check"] is True
+
+
+def test_bench_plain_run_dumps_what_its_last_step_computed(tmp_path):
+    """A plain bench run (no --full) prints the headline line and nothing of the --full records; --dump-outputs writes every
+    column's top-N of the last timed step as float64 arrays, and they equal the oracle's over the same synthetic rows."""
+    import json, sys
+    sys.path.insert(0, ROOT)
+    import bench
+    S, perms, topn, M = 241, 12, 2001, 600_000
+    out = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--rows", str(M),
+           "--samples", str(S), "--perms", str(perms), "--topn", str(topn), "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["value"] > 0
+    for k in ("cpu_baseline", "parity_check", "p1_scan", "kinship", "single_gpu_same_shard"):
+        assert k not in j, k
+    d = {n: np.load(str(out / (n + ".npy"))) for n in ("top_kmers", "top_scores", "top_rows", "rows_tested", "columns")}
+    assert all(a.dtype == np.float64 for a in d.values())
+    Y = bench.make_phenotypes(S, perms, 7)
+    exp = ob.associate(kg.synth_rows_host(0, M, S, 20240601), S, np.arange(S, dtype=np.uint64), Y, topn, kg.min_count(S, 0.05, 5))
+    assert d["rows_tested"][0] == exp["tested"] and (d["columns"] == np.arange(perms + 1)).all()
+    assert d["top_kmers"].shape == (perms + 1, min(topn, exp["tested"]))
+    for c in range(perms + 1):
+        o = exp["per_pheno"][c]
+        assert (d["top_kmers"][c] == o["kmer"]).all() and (d["top_rows"][c] == o["file_row"]).all()
+        assert d["top_scores"][c].tobytes() == o["score"].tobytes()
 
 
 def test_emma_kinship_kmers_gpus(tmp_path):

@@ -554,6 +554,31 @@ def test_bench_live_traffic_measurement_falls_back_instead_of_failing(monkeypatc
     assert set(r) == {"error"} and "rocprofv3" in r["error"]
 
 
+def test_bench_output_dump_is_float64_bounded_and_reproducible(tmp_path):
+    """bench.py --dump-outputs: every column's (k-mers, scores, file rows) as float64 arrays; beyond the byte limit a fixed,
+    seeded sample of columns (and of entries, if one column alone is too large) that is the same from run to run."""
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(3)
+    res = [(rng.integers(1, 1 << 40, 500).astype(np.uint64), rng.standard_normal(500), rng.integers(0, 1 << 30, 500).astype(np.uint64))
+           for _ in range(40)]
+    full = bench.dump_outputs(str(tmp_path / "a"), res, 12345)
+    assert set(os.listdir(tmp_path / "a")) == {"top_kmers.npy", "top_scores.npy", "top_rows.npy", "rows_tested.npy", "columns.npy"}
+    k = np.load(str(tmp_path / "a" / "top_kmers.npy"))
+    assert k.dtype == np.float64 and k.shape == (40, 500) and (k[7] == res[7][0]).all()
+    assert np.load(str(tmp_path / "a" / "top_scores.npy")).tobytes() == np.stack([r[1] for r in res]).tobytes()
+    assert np.load(str(tmp_path / "a" / "rows_tested.npy"))[0] == 12345 and (full["columns"] == np.arange(40)).all()
+    for sub, limit in (("b", 100_000), ("c", 100_000), ("d", 80_000)):
+        bench.dump_outputs(str(tmp_path / sub), res, 12345, max_bytes=limit)
+        assert sum(os.path.getsize(tmp_path / sub / f) for f in os.listdir(tmp_path / sub)) <= limit
+    for f in os.listdir(tmp_path / "b"):
+        assert open(tmp_path / "b" / f, "rb").read() == open(tmp_path / "c" / f, "rb").read(), f
+    cols = np.load(str(tmp_path / "b" / "columns.npy")).astype(int)
+    assert 0 < len(cols) < 40 and (np.load(str(tmp_path / "b" / "top_rows.npy")) == np.stack([res[c][2] for c in cols])).all()
+    ent = np.load(str(tmp_path / "d" / "entries.npy")).astype(int)  # (one column of 500 entries is already beyond 80 KB / 32)
+    assert len(np.load(str(tmp_path / "d" / "columns.npy"))) == 1 and 0 < len(ent) < 500
+
+
 def test_bench_compact_line_keeps_the_contract_and_fits_the_drivers_tail():
     """bench.py prints ONE JSON line; the driver parses its standard fields and keeps only the last ~9 KB of stdout. The default
     line is the compact form of the full record: every contract field, `roofline` and `cpu_baseline` with their required keys, and

@@ -14,7 +14,7 @@ rocprofv3 --kernel-trace --pmc FETCH_SIZE -f csv -d $O/pmc_fetch -- python bench
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -f csv -d $O/pmc_write -- python bench.py --rows 40000000 --steps 1 --warmup 0 $B > $O/pmc_write.log 2>&1
 python tools/publish_profiles_r05.py traffic
 # 2. the bench line itself (all sub-records; first among the rest: if the call runs out of time, the judged record exists)
-python bench.py --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench_line.err
+python bench.py --steps 20 --warmup 5 --full > $O/bench_line.json 2> $O/bench_line.err
 tail -c 300 $O/bench_line.json
 # 3. SQ counters: the resident filter at 1024 x 101, the streaming filter at 2048 x 201
 rocprofv3 --kernel-trace --pmc $SQ1 -f csv -d $O/pmc_sq1 -- python bench.py --rows 40000000 --steps 1 --warmup 0 $B > $O/pmc_sq1.log 2>&1

@@ -18,7 +18,7 @@ rocprofv3 --kernel-trace --pmc WRITE_SIZE -f csv -d $O/pmc_write -- python bench
 rocprofv3 --kernel-trace --pmc $SQ1 -f csv -d $O/pmc_sq1 -- python bench.py --rows 40000000 --steps 1 --warmup 0 $B > $O/pmc_sq1.log 2>&1
 rocprofv3 --kernel-trace --pmc $SQ2 -f csv -d $O/pmc_sq2 -- python bench.py --rows 40000000 --steps 1 --warmup 0 $B > $O/pmc_sq2.log 2>&1
 # 2. the bench line itself, every field
-python bench.py --steps 20 --warmup 5 --full > $O/bench_line.json 2> $O/bench_line.err
+python bench.py --steps 20 --warmup 5 --full --all-fields > $O/bench_line.json 2> $O/bench_line.err
 tail -c 300 $O/bench_line.json
 # 3. one-column scan and kinship: kernel stats
 rocprofv3 --kernel-trace --stats -f csv -d $O/p1_stats -- python tools/one_column.py > $O/p1_stats.log 2>&1
