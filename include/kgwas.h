@@ -224,8 +224,9 @@ typedef struct kgwas_scan_stats {
  * kgwas_scan_stats to a newer library: compare KGWAS_ABI_VERSION with kgwas_abi_version() at start-up.
  * Version 6 (round 6): no struct changed; new entry points kgwas_heap_selfcheck, kgwas_scan_select_mode and the test hook
  * kgwas_scan_debug_residuals; kgwas_scan_lowest takes a non-const session (it always mutated it); kgwas_scan_stats.coarse_mx32 is
- * always 0 (the 32 x 32 x 64 filter form was removed). */
-#define KGWAS_ABI_VERSION 6
+ * always 0 (the 32 x 32 x 64 filter form was removed).
+ * Version 7: no struct changed; new entry points kgwas_snpkin_* (emma_kinship). */
+#define KGWAS_ABI_VERSION 7
 uint32_t kgwas_abi_version(void);
 
 int kgwas_scan_create(const kgwas_scan_params* p, kgwas_scan** out);
@@ -422,6 +423,32 @@ int kgwas_snps_best(kgwas_snps* s, const float* Y, uint64_t n_pheno, uint64_t to
 int kgwas_snps_write(kgwas_snps* s, uint64_t n_lists, const char* const* out_bases, const uint64_t* counts,
                      const uint64_t* indices, uint64_t stride);
 void kgwas_snps_close(kgwas_snps* s);
+
+/* ------------------------------------------------------------------------------------
+ * SNP kinship = emma_kinship (src/emma_kinship.cpp): the EMMA kinship of a PLINK SNP matrix. For every SNP with at least
+ * one called sample and every pair r > c, K[r][c] += a_r*a_c + (1-a_r)*(1-a_c), once with pass A's values (hom 0, het 0,
+ * hom-alt 1, missing n_alt/n_total) and once with pass B's (het 1, missing (n_alt+n_het)/n_total); each pair's sum is
+ * accumulated in SNP order with one IEEE rounding per operation, so it is bit-identical to the reference's.
+ * open     : <base>.bed / <base>.fam guards with the reference's messages in its order ("error:\t" + text; missing files
+ *            KGWAS_ERR_IO, sizes KGWAS_ERR_FORMAT; a .fam without lines KGWAS_ERR_ARG - the reference divides by zero),
+ *            all before the device is touched; then the session on `device`
+ * info     : S samples (lines of the .fam), M SNPs, bytes per SNP
+ * feed_bed : n_snps SNPs of the .bed body (file layout, without the 3 magic bytes) from host memory, after those fed
+ *            before (several feeds equal one)
+ * feed_file: the whole .bed body, streamed in chunks (file read, copy and kernels overlap)
+ * sums     : the undivided sums, lower[r * S + c] for c < r (the other entries 0), and the SNPs used so far
+ * matrix   : the finished S x S matrix: sums / (2 n_used) mirrored, diagonal 1 (0 / 0 = -nan when no SNP was used)
+ * format   : the text emma_kinship prints for K (plot_kinship, :55-68). Returns needed bytes.
+ * ---------------------------------------------------------------------------------- */
+typedef struct kgwas_snpkin kgwas_snpkin;
+int kgwas_snpkin_open(const char* base_bedbim, int32_t device, kgwas_snpkin** out);
+int kgwas_snpkin_info(const kgwas_snpkin* h, uint64_t* n_samples, uint64_t* n_snps, uint64_t* bytes_per_snp);
+int kgwas_snpkin_feed_bed(kgwas_snpkin* h, const uint8_t* body, uint64_t n_snps);
+int kgwas_snpkin_feed_file(kgwas_snpkin* h);
+int kgwas_snpkin_sums(kgwas_snpkin* h, double* lower, uint64_t* n_used);
+int kgwas_snpkin_matrix(kgwas_snpkin* h, double* K, uint64_t* n_used);
+uint64_t kgwas_snpkin_format(uint64_t n_samples, const double* K, char* out, uint64_t cap);
+void kgwas_snpkin_close(kgwas_snpkin* h);
 
 /* ------------------------------------------------------------------------------------
  * Seeded synthetic table rows: kmer = row + 1, per-row frequency q/256 with

@@ -26,6 +26,7 @@
 //   KGWAS_CLI_FULL_TEARDOWN=1  the command-line tools destroy their sessions instead of _exit
 //   KGWAS_AUTO_PARALLEL=1      associate_kmers: replay threads = the CPUs the process may use, whatever --parallel says
 //   KGWAS_DEVICE=n             associate_snps: device ordinal
+//   KGWAS_SNPKIN_CHUNK_SNPS=n  (test hook) SNPs per launch of a kgwas_snpkin session (default: about 128 MiB of per-sample values)
 //   KGWAS_DEBUG_SLOW_WORKER=w:pct:min_us   (test hook) slows one replay worker down
 //   KGWAS_DEBUG_RESIDUALS=1    (test hook) sessions keep their filters' quantisation residuals (kgwas_scan_debug_residuals)
 //

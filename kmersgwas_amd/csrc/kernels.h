@@ -257,6 +257,18 @@ hipError_t launch_snp_planes(const uint8_t* bed, uint64_t n_snps, uint32_t bytes
 hipError_t launch_snp_score(const uint32_t* planes, uint64_t n_snps, uint32_t ndw, const float* Yperm, uint32_t L, uint32_t n_pheno,
                             double mac, double* scores, hipStream_t st);
 
+// SNP kinship (snpkin_kernels.hip): a chunk's .bed bytes -> per-SNP missing-call values params[snp] and every sample's
+// values vals[snp][S] (32 bytes each), used SNPs counted into n_used[TESTED_SHARDS]; then the pair sums of the lower-triangular
+// tiles (tiles[i] = first row, first column; rows_per_wave 4 or 8 rows x 64 columns) advanced over the chunk's SNPs in order.
+uint32_t snpkin_vals_stride(uint32_t S);  // entries per SNP: S + 8
+size_t snpkin_vals_bytes(uint32_t S, uint32_t chunk_snps);
+size_t snpkin_params_bytes(uint32_t chunk_snps);
+hipError_t launch_snpkin_prep(const uint8_t* bed, uint32_t n_snps, uint32_t bytes_per_snp, uint32_t S, void* params, void* vals,
+                              unsigned long long* n_used, hipStream_t st);
+hipError_t launch_snpkin_accumulate(int rows_per_wave, const uint8_t* bed, uint32_t n_snps, uint32_t bytes_per_snp, uint32_t S,
+                                    const void* params, const void* vals, const uint2* tiles, uint32_t n_tiles, double* sums,
+                                    hipStream_t st);
+
 // Squeeze: out[r][2*W_m dwords] bit i = file bit colmap[i] (colmap[i] == 0xFFFFFFFF -> 0).
 hipError_t launch_squeeze(const uint64_t* file_rows, uint64_t file_stride_w, uint64_t n_rows, const uint32_t* colmap,
                           uint32_t W_m, uint32_t W_f, uint32_t* out, hipStream_t st);

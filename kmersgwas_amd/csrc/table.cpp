@@ -79,6 +79,42 @@ void parallel_items(unsigned threads, size_t n, const F& fn) {
     });
 }
 
+// An n x n matrix as the reference's `cout << v` prints it (tab-separated, one row per line): `os << v` is printf's %g
+// (precision 6), which std::to_chars(general, 6) is specified to reproduce; the rows are formatted by a few threads (one
+// ostringstream over 1135 x 1135 cells took 0.2 s). cell(i, j) gives the value. Returns the bytes needed, writes up to cap.
+template <class Cell>
+uint64_t format_square(uint64_t n, char* out, uint64_t cap, const Cell& cell) {
+    const unsigned T = (unsigned)std::min<uint64_t>(std::max(1u, std::min(16u, usable_cpus())), std::max<uint64_t>(n / 32, 1));
+    const uint64_t per = (n + T - 1) / T;
+    std::vector<std::string> part(T);
+    parallel_items(T, T, [&](size_t t) {
+        std::string& o = part[t];
+        const uint64_t i0 = std::min<uint64_t>(t * per, n), i1 = std::min<uint64_t>(i0 + per, n);
+        o.reserve((i1 - i0) * n * 12 + 16);
+        char cell_text[64];
+        for (uint64_t i = i0; i < i1; i++) {
+            for (uint64_t j = 0; j < n; j++) {
+                if (j > 0) o.push_back('\t');
+                const auto r = std::to_chars(cell_text, cell_text + sizeof(cell_text), cell(i, j), std::chars_format::general, 6);
+                o.append(cell_text, (size_t)(r.ptr - cell_text));
+            }
+            o.push_back('\n');
+        }
+    });
+    uint64_t total = 0;
+    for (const std::string& o : part) total += o.size();
+    if (out && cap) {
+        uint64_t at = 0;
+        for (const std::string& o : part) {
+            if (at >= cap) break;
+            const uint64_t m = std::min<uint64_t>(o.size(), cap - at);
+            memcpy(out + at, o.data(), m);
+            at += m;
+        }
+    }
+    return total;
+}
+
 struct FdFile {  // output file written in large pieces; open only while a piece is written
     // (A process that holds hundreds of descriptors at once grows its descriptor table, and in a multi-threaded process the
     // kernel waits for an RCU grace period every time it does - 100 ms and more on a 256-CPU host, found as 0.3 s of
@@ -564,44 +600,17 @@ int kgwas_write_plink(const char* out_base, kgwas_table* t, const uint64_t* col,
 
 // emma_kinship_kmers' output (src/emma_kinship_kmers.cpp:95-111)
 uint64_t kgwas_kinship_format(uint64_t n_acc, const uint64_t* K, uint64_t n_used, char* out, uint64_t cap) {
-    // `os << v` of the reference is printf's %g (precision 6), which std::to_chars(general, 6) is specified to reproduce; the
-    // rows are formatted by a few threads (one ostringstream over 1135 x 1135 cells took 0.2 s, and the tool asked twice).
-    const unsigned T = (unsigned)std::min<uint64_t>(std::max(1u, std::min(16u, usable_cpus())), std::max<uint64_t>(n_acc / 32, 1));
-    const uint64_t per = (n_acc + T - 1) / T;
-    std::vector<std::string> part(T);
-    parallel_items(T, T, [&](size_t t) {
-        std::string& o = part[t];
-        const uint64_t i0 = std::min<uint64_t>(t * per, n_acc), i1 = std::min<uint64_t>(i0 + per, n_acc);
-        o.reserve((i1 - i0) * n_acc * 12 + 16);
-        char cell[64];
-        for (uint64_t i = i0; i < i1; i++) {
-            for (uint64_t j = 0; j < n_acc; j++) {
-                if (j > 0) o.push_back('\t');
-                double v;
-                if (i == j)
-                    v = 1;
-                else {
-                    const uint64_t k = (j < i) ? K[i * n_acc + j] : K[j * n_acc + i];
-                    v = static_cast<double>(k) / static_cast<double>(n_used);
-                }
-                const auto r = std::to_chars(cell, cell + sizeof(cell), v, std::chars_format::general, 6);
-                o.append(cell, (size_t)(r.ptr - cell));
-            }
-            o.push_back('\n');
-        }
+    return format_square(n_acc, out, cap, [&](uint64_t i, uint64_t j) {
+        if (i == j) return 1.0;
+        const uint64_t k = (j < i) ? K[i * n_acc + j] : K[j * n_acc + i];
+        return static_cast<double>(k) / static_cast<double>(n_used);
     });
-    uint64_t total = 0;
-    for (const std::string& o : part) total += o.size();
-    if (out && cap) {
-        uint64_t at = 0;
-        for (const std::string& o : part) {
-            if (at >= cap) break;
-            const uint64_t n = std::min<uint64_t>(o.size(), cap - at);
-            memcpy(out + at, o.data(), n);
-            at += n;
-        }
-    }
-    return total;
+}
+
+// emma_kinship's output (plot_kinship, src/emma_kinship.cpp:55-68): every cell of the finished S x S matrix, NaN included
+// (to_chars prints the sign of a NaN as printf does: "-nan" for x86's default NaN)
+uint64_t kgwas_snpkin_format(uint64_t S, const double* K, char* out, uint64_t cap) {
+    return format_square(S, out, cap, [&](uint64_t i, uint64_t j) { return K[i * S + j]; });
 }
 
 }  // extern "C"

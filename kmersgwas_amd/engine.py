@@ -7,6 +7,7 @@ Names follow the reference's classes (src/kmers_multiple_databases.h, src/best_a
   AssociationScan       <- load_kmers + add_kmers_to_heap over all columns (pass 1) (a-3 .. a-8)
   BestAssociationsHeap  <- BestAssociationsHeap                                    (a-7)
   Kinship               <- update_emma_kinshhip_calculation / emma_kinship_kmers    (a-9)
+  SnpKinship            <- emma_kinship (the kinship of a PLINK SNP matrix)          (f-5)
 
 Everything numeric happens inside libkgwas (HIP kernels on the GPU + the std::priority_queue
 replay); this module only moves buffers.
@@ -615,3 +616,60 @@ class SnpsDataBase:
             self.close()
         except Exception:
             pass
+
+
+class SnpKinship:
+    """emma_kinship (src/emma_kinship.cpp): the EMMA kinship of <base>.bed / <base>.fam, accumulated on the GPU with the
+    reference's rounding (bit-identical sums). Opening runs the reference's file guards before the device is touched."""
+
+    def __init__(self, base_bedbim: str, device: int = 0):
+        self._h = C.c_void_p()
+        check(lib.kgwas_snpkin_open(base_bedbim.encode(), device, C.byref(self._h)))
+        S, M, b = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        check(lib.kgwas_snpkin_info(self._h, C.byref(S), C.byref(M), C.byref(b)))
+        self.n_samples, self.n_snps, self.bytes_per_snp = S.value, M.value, b.value
+
+    def feed_bed(self, body):
+        """SNPs of a .bed body (file layout, without the 3 magic bytes), after those fed before."""
+        body = np.ascontiguousarray(np.frombuffer(body, np.uint8) if isinstance(body, (bytes, bytearray, memoryview)) else body, np.uint8)
+        if body.size % self.bytes_per_snp:
+            raise ValueError("feed_bed: %d bytes are not whole SNPs of %d bytes" % (body.size, self.bytes_per_snp))
+        check(lib.kgwas_snpkin_feed_bed(self._h, ptr(body), body.size // self.bytes_per_snp))
+
+    def feed_file(self):
+        """The whole .bed, streamed."""
+        check(lib.kgwas_snpkin_feed_file(self._h))
+
+    def sums(self):
+        """(undivided sums: [r, c] for c < r, other entries 0; SNPs used)."""
+        out = np.zeros((self.n_samples, self.n_samples), np.float64)
+        n = C.c_uint64()
+        check(lib.kgwas_snpkin_sums(self._h, ptr(out), C.byref(n)))
+        return out, n.value
+
+    def matrix(self):
+        """(the finished S x S kinship matrix, SNPs used)."""
+        K = np.zeros((self.n_samples, self.n_samples), np.float64)
+        n = C.c_uint64()
+        check(lib.kgwas_snpkin_matrix(self._h, ptr(K), C.byref(n)))
+        return K, n.value
+
+    def close(self):
+        if self._h:
+            lib.kgwas_snpkin_close(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def snp_kinship_format(K: np.ndarray) -> bytes:
+    """The text emma_kinship prints for the matrix K."""
+    K = np.ascontiguousarray(K, np.float64)
+    need = lib.kgwas_snpkin_format(K.shape[0], ptr(K), None, 0)
+    buf = C.create_string_buffer(int(need) + 1)
+    lib.kgwas_snpkin_format(K.shape[0], ptr(K), buf, need)
+    return buf.raw[:need]
