@@ -376,7 +376,7 @@ hipError_t launch_squeeze(const uint64_t* file_rows, uint64_t file_stride_w, uin
                           uint32_t W_m, uint32_t W_f, uint32_t* out, hipStream_t st) {
     if (n_rows == 0) return hipSuccess;
     const size_t lds = (size_t)64u * ((2u * W_f + 1u) + (2u * W_m + 1u)) * 4u;
-    if (lds > 160u * 1024u) return hipErrorInvalidValue;
+    if (lds > 160u * 1024u) return hipErrorInvalidValue;  // (W_f + W_m > SQUEEZE_MAX_WORDS: check_squeeze_fits refuses it earlier)
     hipError_t e = ensure_dyn_lds((const void*)squeeze_kernel, lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(squeeze_kernel, dim3((uint32_t)((n_rows + 63) / 64)), dim3(256), lds, st, file_rows,

@@ -269,7 +269,11 @@ hipError_t launch_snpkin_accumulate(int rows_per_wave, const uint8_t* bed, uint3
                                     const void* params, const void* vals, const uint2* tiles, uint32_t n_tiles, double* sums,
                                     hipStream_t st);
 
-// Squeeze: out[r][2*W_m dwords] bit i = file bit colmap[i] (colmap[i] == 0xFFFFFFFF -> 0).
+// Squeeze: out[r][2*W_m dwords] bit i = file bit colmap[i] (colmap[i] == 0xFFFFFFFF -> 0). A block stages 64 file rows
+// and 64 squeezed rows in LDS: it exists while W_f + W_m <= SQUEEZE_MAX_WORDS (all of the table phenotyped: up to 10 176
+// accessions; any subset or order: up to 20 288 accessions in the table). check_squeeze_fits throws KGWAS_ERR_ARG beyond.
+constexpr uint64_t SQUEEZE_MAX_WORDS = 319;
+void check_squeeze_fits(const char* who, uint64_t S_f, uint64_t S);
 hipError_t launch_squeeze(const uint64_t* file_rows, uint64_t file_stride_w, uint64_t n_rows, const uint32_t* colmap,
                           uint32_t W_m, uint32_t W_f, uint32_t* out, hipStream_t st);
 

@@ -106,7 +106,7 @@ int kgwas_kinship_create(int32_t device, uint64_t n_acc_file, uint64_t min_count
         k->S_pad = (uint32_t)((n_acc_file + 127) / 128 * 128);  // whole 128 x 128 Gram tiles
         if (!kin_transpose_rows_per_block(1 + k->W_f, k->S_pad))
             throw Error(KGWAS_ERR_ARG, "kgwas_kinship_create: " + std::to_string(n_acc_file) +
-                                           " accessions exceed what the bit-transpose kernel can stage in LDS (about 9900)");
+                                           " accessions exceed what the bit-transpose kernel can stage in LDS (at most 10112)");
         k->chunk_rows = 1ull << 20;  // the reference's own batch size (src/emma_kinship_kmers.cpp:89)
         k->n_rw_cap = (k->chunk_rows + 511) / 512 * 16;
         KGWAS_HIP(hipStreamCreateWithFlags(&k->stream, hipStreamNonBlocking));
@@ -125,6 +125,9 @@ int kgwas_kinship_create(int32_t device, uint64_t n_acc_file, uint64_t min_count
         KGWAS_HIP(hipMalloc((void**)&k->d_n, TESTED_SHARDS * 8));
         KGWAS_HIP(hipMemset(k->d_H, 0, (size_t)k->S_pad * k->S_pad * 8));
         KGWAS_HIP(hipMemset(k->d_n, 0, TESTED_SHARDS * 8));
+        // (hipMemset runs on the null stream, which the session's non-blocking streams do not wait for: without this the
+        // zeroing could land after the first feed's kernels and wipe its counts)
+        KGWAS_HIP(hipStreamSynchronize(nullptr));
         *out = k.release();
     });
 }

@@ -634,6 +634,7 @@ int kgwas_scan_reset(kgwas_scan* s) {
         s->rows_submitted = 0;
         s->pat_upper = 0;
         KGWAS_HIP(hipMemset(s->d_pat_cnt.p, 0, 8));
+        KGWAS_HIP(hipStreamSynchronize(nullptr));  // (a null-stream memset: the session's non-blocking streams do not wait for it)
         s->rows_done = 0;
         s->finished = false;
         const kgwas_scan_stats old = s->st;

@@ -49,6 +49,7 @@ int kgwas_scan_create(const kgwas_scan_params* p, kgwas_scan** out) {
         }
         s->direct = true;
         for (uint64_t i = 0; i < s->S; i++) s->direct = s->direct && (s->col[i] == i);
+        if (!s->direct) check_squeeze_fits("kgwas_scan_create", s->S_f, s->S);  // (a subset or reordered panel is squeezed per chunk)
 
         bool finite = true;
         for (float v : s->Y) finite = finite && std::isfinite(v);
@@ -229,6 +230,7 @@ int kgwas_scan_create(const kgwas_scan_params* p, kgwas_scan** out) {
         KGWAS_HIP(hipMemset(s->d_pat_cnt.p, 0, 8));
         KGWAS_HIP(hipMemset(s->d_thr.p, 0, P * sizeof(double)));  // 0 = "nothing is filtered" until the heaps say otherwise
         KGWAS_HIP(hipMemset(s->d_thr_host.p, 0, P * sizeof(double)));
+        KGWAS_HIP(hipStreamSynchronize(nullptr));  // (null-stream memsets: the session's non-blocking streams do not wait for them)
         s->d_topn.alloc(P);
         s->d_sel.alloc(P);
         s->h_sel.alloc(P);

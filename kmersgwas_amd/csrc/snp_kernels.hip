@@ -74,7 +74,10 @@ __global__ void __launch_bounds__(256) snp_score_kernel(const uint32_t* planes, 
     if (!((mac > S_gi) || (mac > (N - S_gi)))) {  // :157-158
         const double yigi = __dadd_rn((double)dp[0], __dmul_rn((double)dp[2], 0.5));
         const double score_sum = (double)dp[1];
-        double r = __dsub_rn(__dmul_rn(N, yigi), __dmul_rn(S_gi, score_sum));
+        const double p1 = __dmul_rn(N, yigi), p2 = __dmul_rn(S_gi, score_sum);
+        // a NaN phenotype value: SSE's subsd returns its first NaN operand as it is, where v_add_f64 with a negated operand
+        // would flip the sign of a NaN p2
+        double r = isnan(p1) ? p1 : isnan(p2) ? p2 : __dsub_rn(p1, p2);
         r = __dmul_rn(r, r);
         const double den = __dmul_rn(N, __dsub_rn(__dmul_rn(N, S_gi_2), __dmul_rn(S_gi, S_gi)));
         out = r / den;

@@ -125,6 +125,7 @@ void device_init(kgwas_snpkin* h) {
     KGWAS_HIP(hipMemset(h->d_sums.p, 0, h->S * h->S * sizeof(double)));
     h->d_n.alloc(TESTED_SHARDS);
     KGWAS_HIP(hipMemset(h->d_n.p, 0, TESTED_SHARDS * sizeof(unsigned long long)));
+    KGWAS_HIP(hipStreamSynchronize(nullptr));  // (null-stream memsets: the non-blocking streams below do not wait for them)
 }
 
 // n_snps SNPs in chunks; fill(dst, first, count) writes SNPs [first, first + count) of this feed into pinned memory.

@@ -73,6 +73,8 @@ struct SnpScorer {
         L = 64 * W_m;
         ndw = 2 * W_m;
         chunk = std::max<uint64_t>(1024, std::min<uint64_t>(1u << 20, (512ull << 20) / std::max<uint64_t>(8 * P, s->bytes_per_snp)));
+        const long long forced = opt_int("KGWAS_SNP_CHUNK_SNPS", 0);
+        if (forced > 0) chunk = (uint64_t)std::min<long long>(forced, 1 << 20);
         // permute_scores (src/kmer_general.cpp:155-167) of the zero-padded column: R[128b+4s+l] = V[128b+32l+31-s]
         std::vector<float> Yperm(P * L, 0.0f), V(L);
         for (uint64_t j = 0; j < P; j++) {

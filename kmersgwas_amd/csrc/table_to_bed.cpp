@@ -32,6 +32,15 @@ struct Dev {
     }
 };
 }  // namespace
+
+void check_squeeze_fits(const char* who, uint64_t S_f, uint64_t S) {
+    const uint64_t W_f = (S_f + 63) / 64, W_m = 2 * ((S + 127) / 128);
+    if (W_f + W_m > SQUEEZE_MAX_WORDS)
+        throw Error(KGWAS_ERR_ARG, std::string(who) + ": " + std::to_string(S) + " phenotyped of " + std::to_string(S_f) +
+                                       " accessions exceed the squeeze kernel's LDS (table words + phenotype-order words <= " +
+                                       std::to_string(SQUEEZE_MAX_WORDS) +
+                                       ": at most 10176 accessions when all are phenotyped, 20288 in the table for a subset)");
+}
 }  // namespace kgwas
 
 using namespace kgwas;
@@ -51,10 +60,13 @@ extern "C" int kgwas_table_to_bed(kgwas_table* t, const uint64_t* col, uint64_t 
         const uint64_t S = n_acc;
         for (uint64_t i = 0; i < S; i++)
             if (col[i] >= S_f) throw Error(KGWAS_ERR_ARG, "kgwas_table_to_bed: column index out of range");
+        check_squeeze_fits("kgwas_table_to_bed", S_f, S);  // (before any allocation or output file)
         const uint32_t W_m = (uint32_t)(2 * ((S + 127) / 128));  // m_hash_words rounded to the 128-bit unit (:51)
         const uint32_t bpr = (uint32_t)((S + 3) / 4);            // write_PA: one byte per 4 accessions
         const uint64_t stride = 1 + W_f;
-        const uint64_t piece = std::max<uint64_t>(1024, std::min<uint64_t>(1u << 20, (256ull << 20) / (8 * stride)));
+        uint64_t piece = std::max<uint64_t>(1024, std::min<uint64_t>(1u << 20, (256ull << 20) / (8 * stride)));
+        const long long forced = opt_int("KGWAS_BED_PIECE_ROWS", 0);
+        if (forced > 0) piece = (uint64_t)std::min<long long>(forced, 1 << 20);
 
         std::vector<uint32_t> colmap(64ull * W_m, 0xFFFFFFFFu);
         for (uint64_t i = 0; i < S; i++) colmap[i] = (uint32_t)col[i];
