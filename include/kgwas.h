@@ -225,8 +225,9 @@ typedef struct kgwas_scan_stats {
  * Version 6 (round 6): no struct changed; new entry points kgwas_heap_selfcheck, kgwas_scan_select_mode and the test hook
  * kgwas_scan_debug_residuals; kgwas_scan_lowest takes a non-const session (it always mutated it); kgwas_scan_stats.coarse_mx32 is
  * always 0 (the 32 x 32 x 64 filter form was removed).
- * Version 7: no struct changed; new entry points kgwas_snpkin_* (emma_kinship). */
-#define KGWAS_ABI_VERSION 7
+ * Version 7: no struct changed; new entry points kgwas_snpkin_* (emma_kinship).
+ * Version 8: no struct changed; new entry points kgwas_kmer_encode, kgwas_filter_kmers, kgwas_filter_kmers_write (filter_kmers). */
+#define KGWAS_ABI_VERSION 8
 uint32_t kgwas_abi_version(void);
 
 int kgwas_scan_create(const kgwas_scan_params* p, kgwas_scan** out);
@@ -405,6 +406,23 @@ int kgwas_write_plink_many(uint64_t n_cols, const char* const* out_bases, kgwas_
 int kgwas_table_to_bed(kgwas_table* t, const uint64_t* col, uint64_t n_acc, const char* const* acc_names, const float* y,
                        uint64_t min_count, uint64_t batch_size, int unique_patterns, const char* out_base, int device,
                        uint64_t* n_batches, uint64_t* n_written);
+
+/* ------------------------------------------------------------------------------------
+ * filter_kmers (src/filter_kmers.cpp): the presence/absence rows of listed k-mers.
+ * kgwas_kmer_encode: kmer2bits (src/kmer_general.cpp:260-283) of word[0, len), 1 <= len <= 32 - the canonical code
+ * min(b, reverse complement of b); a character other than A, C, G, T -> KGWAS_ERR_FORMAT "Ilegal kmer".
+ * kgwas_filter_kmers: the reference's merge-join (:152-177) of the sorted codes (any order; the library sorts a copy,
+ * duplicates kept) with the table's rows in file order, exact also where the table's keys descend. Emitted rows go to
+ * file_rows[i] (file row index) and rows[i * (1 + W_f) ..] (the raw row), in file order; the caller gives room for
+ * min(n, table rows) of them, and either may be NULL. kgwas_filter_kmers_write writes the reference's output file instead
+ * (header "kmer\t<name>...", then bits2kmer31(key, k) and "\t0" / "\t1" per accession for each emitted row; k of the table,
+ * 1..32), formatted on the device; a failed write (a full disk) is KGWAS_ERR_IO. Both run on `device`.
+ * ---------------------------------------------------------------------------------- */
+int kgwas_kmer_encode(const char* word, uint64_t len, uint64_t* code);
+int kgwas_filter_kmers(kgwas_table* t, const uint64_t* codes, uint64_t n, int32_t device, uint64_t* file_rows, uint64_t* rows,
+                       uint64_t* n_found);
+int kgwas_filter_kmers_write(kgwas_table* t, const uint64_t* codes, uint64_t n, int32_t device, const char* out_path,
+                             uint64_t* n_found);
 
 /* ------------------------------------------------------------------------------------
  * SNP twin of the scorer: MultipleSNPsDataBases (src/snps_multiple_databases.h:25-63) for associate_snps

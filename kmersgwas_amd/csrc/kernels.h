@@ -269,6 +269,27 @@ hipError_t launch_snpkin_accumulate(int rows_per_wave, const uint8_t* bed, uint3
                                     const void* params, const void* vals, const uint2* tiles, uint32_t n_tiles, double* sums,
                                     hipStream_t st);
 
+// filter_kmers (filter_kernels.hip), on one device piece of n_rows table rows (stride 1 + W_f words) and the sorted list
+// L[0, n): fk_match gives each row lower_bound / count in L, its run-head mark (r + 1 where the key differs from the previous
+// row's, carry_key before row 0 when has_prev) and atomically the piece's first descent (*first_desc, preset to
+// 0xFFFFFFFF). spl[j] = L[j * B], j < ns <= FK_SPLITTERS, is staged in LDS. fk_select max-scans the marks into run_start,
+// flags the rows the merge-join emits before the first descent (carry_run: rows of the piece's first run seen before it),
+// compacts their offsets into sel / *n_sel and fills info[0..3] (last row's run length and key; at a descent d > 0, row
+// d - 1's). fk_keys copies keys of rows [r0, n_rows) to keys[0 ..); fk_gather copies rows sel[0, m) whole; fk_format writes
+// their text lines (k + 2 S_f + 1 bytes each) to text, whose size must be a multiple of 16 bytes covering m lines.
+constexpr uint32_t FK_SPLITTERS = 4096;
+hipError_t launch_fk_match(const uint64_t* rows, uint64_t stride, uint32_t n_rows, const uint64_t* L, uint64_t n,
+                           const uint64_t* spl, uint32_t ns, uint64_t B, uint64_t carry_key, bool has_prev, uint64_t* lb,
+                           uint64_t* cnt, uint32_t* head, uint32_t* first_desc, hipStream_t st);
+size_t fk_scan_temp_bytes(uint32_t max_rows);  // temp storage of fk_select (0: the query failed)
+hipError_t launch_fk_select(const uint64_t* rows, uint64_t stride, uint32_t n_rows, const uint64_t* cnt, const uint32_t* head,
+                            uint32_t* run_start, uint64_t carry_run, const uint32_t* first_desc, uint8_t* emit, uint32_t* sel,
+                            uint32_t* n_sel, uint64_t* info, void* temp, size_t temp_bytes, hipStream_t st);
+hipError_t launch_fk_keys(const uint64_t* rows, uint64_t stride, uint32_t r0, uint32_t n_rows, uint64_t* keys, hipStream_t st);
+hipError_t launch_fk_gather(const uint64_t* rows, uint64_t stride, const uint32_t* sel, uint32_t m, uint64_t* out, hipStream_t st);
+hipError_t launch_fk_format(const uint64_t* rows, uint64_t stride, const uint32_t* sel, uint32_t m, uint32_t k, uint32_t S_f,
+                            void* text, hipStream_t st);
+
 // Squeeze: out[r][2*W_m dwords] bit i = file bit colmap[i] (colmap[i] == 0xFFFFFFFF -> 0). A block stages 64 file rows
 // and 64 squeezed rows in LDS: it exists while W_f + W_m <= SQUEEZE_MAX_WORDS (all of the table phenotyped: up to 10 176
 // accessions; any subset or order: up to 20 288 accessions in the table). check_squeeze_fits throws KGWAS_ERR_ARG beyond.

@@ -8,6 +8,7 @@ Names follow the reference's classes (src/kmers_multiple_databases.h, src/best_a
   BestAssociationsHeap  <- BestAssociationsHeap                                    (a-7)
   Kinship               <- update_emma_kinshhip_calculation / emma_kinship_kmers    (a-9)
   SnpKinship            <- emma_kinship (the kinship of a PLINK SNP matrix)          (f-5)
+  filter_kmers          <- filter_kmers (rows of listed k-mers)                       (f-6)
 
 Everything numeric happens inside libkgwas (HIP kernels on the GPU + the std::priority_queue
 replay); this module only moves buffers.
@@ -564,6 +565,35 @@ def table_to_bed(out_base: str, table: KmersTable, col, acc_names: Sequence[str]
     check(lib.kgwas_table_to_bed(table._h, ptr(col), len(col), arr, ptr(y), min_count, batch_size, 1 if unique_patterns else 0,
                                  out_base.encode(), device, C.byref(nb), C.byref(nw)))
     return nb.value, nw.value
+
+
+def kmer2bits(word: str) -> int:
+    """kmer2bits (src/kmer_general.cpp:260-283): the canonical 2-bit code of a k-mer of 1 to 32 bases, min(code, reverse
+    complement); any character but A, C, G, T raises KgwasError (KGWAS_ERR_FORMAT, "Ilegal kmer")."""
+    b = word.encode()
+    out = C.c_uint64(0)
+    check(lib.kgwas_kmer_encode(b, len(b), C.byref(out)))
+    return out.value
+
+
+def filter_kmers(table: KmersTable, codes, device: int = 0):
+    """filter_kmers (src/filter_kmers.cpp) on the GPU: the rows the reference's merge-join of the sorted codes with the
+    table emits, in file order. Returns (file_rows uint64[m], rows uint64[m, 1 + W_f])."""
+    codes = np.ascontiguousarray(codes, np.uint64).reshape(-1)
+    cap = min(len(codes), table.n_rows)
+    file_rows = np.zeros(max(cap, 1), np.uint64)
+    rows = np.zeros((max(cap, 1), 1 + table.words_per_row), np.uint64)
+    m = C.c_uint64(0)
+    check(lib.kgwas_filter_kmers(table._h, ptr(codes), len(codes), device, ptr(file_rows), ptr(rows), C.byref(m)))
+    return file_rows[:m.value].copy(), rows[:m.value].copy()
+
+
+def filter_kmers_write(path: str, table: KmersTable, codes, device: int = 0) -> int:
+    """filter_kmers' output file for `codes` (header, then one text line per emitted row). Returns the rows written."""
+    codes = np.ascontiguousarray(codes, np.uint64).reshape(-1)
+    m = C.c_uint64(0)
+    check(lib.kgwas_filter_kmers_write(table._h, ptr(codes), len(codes), device, path.encode(), C.byref(m)))
+    return m.value
 
 
 class SnpsDataBase:
