@@ -1,10 +1,12 @@
 // env.h — every environment switch of libkgwas and its tools, in one place.
 //
 // OPTIONS (kgwas::opt_*): the product's run-time switches. Each one is documented in the table below, is read where it acts, and
-// is walked by the test matrix (tests/, tools/fuzz_parity.py) - none selects code the default tests do not reach:
+// is walked by the test matrix (tests/, tools/fuzz_parity.py) - none selects code the default tests do not reach. Those of the
+// filter plan (KGWAS_COARSE_MX .. KGWAS_NARROW, KGWAS_DEBUG_RESIDUALS) are read once per session, with the exp_* knobs the plan
+// uses, by read_filter_opts (scan_plan.cpp):
 //
 //   KGWAS_FULL_REPLAY=1        every column is replayed push by push (no select mode)
-//   KGWAS_COARSE_MX=0|1        filter family: 0 int8 (score_coarse.hip), 1 block-scaled FP4 x FP6/FP4 (score_mx.hip); unset: by plan
+//   KGWAS_COARSE_MX=0|1        filter family: 0 int8 (score_coarse.hip), 1 block-scaled FP4 x FP6/FP4 (score_mx.hip); unset or empty: by plan
 //   KGWAS_COARSE_SLICES=1|2    force the one- / two-slice operand set (unset: chosen per chunk / by plan)
 //   KGWAS_MX_S1=6              block-scaled filter: FP6 second slice instead of FP4
 //   KGWAS_MXS=0..3             operand-streaming form (score_mxs.hip): never / where the resident form degenerates (default) /

@@ -1,7 +1,7 @@
 // scan_internal.h — the association-scan session's internals shared by scan_host.cpp (CPU topology, heaps), scan_gpu.cpp
 // (chunk submission: kernels, thresholds, record copies), scan_replay.cpp (streaming replay + the feed loop),
-// scan_create.cpp (session set-up: operand sets of the filters) and scan_api.cpp (the C ABI). Not a public header: the
-// boundary is include/kgwas.h.
+// scan_plan.cpp (a session's plan and the operand sets of its filters, on the host), scan_create.cpp (session set-up) and
+// scan_api.cpp (the C ABI). Not a public header: the boundary is include/kgwas.h.
 //
 // The association-scan session: pass 1 of associate_kmers (src/associate_kmers.cpp:99-148)
 // re-designed around the GPU.
@@ -463,7 +463,7 @@ struct kgwas_scan {
     uint64_t rows_submitted = 0;  // rows handed to the GPU (replayed or still in flight)
     // coarse int8 filter (sparse phase)
     bool coarse = false;
-    uint32_t coarse_T = 0, n_kgroups = 0;  // coarse_T: most operand tiles the LDS can hold
+    uint32_t n_kgroups = 0;  // 512-sample groups
     // Operand sets of the filter: mode[0] = one int8 slice per column (half the matrix work, ~2.5 survivors per
     // candidate), mode[1] = two slices (~1). Both may be resident; each chunk picks one (pick_coarse_mode).
     struct CoarsePart {  // one launch of the filter: n_lgroups LDS groups of T operand tiles over a range of columns
@@ -493,7 +493,7 @@ struct kgwas_scan {
     PinBuf<uint32_t> h_sel_info;
     bool sel_valid = false;  // h_sel holds the minima the heaps will have once the pending dense rows are pushed
     double infl_obs[2] = {4.0, 1.1};  // survivors per candidate of the last finished chunk of each mode
-    double mode_k = 0.09;
+    double mode_k = 0;  // (FilterOpts::mode_k)
     std::chrono::steady_clock::time_point t_feed0;  // KGWAS_TRACE: the timeline's origin (start of the current feed)
     double t_ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_feed0).count(); }
     uint64_t sum_topn = 0;  // over the columns
@@ -684,4 +684,75 @@ void replay_group(kgwas_scan* s, Slot& sl, size_t g, ReplayAcc& acc);
 void add_replay_stats(kgwas_scan* s, const ReplayAcc& a);
 void replay_worker(kgwas_scan* s, size_t w);
 void feed_device_impl(kgwas_scan* s, const uint64_t* d_rows, uint64_t n_rows, uint64_t first_row);
+// ---- scan_plan.cpp: a session's plan and the host side of its operands (no device calls)
+struct FilterOpts {  // every switch the plan reads (env.h), read once per session
+    int coarse_mx = -1;            // KGWAS_COARSE_MX: 0 int8, 1 block-scaled, -1 by plan (unset or set but empty)
+    int coarse_slices = -1;        // KGWAS_COARSE_SLICES: 1 | 2 that set alone, 0 set to another value, -1 unset
+    bool mx_s1_fp6 = false;        // KGWAS_MX_S1=6
+    int mxs = 1, mxs_form = 0;     // KGWAS_MXS, KGWAS_MXS_FORM
+    bool narrow = true;            // KGWAS_NARROW (0: false)
+    bool debug_residuals = false;  // KGWAS_DEBUG_RESIDUALS
+    // experiments: KGWAS_COARSE_MIXED, KGWAS_COARSE_NOSPLIT (split = false), KGWAS_NARROW_PACK, KGWAS_CAP_MULT (-1: by
+    // filter), KGWAS_CAP_BUDGET, KGWAS_MODE_K (pick_coarse_mode)
+    bool mixed = true, split = true, narrow_pack = true;
+    long long cap_mult = -1, cap_budget = 4ll << 20;
+    double mode_k = 0.09;
+};
+FilterOpts read_filter_opts();
+struct ScanShape {
+    uint64_t S, L, W_m, W_f, P, max_topn;
+    bool direct, finite, chain_safe;
+};
+// One launch of an operand set: `groups` LDS groups of T operand tiles over the columns [j0, j0 + n), cper per group. The
+// streaming form (stream = 1 + launch_mxs's form): `groups` column groups of T column tiles, ng of them per grid block.
+struct FilterPart {
+    uint64_t j0, n, cper;
+    uint32_t T;
+    uint64_t groups;
+    uint32_t stream = 0, ng = 1;
+};
+struct FilterSet {  // kgwas_scan::cmode[slices - 1]; slices = 0: not built
+    bool mx = false;  // block-scaled (else int8)
+    uint32_t slices = 0, s1_fp6 = 0;
+    uint32_t n_full = 0, n_quarter = 0, n_steps = 0;  // block-scaled: 512-sample groups, 128-sample quarters, K = 128 steps
+    std::vector<FilterPart> parts;  // one or two
+    uint32_t tile_slices = 0;     // operand tiles a row is multiplied with, all parts and groups
+    double tile_slices_eq = 0;    // block-scaled: the same in int8 tile-slice equivalents
+};
+struct ScanPlan {
+    uint32_t kernel = 0;  // the exact scorer
+    bool coarse = false, narrow = false, narrow_pack1 = false;
+    bool use_mx = false;      // the block-scaled family (else int8, perhaps with a block-scaled two-slice set: mixed)
+    bool keep_resid = false;  // KGWAS_DEBUG_RESIDUALS on a filter session
+    uint32_t n_kgroups = 0;
+    uint64_t chunk_max = 0, dense_rows = 0, dense_chunk = 0;
+    uint32_t cap = 0;
+    FilterSet set[2];
+};
+// Every plan decision; throws the plan's argument errors. resid: the session's dbg_resid, sized here when kept (the
+// one-slice test fills form 0).
+ScanPlan plan_scan(const kgwas_scan_params& p, const ScanShape& sh, const FilterOpts& o, const std::vector<float>& Y,
+                   std::vector<double> resid[3]);
+struct ExactLayouts {
+    std::vector<uint32_t> dmask, colmap;
+    std::vector<float> Yperm, Ymfma, sums;
+    uint32_t nb_full = 0;  // see kgwas_scan::nb_full
+};
+ExactLayouts exact_layouts(const ScanShape& sh, const std::vector<uint64_t>& col, const std::vector<float>& Y);
+// The filters' operands; resid (or null): [column * S + sample] of the form's dbg_resid
+struct NarrowOperands {
+    std::vector<uint8_t> Bn;
+    std::vector<NarrowCol> ncols;
+};
+NarrowOperands narrow_operands(const ScanShape& sh, const ScanPlan& pl, const std::vector<float>& Y, const std::vector<float>& sums,
+                               double* resid);
+struct PartOperands {
+    std::vector<uint8_t> Bq;
+    std::vector<CoarseCol> cols;
+    float eg_max = 0, rall_max = 0, rmax_max = 0;  // error terms in units of Dc, maxima over the part's columns
+};
+PartOperands int8_operands(const ScanShape& sh, uint32_t n_kgroups, const FilterSet& fs, const FilterPart& fp, const std::vector<float>& Y,
+                           const std::vector<float>& sums, double* resid);
+PartOperands block_scaled_operands(const ScanShape& sh, const FilterSet& fs, const FilterPart& fp, const std::vector<float>& Y,
+                                   const std::vector<float>& sums, double* resid);
 }  // namespace kgwas

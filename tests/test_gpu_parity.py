@@ -367,7 +367,7 @@ def test_block_scaled_filter_streaming_form(monkeypatch, S_f, S, P, kind, reorde
     scan.feed_host(rows[cut:], cut)
     scan.finish()
     st = scan.stats()
-    # the plan of scan_create.cpp: column groups of ct tiles, ng of them per block, `og` operand groups a row passes through
+    # the plan of scan_plan.cpp: column groups of ct tiles, ng of them per block, `og` operand groups a row passes through
     if P + 1 <= 112:
         ng, g, ct, stream = 1, 1, max(3, (P + 1 + 15) // 16), 1
     elif form in (1, 2):
@@ -1302,7 +1302,7 @@ def test_numeric_edges_of_the_phenotype_values(kernel, kind, S, P):
 def test_more_than_5120_samples(monkeypatch, S, P, mxs):
     """Beyond 5120 accessions no filter keeps a whole column tile's operands in LDS. With the operand-streaming form of the
     block-scaled filter (score_mxs.hip, the default) such sessions are filtered all the same - one operand group, at least three
-    column tiles, however few columns; without it (KGWAS_MXS=0) the operand sets are not built (scan_create.cpp) and the session
+    column tiles, however few columns; without it (KGWAS_MXS=0) the operand sets are not built (scan_plan.cpp) and the session
     must say which exact scorer runs instead. The heaps equal the oracle's either way."""
     monkeypatch.setenv("KGWAS_MXS", str(mxs))
     rows = random_table(6000, S, seed=S, dup_frac=0.2)
@@ -1399,7 +1399,7 @@ def test_four_hundred_phenotype_columns(S, P, topn):
 
 
 def test_too_many_phenotype_columns_is_a_clean_argument_error():
-    """Survivor keys are `column << row_bits | row` in 32 bits (scan_create.cpp): 2^22 columns and more cannot get a filter
+    """Survivor keys are `column << row_bits | row` in 32 bits (scan_plan.cpp): 2^22 columns and more cannot get a filter
     session - KGWAS_ERR_ARG with a message before anything is allocated on the device, no crash; the library stays usable."""
     from kmersgwas_amd import capi
     S, P = 16, 1 << 22
@@ -1425,7 +1425,7 @@ def test_too_many_phenotype_columns_is_a_clean_argument_error():
 # ---- round 6: rows on which the filters' error bound is TIGHT ----------------------------------------------------------------
 
 def _two_slice_lattice():
-    """The integers t = 8 a6 + a4 the block-scaled filter's FP6 + FP4 slices can encode (scan_create.cpp: A6, A4), ascending."""
+    """The integers t = 8 a6 + a4 the block-scaled filter's FP6 + FP4 slices can encode (scan_plan.cpp: A6, A4), ascending."""
     a6 = list(range(0, 16)) + list(range(16, 31, 2)) + list(range(32, 61, 4))
     a4 = [0, 1, 2, 3, 4, 6, 8, 12]
     s6 = sorted(set(a6) | set(-x for x in a6))
@@ -1457,7 +1457,7 @@ def _midpoint_phenotype(S, lattice, t_max, seed, eps):
 @pytest.mark.parametrize("S", [1024, 1135])
 def test_adversarial_rows_at_the_filters_bound(name, env, P, form, S, monkeypatch):
     """The filters keep a pair iff it cannot be PROVEN to lose: |yigi_ref - yc| <= Eg + min(Rall, N1 rmax), Rall the larger one-sign
-    sum of the quantisation residuals (scan_create.cpp). Random tables never come near that bound - a row's residuals cancel.
+    sum of the quantisation residuals (scan_plan.cpp). Random tables never come near that bound - a row's residuals cancel.
     Here they do not: phenotype values on the midpoints of the slices' grids (residuals of almost half a step, the maximum),
     and rows whose set bits are EXACTLY the samples with a positive (or exactly those with a negative) residual - read from the
     session itself (kgwas_scan_debug_residuals) -, so that sum g_i resid_i = Rall: the bound is attained, and only the
