@@ -226,8 +226,9 @@ typedef struct kgwas_scan_stats {
  * kgwas_scan_debug_residuals; kgwas_scan_lowest takes a non-const session (it always mutated it); kgwas_scan_stats.coarse_mx32 is
  * always 0 (the 32 x 32 x 64 filter form was removed).
  * Version 7: no struct changed; new entry points kgwas_snpkin_* (emma_kinship).
- * Version 8: no struct changed; new entry points kgwas_kmer_encode, kgwas_filter_kmers, kgwas_filter_kmers_write (filter_kmers). */
-#define KGWAS_ABI_VERSION 8
+ * Version 8: no struct changed; new entry points kgwas_kmer_encode, kgwas_filter_kmers, kgwas_filter_kmers_write (filter_kmers).
+ * Version 9: no struct changed; new entry point kgwas_build_table (build_kmers_table). */
+#define KGWAS_ABI_VERSION 9
 uint32_t kgwas_abi_version(void);
 
 int kgwas_scan_create(const kgwas_scan_params* p, kgwas_scan** out);
@@ -423,6 +424,20 @@ int kgwas_filter_kmers(kgwas_table* t, const uint64_t* codes, uint64_t n, int32_
                        uint64_t* n_found);
 int kgwas_filter_kmers_write(kgwas_table* t, const uint64_t* codes, uint64_t n, int32_t device, const char* out_path,
                              uint64_t* n_found);
+
+/* ------------------------------------------------------------------------------------
+ * build_kmers_table (src/build_kmers_table.cpp, src/kmers_merge_multiple_databaes.cpp): the k-mers table from the sorted
+ * all-k-mers file and the n accessions' sorted k-mer files (64-bit little-endian words, top two bits flags; length size >> 3).
+ * Writes <out_base>.table (prefix, n, kmer_len, then one row per used all-k-mers word: the masked word and ceil(n / 64) words
+ * of bits) and, when names is not NULL, <out_base>.names (one name per line) before any input is opened. The rows and bits are
+ * the reference's, its 5001 key windows and first-insert-wins hash map included, also for inputs that descend or repeat keys
+ * (DESIGN.md 4.9); the match runs on `device`. The all-k-mers file is opened first, then the accessions' in order, and the
+ * .table is created after all of them: a file of fewer than 8 bytes -> KGWAS_ERR_FORMAT "sorted kmer file is empty: <path>", one
+ * that cannot be opened -> KGWAS_ERR_FORMAT "can't open file: <path>". kmer_len must be within 1..31. *n_rows (may be NULL):
+ * rows written. Files are opened as they are read, a few at a time: n is not bound by the descriptor limit.
+ * ---------------------------------------------------------------------------------- */
+int kgwas_build_table(const char* all_kmers_path, const char* const* kmer_paths, const char* const* names, uint64_t n,
+                      uint32_t kmer_len, int32_t device, const char* out_base, uint64_t* n_rows);
 
 /* ------------------------------------------------------------------------------------
  * SNP twin of the scorer: MultipleSNPsDataBases (src/snps_multiple_databases.h:25-63) for associate_snps

@@ -290,6 +290,17 @@ hipError_t launch_fk_gather(const uint64_t* rows, uint64_t stride, const uint32_
 hipError_t launch_fk_format(const uint64_t* rows, uint64_t stride, const uint32_t* sel, uint32_t m, uint32_t k, uint32_t S_f,
                             void* text, hipStream_t st);
 
+// build_kmers_table (build_kernels.hip), on one piece of the all-k-mers list resident on the device: A[0, n) raw words,
+// rows n x stride words (stride = 1 + ceil(accessions / 64)). bt_init masks A's flag bits in place and writes rows[r] = [A[r]]
+// [zeros]. bt_match takes m raw words of one accession (its flag bits are masked on the fly) and ORs the accession's bit into
+// row lower_bound(A, x) wherever that row's key is x; A must not descend, and spl[j] = A[j * B] for all ns = ceil(n / B) <=
+// FK_SPLITTERS splitters (masked). *descends (zeroed by the caller) is set to 1 when a word is below the one before it
+// (carry_key before word 0 when has_prev).
+hipError_t launch_bt_init(uint64_t* A, uint64_t n, uint64_t stride, uint64_t* rows, hipStream_t st);
+hipError_t launch_bt_match(const uint64_t* A, uint64_t n, const uint64_t* spl, uint32_t ns, uint64_t B, const uint64_t* slice,
+                           uint32_t m, uint64_t carry_key, bool has_prev, uint64_t* rows, uint64_t stride, uint64_t accession,
+                           uint32_t* descends, hipStream_t st);
+
 // Squeeze: out[r][2*W_m dwords] bit i = file bit colmap[i] (colmap[i] == 0xFFFFFFFF -> 0). A block stages 64 file rows
 // and 64 squeezed rows in LDS: it exists while W_f + W_m <= SQUEEZE_MAX_WORDS (all of the table phenotyped: up to 10 176
 // accessions; any subset or order: up to 20 288 accessions in the table). check_squeeze_fits throws KGWAS_ERR_ARG beyond.

@@ -9,6 +9,7 @@ Names follow the reference's classes (src/kmers_multiple_databases.h, src/best_a
   Kinship               <- update_emma_kinshhip_calculation / emma_kinship_kmers    (a-9)
   SnpKinship            <- emma_kinship (the kinship of a PLINK SNP matrix)          (f-5)
   filter_kmers          <- filter_kmers (rows of listed k-mers)                       (f-6)
+  build_kmers_table     <- build_kmers_table (the table from sorted k-mer files)      (f-7)
 
 Everything numeric happens inside libkgwas (HIP kernels on the GPU + the std::priority_queue
 replay); this module only moves buffers.
@@ -593,6 +594,21 @@ def filter_kmers_write(path: str, table: KmersTable, codes, device: int = 0) -> 
     codes = np.ascontiguousarray(codes, np.uint64).reshape(-1)
     m = C.c_uint64(0)
     check(lib.kgwas_filter_kmers_write(table._h, ptr(codes), len(codes), device, path.encode(), C.byref(m)))
+    return m.value
+
+
+def build_kmers_table(all_kmers_path: str, kmer_paths: Sequence[str], names: Sequence[str] | None, kmer_len: int, out_base: str,
+                      device: int = 0) -> int:
+    """build_kmers_table (src/build_kmers_table.cpp) on the GPU: writes out_base.table from the sorted all-k-mers file and the
+    accessions' sorted k-mer files (64-bit words), and out_base.names when `names` is given. Returns the rows written."""
+    paths = (C.c_char_p * len(kmer_paths))(*[os.fsencode(p) for p in kmer_paths])
+    nm = None
+    if names is not None:
+        if len(names) != len(kmer_paths):
+            raise ValueError("build_kmers_table: %d names for %d files" % (len(names), len(kmer_paths)))
+        nm = (C.c_char_p * len(names))(*[a.encode() for a in names])
+    m = C.c_uint64(0)
+    check(lib.kgwas_build_table(os.fsencode(all_kmers_path), paths, nm, len(kmer_paths), kmer_len, device, os.fsencode(out_base), C.byref(m)))
     return m.value
 
 
