@@ -227,8 +227,9 @@ typedef struct kgwas_scan_stats {
  * always 0 (the 32 x 32 x 64 filter form was removed).
  * Version 7: no struct changed; new entry points kgwas_snpkin_* (emma_kinship).
  * Version 8: no struct changed; new entry points kgwas_kmer_encode, kgwas_filter_kmers, kgwas_filter_kmers_write (filter_kmers).
- * Version 9: no struct changed; new entry point kgwas_build_table (build_kmers_table). */
-#define KGWAS_ABI_VERSION 9
+ * Version 9: no struct changed; new entry point kgwas_build_table (build_kmers_table).
+ * Version 10: no struct changed; new entry point kgwas_scan_debug_survivors (test hook). */
+#define KGWAS_ABI_VERSION 10
 uint32_t kgwas_abi_version(void);
 
 int kgwas_scan_create(const kgwas_scan_params* p, kgwas_scan** out);
@@ -283,6 +284,20 @@ int kgwas_scan_select_mode(const kgwas_scan* s, int* on);
  * sum_i g_i resid_i = Rall: the filters' bound |yigi_ref - yc| <= Eg + min(Rall, N1 rmax) is tight there, which is where a test
  * has to look for lost pushes (tests/test_gpu_parity.py::test_adversarial_rows_at_the_filters_bound). */
 int kgwas_scan_debug_residuals(const kgwas_scan* s, uint32_t form, uint64_t column, double* out);
+/* Test hook (filter sessions created under KGWAS_DEBUG_SURVIVORS=1, else KGWAS_ERR_STATE): what the filter kept, chunk by chunk.
+ * Such a session logs every sparse chunk that went through a filter, in submission order: the n_pheno thresholds as that chunk's
+ * filter launches read them (a stream-ordered copy of the array the kernels are given, taken behind the chunk's prep launch - the
+ * narrow path raises thresholds there - and before its first filter launch) and its survivors. The survivors are taken from the
+ * KEY LIST behind the key launch (not from the bitmap in front of it), so the bitmap-to-keys kernels are observed as well and the
+ * wide and the narrow path report in one form: (column, row in chunk) pairs in list order - columns ascending, rows ascending
+ * within a column; the column is the one the key itself names. The copies are synchronous: the hook serialises the scan; without
+ * it a session launches, copies and allocates nothing more than before. kgwas_scan_reset empties the log.
+ * *n_chunks (may be NULL): logged chunks. With info, thr or pairs non-NULL, chunk < *n_chunks selects one:
+ *   info[0..4] = first_row, n_rows, operand set (0 one-slice, 1 two-slice set - kgwas_scan_stats.coarse_mode_* -, 2 narrow filter),
+ *                1 if the key list overflowed (no pairs are logged then; the chunk's re-run by the exact scorer is not logged
+ *                either), number of pairs;
+ *   thr[n_pheno]; pairs[2 * info[4]] = column, row, column, row, ... (call once for info[4], then with the buffer). */
+int kgwas_scan_debug_survivors(const kgwas_scan* s, uint64_t* n_chunks, uint64_t chunk, uint64_t* info, double* thr, uint32_t* pairs);
 int kgwas_scan_absorb(kgwas_scan* s, uint64_t n_shards, const uint64_t* counts, const uint64_t* const* kmer,
                       const double* const* score, const uint64_t* const* row);
 /* The part of the recorded history that can still matter after heaps whose minima are thr[j]: entries with

@@ -35,6 +35,8 @@
 //   KGWAS_BUILD_BLOCK_WORDS=n  (test hook) words per read block of an accession's slice in kgwas_build_table (default 65 536)
 //   KGWAS_DEBUG_SLOW_WORKER=w:pct:min_us   (test hook) slows one replay worker down
 //   KGWAS_DEBUG_RESIDUALS=1    (test hook) sessions keep their filters' quantisation residuals (kgwas_scan_debug_residuals)
+//   KGWAS_DEBUG_SURVIVORS=1    (test hook) filter sessions log every filtered chunk's thresholds and survivors, synchronously
+//                              (kgwas_scan_debug_survivors)
 //
 // EXPERIMENTS (kgwas::exp_*): tuning and ablation knobs of tools/ (chunk-size policies, block sizes, prefetch distances, older
 // forms of a step kept for A/B runs). They exist only in a build with -DKGWAS_EXPERIMENTS (`make EXPERIMENTS=1`); in the

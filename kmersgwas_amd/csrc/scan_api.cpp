@@ -553,6 +553,26 @@ int kgwas_scan_debug_residuals(const kgwas_scan* s, uint32_t form, uint64_t colu
     });
 }
 
+int kgwas_scan_debug_survivors(const kgwas_scan* s, uint64_t* n_chunks, uint64_t chunk, uint64_t* info, double* thr, uint32_t* pairs) {
+    return guarded([&] {
+        if (!s) throw Error(KGWAS_ERR_ARG, "kgwas_scan_debug_survivors: null session");
+        if (!s->dbg_keep_surv) throw Error(KGWAS_ERR_STATE, "kgwas_scan_debug_survivors: the session was not created under KGWAS_DEBUG_SURVIVORS=1 (or has no filter)");
+        if (n_chunks) *n_chunks = s->dbg_chunks.size();
+        if (!info && !thr && !pairs) return;
+        if (chunk >= s->dbg_chunks.size()) throw Error(KGWAS_ERR_ARG, "kgwas_scan_debug_survivors: no such chunk");
+        const kgwas_scan::DbgChunk& ch = s->dbg_chunks[chunk];
+        if (info) {
+            info[0] = ch.first_row;
+            info[1] = ch.n_rows;
+            info[2] = ch.set;
+            info[3] = ch.overflow;
+            info[4] = ch.pairs.size() / 2;
+        }
+        if (thr) memcpy(thr, ch.thr.data(), s->n_pheno * sizeof(double));
+        if (pairs && !ch.pairs.empty()) memcpy(pairs, ch.pairs.data(), ch.pairs.size() * sizeof(uint32_t));
+    });
+}
+
 int kgwas_scan_select_mode(const kgwas_scan* s, int* on) {
     return guarded([&] {
         if (!s || !on) throw Error(KGWAS_ERR_ARG, "kgwas_scan_select_mode: null argument");
@@ -637,6 +657,7 @@ int kgwas_scan_reset(kgwas_scan* s) {
         KGWAS_HIP(hipStreamSynchronize(nullptr));  // (a null-stream memset: the session's non-blocking streams do not wait for it)
         s->rows_done = 0;
         s->finished = false;
+        s->dbg_chunks.clear();
         const kgwas_scan_stats old = s->st;
         s->st = kgwas_scan_stats{};
         s->st.kernel_used = old.kernel_used;

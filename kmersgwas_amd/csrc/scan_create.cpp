@@ -382,6 +382,7 @@ int kgwas_scan_create(const kgwas_scan_params* p, kgwas_scan** out) {
         s->cap = pl.cap;
         s->mode_k = opts.mode_k;
         s->dbg_keep_resid = pl.keep_resid;
+        s->dbg_keep_surv = pl.keep_surv;
 
         const CreateTrace tcreate;
         create_streams(s.get(), tcreate);

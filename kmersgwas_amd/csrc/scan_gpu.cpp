@@ -299,6 +299,45 @@ int pick_coarse_mode(const kgwas_scan* s) {
     return cand_row * std::max(0.0, s->infl_obs[0] - s->infl_obs[1]) < s->mode_k * (tiles1 - tiles0) ? 0 : 1;
 }
 
+// KGWAS_DEBUG_SURVIVORS (test hook, kgwas_scan::DbgChunk): the thresholds a filtered chunk's filter launches are about to read.
+// Synchronous - the hook may cost what it likes; without it nothing here runs.
+static void dbg_log_thresholds(kgwas_scan* s, const double* d_thr, uint64_t n_rows, uint64_t first_row, uint32_t set) {
+    kgwas_scan::DbgChunk ch;
+    ch.first_row = first_row;
+    ch.n_rows = n_rows;
+    ch.set = set;
+    ch.thr.resize(s->n_pheno);
+    KGWAS_HIP(hipMemcpyAsync(ch.thr.data(), d_thr, s->n_pheno * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    KGWAS_HIP(hipStreamSynchronize(s->stream));
+    s->dbg_chunks.push_back(std::move(ch));
+}
+
+// ... and its survivors, behind the key launch: the key list, decoded to (column, row in chunk) pairs in list order
+static void dbg_log_survivors(kgwas_scan* s) {
+    kgwas_scan::DbgChunk& ch = s->dbg_chunks.back();
+    const uint64_t P = s->n_pheno;
+    std::vector<uint32_t> off(P), cnt(P);
+    uint32_t total = 0;
+    KGWAS_HIP(hipMemcpyAsync(off.data(), s->d_surv_off.p, P * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+    KGWAS_HIP(hipMemcpyAsync(cnt.data(), s->d_surv_cnt.p, P * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+    KGWAS_HIP(hipMemcpyAsync(&total, s->d_key_count.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+    KGWAS_HIP(hipStreamSynchronize(s->stream));
+    ch.overflow = total > s->key_slots ? 1u : 0u;
+    if (ch.overflow || !total) return;  // (an overflowed list's ranges are emptied by the key kernels)
+    std::vector<uint32_t> keys(total);
+    KGWAS_HIP(hipMemcpyAsync(keys.data(), s->d_surv_sorted.p, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+    KGWAS_HIP(hipStreamSynchronize(s->stream));
+    const uint32_t row_mask = s->row_key_bits >= 32 ? 0xFFFFFFFFu : (1u << s->row_key_bits) - 1u;
+    for (uint64_t p = 0; p < P; p++) {
+        if ((uint64_t)off[p] + cnt[p] > total) throw Error(KGWAS_ERR_STATE, "survivor log: a column's key range leaves the list");
+        for (uint32_t i = 0; i < cnt[p]; i++) {
+            const uint32_t key = keys[off[p] + i];
+            ch.pairs.push_back(s->row_key_bits >= 32 ? 0u : key >> s->row_key_bits);  // the column the KEY names, not the range it lies in
+            ch.pairs.push_back(key & row_mask);
+        }
+    }
+}
+
 // count_hist: first (and only) scoring of these rows in the sparse phase -> their candidates feed the
 // device-side threshold histograms. Overflow re-runs must not count the same rows twice.
 void submit_sparse(kgwas_scan* s, Slot& sl, const uint64_t* d_rows, uint64_t n_rows, uint64_t first_row,
@@ -375,6 +414,7 @@ void submit_sparse(kgwas_scan* s, Slot& sl, const uint64_t* d_rows, uint64_t n_r
         c.min_count = a.min_count;
         c.n_kgroups = s->n_kgroups;
         const int cm = s->narrow ? 0 : pick_coarse_mode(s);
+        if (s->dbg_keep_surv) dbg_log_thresholds(s, a.thr, n_rows, first_row, s->narrow ? 2u : (uint32_t)cm);
         const kgwas_scan::CoarseMode& M = s->cmode[cm];
         sl.coarse_mode = cm;
         sl.cand_est = (double)s->sum_topn * (double)n_rows / (double)std::max<uint64_t>(s->rows_submitted, 1);
@@ -471,11 +511,13 @@ void submit_sparse(kgwas_scan* s, Slot& sl, const uint64_t* d_rows, uint64_t n_r
             // record written in place by the re-score kernel - a chunk is five launches, not thirteen
             KGWAS_HIP(launch_narrow_keys(s->d_bitmap.p, n_words, n_rows, (uint32_t)s->n_pheno, s->d_bm_blocks.p, s->d_surv_sorted.p, s->key_slots,
                                          s->row_key_bits, s->d_surv_off.p, s->d_surv_cnt.p, s->d_key_count.p, s->d_tile_pref.p, sl.d_meta.p, sl.d_tested.p, s->stream));
+            if (s->dbg_keep_surv) dbg_log_survivors(s);
             KGWAS_HIP(bind_stop(sl.ev_k1, s->stream, [&] { return launch_rescore_direct(a, s->d_surv_sorted.p, s->d_surv_off.p, s->d_surv_cnt.p, s->row_key_bits, s->d_tile_pref.p, s->stream); }));
         } else {
         KGWAS_HIP(launch_bitmap_keys(s->d_bitmap.p, n_words, n_rows, (uint32_t)s->n_pheno, s->d_bm_blocks.p, s->d_bm_mask.p, s->d_surv_sorted.p, s->key_slots,
                                      s->row_key_bits, s->d_surv_off.p, s->d_surv_cnt.p, s->d_key_count.p, s->d_tile_pref.p, /*nibble_transposed=*/!s->narrow, s->stream));
         s->bitmap_clean = true;
+        if (s->dbg_keep_surv) dbg_log_survivors(s);
         a.so_score = sl.d_so_score.p;
         a.so_kmer = sl.d_so_kmer.p;
         a.so_row = sl.d_so_row.p;

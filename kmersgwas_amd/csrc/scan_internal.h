@@ -568,6 +568,20 @@ struct kgwas_scan {
     // set (block-scaled or int8, whichever was built), [2] narrow filter; [column * S + sample]
     bool dbg_keep_resid = false;
     std::vector<double> dbg_resid[3];
+    // KGWAS_DEBUG_SURVIVORS (test hook): one entry per sparse chunk that went through a filter (submit_sparse, use_coarse), in
+    // submission order: the thresholds its filter launches read (a copy of the array the kernels are given, queued behind the prep
+    // launch - the narrow path raises thresholds there - and before the first filter launch) and its survivors, decoded from the
+    // KEY LIST behind the key launch (d_surv_sorted / d_surv_off / d_surv_cnt: one form for the wide and the narrow path, and
+    // the bitmap-to-keys kernels are part of what is observed). set: coarse_mode, 2 = the narrow filter. A chunk whose key list
+    // overflowed is flagged and has no pairs; its re-run by the exact scorer is not logged.
+    struct DbgChunk {
+        uint64_t first_row = 0, n_rows = 0;
+        uint32_t set = 0, overflow = 0;
+        std::vector<double> thr;       // n_pheno
+        std::vector<uint32_t> pairs;   // (column, row in chunk), in key-list order
+    };
+    bool dbg_keep_surv = false;
+    std::vector<DbgChunk> dbg_chunks;
     // record_history = 2 sessions (the later shards of a cross-shard merge): their columns stay in select mode whatever their
     // ties - such a session is asked for its final minima and for its records above a threshold (kgwas_scan_lowest,
     // kgwas_scan_history_above: both served from the logs), not for result lists
@@ -692,6 +706,7 @@ struct FilterOpts {  // every switch the plan reads (env.h), read once per sessi
     int mxs = 1, mxs_form = 0;     // KGWAS_MXS, KGWAS_MXS_FORM
     bool narrow = true;            // KGWAS_NARROW (0: false)
     bool debug_residuals = false;  // KGWAS_DEBUG_RESIDUALS
+    bool debug_survivors = false;  // KGWAS_DEBUG_SURVIVORS
     // experiments: KGWAS_COARSE_MIXED, KGWAS_COARSE_NOSPLIT (split = false), KGWAS_NARROW_PACK, KGWAS_CAP_MULT (-1: by
     // filter), KGWAS_CAP_BUDGET, KGWAS_MODE_K (pick_coarse_mode)
     bool mixed = true, split = true, narrow_pack = true;
@@ -724,6 +739,7 @@ struct ScanPlan {
     bool coarse = false, narrow = false, narrow_pack1 = false;
     bool use_mx = false;      // the block-scaled family (else int8, perhaps with a block-scaled two-slice set: mixed)
     bool keep_resid = false;  // KGWAS_DEBUG_RESIDUALS on a filter session
+    bool keep_surv = false;   // KGWAS_DEBUG_SURVIVORS on a filter session
     uint32_t n_kgroups = 0;
     uint64_t chunk_max = 0, dense_rows = 0, dense_chunk = 0;
     uint32_t cap = 0;

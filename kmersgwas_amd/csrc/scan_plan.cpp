@@ -16,6 +16,7 @@ FilterOpts read_filter_opts() {
     o.mxs_form = (int)opt_int("KGWAS_MXS_FORM", 0);
     o.narrow = !(opt_int("KGWAS_NARROW", 1) == 0);
     o.debug_residuals = opt_set("KGWAS_DEBUG_RESIDUALS");
+    o.debug_survivors = opt_set("KGWAS_DEBUG_SURVIVORS");
     o.mixed = !(exp_int("KGWAS_COARSE_MIXED", 1) == 0);
     o.split = !exp_set("KGWAS_COARSE_NOSPLIT");
     o.narrow_pack = !(exp_int("KGWAS_NARROW_PACK", 1) == 0);
@@ -369,6 +370,8 @@ ScanPlan plan_scan(const kgwas_scan_params& p, const ScanShape& sh, const Filter
     // test hook (kgwas_scan_debug_residuals): keep every filter form's quantisation residuals, so that a test can build the
     // rows on which the bound |yigi_ref - yc| <= Eg + min(Rall, N1 * rmax) is TIGHT (tests/test_gpu_parity.py, adversarial bound)
     pl.keep_resid = o.debug_residuals;
+    // test hook (kgwas_scan_debug_survivors): log every filtered chunk's thresholds and survivors (scan_gpu.cpp, submit_sparse)
+    pl.keep_surv = o.debug_survivors;
     if (pl.keep_resid)
         for (int f = 0; f < 3; f++) resid[f].assign(P * S, 0.0);
     // One slice halves the matrix work but widens the bound; it is offered when, for every column, the bound

@@ -67,3 +67,17 @@ def synth_rows_numpy(first_row, n_rows, n_acc, seed):
                 acc &= np.uint64((1 << (n_acc & 63)) - 1)
             out[:, w] = acc
     return out
+
+
+def check_topn(scan, oracle_res, n_pheno, check_pushes=True):
+    # no effective add_association lost or invented on the way (ties make this visible). Columns whose lists were made by
+    # selection (no tie among their N + 1 largest scores: kmersgwas_amd/csrc/scan_lazy.cpp) were never replayed and have no push
+    # count; KGWAS_FULL_REPLAY=1 replays every column.
+    if check_pushes and scan.stats()["columns_selected"] == 0:
+        assert scan.stats()["heap_pushes"] == oracle_res["pushes"], (scan.stats()["heap_pushes"], oracle_res["pushes"])
+    for j in range(n_pheno):
+        k, s, r = scan.result(j)
+        o = oracle_res["per_pheno"][j]
+        assert (k == o["kmer"]).all(), "k-mer identities differ for column %d" % j
+        assert (r == o["file_row"]).all(), "row ids differ for column %d" % j
+        assert s.tobytes() == o["score"].tobytes(), "scores differ for column %d" % j

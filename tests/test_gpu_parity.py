@@ -10,25 +10,11 @@ import pytest
 import kmersgwas_amd as kg
 from oracle import binding as ob
 from oracle import oracle_np as onp
-from helpers import random_table, phenotypes, synth_rows_numpy
+from helpers import random_table, phenotypes, synth_rows_numpy, check_topn as _check_topn
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 KERNELS = [kg.KERNEL_VALU, kg.KERNEL_MFMA, kg.KERNEL_COARSE]
-
-
-def _check_topn(scan, oracle_res, n_pheno, check_pushes=True):
-    # no effective add_association lost or invented on the way (ties make this visible). Columns whose lists were made by
-    # selection (no tie among their N + 1 largest scores: kmersgwas_amd/csrc/scan_lazy.cpp) were never replayed and have no push
-    # count; KGWAS_FULL_REPLAY=1 replays every column.
-    if check_pushes and scan.stats()["columns_selected"] == 0:
-        assert scan.stats()["heap_pushes"] == oracle_res["pushes"], (scan.stats()["heap_pushes"], oracle_res["pushes"])
-    for j in range(n_pheno):
-        k, s, r = scan.result(j)
-        o = oracle_res["per_pheno"][j]
-        assert (k == o["kmer"]).all(), "k-mer identities differ for column %d" % j
-        assert (r == o["file_row"]).all(), "row ids differ for column %d" % j
-        assert s.tobytes() == o["score"].tobytes(), "scores differ for column %d" % j
 
 
 @pytest.mark.parametrize("kernel", KERNELS)
