@@ -228,8 +228,9 @@ typedef struct kgwas_scan_stats {
  * Version 7: no struct changed; new entry points kgwas_snpkin_* (emma_kinship).
  * Version 8: no struct changed; new entry points kgwas_kmer_encode, kgwas_filter_kmers, kgwas_filter_kmers_write (filter_kmers).
  * Version 9: no struct changed; new entry point kgwas_build_table (build_kmers_table).
- * Version 10: no struct changed; new entry point kgwas_scan_debug_survivors (test hook). */
-#define KGWAS_ABI_VERSION 10
+ * Version 10: no struct changed; new entry point kgwas_scan_debug_survivors (test hook).
+ * Version 11: no struct changed; new entry point kgwas_list_kmers (list_kmers_found_in_multiple_samples). */
+#define KGWAS_ABI_VERSION 11
 uint32_t kgwas_abi_version(void);
 
 int kgwas_scan_create(const kgwas_scan_params* p, kgwas_scan** out);
@@ -453,6 +454,26 @@ int kgwas_filter_kmers_write(kgwas_table* t, const uint64_t* codes, uint64_t n, 
  * ---------------------------------------------------------------------------------- */
 int kgwas_build_table(const char* all_kmers_path, const char* const* kmer_paths, const char* const* names, uint64_t n,
                       uint32_t kmer_len, int32_t device, const char* out_base, uint64_t* n_rows);
+
+/* ------------------------------------------------------------------------------------
+ * list_kmers_found_in_multiple_samples (src/list_kmers_found_in_multiple_samples.cpp): the k-mers shared by the n accessions'
+ * sorted k-mer files (64-bit little-endian words, length size >> 3; bits 62-63 a strand flag: 1 canonical form only, 2
+ * non-canonical only, 3 both; bits 0-61 the key). Per key window of the reference (5001 of them) and key it counts the words,
+ * count_all, and those with flag 1 and flag 2; a key with count_all >= mac passes when both strand sides, count_canonical +
+ * count_both and count_non_canonical + count_both, are >= ceil(min_strand_percent * count_all) as doubles (any double; NaN passes
+ * nothing). Writes <out_path> (the passing keys, 8 bytes each, ascending within a window, windows in order), <out_path>
+ * .no_pass_kmers (a header, then "k-mer\tall\tcanonical\tnon-canonical\tboth" per key that reached mac and failed),
+ * .shareness, .stats.only_canonical, .stats.only_non_canonical and .stats.both ((n + 1) x (n + 1) counts over all distinct
+ * keys). counts (may be NULL): keys passed, keys that reached mac but failed the strand rule, keys below mac. The counts are
+ * the reference's also for inputs that descend or repeat keys; the counting runs on `device`. The files are
+ * opened in order and the outputs created after all of them: a file of fewer than 8 bytes -> KGWAS_ERR_FORMAT "sorted kmer
+ * file is empty: <path>", one that cannot be opened -> KGWAS_ERR_FORMAT "can't open file: <path>". Three inputs on which the
+ * reference has undefined behaviour are KGWAS_ERR_FORMAT too: n >= 2^20 (refused before any file or the device is touched), a
+ * used word with flag 0 (the message names the file), a key counted more than n times in one window (it names the k-mer).
+ * kmer_len must be within 1..31. Files are opened as they are read, a few at a time: n is not bound by the descriptor limit.
+ * ---------------------------------------------------------------------------------- */
+int kgwas_list_kmers(const char* const* kmer_paths, uint64_t n, uint32_t kmer_len, uint64_t mac, double min_strand_percent,
+                     int32_t device, const char* out_path, uint64_t counts[3]);
 
 /* ------------------------------------------------------------------------------------
  * SNP twin of the scorer: MultipleSNPsDataBases (src/snps_multiple_databases.h:25-63) for associate_snps

@@ -11,10 +11,6 @@
 // single window larger than the piece budget, go through host_piece below: the reference's loop itself, from the same
 // slices. The finished rows of a piece are written by a thread of their own while the next piece is matched. No CPU
 // fallback: without a device the call fails with KGWAS_ERR_DEVICE.
-#include <fcntl.h>
-#include <sys/stat.h>
-#include <unistd.h>
-
 #include <algorithm>
 #include <atomic>
 #include <cerrno>
@@ -27,80 +23,14 @@
 #include "common.h"
 #include "ingest.h"
 #include "kernels.h"
+#include "sorted_file_io.h"
 
 using namespace kgwas;
 
 namespace {
 
-constexpr uint64_t KEY_MASK = 0x3FFFFFFFFFFFFFFFull;  // the top two bits of a word are flags (src/kmers_single_database.cpp:147)
+constexpr uint64_t KEY_MASK = SORTED_KEY_MASK;
 constexpr uint64_t TOTAL_ITER = 5000;                 // src/build_kmers_table.cpp:98; windows 1 .. TOTAL_ITER + 1 are run
-
-struct Fd {
-    int fd = -1;
-    Fd() = default;
-    Fd(const Fd&) = delete;
-    Fd& operator=(const Fd&) = delete;
-    ~Fd() { reset(); }
-    void reset() {
-        if (fd >= 0) ::close(fd);
-        fd = -1;
-    }
-};
-
-void write_all(int fd, const void* data, size_t n, const std::string& path) {
-    const char* d = static_cast<const char*>(data);
-    while (n) {
-        const ssize_t w = ::write(fd, d, n);
-        if (w < 0 && errno == EINTR) continue;
-        if (w <= 0) throw Error(KGWAS_ERR_IO, "write error on " + path + ": " + std::strerror(w < 0 ? errno : EIO));
-        d += w;
-        n -= (size_t)w;
-    }
-}
-
-void open_input(Fd& f, const std::string& path) {
-    f.reset();
-    f.fd = ::open(path.c_str(), O_RDONLY);
-    if (f.fd < 0) throw Error(KGWAS_ERR_FORMAT, "can't open file: " + path);  // (a std::logic_error of the reference)
-}
-
-// words [off, off + cnt) of the file
-void read_words(int fd, uint64_t* dst, uint64_t off, uint64_t cnt, const std::string& path) {
-    char* d = reinterpret_cast<char*>(dst);
-    uint64_t o = off * 8, n = cnt * 8;
-    while (n) {
-        const ssize_t r = ::pread(fd, d, n, (off_t)o);
-        if (r < 0 && errno == EINTR) continue;
-        if (r <= 0) throw Error(KGWAS_ERR_IO, "read error on " + path + (r < 0 ? std::string(": ") + std::strerror(errno) : ": file got shorter"));
-        d += r;
-        o += (uint64_t)r;
-        n -= (uint64_t)r;
-    }
-}
-
-// KmersSingleDataBaseSortedFile::open_file (:109-132): the file's length in words, size >> 3
-uint64_t words_in_file(const std::string& path) {
-    Fd f;
-    open_input(f, path);
-    struct stat sb;
-    if (fstat(f.fd, &sb) != 0) throw Error(KGWAS_ERR_FORMAT, "can't open file: " + path);
-    const uint64_t w = (uint64_t)sb.st_size >> 3;
-    if (w == 0) throw Error(KGWAS_ERR_FORMAT, "sorted kmer file is empty: " + path);
-    return w;
-}
-
-// Index of the first word of h[0, cnt) whose masked value is above thr; cnt when there is none.
-uint64_t first_above(const uint64_t* h, uint64_t cnt, uint64_t thr) {
-    for (uint64_t o = 0; o < cnt; o += 256) {  // (a group at a time without an early exit: the compiler vectorises the test)
-        const uint64_t e = std::min(cnt, o + 256);
-        uint64_t any = 0;
-        for (uint64_t i = o; i < e; i++) any |= (uint64_t)((h[i] & KEY_MASK) > thr);
-        if (any)
-            for (uint64_t i = o; i < e; i++)
-                if ((h[i] & KEY_MASK) > thr) return i;
-    }
-    return cnt;
-}
 
 struct Builder {
     std::string all_path;

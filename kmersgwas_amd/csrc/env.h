@@ -33,6 +33,10 @@
 //   KGWAS_BED_PIECE_ROWS=n     (test hook) table rows per piece of kgwas_table_to_bed (default: up to 2^20, about 256 MiB of rows)
 //   KGWAS_BUILD_PIECE_ROWS=n   (test hook) all-k-mers rows per piece of kgwas_build_table (default: about 256 MiB of rows; a piece is whole key windows)
 //   KGWAS_BUILD_BLOCK_WORDS=n  (test hook) words per read block of an accession's slice in kgwas_build_table (default 65 536)
+//   KGWAS_LIST_PIECE_WORDS=n   (test hook) words per piece of kgwas_list_kmers (default 2^25, 256 MiB; a piece is whole key windows)
+//   KGWAS_LIST_BUCKET_WORDS=n  (test hook) words aimed at per key-range bucket of a piece (default 2048); the LDS table of a bucket
+//                              has twice as many slots, within 64 .. 4096
+//   KGWAS_LIST_BLOCK_WORDS=n   (test hook) words per read block of a file's slice in kgwas_list_kmers (default 65 536)
 //   KGWAS_DEBUG_SLOW_WORKER=w:pct:min_us   (test hook) slows one replay worker down
 //   KGWAS_DEBUG_RESIDUALS=1    (test hook) sessions keep their filters' quantisation residuals (kgwas_scan_debug_residuals)
 //   KGWAS_DEBUG_SURVIVORS=1    (test hook) filter sessions log every filtered chunk's thresholds and survivors, synchronously

@@ -301,6 +301,50 @@ hipError_t launch_bt_match(const uint64_t* A, uint64_t n, const uint64_t* spl, u
                            uint32_t m, uint64_t carry_key, bool has_prev, uint64_t* rows, uint64_t stride, uint64_t accession,
                            uint32_t* descends, hipStream_t st);
 
+// list_kmers_found_in_multiple_samples (list_kernels.hip), on one piece whose raw words lie in `words` as n_seg segments
+// (seg_off / seg_len: one read block of one accession's slice each, non-descending). ll_check looks at one segment as it lands:
+// flags[0] = 1 when it descends (carry_key before word 0 when has_prev), flags[1] = min(file) over words with flag 0 (preset
+// 0xFFFFFFFF). ll_splitters sorts m regularly sampled keys into `sample`; bucket b of nb is the key range [sample[b m / nb],
+// sample[(b + 1) m / nb]). ll_count, one workgroup per bucket, counts the bucket's words per key in an LDS table of `slots`
+// (a power of two <= LL_MAX_SLOTS), applies mac and need[count_all] (the smallest count of a strand side that passes, or
+// LL_NEED_NONE), stages the passing keys and the no-pass records (key, packed counts: all | canonical << 21 | non-canonical
+// << 42) at bk_base[b] and adds the distinct keys to stats: the three (N + 1)^2 matrices (canonical, non-canonical, both), the
+// N + 1 shareness counts, TESTED_SHARDS counters of keys below mac. flags[2] = 1: a table filled (nothing of that bucket is
+// written), flags[3] = 1: a key counted more than N times (*err_key = the smallest, preset to all ones). bk_* have nb + 1
+// entries and are zeroed by the caller. ll_gather scans bk_pass / bk_np into off_pass / off_np (entry nb = the totals) and
+// copies the staged records to the contiguous outputs; ll_commit adds a piece's stats to the run's and zeroes them.
+constexpr uint32_t LL_MAX_SLOTS = 4096;
+constexpr uint32_t LL_NEED_NONE = 0xFFFFFFFFu;
+struct ListArgs {
+    const uint64_t* words;
+    const uint32_t* seg_off;
+    const uint32_t* seg_len;
+    uint32_t n_seg;
+    const uint64_t* sample;
+    uint32_t m, nb, slots;
+    uint64_t N, mac;
+    const uint32_t* need;  // [N + 1]
+    uint64_t* stage_pass;  // [words in the piece], as stage_np_key and stage_np_cnt
+    uint64_t* stage_np_key;
+    uint64_t* stage_np_cnt;
+    uint32_t* bk_base;  // [nb + 1], as bk_pass and bk_np
+    uint32_t* bk_pass;
+    uint32_t* bk_np;
+    unsigned long long* stats;  // [3 (N + 1)^2 + (N + 1) + TESTED_SHARDS]
+    uint32_t* flags;            // [4]
+    unsigned long long* err_key;
+};
+hipError_t launch_ll_check(const uint64_t* words, uint32_t m, uint64_t carry_key, bool has_prev, uint32_t file, uint32_t* flags,
+                           hipStream_t st);
+size_t ll_temp_bytes(uint32_t max_sample, uint32_t max_buckets);  // temp storage of ll_splitters and ll_gather (0: the query failed)
+hipError_t launch_ll_splitters(const uint64_t* words, uint64_t total, uint32_t m, uint64_t* sample_raw, uint64_t* sample, void* temp,
+                               size_t temp_bytes, hipStream_t st);
+size_t ll_count_lds_bytes(uint32_t slots);
+hipError_t launch_ll_count(const ListArgs& a, hipStream_t st);
+hipError_t launch_ll_gather(const ListArgs& a, uint32_t* off_pass, uint32_t* off_np, uint64_t* out_pass, uint64_t* out_np_key,
+                            uint64_t* out_np_cnt, void* temp, size_t temp_bytes, hipStream_t st);
+hipError_t launch_ll_commit(unsigned long long* total, unsigned long long* piece, uint64_t n, hipStream_t st);
+
 // Squeeze: out[r][2*W_m dwords] bit i = file bit colmap[i] (colmap[i] == 0xFFFFFFFF -> 0). A block stages 64 file rows
 // and 64 squeezed rows in LDS: it exists while W_f + W_m <= SQUEEZE_MAX_WORDS (all of the table phenotyped: up to 10 176
 // accessions; any subset or order: up to 20 288 accessions in the table). check_squeeze_fits throws KGWAS_ERR_ARG beyond.

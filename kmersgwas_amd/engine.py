@@ -612,6 +612,18 @@ def build_kmers_table(all_kmers_path: str, kmer_paths: Sequence[str], names: Seq
     return m.value
 
 
+def list_kmers_found_in_multiple_samples(kmer_paths: Sequence[str], kmer_len: int, mac: int, min_strand_percent: float, out_path: str,
+                                         device: int = 0) -> tuple[int, int, int]:
+    """list_kmers_found_in_multiple_samples (src/list_kmers_found_in_multiple_samples.cpp) on the GPU: from the accessions' sorted
+    k-mer files (64-bit words, the top two bits a strand flag) writes out_path (the keys found in at least `mac` files and on both
+    strands in at least min_strand_percent of them) and out_path.no_pass_kmers / .shareness / .stats.*. Returns the numbers of keys
+    that passed, that reached mac but failed the strand rule, and that stayed below mac."""
+    paths = (C.c_char_p * len(kmer_paths))(*[os.fsencode(p) for p in kmer_paths])
+    counts = (C.c_uint64 * 3)()
+    check(lib.kgwas_list_kmers(paths, len(kmer_paths), kmer_len, mac, float(min_strand_percent), device, os.fsencode(out_path), counts))
+    return counts[0], counts[1], counts[2]
+
+
 class SnpsDataBase:
     """MultipleSNPsDataBases (src/snps_multiple_databases.h:25-63): a PLINK bed/bim/fam trio restricted to the
     phenotyped samples (phenotype order); scoring runs on the GPU."""
