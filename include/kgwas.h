@@ -229,8 +229,9 @@ typedef struct kgwas_scan_stats {
  * Version 8: no struct changed; new entry points kgwas_kmer_encode, kgwas_filter_kmers, kgwas_filter_kmers_write (filter_kmers).
  * Version 9: no struct changed; new entry point kgwas_build_table (build_kmers_table).
  * Version 10: no struct changed; new entry point kgwas_scan_debug_survivors (test hook).
- * Version 11: no struct changed; new entry point kgwas_list_kmers (list_kmers_found_in_multiple_samples). */
-#define KGWAS_ABI_VERSION 11
+ * Version 11: no struct changed; new entry point kgwas_list_kmers (list_kmers_found_in_multiple_samples).
+ * Version 12: no struct changed; new entry points kgwas_count_kmers_files, kgwas_count_kmers_bases (count_kmers_with_strand). */
+#define KGWAS_ABI_VERSION 12
 uint32_t kgwas_abi_version(void);
 
 int kgwas_scan_create(const kgwas_scan_params* p, kgwas_scan** out);
@@ -474,6 +475,38 @@ int kgwas_build_table(const char* all_kmers_path, const char* const* kmer_paths,
  * ---------------------------------------------------------------------------------- */
 int kgwas_list_kmers(const char* const* kmer_paths, uint64_t n, uint32_t kmer_len, uint64_t mac, double min_strand_percent,
                      int32_t device, const char* out_path, uint64_t counts[3]);
+
+/* ------------------------------------------------------------------------------------
+ * count_kmers_with_strand: an accession's sorted k-mer file from its reads. A tool of this project, not a drop-in: it stands
+ * where the reference pipeline runs `kmc -ci<T>`, `kmc -ci0 -b` and kmers_add_strand_information (src/
+ * kmers_add_strand_information.cpp:32-38,119-145; a KMC database reader, not built here), and its output format, flag rule,
+ * sort order and summary numbers are that tool's. The rules:
+ * A window is kmer_len consecutive bytes of one read, all of them A, C, G, T in either case; a window with any other byte is
+ * skipped, and no window spans two reads or files. Its code a is kgwas_kmer_encode's (A=0, C=1, G=2, T=3, first base most
+ * significant), b the code of its reverse complement. If a < b the window's key is a and its flag 0x4000000000000000 (seen in
+ * canonical form), otherwise the key is b and the flag 0x8000000000000000 (a palindrome, a == b, gets this one, as
+ * is_canonized_kmer_representation_flag gives it). count(key) is the number of windows with that key over all reads, flags(key)
+ * the OR of their flags. A key is kept iff ci <= count <= cx. <out_path> holds key | flags of the kept keys, 8 bytes
+ * little-endian, ascending by key; a run that keeps nothing writes an empty file. counts (may be NULL): [0] kept keys, [1]
+ * distinct oriented k-mers (distinct a), [2] distinct oriented k-mers whose key is kept, [3..6] kept keys with flag 0, 1, 2, 3
+ * ([3] is always 0), [7] all counted windows. These are what the three reference commands give for the same reads if KMC
+ * counts by these rules: by construction, not checked against a KMC run.
+ * kgwas_count_kmers_files: n FASTA or FASTQ files, plain text, "-" standard input; the format is decided per file from its first
+ * byte, '>' FASTA, '@' FASTQ, an empty file has no reads, anything else -> KGWAS_ERR_FORMAT "<path>: neither FASTA nor FASTQ".
+ * FASTQ is four lines per record ('@...', sequence, '+...', quality - which may begin with '@'); a last record with fewer than
+ * four lines, or a record without '@' / '+' at the head of its first / third line, -> KGWAS_ERR_FORMAT naming the file. In
+ * FASTA a read is the concatenation of the lines up to the next line that begins with '>'. A trailing '\r' is dropped from
+ * every line; a missing final newline is fine. A file that cannot be opened -> KGWAS_ERR_IO "can't open file: <path>".
+ * kgwas_count_kmers_bases: the reads as one byte stream in which every byte other than A, C, G, T (either case) separates
+ * reads; host memory, or device memory of `device` when on_device is not 0.
+ * Both: kmer_len within 1..31, ci > cx -> KGWAS_ERR_ARG, no HIP device -> KGWAS_ERR_DEVICE. All inputs are opened and their
+ * format byte checked before <out_path> is created. The bases stay resident on the device and are counted in key-range passes;
+ * an input whose bases do not fit beside one pass's buffers -> KGWAS_ERR_ARG with both sizes.
+ * ---------------------------------------------------------------------------------- */
+int kgwas_count_kmers_files(const char* const* paths, uint64_t n, uint32_t kmer_len, uint64_t ci, uint64_t cx, int32_t device,
+                            const char* out_path, uint64_t counts[8]);
+int kgwas_count_kmers_bases(const void* bases, uint64_t n_bytes, int on_device, uint32_t kmer_len, uint64_t ci, uint64_t cx,
+                            int32_t device, const char* out_path, uint64_t counts[8]);
 
 /* ------------------------------------------------------------------------------------
  * SNP twin of the scorer: MultipleSNPsDataBases (src/snps_multiple_databases.h:25-63) for associate_snps

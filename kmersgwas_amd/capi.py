@@ -38,6 +38,7 @@ SYMBOLS = [
     "kgwas_kinship_from_partials", "kgwas_kinship_get_stats", "kgwas_kinship_destroy", "kgwas_kinship_format",
     "kgwas_write_plink", "kgwas_write_plink_many", "kgwas_table_to_bed",
     "kgwas_kmer_encode", "kgwas_filter_kmers", "kgwas_filter_kmers_write", "kgwas_build_table", "kgwas_list_kmers",
+    "kgwas_count_kmers_files", "kgwas_count_kmers_bases",
     "kgwas_snps_open", "kgwas_snps_info", "kgwas_snps_scores", "kgwas_snps_best", "kgwas_snps_write", "kgwas_snps_close",
     "kgwas_snpkin_open", "kgwas_snpkin_info", "kgwas_snpkin_feed_bed", "kgwas_snpkin_feed_file", "kgwas_snpkin_sums",
     "kgwas_snpkin_matrix", "kgwas_snpkin_format", "kgwas_snpkin_close",
@@ -141,7 +142,7 @@ lib.kgwas_version.restype = C.c_int
 lib.kgwas_device_count.argtypes = [C.POINTER(C.c_int)]
 lib.kgwas_abi_version.argtypes = []
 lib.kgwas_abi_version.restype = C.c_uint32
-ABI_VERSION = 11  # KGWAS_ABI_VERSION of include/kgwas.h this mirror was written against
+ABI_VERSION = 12  # KGWAS_ABI_VERSION of include/kgwas.h this mirror was written against
 if lib.kgwas_abi_version() != ABI_VERSION:
     raise ImportError("libkgwas.so speaks ABI version %d, kmersgwas_amd/capi.py %d: rebuild (make -C kmersgwas_amd/csrc)" % (lib.kgwas_abi_version(), ABI_VERSION))
 lib.kgwas_host_cpu_quota.argtypes = []
@@ -246,6 +247,8 @@ lib.kgwas_filter_kmers.argtypes = [_vp, _vp, _u64, _i32, _vp, _vp, _pu64]
 lib.kgwas_filter_kmers_write.argtypes = [_vp, _vp, _u64, _i32, C.c_char_p, _pu64]
 lib.kgwas_build_table.argtypes = [C.c_char_p, _pstr, _pstr, _u64, _u32, _i32, C.c_char_p, _pu64]
 lib.kgwas_list_kmers.argtypes = [_pstr, _u64, _u32, _u64, C.c_double, _i32, C.c_char_p, _pu64]
+lib.kgwas_count_kmers_files.argtypes = [_pstr, _u64, _u32, _u64, _u64, _i32, C.c_char_p, _pu64]
+lib.kgwas_count_kmers_bases.argtypes = [_vp, _u64, C.c_int, _u32, _u64, _u64, _i32, C.c_char_p, _pu64]
 lib.kgwas_synth_rows_device.argtypes = [_vp, _u64, _u64, _u64, _u64, _vp]
 lib.kgwas_synth_rows_host.argtypes = [_vp, _u64, _u64, _u64, _u64]
 

@@ -37,6 +37,11 @@
 //   KGWAS_LIST_BUCKET_WORDS=n  (test hook) words aimed at per key-range bucket of a piece (default 2048); the LDS table of a bucket
 //                              has twice as many slots, within 64 .. 4096
 //   KGWAS_LIST_BLOCK_WORDS=n   (test hook) words per read block of a file's slice in kgwas_list_kmers (default 65 536)
+//   KGWAS_COUNT_PASS_WORDS=n   (test hook) sort words per key-range pass of kgwas_count_kmers_* (default: from the bases and the free
+//                              device memory, at most 2^30)
+//   KGWAS_COUNT_PIECE_BYTES=n  (test hook) bytes per pinned upload piece of kgwas_count_kmers_* (default 8 MiB); when set, a file is
+//                              read in blocks of 8 pieces by at most 3 threads and a device segment of the base stream holds 64 pieces
+//   KGWAS_COUNT_PARSE_ONLY=1   kgwas_count_kmers_files stops behind the parse and the upload (the tool's timing mode: no output file)
 //   KGWAS_DEBUG_SLOW_WORKER=w:pct:min_us   (test hook) slows one replay worker down
 //   KGWAS_DEBUG_RESIDUALS=1    (test hook) sessions keep their filters' quantisation residuals (kgwas_scan_debug_residuals)
 //   KGWAS_DEBUG_SURVIVORS=1    (test hook) filter sessions log every filtered chunk's thresholds and survivors, synchronously

@@ -345,6 +345,30 @@ hipError_t launch_ll_gather(const ListArgs& a, uint32_t* off_pass, uint32_t* off
                             uint64_t* out_np_cnt, void* temp, size_t temp_bytes, hipStream_t st);
 hipError_t launch_ll_commit(unsigned long long* total, unsigned long long* piece, uint64_t n, hipStream_t st);
 
+// count_kmers_with_strand (count_kernels.hip), on a base stream resident on the device: bytes, A C G T in either case are bases
+// and every other byte separates reads. ck_encode appends the sort words (key << 1) | orient (orient 0: the window is its own
+// canonical form) of the windows of kmer_len bases whose canonical key lies in [lo, hi) to words[0, cap), claiming room from
+// ctr[0]; ctr[1] counts the orient-1 words among them (both zeroed by the caller). A claim that ends above cap writes nothing:
+// ctr[0] > cap afterwards means the pass did not fit, and ctr still holds the true counts. ck_sample writes the canonical keys
+// of m regularly spaced windows (all ones where the window is not counted), ck_sort_sample sorts them on all 64 bits. ck_sort
+// sorts a pass's n <= CK_MAX_PASS_WORDS words on bits [0, 2 kmer_len + 1). ck_heads writes the positions of the run heads (a
+// word whose key differs from its predecessor's) to heads, off[ceil(n / 2048)] = their number; ck_reduce turns run r into its
+// count and flags (0x4000... an orient-0 word, 0x8000... an orient-1 word), keeps it iff ci <= count <= cx, writes the kept
+// key | flags in order to out (which may be `sorted`; res may not), off[ceil(n_runs / 2048)] = their number, and adds to
+// counts[0..6] as kgwas_count_kmers_* documents them. blk and off have ck_blocks(max words of a pass) entries.
+constexpr uint64_t CK_MAX_PASS_WORDS = 1ull << 30;
+uint32_t ck_blocks(uint64_t max_words);
+size_t ck_temp_bytes(uint64_t max_words, uint32_t max_sample, uint32_t kmer_len);  // temp storage of the sorts and scans (0: the query failed)
+hipError_t launch_ck_encode(const uint8_t* bases, uint64_t n, uint32_t kmer_len, uint64_t lo, uint64_t hi, uint64_t* words, uint64_t cap,
+                            unsigned long long* ctr, hipStream_t st);
+hipError_t launch_ck_sample(const uint8_t* bases, uint64_t n, uint32_t kmer_len, uint32_t m, uint64_t* sample, hipStream_t st);
+hipError_t launch_ck_sort_sample(const uint64_t* raw, uint64_t* sorted, uint32_t m, void* temp, size_t temp_bytes, hipStream_t st);
+hipError_t launch_ck_sort(const uint64_t* words, uint64_t* sorted, uint64_t n, uint32_t kmer_len, void* temp, size_t temp_bytes, hipStream_t st);
+hipError_t launch_ck_heads(const uint64_t* sorted, uint64_t n, uint32_t* blk, uint32_t* off, uint32_t* heads, void* temp, size_t temp_bytes,
+                           hipStream_t st);
+hipError_t launch_ck_reduce(const uint64_t* sorted, uint64_t n, const uint32_t* heads, uint32_t n_runs, uint64_t ci, uint64_t cx, uint64_t* res,
+                            uint32_t* blk, uint32_t* off, uint64_t* out, unsigned long long* counts, void* temp, size_t temp_bytes, hipStream_t st);
+
 // Squeeze: out[r][2*W_m dwords] bit i = file bit colmap[i] (colmap[i] == 0xFFFFFFFF -> 0). A block stages 64 file rows
 // and 64 squeezed rows in LDS: it exists while W_f + W_m <= SQUEEZE_MAX_WORDS (all of the table phenotyped: up to 10 176
 // accessions; any subset or order: up to 20 288 accessions in the table). check_squeeze_fits throws KGWAS_ERR_ARG beyond.

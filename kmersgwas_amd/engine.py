@@ -624,6 +624,39 @@ def list_kmers_found_in_multiple_samples(kmer_paths: Sequence[str], kmer_len: in
     return counts[0], counts[1], counts[2]
 
 
+def count_kmers(reads, kmer_len: int, ci: int, cx: int, out_path: str, device: int = 0) -> tuple[int, ...]:
+    """count_kmers_with_strand on the GPU: writes the accession's sorted k-mer file out_path (key | strand flags of the canonical
+    k-mers counted ci..cx times, ascending) from its reads and returns the eight counters of kgwas_count_kmers_files (kept keys,
+    distinct oriented k-mers, those whose key is kept, kept keys by flag 0..3, counted windows). `reads` is a path or a sequence of
+    paths of FASTA / FASTQ files ("-": standard input), or the bases themselves - bytes, a uint8 NumPy array, or a uint8 torch
+    tensor on the host or on `device` - as one stream in which every byte other than A, C, G, T separates reads."""
+    counts = (C.c_uint64 * 8)()
+    out = os.fsencode(out_path)
+    if isinstance(reads, (str, os.PathLike)):
+        reads = [reads]
+    if isinstance(reads, (list, tuple)):
+        paths = (C.c_char_p * len(reads))(*[os.fsencode(p) for p in reads])
+        check(lib.kgwas_count_kmers_files(paths, len(reads), kmer_len, ci, cx, device, out, counts))
+    elif isinstance(reads, (bytes, bytearray, memoryview, np.ndarray)):
+        a = np.ascontiguousarray(np.frombuffer(reads, np.uint8) if not isinstance(reads, np.ndarray) else reads)
+        if a.dtype != np.uint8:
+            raise TypeError("count_kmers: the bases must be uint8")
+        check(lib.kgwas_count_kmers_bases(ptr(a), a.size, 0, kmer_len, ci, cx, device, out, counts))
+    elif hasattr(reads, "data_ptr"):  # a torch tensor
+        import torch
+        if reads.dtype != torch.uint8:
+            raise TypeError("count_kmers: the bases must be uint8")
+        t = reads.contiguous()
+        if t.is_cuda:
+            if t.device.index != device:
+                raise ValueError("count_kmers: the tensor is on device %s, the count runs on device %d" % (t.device.index, device))
+            torch.cuda.synchronize(t.device)
+        check(lib.kgwas_count_kmers_bases(C.c_void_p(t.data_ptr()), t.numel(), 1 if t.is_cuda else 0, kmer_len, ci, cx, device, out, counts))
+    else:
+        raise TypeError("count_kmers: paths, bytes, a uint8 array or a uint8 tensor, not %s" % type(reads).__name__)
+    return tuple(counts)
+
+
 class SnpsDataBase:
     """MultipleSNPsDataBases (src/snps_multiple_databases.h:25-63): a PLINK bed/bim/fam trio restricted to the
     phenotyped samples (phenotype order); scoring runs on the GPU."""
