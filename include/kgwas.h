@@ -230,8 +230,9 @@ typedef struct kgwas_scan_stats {
  * Version 9: no struct changed; new entry point kgwas_build_table (build_kmers_table).
  * Version 10: no struct changed; new entry point kgwas_scan_debug_survivors (test hook).
  * Version 11: no struct changed; new entry point kgwas_list_kmers (list_kmers_found_in_multiple_samples).
- * Version 12: no struct changed; new entry points kgwas_count_kmers_files, kgwas_count_kmers_bases (count_kmers_with_strand). */
-#define KGWAS_ABI_VERSION 12
+ * Version 12: no struct changed; new entry points kgwas_count_kmers_files, kgwas_count_kmers_bases (count_kmers_with_strand).
+ * Version 13: no struct changed; new struct kgwas_lmm_stats and entry points kgwas_sym_eigen, kgwas_lmm_* (lmm_lrt). */
+#define KGWAS_ABI_VERSION 13
 uint32_t kgwas_abi_version(void);
 
 int kgwas_scan_create(const kgwas_scan_params* p, kgwas_scan** out);
@@ -551,6 +552,58 @@ int kgwas_snpkin_sums(kgwas_snpkin* h, double* lower, uint64_t* n_used);
 int kgwas_snpkin_matrix(kgwas_snpkin* h, double* K, uint64_t* n_used);
 uint64_t kgwas_snpkin_format(uint64_t n_samples, const double* K, char* out, uint64_t cap);
 void kgwas_snpkin_close(kgwas_snpkin* h);
+
+/* ------------------------------------------------------------------------------------
+ * lmm_lrt: the mixed-model likelihood-ratio test of the best k-mers (or SNPs). A tool of this project, not a drop-in: it
+ * stands where the pipeline starts `gemma -bfile B -lmm 2 -k pheno.kinship -outdir D -o NAME -maf f -miss 0.5` once per
+ * phenotype column (kmers_gwas.py:150-165) and reads the p_lrt column of the results (functions.py:93-112). The statistic is
+ * the ML likelihood-ratio test of y = W a + x b + u + e, u ~ N(0, lambda K / tau), e ~ N(0, I / tau), W = 1; the reference tree
+ * ships an independent formulation of it in src/R/emma.R:495-616 (emma.ML.LRT, emma.MLE, emma.eigen.R.wo.Z,
+ * emma.delta.ML.LL.wo.Z), which the tests restate. DESIGN.md 4.12 has the formulas and the fixed maximisation procedure.
+ * Added in ABI version 13.
+ * sym_eigen: K (n x n, row-major; its symmetric part is used) = U diag(d) U^T, d ascending, U row-major with eigenvector c in
+ *            column c. Householder tridiagonalisation and implicit QL on `threads` host threads (0: the CPUs this process may
+ *            use); the result does not depend on `threads`. Needs no GPU.
+ * create   : eigendecomposes K, sets |d_i| < 1e-8 to 0 and refuses a d_i < -1e-8 with KGWAS_ERR_FORMAT "Kinship matrix is not
+ *            positive semi-definite" (transform_and_permute_phenotypes.R:54), all before the device is touched; then the session
+ *            on `device`. lambda is searched in [lmin, lmax] (GEMMA's defaults: 1e-5, 1e5). chunk_variants (0: 10240, rounded up
+ *            to 32) variants are on the device at a time. n within 3..65535.
+ * null     : the null model's maximised log-likelihood and its lambda for phenotype y[n] (finite, not constant).
+ * test_bed : n_variants variants of a SNP-major .bed body (file layout without the 3 magic bytes, (n + 3) / 4 bytes each, the
+ *            handle's individuals in order). Code 00 -> 2, 10 -> 1, 11 -> 0, 01 (missing) -> the mean of the others; af = mean /
+ *            2, n_miss = number of 01 codes. A variant is not tested when min(af, 1 - af) < maf, when n_miss / n > miss or when
+ *            it is constant: tested = 0 and lrt, lambda, p are NaN. Otherwise lrt = max(0, 2 (l1 - l0)), lambda the H1 maximiser
+ *            and p = erfc(sqrt(lrt / 2)). Outputs are host arrays of n_variants entries; any may be NULL. A variant's numbers
+ *            are bit-identical from run to run, in any order and for any chunk_variants.
+ * run_files: the lmm_lrt tool's file layer. kinship_path: a text matrix, one row per .fam line (a different number of rows or
+ *            columns -> KGWAS_ERR_FORMAT); per bed i, <bfile_bases[i]>.bed/.bim/.fam in and out_paths[i] out (chr rs ps n_miss
+ *            allele1 allele0 af l_mle p_lrt, tab-separated, tested variants in .bim order) plus a log beside it (".assoc.txt"
+ *            replaced by ".log.txt"). The phenotype is field 5 + pheno_col of the .fam; individuals with "-9" or "NA" are
+ *            dropped from K, y and the .bed. Consecutive beds that keep the same individuals share one eigendecomposition.
+ *            total (may be NULL): the run's summed stats.
+ * read_kinship / read_fam / format_assoc: the parsers and the line formatter of run_files (no GPU). read_fam gives every line's
+ *            value (NaN when missing) and keep flag, up to cap entries, and the number of lines. format_assoc returns the bytes
+ *            needed and writes them if cap allows; chr == NULL gives the header line.
+ * ---------------------------------------------------------------------------------- */
+typedef struct kgwas_lmm kgwas_lmm;
+typedef struct kgwas_lmm_stats {
+    double eigen_ms, rotate_ms, grid_ms, refine_ms; /* host eigendecomposition; kernels: prep + rotate, grid sums, refine */
+    uint64_t variants_read, variants_tested, chunks, eigendecompositions, n_individuals;
+} kgwas_lmm_stats;
+int kgwas_sym_eigen(uint64_t n, const double* K, double* d, double* U, uint32_t threads);
+int kgwas_lmm_create(uint64_t n, const double* K, int32_t device, double lmin, double lmax, uint64_t chunk_variants, kgwas_lmm** out);
+int kgwas_lmm_null(kgwas_lmm* h, const double* y, double* logl0, double* lambda0);
+int kgwas_lmm_test_bed(kgwas_lmm* h, const double* y, const uint8_t* bed_body, uint64_t n_variants, double maf, double miss, double* lrt,
+                       double* lambda, double* p, double* af, uint32_t* n_miss, uint8_t* tested);
+int kgwas_lmm_run_files(const char* kinship_path, uint64_t n_beds, const char* const* bfile_bases, const char* const* out_paths,
+                        uint32_t pheno_col, double maf, double miss, double lmin, double lmax, uint64_t chunk_variants, int32_t device,
+                        kgwas_lmm_stats* total);
+int kgwas_lmm_get_stats(const kgwas_lmm* h, kgwas_lmm_stats* out);
+void kgwas_lmm_destroy(kgwas_lmm* h);
+int kgwas_lmm_read_kinship(const char* path, uint64_t n_expected, double* K);
+int kgwas_lmm_read_fam(const char* path, uint32_t pheno_col, uint64_t cap, double* values, uint8_t* keep, uint64_t* n_lines);
+uint64_t kgwas_lmm_format_assoc(const char* chr, const char* rs, const char* ps, uint32_t n_miss, const char* allele1, const char* allele0,
+                                double af, double l_mle, double p_lrt, char* out, uint64_t cap);
 
 /* ------------------------------------------------------------------------------------
  * Seeded synthetic table rows: kmer = row + 1, per-row frequency q/256 with

@@ -42,6 +42,8 @@ SYMBOLS = [
     "kgwas_snps_open", "kgwas_snps_info", "kgwas_snps_scores", "kgwas_snps_best", "kgwas_snps_write", "kgwas_snps_close",
     "kgwas_snpkin_open", "kgwas_snpkin_info", "kgwas_snpkin_feed_bed", "kgwas_snpkin_feed_file", "kgwas_snpkin_sums",
     "kgwas_snpkin_matrix", "kgwas_snpkin_format", "kgwas_snpkin_close",
+    "kgwas_sym_eigen", "kgwas_lmm_create", "kgwas_lmm_null", "kgwas_lmm_test_bed", "kgwas_lmm_run_files", "kgwas_lmm_get_stats",
+    "kgwas_lmm_destroy", "kgwas_lmm_read_kinship", "kgwas_lmm_read_fam", "kgwas_lmm_format_assoc",
     "kgwas_synth_rows_device", "kgwas_synth_rows_host",
 ]
 
@@ -94,6 +96,17 @@ class ScanStats(C.Structure):
         return d
 
 
+class LmmStats(C.Structure):
+    _fields_ = [
+        ("eigen_ms", C.c_double), ("rotate_ms", C.c_double), ("grid_ms", C.c_double), ("refine_ms", C.c_double),
+        ("variants_read", C.c_uint64), ("variants_tested", C.c_uint64), ("chunks", C.c_uint64),
+        ("eigendecompositions", C.c_uint64), ("n_individuals", C.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 if not os.path.exists(LIB_PATH):
     raise ImportError(
         "libkgwas.so not found at %s — build it with `make -C kmersgwas_amd/csrc` "
@@ -142,7 +155,7 @@ lib.kgwas_version.restype = C.c_int
 lib.kgwas_device_count.argtypes = [C.POINTER(C.c_int)]
 lib.kgwas_abi_version.argtypes = []
 lib.kgwas_abi_version.restype = C.c_uint32
-ABI_VERSION = 12  # KGWAS_ABI_VERSION of include/kgwas.h this mirror was written against
+ABI_VERSION = 13  # KGWAS_ABI_VERSION of include/kgwas.h this mirror was written against
 if lib.kgwas_abi_version() != ABI_VERSION:
     raise ImportError("libkgwas.so speaks ABI version %d, kmersgwas_amd/capi.py %d: rebuild (make -C kmersgwas_amd/csrc)" % (lib.kgwas_abi_version(), ABI_VERSION))
 lib.kgwas_host_cpu_quota.argtypes = []
@@ -249,6 +262,18 @@ lib.kgwas_build_table.argtypes = [C.c_char_p, _pstr, _pstr, _u64, _u32, _i32, C.
 lib.kgwas_list_kmers.argtypes = [_pstr, _u64, _u32, _u64, C.c_double, _i32, C.c_char_p, _pu64]
 lib.kgwas_count_kmers_files.argtypes = [_pstr, _u64, _u32, _u64, _u64, _i32, C.c_char_p, _pu64]
 lib.kgwas_count_kmers_bases.argtypes = [_vp, _u64, C.c_int, _u32, _u64, _u64, _i32, C.c_char_p, _pu64]
+lib.kgwas_sym_eigen.argtypes = [_u64, _vp, _vp, _vp, _u32]
+lib.kgwas_lmm_create.argtypes = [_u64, _vp, _i32, _dbl, _dbl, _u64, _pp]
+lib.kgwas_lmm_null.argtypes = [_vp, _vp, _pdbl, _pdbl]
+lib.kgwas_lmm_test_bed.argtypes = [_vp, _vp, _vp, _u64, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp]
+lib.kgwas_lmm_run_files.argtypes = [C.c_char_p, _u64, _pstr, _pstr, _u32, _dbl, _dbl, _dbl, _dbl, _u64, _i32, C.POINTER(LmmStats)]
+lib.kgwas_lmm_get_stats.argtypes = [_vp, C.POINTER(LmmStats)]
+lib.kgwas_lmm_destroy.argtypes = [_vp]
+lib.kgwas_lmm_destroy.restype = None
+lib.kgwas_lmm_read_kinship.argtypes = [C.c_char_p, _u64, _vp]
+lib.kgwas_lmm_read_fam.argtypes = [C.c_char_p, _u32, _u64, _vp, _vp, _pu64]
+lib.kgwas_lmm_format_assoc.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, _u32, C.c_char_p, C.c_char_p, _dbl, _dbl, _dbl, C.c_char_p, _u64]
+lib.kgwas_lmm_format_assoc.restype = _u64
 lib.kgwas_synth_rows_device.argtypes = [_vp, _u64, _u64, _u64, _u64, _vp]
 lib.kgwas_synth_rows_host.argtypes = [_vp, _u64, _u64, _u64, _u64]
 

@@ -1,0 +1,128 @@
+// lmm_lrt — the mixed-model likelihood-ratio test of the variants of PLINK files, on GPU 0 (kgwas_lmm_*). A tool of this
+// project that takes the GEMMA command line the pipeline issues (kmers_gwas.py:150-165),
+//     lmm_lrt -bfile B -lmm 2 -k KINSHIP -outdir D -o NAME [-n i] [-maf f] [-miss f] [-lmin x] [-lmax x]
+// and writes D/NAME.assoc.txt (chr rs ps n_miss allele1 allele0 af l_mle p_lrt; p_lrt is field 9, which functions.py reads)
+// and D/NAME.log.txt. Its own addition: --bfiles LIST, a file of "bfile<TAB>name" lines that all run against one
+// eigendecomposition of the kinship matrix. Defaults of -maf, -miss, -lmin, -lmax and -outdir are GEMMA's.
+#include <sys/stat.h>
+
+#include <cstdlib>
+#include <fstream>
+#include <iostream>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "../../include/kgwas.h"
+#include "cli_args.h"
+
+using namespace std;
+
+static void usage(const char* prog) {
+    cerr << "usage: " << prog
+         << " -bfile B | --bfiles LIST  -lmm 2  -k KINSHIP  [-outdir D] [-o NAME] [-n i] [-maf f] [-miss f] [-lmin x] [-lmax x]\n"
+            "  -bfile B       PLINK base name (B.bed, B.bim, B.fam)\n"
+            "  --bfiles LIST  file of 'bfile<TAB>name' lines: every bfile is tested, output D/name.assoc.txt\n"
+            "  -lmm 2         the likelihood-ratio test (the only test built)\n"
+            "  -k FILE        kinship matrix, text, one row per .fam line\n"
+            "  -outdir D      output directory (default ./output), -o NAME output prefix (default result)\n"
+            "  -n i           phenotype column of the .fam, from 1 (default 1)\n"
+            "  -maf f         minor allele frequency filter (default 0.01), -miss f missingness filter (default 0.05)\n"
+            "  -lmin x, -lmax x  search range of lambda (defaults 1e-5, 1e5)\n";
+}
+
+static double num(const string& name, const string& s) {
+    try {
+        size_t pos = 0;
+        const double v = stod(s, &pos);
+        if (pos != s.size()) throw invalid_argument("");
+        return v;
+    } catch (const exception&) {
+        cerr << "lmm_lrt: argument '" << s << "' of " << name << " failed to parse" << endl;
+        exit(1);
+    }
+}
+
+int main(int argc, char* argv[]) {
+    static const char* const valued[] = {"bfile", "bfiles", "lmm", "k", "outdir", "o", "n", "maf", "miss", "lmin", "lmax", "chunk_variants"};
+    map<string, string> a;
+    for (int i = 1; i < argc; i++) {
+        string s = argv[i];
+        if (s == "-h" || s == "--help" || s == "-help") {
+            usage(argv[0]);
+            return 0;
+        }
+        const size_t dashes = s.rfind("--", 0) == 0 ? 2 : s.rfind("-", 0) == 0 ? 1 : 0;
+        const string name = s.substr(dashes);
+        bool known = false;
+        for (const char* v : valued) known |= name == v;
+        if (!dashes || !known) {
+            cerr << "lmm_lrt: unknown option '" << s << "'" << endl;
+            usage(argv[0]);
+            return 1;
+        }
+        if (i + 1 >= argc) {
+            cerr << "lmm_lrt: option '" << s << "' is missing an argument" << endl;
+            return 1;
+        }
+        a[name] = argv[++i];
+    }
+    if (!a.count("lmm") || a["lmm"] != "2") {
+        cerr << "lmm_lrt: -lmm " << (a.count("lmm") ? a["lmm"] : string("(missing)"))
+             << ": only -lmm 2, the likelihood-ratio test, is built (no Wald or score test)" << endl;
+        return 1;
+    }
+    if (!a.count("k") || a.count("bfile") + a.count("bfiles") != 1) {
+        cerr << "lmm_lrt: need -k and one of -bfile, --bfiles" << endl;
+        usage(argv[0]);
+        return 1;
+    }
+    const string outdir = a.count("outdir") ? a["outdir"] : "./output";
+    vector<string> bases, outs;
+    if (a.count("bfile")) {
+        bases.push_back(a["bfile"]);
+        outs.push_back(outdir + "/" + (a.count("o") ? a["o"] : string("result")) + ".assoc.txt");
+    } else {
+        ifstream f(a["bfiles"]);
+        if (!f.is_open()) {
+            cerr << "lmm_lrt: can't open " << a["bfiles"] << endl;
+            return 1;
+        }
+        for (string line; getline(f, line);) {
+            if (!line.empty() && line.back() == '\r') line.pop_back();
+            if (line.empty()) continue;
+            const size_t tab = line.find('\t');
+            if (tab == string::npos || tab == 0 || tab + 1 == line.size()) {
+                cerr << "lmm_lrt: " << a["bfiles"] << ": a line is not 'bfile<TAB>name': " << line << endl;
+                return 1;
+            }
+            bases.push_back(line.substr(0, tab));
+            outs.push_back(outdir + "/" + line.substr(tab + 1) + ".assoc.txt");
+        }
+    }
+    const double maf = a.count("maf") ? num("-maf", a["maf"]) : 0.01, miss = a.count("miss") ? num("-miss", a["miss"]) : 0.05;
+    const double lmin = a.count("lmin") ? num("-lmin", a["lmin"]) : 1e-5, lmax = a.count("lmax") ? num("-lmax", a["lmax"]) : 1e5;
+    const double col = a.count("n") ? num("-n", a["n"]) : 1, chunk = a.count("chunk_variants") ? num("--chunk_variants", a["chunk_variants"]) : 0;
+    if (col < 1 || col > 1e6 || col != (double)(uint32_t)col || chunk < 0 || chunk > 1e9) {
+        cerr << "lmm_lrt: -n or --chunk_variants out of range" << endl;
+        return 1;
+    }
+    (void)mkdir(outdir.c_str(), 0777);  // (an existing directory is fine; a failure shows when the output is written)
+    vector<const char*> bp, op;
+    for (size_t i = 0; i < bases.size(); i++) {
+        bp.push_back(bases[i].c_str());
+        op.push_back(outs[i].c_str());
+    }
+    kgwas_lmm_stats st{};
+    const int rc = kgwas_lmm_run_files(a["k"].c_str(), bases.size(), bp.data(), op.data(), (uint32_t)col, maf, miss, lmin, lmax,
+                                       (uint64_t)chunk, 0, &st);
+    if (rc != KGWAS_OK) {
+        cerr << "lmm_lrt: " << kgwas_last_error() << endl;
+        return rc == KGWAS_ERR_DEVICE ? 3 : 1;
+    }
+    cerr << "[kgwas] lmm_lrt: files=" << bases.size() << " individuals=" << st.n_individuals << " variants_read=" << st.variants_read
+         << " variants_tested=" << st.variants_tested << " eigendecompositions=" << st.eigendecompositions << " ms: eigen=" << st.eigen_ms
+         << " rotate=" << st.rotate_ms << " grid=" << st.grid_ms << " refine=" << st.refine_ms << endl;
+    cli_finish();
+    return 0;
+}

@@ -1,0 +1,490 @@
+// lmm.cpp — kgwas_lmm_*: the mixed-model likelihood-ratio test that the pipeline takes from `gemma -lmm 2` (kmers_gwas.py:150-165),
+// for the variants of PLINK .bed files, on the GPU (lmm_kernels.hip).
+//
+// create   : K's eigendecomposition on host threads (sym_eigen.cpp), the positive-semi-definite guard, then the device session:
+//            U, d, wt = U^T 1, the grid of 101 lambdas and the table of h and dh/dlog lambda at them. All of it is shared by
+//            every phenotype and .bed given to the handle;
+// null     : yt = U^T (y - mean y) on the host in index order, the sums without x at the grid points, the null model's maximum;
+// test_bed : per chunk of variants the raw bytes go to the device, then prep, rotate, grid and refine run in order on one stream;
+// run_files: the file layer of the lmm_lrt tool - kinship text, .fam phenotype column, .bim, .bed in, .assoc.txt and .log.txt out.
+//            Individuals without a phenotype are dropped from K, y and the .bed rows before anything else; beds that keep the
+//            same individuals share one handle, so one eigendecomposition.
+// No CPU fallback: the statistics need the GPU. The parsers and the formatter run without one.
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <fstream>
+#include <memory>
+#include <sstream>
+#include <string>
+#include <vector>
+
+#include "common.h"
+#include "ingest.h"
+#include "lmm_kernels.h"
+
+using namespace kgwas;
+
+struct kgwas_lmm {
+    int device = 0;
+    uint64_t n = 0;
+    LmmDims dm{};
+    double lmin = 0, lmax = 0;
+    uint32_t chunk = 0;
+    std::vector<double> U, d;
+    std::vector<double> y_cur;
+    bool have_null = false;
+    double l0 = 0, lambda0 = 0;
+    kgwas_lmm_stats st{};
+    bool on_device = false;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    DevBuf<double> d_U, d_d, d_wt, d_yt, d_HB, d_grid, d_base, d_null, d_Xt, d_G, d_lrt, d_lam, d_p;
+    DevBuf<uint8_t> d_bed, d_codes;
+    DevBuf<LmmVariant> d_vars;
+    ~kgwas_lmm() {
+        if (!on_device) return;
+        (void)hipSetDevice(device);
+        if (stream) (void)hipStreamSynchronize(stream);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+namespace {
+
+double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+template <class T>
+void upload(DevBuf<T>& b, const std::vector<T>& v) {
+    b.alloc(v.size());
+    KGWAS_HIP(hipMemcpy(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+}
+
+void device_init(kgwas_lmm* h) {
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) throw Error(KGWAS_ERR_DEVICE, "no HIP device available: libkgwas has no CPU fallback");
+    if (h->device < 0 || h->device >= nd) throw Error(KGWAS_ERR_ARG, "device ordinal out of range");
+    KGWAS_HIP(hipSetDevice(h->device));
+    h->on_device = true;
+    const uint64_t n = h->n, ldi = h->dm.ldi, n16 = h->dm.n16;
+    std::vector<double> Up(n16 * ldi, 0.0), dp(ldi, 0.0), wt(ldi, 0.0), HB(ldi * LMM_HB_COLS, 0.0), grid(2 * LMM_GRID);
+    for (uint64_t k = 0; k < n; k++) {
+        memcpy(&Up[k * ldi], &h->U[k * n], n * sizeof(double));
+        for (uint64_t i = 0; i < n; i++) wt[i] += h->U[k * n + i];  // U^T 1, in row order
+    }
+    for (uint64_t i = 0; i < n; i++) dp[i] = h->d[i];
+    const double tmin = std::log(h->lmin), tmax = std::log(h->lmax);
+    for (uint32_t g = 0; g < LMM_GRID; g++) {
+        const double t = g == 0 ? tmin : g == LMM_GRID - 1 ? tmax : tmin + (double)g * ((tmax - tmin) / (double)(LMM_GRID - 1));
+        grid[LMM_GRID + g] = t;
+        grid[g] = g == 0 ? h->lmin : g == LMM_GRID - 1 ? h->lmax : std::exp(t);
+    }
+    for (uint64_t i = 0; i < n; i++)
+        for (uint32_t g = 0; g < LMM_GRID; g++) {
+            const double hh = 1.0 / (grid[g] * dp[i] + 1.0);
+            HB[i * LMM_HB_COLS + g] = hh;
+            HB[i * LMM_HB_COLS + LMM_GRID + g] = hh * hh - hh;
+        }
+    upload(h->d_U, Up);
+    upload(h->d_d, dp);
+    upload(h->d_wt, wt);
+    upload(h->d_HB, HB);
+    upload(h->d_grid, grid);
+    h->d_yt.alloc(ldi);
+    h->d_base.alloc(LMM_GRID * LMM_BASE);
+    h->d_null.alloc(2);
+    const uint64_t c = h->chunk;
+    h->d_Xt.alloc(c * ldi);
+    h->d_G.alloc(c * 3 * LMM_HB_COLS);
+    h->d_lrt.alloc(c);
+    h->d_lam.alloc(c);
+    h->d_p.alloc(c);
+    h->d_bed.alloc(c * h->dm.bps);
+    h->d_codes.alloc(c * h->dm.bpsp);
+    h->d_vars.alloc(c);
+    KGWAS_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    for (hipEvent_t& e : h->ev) KGWAS_HIP(hipEventCreate(&e));
+}
+
+void fit_null(kgwas_lmm* h, const double* y) {
+    const uint64_t n = h->n;
+    if (h->have_null && memcmp(h->y_cur.data(), y, n * sizeof(double)) == 0) return;
+    double mean = 0;
+    for (uint64_t k = 0; k < n; k++) {
+        if (!std::isfinite(y[k])) throw Error(KGWAS_ERR_ARG, "kgwas_lmm: a phenotype value is not finite");
+        mean += y[k];
+    }
+    mean /= (double)n;
+    std::vector<double> yt(h->dm.ldi, 0.0);
+    bool varies = false;
+    for (uint64_t k = 0; k < n; k++) {
+        const double yc = y[k] - mean;
+        varies |= yc != 0;
+        const double* u = &h->U[k * n];
+        for (uint64_t i = 0; i < n; i++) yt[i] += u[i] * yc;
+    }
+    if (!varies) throw Error(KGWAS_ERR_ARG, "kgwas_lmm: the phenotype is constant");
+    KGWAS_HIP(hipSetDevice(h->device));
+    h->have_null = false;
+    KGWAS_HIP(hipMemcpyAsync(h->d_yt.p, yt.data(), yt.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    KGWAS_HIP(launch_lmm_base(h->dm, h->d_d.p, h->d_wt.p, h->d_yt.p, h->d_grid.p, h->d_base.p, h->stream));
+    KGWAS_HIP(launch_lmm_null(h->dm, h->d_d.p, h->d_wt.p, h->d_yt.p, h->d_grid.p, h->d_base.p, h->d_null.p, h->stream));
+    double out[2];
+    KGWAS_HIP(hipMemcpyAsync(out, h->d_null.p, sizeof(out), hipMemcpyDeviceToHost, h->stream));
+    KGWAS_HIP(hipStreamSynchronize(h->stream));  // (yt is read by the copy until here)
+    h->l0 = out[0];
+    h->lambda0 = out[1];
+    h->y_cur.assign(y, y + n);
+    h->have_null = true;
+}
+
+void test_bed(kgwas_lmm* h, const double* y, const uint8_t* body, uint64_t nv, double maf, double miss, double* lrt, double* lam,
+              double* p, double* af, uint32_t* n_miss, uint8_t* tested) {
+    fit_null(h, y);
+    KGWAS_HIP(hipSetDevice(h->device));
+    std::vector<LmmVariant> vars;
+    for (uint64_t pos = 0; pos < nv; pos += h->chunk) {
+        const uint32_t c = (uint32_t)std::min<uint64_t>(h->chunk, nv - pos);
+        hipStream_t st = h->stream;
+        KGWAS_HIP(hipMemcpyAsync(h->d_bed.p, body + pos * h->dm.bps, (size_t)c * h->dm.bps, hipMemcpyHostToDevice, st));
+        KGWAS_HIP(hipEventRecord(h->ev[0], st));
+        KGWAS_HIP(launch_lmm_prep(h->d_bed.p, c, h->dm, maf, miss, h->d_codes.p, h->d_vars.p, st));
+        KGWAS_HIP(launch_lmm_rotate(h->d_codes.p, h->d_vars.p, c, h->dm, h->d_U.p, h->d_Xt.p, st));
+        KGWAS_HIP(hipEventRecord(h->ev[1], st));
+        KGWAS_HIP(launch_lmm_grid(h->d_Xt.p, c, h->dm, h->d_wt.p, h->d_yt.p, h->d_HB.p, h->d_G.p, st));
+        KGWAS_HIP(hipEventRecord(h->ev[2], st));
+        KGWAS_HIP(launch_lmm_refine(h->d_Xt.p, h->d_G.p, h->d_vars.p, c, h->dm, h->d_d.p, h->d_wt.p, h->d_yt.p, h->d_grid.p, h->d_base.p,
+                                    h->l0, h->d_lrt.p, h->d_lam.p, h->d_p.p, st));
+        KGWAS_HIP(hipEventRecord(h->ev[3], st));
+        if (lrt) KGWAS_HIP(hipMemcpyAsync(lrt + pos, h->d_lrt.p, c * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (lam) KGWAS_HIP(hipMemcpyAsync(lam + pos, h->d_lam.p, c * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (p) KGWAS_HIP(hipMemcpyAsync(p + pos, h->d_p.p, c * sizeof(double), hipMemcpyDeviceToHost, st));
+        vars.resize(c);
+        KGWAS_HIP(hipMemcpyAsync(vars.data(), h->d_vars.p, c * sizeof(LmmVariant), hipMemcpyDeviceToHost, st));
+        KGWAS_HIP(hipStreamSynchronize(st));
+        float ms[3] = {0, 0, 0};
+        for (int k = 0; k < 3; k++) KGWAS_HIP(hipEventElapsedTime(&ms[k], h->ev[k], h->ev[k + 1]));
+        h->st.rotate_ms += ms[0];
+        h->st.grid_ms += ms[1];
+        h->st.refine_ms += ms[2];
+        h->st.chunks++;
+        for (uint32_t v = 0; v < c; v++) {
+            if (af) af[pos + v] = vars[v].af;
+            if (n_miss) n_miss[pos + v] = vars[v].n_miss;
+            if (tested) tested[pos + v] = (uint8_t)vars[v].tested;
+            h->st.variants_tested += vars[v].tested;
+        }
+        h->st.variants_read += c;
+    }
+}
+
+kgwas_lmm* create(uint64_t n, const double* K, int device, double lmin, double lmax, uint64_t chunk_variants) {
+    if (!K) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_create: null argument");
+    if (n < 3 || n >= (1ull << 16)) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_create: the number of individuals must be within 3..65535");
+    if (!(lmin > 0) || !(lmax > lmin) || !std::isfinite(lmax)) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_create: need 0 < lmin < lmax");
+    std::unique_ptr<kgwas_lmm> h(new kgwas_lmm);
+    h->device = device;
+    h->n = n;
+    h->lmin = lmin;
+    h->lmax = lmax;
+    h->dm.n = (uint32_t)n;
+    h->dm.ldi = (uint32_t)((n + 63) / 64 * 64);
+    h->dm.n16 = (uint32_t)((n + 15) / 16 * 16);
+    h->dm.bps = (uint32_t)((n + 3) / 4);
+    h->dm.bpsp = h->dm.n16 / 4;
+    if (!chunk_variants) chunk_variants = 10240;  // a whole 10 001-variant file of pass 2 in one chunk (Xt: 94 MB at n = 1135)
+    h->chunk = (uint32_t)((std::min<uint64_t>(chunk_variants, 1u << 16) + LMM_VTILE - 1) / LMM_VTILE * LMM_VTILE);
+    h->U.resize(n * n);
+    h->d.resize(n);
+    const double t0 = now_ms();
+    const int rc = kgwas_sym_eigen(n, K, h->d.data(), h->U.data(), 0);
+    if (rc != KGWAS_OK) throw Error(rc, kgwas_last_error());
+    h->st.eigen_ms = now_ms() - t0;
+    h->st.eigendecompositions = 1;
+    h->st.n_individuals = n;
+    // transform_and_permute_phenotypes.R:54 (is.positive.semi.definite, tolerance 1e-8)
+    for (double& v : h->d) {
+        if (v < -1e-8) throw Error(KGWAS_ERR_FORMAT, "Kinship matrix is not positive semi-definite");
+        if (std::fabs(v) < 1e-8) v = 0;
+    }
+    device_init(h.get());
+    return h.release();
+}
+
+// ---- files ----
+
+std::vector<std::string> split_ws(const std::string& line) {
+    std::vector<std::string> f;
+    size_t i = 0;
+    while (i < line.size()) {
+        while (i < line.size() && (line[i] == ' ' || line[i] == '\t' || line[i] == '\r')) i++;
+        size_t j = i;
+        while (j < line.size() && line[j] != ' ' && line[j] != '\t' && line[j] != '\r') j++;
+        if (j > i) f.push_back(line.substr(i, j - i));
+        i = j;
+    }
+    return f;
+}
+
+std::vector<std::string> read_lines(const std::string& path, const char* what) {
+    std::ifstream f(path);
+    if (!f.is_open()) throw Error(KGWAS_ERR_IO, std::string("can't open ") + what + " file: " + path);
+    std::vector<std::string> lines;
+    for (std::string l; std::getline(f, l);)
+        if (l.find_first_not_of(" \t\r") != std::string::npos) lines.push_back(l);
+    return lines;
+}
+
+std::vector<double> read_kinship(const std::string& path, uint64_t n_expected) {
+    const std::vector<std::string> lines = read_lines(path, "kinship");
+    if (lines.size() != n_expected)
+        throw Error(KGWAS_ERR_FORMAT, "kinship file " + path + " has " + std::to_string(lines.size()) + " rows, the .fam has " +
+                                          std::to_string(n_expected) + " individuals");
+    std::vector<double> K(n_expected * n_expected);
+    for (uint64_t r = 0; r < n_expected; r++) {
+        const char* s = lines[r].c_str();
+        uint64_t c = 0;
+        for (;; c++) {
+            char* end = nullptr;
+            const double v = strtod(s, &end);
+            if (end == s) break;
+            if (c < n_expected) K[r * n_expected + c] = v;
+            s = end;
+        }
+        while (*s == ' ' || *s == '\t' || *s == '\r') s++;
+        if (*s) throw Error(KGWAS_ERR_FORMAT, "kinship file " + path + ": row " + std::to_string(r + 1) + " holds text that is no number");
+        if (c != n_expected)
+            throw Error(KGWAS_ERR_FORMAT, "kinship file " + path + ": row " + std::to_string(r + 1) + " has " + std::to_string(c) +
+                                              " values, expected " + std::to_string(n_expected));
+    }
+    return K;
+}
+
+// values[i] and keep[i] of every .fam line; the phenotype is field 5 + pheno_col (1-based), "-9" and "NA" are missing
+void read_fam(const std::string& path, uint32_t pheno_col, std::vector<double>& values, std::vector<uint8_t>& keep) {
+    if (pheno_col < 1) throw Error(KGWAS_ERR_ARG, "the phenotype column (-n) starts at 1");
+    const std::vector<std::string> lines = read_lines(path, "fam");
+    values.assign(lines.size(), std::nan(""));
+    keep.assign(lines.size(), 0);
+    for (size_t i = 0; i < lines.size(); i++) {
+        const std::vector<std::string> f = split_ws(lines[i]);
+        if (f.size() < 5u + pheno_col)
+            throw Error(KGWAS_ERR_FORMAT, path + ": line " + std::to_string(i + 1) + " has no phenotype column " + std::to_string(pheno_col));
+        const std::string& t = f[4 + pheno_col];
+        if (t == "-9" || t == "NA") continue;
+        char* end = nullptr;
+        const double v = strtod(t.c_str(), &end);
+        if (end == t.c_str() || *end || !std::isfinite(v))
+            throw Error(KGWAS_ERR_FORMAT, path + ": line " + std::to_string(i + 1) + ": phenotype '" + t + "' is no number");
+        values[i] = v;
+        keep[i] = 1;
+    }
+}
+
+uint64_t format_assoc(const char* chr, const char* rs, const char* ps, uint32_t n_miss, const char* a1, const char* a0, double af,
+                      double l_mle, double p, char* out, uint64_t cap) {
+    char buf[1024];
+    int len;
+    if (!chr)
+        len = snprintf(buf, sizeof(buf), "chr\trs\tps\tn_miss\tallele1\tallele0\taf\tl_mle\tp_lrt\n");
+    else
+        len = snprintf(buf, sizeof(buf), "%s\t%s\t%s\t%u\t%s\t%s\t%.3f\t%.6e\t%.6e\n", chr, rs, ps, n_miss, a1, a0, af, l_mle, p);
+    if (len < 0 || (size_t)len >= sizeof(buf)) throw Error(KGWAS_ERR_FORMAT, "a .bim line is too long");
+    if (out && cap >= (uint64_t)len) memcpy(out, buf, (size_t)len);
+    return (uint64_t)len;
+}
+
+std::string log_path_of(const std::string& out) {
+    const std::string suf = ".assoc.txt";
+    if (out.size() >= suf.size() && out.compare(out.size() - suf.size(), suf.size(), suf) == 0)
+        return out.substr(0, out.size() - suf.size()) + ".log.txt";
+    return out + ".log.txt";
+}
+
+void add_stats(kgwas_lmm_stats& a, const kgwas_lmm_stats& b) {
+    a.eigen_ms += b.eigen_ms;
+    a.rotate_ms += b.rotate_ms;
+    a.grid_ms += b.grid_ms;
+    a.refine_ms += b.refine_ms;
+    a.variants_read += b.variants_read;
+    a.variants_tested += b.variants_tested;
+    a.chunks += b.chunks;
+    a.eigendecompositions += b.eigendecompositions;
+    a.n_individuals = b.n_individuals;
+}
+
+void run_files(const char* kinship_path, uint64_t n_beds, const char* const* bases, const char* const* outs, uint32_t pheno_col,
+               double maf, double miss, double lmin, double lmax, uint64_t chunk_variants, int device, kgwas_lmm_stats* total) {
+    if (!kinship_path || (n_beds && (!bases || !outs))) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_run_files: null argument");
+    kgwas_lmm_stats sum{};
+    std::vector<double> Kfull;
+    std::unique_ptr<kgwas_lmm> h;
+    std::vector<uint8_t> keep_cur;
+    for (uint64_t b = 0; b < n_beds; b++) {
+        const std::string base = bases[b], out = outs[b];
+        const double t_start = now_ms();
+        std::vector<double> vals;
+        std::vector<uint8_t> keep;
+        read_fam(base + ".fam", pheno_col, vals, keep);
+        const uint64_t nf = vals.size();
+        if (Kfull.empty() || Kfull.size() != nf * nf) Kfull = read_kinship(kinship_path, nf);
+        std::vector<uint32_t> idx;
+        for (uint64_t i = 0; i < nf; i++)
+            if (keep[i]) idx.push_back((uint32_t)i);
+        const uint64_t n = idx.size();
+        if (!h || keep != keep_cur) {
+            if (h) add_stats(sum, h->st);
+            h.reset();
+            std::vector<double> K(n * n), y;
+            for (uint64_t r = 0; r < n; r++)
+                for (uint64_t c = 0; c < n; c++) K[r * n + c] = Kfull[(uint64_t)idx[r] * nf + idx[c]];
+            h.reset(create(n, K.data(), device, lmin, lmax, chunk_variants));
+            keep_cur = keep;
+        }
+        std::vector<double> y(n);
+        for (uint64_t r = 0; r < n; r++) y[r] = vals[idx[r]];
+        const std::vector<std::string> bim = read_lines(base + ".bim", "bim");
+        const uint64_t M = bim.size(), bps_f = (nf + 3) / 4, bps = (n + 3) / 4;
+        std::vector<uint8_t> body;
+        {
+            std::ifstream f(base + ".bed", std::ios::binary | std::ios::ate);
+            if (!f.is_open()) throw Error(KGWAS_ERR_IO, "can't open bed file: " + base + ".bed");
+            const uint64_t size = (uint64_t)f.tellg();
+            if (size != 3 + M * bps_f)
+                throw Error(KGWAS_ERR_FORMAT, base + ".bed has " + std::to_string(size) + " bytes, " + std::to_string(M) + " variants of " +
+                                                  std::to_string(nf) + " individuals need " + std::to_string(3 + M * bps_f));
+            f.seekg(0);
+            uint8_t magic[3];
+            f.read((char*)magic, 3);
+            if (magic[0] != 0x6C || magic[1] != 0x1B || magic[2] != 0x01)
+                throw Error(KGWAS_ERR_FORMAT, base + ".bed: not a SNP-major PLINK .bed (magic 6C 1B 01)");
+            body.resize(M * bps_f);
+            f.read((char*)body.data(), (std::streamsize)body.size());
+            if (!f) throw Error(KGWAS_ERR_IO, "short read of " + base + ".bed");
+        }
+        if (n != nf) {  // the kept individuals' codes, packed again
+            std::vector<uint8_t> packed(M * bps, 0);
+            for (uint64_t v = 0; v < M; v++) {
+                const uint8_t* src = &body[v * bps_f];
+                uint8_t* dst = &packed[v * bps];
+                for (uint64_t r = 0; r < n; r++) dst[r >> 2] |= (uint8_t)(((src[idx[r] >> 2] >> (2 * (idx[r] & 3))) & 3) << (2 * (r & 3)));
+            }
+            body.swap(packed);
+        }
+        std::vector<double> lrt(M), lam(M), p(M), af(M);
+        std::vector<uint32_t> n_miss(M);
+        std::vector<uint8_t> tested(M);
+        const kgwas_lmm_stats before = h->st;
+        test_bed(h.get(), y.data(), body.data(), M, maf, miss, lrt.data(), lam.data(), p.data(), af.data(), n_miss.data(), tested.data());
+        std::string text(format_assoc(nullptr, "", "", 0, "", "", 0, 0, 0, nullptr, 0), '\0');
+        format_assoc(nullptr, "", "", 0, "", "", 0, 0, 0, &text[0], text.size());
+        uint64_t n_tested = 0;
+        for (uint64_t v = 0; v < M; v++) {
+            if (!tested[v]) continue;
+            const std::vector<std::string> f = split_ws(bim[v]);
+            if (f.size() < 6) throw Error(KGWAS_ERR_FORMAT, base + ".bim: line " + std::to_string(v + 1) + " has fewer than 6 fields");
+            char line[1024];
+            const uint64_t len = format_assoc(f[0].c_str(), f[1].c_str(), f[3].c_str(), n_miss[v], f[4].c_str(), f[5].c_str(), af[v], lam[v],
+                                              p[v], line, sizeof(line));
+            text.append(line, len);
+            n_tested++;
+        }
+        FILE* fo = fopen(out.c_str(), "wb");
+        if (!fo || fwrite(text.data(), 1, text.size(), fo) != text.size() || fclose(fo) != 0)
+            throw Error(KGWAS_ERR_IO, "can't write " + out);
+        char log[1024];
+        const int ll = snprintf(log, sizeof(log),
+                                "lmm_lrt: ML likelihood-ratio test (-lmm 2)\nbfile\t%s\nkinship\t%s\nindividuals_in_fam\t%llu\n"
+                                "individuals_used\t%llu\nvariants_read\t%llu\nvariants_tested\t%llu\nlambda0\t%.6e\nlogl_H0\t%.6f\n"
+                                "ms: eigen=%.3f rotate=%.3f grid=%.3f refine=%.3f total=%.3f\n",
+                                base.c_str(), kinship_path, (unsigned long long)nf, (unsigned long long)n, (unsigned long long)M,
+                                (unsigned long long)n_tested, h->lambda0, h->l0, h->st.eigen_ms, h->st.rotate_ms - before.rotate_ms,
+                                h->st.grid_ms - before.grid_ms, h->st.refine_ms - before.refine_ms, now_ms() - t_start);
+        FILE* fl = fopen(log_path_of(out).c_str(), "wb");
+        if (!fl || ll < 0 || fwrite(log, 1, (size_t)std::min<int>(ll, sizeof(log) - 1), fl) == 0 || fclose(fl) != 0)
+            throw Error(KGWAS_ERR_IO, "can't write " + log_path_of(out));
+    }
+    if (h) add_stats(sum, h->st);
+    if (total) *total = sum;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kgwas_lmm_create(uint64_t n, const double* K, int32_t device, double lmin, double lmax, uint64_t chunk_variants, kgwas_lmm** out) {
+    return guarded([&] {
+        if (!out) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_create: null argument");
+        *out = create(n, K, device, lmin, lmax, chunk_variants);
+    });
+}
+
+int kgwas_lmm_null(kgwas_lmm* h, const double* y, double* logl0, double* lambda0) {
+    return guarded([&] {
+        if (!h || !y) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_null: null argument");
+        fit_null(h, y);
+        if (logl0) *logl0 = h->l0;
+        if (lambda0) *lambda0 = h->lambda0;
+    });
+}
+
+int kgwas_lmm_test_bed(kgwas_lmm* h, const double* y, const uint8_t* bed_body, uint64_t n_variants, double maf, double miss, double* lrt,
+                       double* lambda, double* p, double* af, uint32_t* n_miss, uint8_t* tested) {
+    return guarded([&] {
+        if (!h || !y || (!bed_body && n_variants)) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_test_bed: null argument");
+        test_bed(h, y, bed_body, n_variants, maf, miss, lrt, lambda, p, af, n_miss, tested);
+    });
+}
+
+int kgwas_lmm_run_files(const char* kinship_path, uint64_t n_beds, const char* const* bfile_bases, const char* const* out_paths,
+                        uint32_t pheno_col, double maf, double miss, double lmin, double lmax, uint64_t chunk_variants, int32_t device,
+                        kgwas_lmm_stats* total) {
+    return guarded([&] { run_files(kinship_path, n_beds, bfile_bases, out_paths, pheno_col, maf, miss, lmin, lmax, chunk_variants, device, total); });
+}
+
+int kgwas_lmm_get_stats(const kgwas_lmm* h, kgwas_lmm_stats* out) {
+    return guarded([&] {
+        if (!h || !out) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_get_stats: null argument");
+        *out = h->st;
+    });
+}
+
+void kgwas_lmm_destroy(kgwas_lmm* h) { delete h; }
+
+int kgwas_lmm_read_kinship(const char* path, uint64_t n_expected, double* K) {
+    return guarded([&] {
+        if (!path || !K) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_read_kinship: null argument");
+        const std::vector<double> k = read_kinship(path, n_expected);
+        memcpy(K, k.data(), k.size() * sizeof(double));
+    });
+}
+
+int kgwas_lmm_read_fam(const char* path, uint32_t pheno_col, uint64_t cap, double* values, uint8_t* keep, uint64_t* n_lines) {
+    return guarded([&] {
+        if (!path || !n_lines) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_read_fam: null argument");
+        std::vector<double> v;
+        std::vector<uint8_t> k;
+        read_fam(path, pheno_col, v, k);
+        *n_lines = v.size();
+        for (uint64_t i = 0; i < std::min<uint64_t>(cap, v.size()); i++) {
+            if (values) values[i] = v[i];
+            if (keep) keep[i] = k[i];
+        }
+    });
+}
+
+uint64_t kgwas_lmm_format_assoc(const char* chr, const char* rs, const char* ps, uint32_t n_miss, const char* allele1, const char* allele0,
+                                double af, double l_mle, double p_lrt, char* out, uint64_t cap) {
+    uint64_t need = 0;
+    guarded([&] {
+        if (chr && (!rs || !ps || !allele1 || !allele0)) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_format_assoc: null argument");
+        need = format_assoc(chr, rs, ps, n_miss, allele1, allele0, af, l_mle, p_lrt, out, cap);
+    });
+    return need;
+}
+
+}  // extern "C"

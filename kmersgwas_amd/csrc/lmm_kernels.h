@@ -1,0 +1,48 @@
+// lmm_kernels.h — launchers of lmm_kernels.hip (the device side of lmm_lrt) and the layout they share with lmm.cpp.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace kgwas {
+
+constexpr uint32_t LMM_GRID = 101;      // grid points over log lambda: 100 intervals (emma.R's ngrids)
+constexpr uint32_t LMM_HB_COLS = 208;   // the h table's columns: h at the 101 points, then dh/dlog lambda at them, then 6 of zeros
+constexpr uint32_t LMM_BASE = 8;        // per grid point: sum h, sum log h, Sww, Swy, Syy, then Sww', Swy', Syy' (weights dh)
+constexpr uint32_t LMM_VTILE = 32;      // variants per wave of the rotation; chunk buffers are padded to it
+constexpr uint32_t LMM_REFINE_STEPS = 12;
+
+struct LmmVariant {  // what lmm_prep leaves per variant
+    double val[4];   // value of .bed code 0..3, centred: 2 - mean, 0 (missing), 1 - mean, 0 - mean
+    double af;       // mean / 2
+    uint32_t n_miss;
+    uint32_t tested;
+};
+
+// Shapes: n individuals; ldi = n rounded up to 64 (row stride of U, Xt; length of d, wt, yt, zero past n); U has n rounded up to
+// 16 rows (zero past n); bpsp = bytes per variant of the padded code rows (a multiple of 4, zero past the .bed's bytes).
+struct LmmDims {
+    uint32_t n, ldi, n16, bps, bpsp;
+};
+
+// bed[nv][bps] -> codes[nv][bpsp], vars[nv] (counts, af, tested by maf / miss / constant, values)
+hipError_t launch_lmm_prep(const uint8_t* bed, uint32_t nv, LmmDims dm, double maf, double miss, uint8_t* codes, LmmVariant* vars,
+                           hipStream_t st);
+// Xt[v][i] = sum_k U[k][i] val_v[code_v[k]], v < nv rounded up to LMM_VTILE (rows past nv are zero)
+hipError_t launch_lmm_rotate(const uint8_t* codes, const LmmVariant* vars, uint32_t nv, LmmDims dm, const double* U, double* Xt,
+                             hipStream_t st);
+// base[g][LMM_BASE] from d, wt, yt and the grid's lambda[g]
+hipError_t launch_lmm_base(LmmDims dm, const double* d, const double* wt, const double* yt, const double* lambda, double* base,
+                           hipStream_t st);
+// G[v][3][LMM_HB_COLS]: sums over i of HB[i][c] * (xt^2, xt wt, xt yt)
+hipError_t launch_lmm_grid(const double* Xt, uint32_t nv, LmmDims dm, const double* wt, const double* yt, const double* HB, double* G,
+                           hipStream_t st);
+// the null model: out[0] = l0, out[1] = lambda0
+hipError_t launch_lmm_null(LmmDims dm, const double* d, const double* wt, const double* yt, const double* lambda, const double* base,
+                           double* out, hipStream_t st);
+// per tested variant: lrt, lambda, p (NaN for the others)
+hipError_t launch_lmm_refine(const double* Xt, const double* G, const LmmVariant* vars, uint32_t nv, LmmDims dm, const double* d,
+                             const double* wt, const double* yt, const double* lambda, const double* base, double l0, double* lrt,
+                             double* lam, double* p, hipStream_t st);
+
+}  // namespace kgwas

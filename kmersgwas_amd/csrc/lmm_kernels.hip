@@ -1,0 +1,378 @@
+// lmm_kernels.hip — device side of lmm_lrt: the ML likelihood-ratio test of y = W a + x b + u + e, u ~ N(0, lambda K / tau),
+// e ~ N(0, I / tau), W = 1, for every variant of a PLINK .bed chunk (emma.R's emma.ML.LRT is the same statistic).
+//
+// With K = U diag(d) U^T, yt = U^T y, wt = U^T 1, xt = U^T x and h_i = 1 / (lambda d_i + 1):
+//     l(lambda) = n/2 log(n / 2 pi) - n/2 + 1/2 sum log h_i - n/2 log RSS(lambda),
+// RSS the residual of the h-weighted regression of yt on [wt] (H0) or [wt, xt] (H1), and with t = log lambda
+//     dl/dt = 1/2 (sum h_i - n) - n/2 RSS' / RSS,  RSS' = sum h'_i r_i^2,  h' = dh/dt = h^2 - h,  r = yt - [wt xt] beta.
+//
+//   lmm_prep_kernel    one wave per variant: counts of the four codes (integers), af, n_miss, the tested flag, the centred value of
+//                      every code, and the code bytes copied to rows of a 4-byte multiple;
+//   lmm_rotate_kernel  Xt = X U on v_mfma_f64_16x16x4_f64: a wave owns 32 variants x 64 individuals (8 accumulator tiles), A is
+//                      the decoded code (one per lane), B a row of U. The k of a 16-block are taken in the order 4q + s (q the
+//                      lane's quarter, s the step), which lets a lane decode its four codes from ONE byte;
+//   lmm_base_kernel    the sums without x at the 101 grid points (one wave each);
+//   lmm_grid_kernel    G = [xt^2 | xt wt | xt yt] . HB on the same MFMA: per variant the three x sums at all grid points, with
+//                      weights h and h';
+//   lmm_null_kernel / lmm_refine_kernel   one wave per model: l and dl/dt at the grid points, then every interval where dl/dt
+//                      goes from + to - is refined by LMM_REFINE_STEPS bracketing steps (secant with the Illinois correction,
+//                      every third one a bisection) whose sums run over i with lanes striding and a fixed butterfly; the
+//                      evaluated point with the smallest |dl/dt| is the interval's candidate. Both ends and every such point
+//                      are candidates; the largest l wins, the earliest on a tie.
+// Nothing here depends on a variant's neighbours or uses an atomic: a variant's numbers are the same in any batch.
+//
+// f64 MFMA layout (16x16x4): lane l holds A[row l & 15][k l >> 4] and B[k l >> 4][col l & 15]; result register j of lane l is
+// D[row (l >> 4) + 4 j][col l & 15] - not the f32 forms' 4 (l >> 4) + j.
+#include "lmm_kernels.h"
+
+namespace kgwas {
+
+namespace {
+
+using d4 = __attribute__((ext_vector_type(4))) double;
+
+__device__ inline double wave_sum(double v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+__device__ inline uint32_t wave_sum_u32(uint32_t v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
+__global__ void __launch_bounds__(64) lmm_prep_kernel(const uint8_t* __restrict__ bed, LmmDims dm, double maf, double miss,
+                                                      uint8_t* __restrict__ codes, LmmVariant* __restrict__ vars) {
+    const uint32_t v = blockIdx.x, lane = threadIdx.x;
+    const uint8_t* row = bed + (uint64_t)v * dm.bps;
+    uint8_t* out = codes + (uint64_t)v * dm.bpsp;
+    uint32_t c[4] = {0, 0, 0, 0};
+    for (uint32_t b = lane; b < dm.bpsp; b += 64) {
+        const uint32_t byte = b < dm.bps ? row[b] : 0u;
+        out[b] = (uint8_t)byte;
+        const uint32_t valid = b < dm.bps ? min(4u, dm.n - 4u * b) : 0u;
+        for (uint32_t j = 0; j < valid; j++) {
+            const uint32_t code = (byte >> (2u * j)) & 3u;
+            c[0] += code == 0u;
+            c[1] += code == 1u;
+            c[2] += code == 2u;
+            c[3] += code == 3u;
+        }
+    }
+    for (int k = 0; k < 4; k++) c[k] = wave_sum_u32(c[k]);
+    if (lane != 0) return;
+    const uint32_t nn = dm.n - c[1];
+    const double mean = nn ? (double)(2u * c[0] + c[2]) / (double)nn : 0.0;
+    const double af = 0.5 * mean;
+    const bool constant = nn == 0 || c[0] == nn || c[2] == nn || c[3] == nn;
+    LmmVariant o;
+    o.val[0] = 2.0 - mean;
+    o.val[1] = 0.0;
+    o.val[2] = 1.0 - mean;
+    o.val[3] = 0.0 - mean;
+    o.af = af;
+    o.n_miss = c[1];
+    o.tested = !constant && fmin(af, 1.0 - af) >= maf && (double)c[1] / (double)dm.n <= miss;
+    vars[v] = o;
+}
+
+__global__ void __launch_bounds__(256) lmm_rotate_kernel(const uint8_t* __restrict__ codes, const LmmVariant* __restrict__ vars,
+                                                         uint32_t nv, LmmDims dm, const double* __restrict__ U,
+                                                         double* __restrict__ Xt) {
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
+    const uint32_t v0 = blockIdx.x * LMM_VTILE;
+    const uint32_t i0 = (blockIdx.y * 4 + wave) * 64;
+    if (i0 >= dm.ldi) return;
+    d4 acc[2][4];
+    double tv[2][4];
+    const uint8_t* crow[2];
+    for (int m = 0; m < 2; m++) {
+        const uint32_t v = v0 + 16 * m + r;
+        const bool ok = v < nv;
+        for (int k = 0; k < 4; k++) tv[m][k] = ok ? vars[v].val[k] : 0.0;
+        crow[m] = codes + (uint64_t)(ok ? v : 0) * dm.bpsp + q;
+        for (int t = 0; t < 4; t++) acc[m][t] = d4{0, 0, 0, 0};
+    }
+    const double* ucol = U + i0 + r;
+    for (uint32_t k0 = 0; k0 < dm.n16; k0 += 16) {
+        const uint32_t b0 = crow[0][k0 >> 2], b1 = crow[1][k0 >> 2];
+#pragma unroll
+        for (uint32_t s = 0; s < 4; s++) {
+            const uint32_t c0 = (b0 >> (2 * s)) & 3u, c1 = (b1 >> (2 * s)) & 3u;
+            const double a0 = c0 == 0 ? tv[0][0] : c0 == 1 ? tv[0][1] : c0 == 2 ? tv[0][2] : tv[0][3];
+            const double a1 = c1 == 0 ? tv[1][0] : c1 == 1 ? tv[1][1] : c1 == 2 ? tv[1][2] : tv[1][3];
+            const double* urow = ucol + (uint64_t)(k0 + 4 * q + s) * dm.ldi;
+#pragma unroll
+            for (int t = 0; t < 4; t++) {
+                const double b = urow[16 * t];
+                acc[0][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b, acc[0][t], 0, 0, 0);
+                acc[1][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b, acc[1][t], 0, 0, 0);
+            }
+        }
+    }
+    for (int m = 0; m < 2; m++)
+        for (int t = 0; t < 4; t++)
+            for (int j = 0; j < 4; j++)
+                Xt[(uint64_t)(v0 + 16 * m + q + 4 * j) * dm.ldi + i0 + 16 * t + r] = acc[m][t][j];
+}
+
+__global__ void __launch_bounds__(256) lmm_grid_kernel(const double* __restrict__ Xt, uint32_t nv, LmmDims dm,
+                                                       const double* __restrict__ wt, const double* __restrict__ yt,
+                                                       const double* __restrict__ HB, double* __restrict__ G) {
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
+    const uint32_t v0 = (blockIdx.x * 4 + wave) * 16;
+    if (v0 >= nv) return;
+    const uint32_t tile0 = blockIdx.y * 4, n_tiles = LMM_HB_COLS / 16;
+    d4 acc[3][4];
+    for (int c = 0; c < 3; c++)
+        for (int t = 0; t < 4; t++) acc[c][t] = d4{0, 0, 0, 0};
+    const double* xrow = Xt + (uint64_t)(v0 + r) * dm.ldi + 4 * q;  // (rows up to nv rounded up to 16 exist: LMM_VTILE padding)
+    for (uint32_t i0 = 0; i0 < dm.ldi; i0 += 16) {
+#pragma unroll
+        for (uint32_t s = 0; s < 4; s++) {
+            const uint32_t i = i0 + 4 * q + s;
+            const double x = xrow[i0 + s];
+            const double axx = x * x, axw = x * wt[i], axy = x * yt[i];
+            const double* hrow = HB + (uint64_t)i * LMM_HB_COLS + r;
+#pragma unroll
+            for (uint32_t t = 0; t < 4; t++) {
+                if (tile0 + t >= n_tiles) continue;
+                const double b = hrow[16 * (tile0 + t)];
+                acc[0][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(axx, b, acc[0][t], 0, 0, 0);
+                acc[1][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(axw, b, acc[1][t], 0, 0, 0);
+                acc[2][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(axy, b, acc[2][t], 0, 0, 0);
+            }
+        }
+    }
+    for (int j = 0; j < 4; j++) {
+        const uint32_t v = v0 + q + 4 * j;
+        if (v >= nv) continue;
+        for (int c = 0; c < 3; c++)
+            for (uint32_t t = 0; t < 4; t++)
+                if (tile0 + t < n_tiles) G[((uint64_t)v * 3 + c) * LMM_HB_COLS + 16 * (tile0 + t) + r] = acc[c][t][j];
+    }
+}
+
+__global__ void __launch_bounds__(64) lmm_base_kernel(LmmDims dm, const double* __restrict__ d, const double* __restrict__ wt,
+                                                      const double* __restrict__ yt, const double* __restrict__ grid,
+                                                      double* __restrict__ base) {
+    const uint32_t g = blockIdx.x, lane = threadIdx.x;
+    const double lam = grid[g];
+    double s[LMM_BASE] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (uint32_t i = lane; i < dm.n; i += 64) {
+        const double ld = lam * d[i], h = 1.0 / (ld + 1.0), hd = h * h - h, w = wt[i], y = yt[i];
+        s[0] += h;
+        s[1] -= log1p(ld);
+        s[2] += h * w * w;
+        s[3] += h * w * y;
+        s[4] += h * y * y;
+        s[5] += hd * w * w;
+        s[6] += hd * w * y;
+        s[7] += hd * y * y;
+    }
+    for (uint32_t k = 0; k < LMM_BASE; k++) s[k] = wave_sum(s[k]);
+    if (lane < LMM_BASE) base[g * LMM_BASE + lane] = s[lane];
+}
+
+struct Sums {
+    double sh, slog, ww, wy, yy, dww, dwy, dyy;  // as a row of base
+    double xx, xw, xy, dxx, dxw, dxy;
+};
+
+// l and dl/dt from the weighted sums
+template <bool HAS_X>
+__device__ inline void ll_from_sums(const Sums& s, double n, double& l, double& dl) {
+    const double bw0 = s.wy / s.ww;
+    double rss = s.yy - s.wy * bw0, drss;
+    if (HAS_X) {
+        const double xxw = s.xx - s.xw * s.xw / s.ww, xyw = s.xy - s.xw * bw0;
+        const double bx = xyw / xxw, bw = (s.wy - s.xw * bx) / s.ww;
+        rss -= xyw * bx;
+        drss = s.dyy - 2.0 * (bw * s.dwy + bx * s.dxy) + bw * bw * s.dww + 2.0 * bw * bx * s.dxw + bx * bx * s.dxx;
+    } else {
+        drss = s.dyy - 2.0 * bw0 * s.dwy + bw0 * bw0 * s.dww;
+    }
+    l = 0.5 * n * (log(n / 6.283185307179586476925) - 1.0) + 0.5 * s.slog - 0.5 * n * log(rss);
+    dl = 0.5 * (s.sh - n) - 0.5 * n * drss / rss;
+}
+
+// the sums at one lambda, over i with lanes striding; every lane gets them
+template <bool HAS_X, bool WITH_LOG>
+__device__ inline Sums direct_sums(double lam, uint32_t n, const double* __restrict__ d, const double* __restrict__ wt,
+                                   const double* __restrict__ yt, const double* __restrict__ xt) {
+    Sums s = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (uint32_t i = threadIdx.x; i < n; i += 64) {
+        const double ld = lam * d[i], h = 1.0 / (ld + 1.0), hd = h * h - h, w = wt[i], y = yt[i];
+        s.sh += h;
+        if (WITH_LOG) s.slog -= log1p(ld);
+        s.ww += h * w * w;
+        s.wy += h * w * y;
+        s.yy += h * y * y;
+        s.dww += hd * w * w;
+        s.dwy += hd * w * y;
+        s.dyy += hd * y * y;
+        if (HAS_X) {
+            const double x = xt[i];
+            s.xx += h * x * x;
+            s.xw += h * x * w;
+            s.xy += h * x * y;
+            s.dxx += hd * x * x;
+            s.dxw += hd * x * w;
+            s.dxy += hd * x * y;
+        }
+    }
+    s.sh = wave_sum(s.sh);
+    if (WITH_LOG) s.slog = wave_sum(s.slog);
+    s.ww = wave_sum(s.ww), s.wy = wave_sum(s.wy), s.yy = wave_sum(s.yy);
+    s.dww = wave_sum(s.dww), s.dwy = wave_sum(s.dwy), s.dyy = wave_sum(s.dyy);
+    if (HAS_X) {
+        s.xx = wave_sum(s.xx), s.xw = wave_sum(s.xw), s.xy = wave_sum(s.xy);
+        s.dxx = wave_sum(s.dxx), s.dxw = wave_sum(s.dxw), s.dxy = wave_sum(s.dxy);
+    }
+    return s;
+}
+
+// One wave (a block of 64): the maximum of l over the grid's ends and the refined interior points. grid = lambda[101], then
+// t[101] = log lambda. Gv = the variant's three rows of G (HAS_X). s_l, s_dl: LMM_GRID doubles of LDS each.
+template <bool HAS_X>
+__device__ void maximise(uint32_t n, const double* __restrict__ d, const double* __restrict__ wt, const double* __restrict__ yt,
+                         const double* __restrict__ xt, const double* __restrict__ Gv, const double* __restrict__ grid,
+                         const double* __restrict__ base, double* s_l, double* s_dl, double& best_l, double& best_lam) {
+    const double nd = (double)n;
+    for (uint32_t g = threadIdx.x; g < LMM_GRID; g += 64) {
+        const double* b = base + g * LMM_BASE;
+        Sums s = {b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], 0, 0, 0, 0, 0, 0};
+        if (HAS_X) {
+            s.xx = Gv[g], s.xw = Gv[LMM_HB_COLS + g], s.xy = Gv[2 * LMM_HB_COLS + g];
+            s.dxx = Gv[LMM_GRID + g], s.dxw = Gv[LMM_HB_COLS + LMM_GRID + g], s.dxy = Gv[2 * LMM_HB_COLS + LMM_GRID + g];
+        }
+        ll_from_sums<HAS_X>(s, nd, s_l[g], s_dl[g]);
+    }
+    __syncthreads();
+    best_l = s_l[0];
+    best_lam = grid[0];
+    if (s_l[LMM_GRID - 1] > best_l) {
+        best_l = s_l[LMM_GRID - 1];
+        best_lam = grid[LMM_GRID - 1];
+    }
+    for (uint32_t g = 0; g + 1 < LMM_GRID; g++) {
+        double fa = s_dl[g], fb = s_dl[g + 1];
+        if (!(fa > 0.0 && fb <= 0.0)) continue;  // (wave-uniform: LDS values)
+        double ta = grid[LMM_GRID + g], tb = grid[LMM_GRID + g + 1];
+        int side = 0;
+        // the evaluated point with the smallest |dl/dt| so far (an Illinois step overshoots on purpose: the last point
+        // need not be the best one)
+        double t_best = fa < -fb ? ta : tb, f_best = fa < -fb ? fa : -fb;
+        for (uint32_t step = 0; step < LMM_REFINE_STEPS; step++) {
+            double tm = (ta * fb - tb * fa) / (fb - fa);
+            if (step % 3 == 2 || !(tm > ta && tm < tb)) tm = 0.5 * (ta + tb);
+            const Sums s = direct_sums<HAS_X, false>(exp(tm), n, d, wt, yt, xt);
+            double l, dl;
+            ll_from_sums<HAS_X>(s, nd, l, dl);
+            if (fabs(dl) < f_best) {
+                f_best = fabs(dl);
+                t_best = tm;
+            }
+            if (dl > 0.0) {
+                ta = tm, fa = dl;
+                if (side == 1) fb *= 0.5;
+                side = 1;
+            } else {
+                tb = tm, fb = dl;
+                if (side == -1) fa *= 0.5;
+                side = -1;
+            }
+        }
+        // the candidate: l there, with the log-determinant term
+        const double lam = exp(t_best);
+        const Sums s = direct_sums<HAS_X, true>(lam, n, d, wt, yt, xt);
+        double l, dl;
+        ll_from_sums<HAS_X>(s, nd, l, dl);
+        if (l > best_l) {
+            best_l = l;
+            best_lam = lam;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(64) lmm_null_kernel(LmmDims dm, const double* __restrict__ d, const double* __restrict__ wt,
+                                                      const double* __restrict__ yt, const double* __restrict__ grid,
+                                                      const double* __restrict__ base, double* __restrict__ out) {
+    __shared__ double s_l[LMM_GRID], s_dl[LMM_GRID];
+    double l, lam;
+    maximise<false>(dm.n, d, wt, yt, nullptr, nullptr, grid, base, s_l, s_dl, l, lam);
+    if (threadIdx.x == 0) {
+        out[0] = l;
+        out[1] = lam;
+    }
+}
+
+__global__ void __launch_bounds__(64) lmm_refine_kernel(const double* __restrict__ Xt, const double* __restrict__ G,
+                                                        const LmmVariant* __restrict__ vars, LmmDims dm, const double* __restrict__ d,
+                                                        const double* __restrict__ wt, const double* __restrict__ yt,
+                                                        const double* __restrict__ grid, const double* __restrict__ base, double l0,
+                                                        double* __restrict__ lrt, double* __restrict__ lam_out,
+                                                        double* __restrict__ p_out) {
+    __shared__ double s_l[LMM_GRID], s_dl[LMM_GRID];
+    const uint32_t v = blockIdx.x;
+    if (!vars[v].tested) {  // (the whole block leaves)
+        if (threadIdx.x == 0) lrt[v] = lam_out[v] = p_out[v] = __builtin_nan("");
+        return;
+    }
+    double l, lam;
+    maximise<true>(dm.n, d, wt, yt, Xt + (uint64_t)v * dm.ldi, G + (uint64_t)v * 3 * LMM_HB_COLS, grid, base, s_l, s_dl, l, lam);
+    if (threadIdx.x == 0) {
+        const double stat = fmax(0.0, 2.0 * (l - l0));
+        lrt[v] = stat;
+        lam_out[v] = lam;
+        p_out[v] = erfc(sqrt(0.5 * stat));
+    }
+}
+
+}  // namespace
+
+hipError_t launch_lmm_prep(const uint8_t* bed, uint32_t nv, LmmDims dm, double maf, double miss, uint8_t* codes, LmmVariant* vars,
+                           hipStream_t st) {
+    if (!nv) return hipSuccess;
+    hipLaunchKernelGGL(lmm_prep_kernel, dim3(nv), dim3(64), 0, st, bed, dm, maf, miss, codes, vars);
+    return hipGetLastError();
+}
+
+hipError_t launch_lmm_rotate(const uint8_t* codes, const LmmVariant* vars, uint32_t nv, LmmDims dm, const double* U, double* Xt,
+                             hipStream_t st) {
+    if (!nv) return hipSuccess;
+    const dim3 grid((nv + LMM_VTILE - 1) / LMM_VTILE, (dm.ldi / 64 + 3) / 4);
+    hipLaunchKernelGGL(lmm_rotate_kernel, grid, dim3(256), 0, st, codes, vars, nv, dm, U, Xt);
+    return hipGetLastError();
+}
+
+hipError_t launch_lmm_base(LmmDims dm, const double* d, const double* wt, const double* yt, const double* grid, double* base,
+                           hipStream_t st) {
+    hipLaunchKernelGGL(lmm_base_kernel, dim3(LMM_GRID), dim3(64), 0, st, dm, d, wt, yt, grid, base);
+    return hipGetLastError();
+}
+
+hipError_t launch_lmm_grid(const double* Xt, uint32_t nv, LmmDims dm, const double* wt, const double* yt, const double* HB, double* G,
+                           hipStream_t st) {
+    if (!nv) return hipSuccess;
+    const dim3 grid((nv + 63) / 64, (LMM_HB_COLS / 16 + 3) / 4);
+    hipLaunchKernelGGL(lmm_grid_kernel, grid, dim3(256), 0, st, Xt, nv, dm, wt, yt, HB, G);
+    return hipGetLastError();
+}
+
+hipError_t launch_lmm_null(LmmDims dm, const double* d, const double* wt, const double* yt, const double* grid, const double* base,
+                           double* out, hipStream_t st) {
+    hipLaunchKernelGGL(lmm_null_kernel, dim3(1), dim3(64), 0, st, dm, d, wt, yt, grid, base, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_lmm_refine(const double* Xt, const double* G, const LmmVariant* vars, uint32_t nv, LmmDims dm, const double* d,
+                             const double* wt, const double* yt, const double* grid, const double* base, double l0, double* lrt,
+                             double* lam, double* p, hipStream_t st) {
+    if (!nv) return hipSuccess;
+    hipLaunchKernelGGL(lmm_refine_kernel, dim3(nv), dim3(64), 0, st, Xt, G, vars, dm, d, wt, yt, grid, base, l0, lrt, lam, p);
+    return hipGetLastError();
+}
+
+}  // namespace kgwas

@@ -503,6 +503,68 @@ class Kinship:
         self.close()
 
 
+class LmmLrt:
+    """Mixed-model ML likelihood-ratio test (what the pipeline takes from `gemma -lmm 2`) of .bed variants on the GPU.
+
+    K is eigendecomposed once (host threads); every phenotype and .bed given to the object reuses that."""
+
+    def __init__(self, K: np.ndarray, device: int = 0, lmin: float = 1e-5, lmax: float = 1e5, chunk_variants: int = 10240):
+        K = np.ascontiguousarray(K, np.float64)
+        if K.ndim != 2 or K.shape[0] != K.shape[1]:
+            raise ValueError("K must be square")
+        self.n = K.shape[0]
+        self._h = C.c_void_p()
+        check(lib.kgwas_lmm_create(self.n, ptr(K), device, lmin, lmax, chunk_variants, C.byref(self._h)))
+
+    def _y(self, y):
+        y = np.ascontiguousarray(y, np.float64)
+        if y.shape != (self.n,):
+            raise ValueError("y must have one value per individual")
+        return y
+
+    def null(self, y):
+        """(log-likelihood, lambda) of the null model."""
+        l0, lam0 = C.c_double(), C.c_double()
+        check(lib.kgwas_lmm_null(self._h, ptr(self._y(y)), C.byref(l0), C.byref(lam0)))
+        return l0.value, lam0.value
+
+    def test(self, bed, y, maf: float = 0.0, miss: float = 1.0):
+        """bed: the .bed body as bytes or a uint8 array of (n + 3) // 4 bytes per variant. Returns a dict of numpy arrays
+        lrt, lambda, p, af, n_miss, tested (lrt, lambda and p are NaN where tested is False)."""
+        bps = (self.n + 3) // 4
+        body = np.frombuffer(bed, np.uint8) if isinstance(bed, (bytes, bytearray, memoryview)) else np.ascontiguousarray(bed, np.uint8)
+        if body.size % bps:
+            raise ValueError("the .bed body is not a whole number of variants of %d bytes" % bps)
+        m = body.size // bps
+        lrt, lam, p, af = (np.zeros(m) for _ in range(4))
+        n_miss, tested = np.zeros(m, np.uint32), np.zeros(m, np.uint8)
+        check(lib.kgwas_lmm_test_bed(self._h, ptr(self._y(y)), ptr(body), m, maf, miss, ptr(lrt), ptr(lam), ptr(p), ptr(af),
+                                     ptr(n_miss), ptr(tested)))
+        return {"lrt": lrt, "lambda": lam, "p": p, "af": af, "n_miss": n_miss, "tested": tested.astype(bool)}
+
+    def stats(self):
+        st = capi.LmmStats()
+        check(lib.kgwas_lmm_get_stats(self._h, C.byref(st)))
+        return st.as_dict()
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib.kgwas_lmm_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+
+def sym_eigen(K: np.ndarray, threads: int = 0):
+    """K = U diag(d) U^T on host threads: (d ascending, U with eigenvectors in columns)."""
+    K = np.ascontiguousarray(K, np.float64)
+    n = K.shape[0]
+    d, U = np.zeros(n), np.zeros((n, n))
+    check(lib.kgwas_sym_eigen(n, ptr(K), ptr(d), ptr(U), threads))
+    return d, U
+
+
 def kinship_from_partials(H: np.ndarray, n_used: int) -> np.ndarray:
     H = np.ascontiguousarray(H, np.uint64)
     K = np.zeros_like(H)
