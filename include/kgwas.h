@@ -231,8 +231,9 @@ typedef struct kgwas_scan_stats {
  * Version 10: no struct changed; new entry point kgwas_scan_debug_survivors (test hook).
  * Version 11: no struct changed; new entry point kgwas_list_kmers (list_kmers_found_in_multiple_samples).
  * Version 12: no struct changed; new entry points kgwas_count_kmers_files, kgwas_count_kmers_bases (count_kmers_with_strand).
- * Version 13: no struct changed; new struct kgwas_lmm_stats and entry points kgwas_sym_eigen, kgwas_lmm_* (lmm_lrt). */
-#define KGWAS_ABI_VERSION 13
+ * Version 13: no struct changed; new struct kgwas_lmm_stats and entry points kgwas_sym_eigen, kgwas_lmm_* (lmm_lrt).
+ * Version 14: no struct changed; new entry points kgwas_lmm_test_bed_multi, kgwas_lmm_run_file_multi (lmm_lrt --columns). */
+#define KGWAS_ABI_VERSION 14
 uint32_t kgwas_abi_version(void);
 
 int kgwas_scan_create(const kgwas_scan_params* p, kgwas_scan** out);
@@ -581,6 +582,20 @@ void kgwas_snpkin_close(kgwas_snpkin* h);
  *            replaced by ".log.txt"). The phenotype is field 5 + pheno_col of the .fam; individuals with "-9" or "NA" are
  *            dropped from K, y and the .bed. Consecutive beds that keep the same individuals share one eigendecomposition.
  *            total (may be NULL): the run's summed stats.
+ * test_bed_multi (ABI version 14): n_pheno phenotype columns Y[n_pheno][n] against ONE .bed body, the shape of the pipeline's
+ *            SNP branch (kmers_gwas.py:193-223: the phenotype and its permutations over one SNP panel). The .bed is copied, decoded
+ *            and rotated once per chunk, and the grid sums without y are made once; only the sums with y and the refinement run
+ *            per column. lrt, lambda, p are [n_pheno][n_variants]; logl0, lambda0 [n_pheno]; af, n_miss, tested [n_variants]; any
+ *            may be NULL. Every value has the bits that kgwas_lmm_null / kgwas_lmm_test_bed give for that column alone, for any
+ *            chunk_variants and any order of the columns. n_pheno == 0, a non-finite value or a constant column -> KGWAS_ERR_ARG
+ *            (the message names the column, from 0) before any device work; the handle stays usable. The call leaves the
+ *            phenotype that kgwas_lmm_null / kgwas_lmm_test_bed cache untouched. Its device buffers are allocated at the first
+ *            such call (0.55 GB at the default chunk_variants). Stats: variants_read counts a variant once, variants_tested once
+ *            per column; grid_ms takes the shared and the per-column sums.
+ * run_file_multi (ABI version 14): run_files for ONE bfile and n_cols columns of its .fam (pheno_cols, from 1): the .fam, the
+ *            .bim, the .bed and the kinship matrix are read once, K is eigendecomposed once, and out_paths[k] (with its log) gets
+ *            what run_files writes for column pheno_cols[k]. All columns must mark the same .fam lines as missing; otherwise
+ *            KGWAS_ERR_FORMAT, naming the first column that differs from the first one.
  * read_kinship / read_fam / format_assoc: the parsers and the line formatter of run_files (no GPU). read_fam gives every line's
  *            value (NaN when missing) and keep flag, up to cap entries, and the number of lines. format_assoc returns the bytes
  *            needed and writes them if cap allows; chr == NULL gives the header line.
@@ -598,6 +613,12 @@ int kgwas_lmm_test_bed(kgwas_lmm* h, const double* y, const uint8_t* bed_body, u
 int kgwas_lmm_run_files(const char* kinship_path, uint64_t n_beds, const char* const* bfile_bases, const char* const* out_paths,
                         uint32_t pheno_col, double maf, double miss, double lmin, double lmax, uint64_t chunk_variants, int32_t device,
                         kgwas_lmm_stats* total);
+int kgwas_lmm_test_bed_multi(kgwas_lmm* h, uint32_t n_pheno, const double* Y, const uint8_t* bed_body, uint64_t n_variants, double maf,
+                             double miss, double* lrt, double* lambda, double* p, double* logl0, double* lambda0, double* af,
+                             uint32_t* n_miss, uint8_t* tested);
+int kgwas_lmm_run_file_multi(const char* kinship_path, const char* bfile_base, uint32_t n_cols, const uint32_t* pheno_cols,
+                             const char* const* out_paths, double maf, double miss, double lmin, double lmax, uint64_t chunk_variants,
+                             int32_t device, kgwas_lmm_stats* total);
 int kgwas_lmm_get_stats(const kgwas_lmm* h, kgwas_lmm_stats* out);
 void kgwas_lmm_destroy(kgwas_lmm* h);
 int kgwas_lmm_read_kinship(const char* path, uint64_t n_expected, double* K);

@@ -3,13 +3,16 @@
 //     lmm_lrt -bfile B -lmm 2 -k KINSHIP -outdir D -o NAME [-n i] [-maf f] [-miss f] [-lmin x] [-lmax x]
 // and writes D/NAME.assoc.txt (chr rs ps n_miss allele1 allele0 af l_mle p_lrt; p_lrt is field 9, which functions.py reads)
 // and D/NAME.log.txt. Its own addition: --bfiles LIST, a file of "bfile<TAB>name" lines that all run against one
-// eigendecomposition of the kinship matrix. Defaults of -maf, -miss, -lmin, -lmax and -outdir are GEMMA's.
+// eigendecomposition of the kinship matrix; and --columns LIST (with -bfile), a file of "col<TAB>name" lines: the listed phenotype
+// columns of B.fam are all tested in ONE pass over B.bed (the SNP branch's 101 GEMMA runs over one panel, kmers_gwas.py:193-223),
+// output D/name.assoc.txt. Defaults of -maf, -miss, -lmin, -lmax and -outdir are GEMMA's.
 #include <sys/stat.h>
 
 #include <cstdlib>
 #include <fstream>
 #include <iostream>
 #include <map>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -20,9 +23,11 @@ using namespace std;
 
 static void usage(const char* prog) {
     cerr << "usage: " << prog
-         << " -bfile B | --bfiles LIST  -lmm 2  -k KINSHIP  [-outdir D] [-o NAME] [-n i] [-maf f] [-miss f] [-lmin x] [-lmax x]\n"
+         << " -bfile B [--columns LIST] | --bfiles LIST  -lmm 2  -k KINSHIP  [-outdir D] [-o NAME] [-n i] [-maf f] [-miss f] [-lmin x] [-lmax x]\n"
             "  -bfile B       PLINK base name (B.bed, B.bim, B.fam)\n"
             "  --bfiles LIST  file of 'bfile<TAB>name' lines: every bfile is tested, output D/name.assoc.txt\n"
+            "  --columns LIST file of 'col<TAB>name' lines, with -bfile: every listed phenotype column of B.fam (from 1) is tested in\n"
+            "                 one pass over B.bed, output D/name.assoc.txt (no -n, no -o); the columns must share their missing individuals\n"
             "  -lmm 2         the likelihood-ratio test (the only test built)\n"
             "  -k FILE        kinship matrix, text, one row per .fam line\n"
             "  -outdir D      output directory (default ./output), -o NAME output prefix (default result)\n"
@@ -44,7 +49,7 @@ static double num(const string& name, const string& s) {
 }
 
 int main(int argc, char* argv[]) {
-    static const char* const valued[] = {"bfile", "bfiles", "lmm", "k", "outdir", "o", "n", "maf", "miss", "lmin", "lmax", "chunk_variants"};
+    static const char* const valued[] = {"bfile", "bfiles", "lmm", "k", "outdir", "o", "n", "maf", "miss", "lmin", "lmax", "chunk_variants", "columns"};
     map<string, string> a;
     for (int i = 1; i < argc; i++) {
         string s = argv[i];
@@ -72,6 +77,10 @@ int main(int argc, char* argv[]) {
              << ": only -lmm 2, the likelihood-ratio test, is built (no Wald or score test)" << endl;
         return 1;
     }
+    if (a.count("columns") && (a.count("bfiles") || a.count("n") || a.count("o") || !a.count("bfile"))) {
+        cerr << "lmm_lrt: --columns needs -bfile and excludes --bfiles, -n and -o (LIST names the outputs)" << endl;
+        return 1;
+    }
     if (!a.count("k") || a.count("bfile") + a.count("bfiles") != 1) {
         cerr << "lmm_lrt: need -k and one of -bfile, --bfiles" << endl;
         usage(argv[0]);
@@ -79,7 +88,41 @@ int main(int argc, char* argv[]) {
     }
     const string outdir = a.count("outdir") ? a["outdir"] : "./output";
     vector<string> bases, outs;
-    if (a.count("bfile")) {
+    vector<uint32_t> columns;
+    if (a.count("columns")) {
+        ifstream f(a["columns"]);
+        if (!f.is_open()) {
+            cerr << "lmm_lrt: can't open " << a["columns"] << endl;
+            return 1;
+        }
+        set<string> names;
+        for (string line; getline(f, line);) {
+            if (!line.empty() && line.back() == '\r') line.pop_back();
+            if (line.empty()) continue;
+            const size_t tab = line.find('\t');
+            const string col = line.substr(0, tab == string::npos ? 0 : tab), name = tab == string::npos ? string() : line.substr(tab + 1);
+            if (col.empty() || col.size() > 6 || col.find_first_not_of("0123456789") != string::npos || name.empty() ||
+                name.find('\t') != string::npos) {
+                cerr << "lmm_lrt: " << a["columns"] << ": a line is not 'col<TAB>name': " << line << endl;
+                return 1;
+            }
+            if (stoul(col) < 1) {
+                cerr << "lmm_lrt: " << a["columns"] << ": phenotype columns start at 1: " << line << endl;
+                return 1;
+            }
+            if (!names.insert(name).second) {
+                cerr << "lmm_lrt: " << a["columns"] << ": the name '" << name << "' is given twice" << endl;
+                return 1;
+            }
+            columns.push_back((uint32_t)stoul(col));
+            outs.push_back(outdir + "/" + name + ".assoc.txt");
+        }
+        if (columns.empty()) {
+            cerr << "lmm_lrt: " << a["columns"] << " lists no column" << endl;
+            return 1;
+        }
+        bases.push_back(a["bfile"]);
+    } else if (a.count("bfile")) {
         bases.push_back(a["bfile"]);
         outs.push_back(outdir + "/" + (a.count("o") ? a["o"] : string("result")) + ".assoc.txt");
     } else {
@@ -109,18 +152,18 @@ int main(int argc, char* argv[]) {
     }
     (void)mkdir(outdir.c_str(), 0777);  // (an existing directory is fine; a failure shows when the output is written)
     vector<const char*> bp, op;
-    for (size_t i = 0; i < bases.size(); i++) {
-        bp.push_back(bases[i].c_str());
-        op.push_back(outs[i].c_str());
-    }
+    for (const string& b : bases) bp.push_back(b.c_str());
+    for (const string& o : outs) op.push_back(o.c_str());
     kgwas_lmm_stats st{};
-    const int rc = kgwas_lmm_run_files(a["k"].c_str(), bases.size(), bp.data(), op.data(), (uint32_t)col, maf, miss, lmin, lmax,
-                                       (uint64_t)chunk, 0, &st);
+    const int rc = columns.empty() ? kgwas_lmm_run_files(a["k"].c_str(), bases.size(), bp.data(), op.data(), (uint32_t)col, maf, miss, lmin,
+                                                         lmax, (uint64_t)chunk, 0, &st)
+                                   : kgwas_lmm_run_file_multi(a["k"].c_str(), bp[0], (uint32_t)columns.size(), columns.data(), op.data(), maf,
+                                                              miss, lmin, lmax, (uint64_t)chunk, 0, &st);
     if (rc != KGWAS_OK) {
         cerr << "lmm_lrt: " << kgwas_last_error() << endl;
         return rc == KGWAS_ERR_DEVICE ? 3 : 1;
     }
-    cerr << "[kgwas] lmm_lrt: files=" << bases.size() << " individuals=" << st.n_individuals << " variants_read=" << st.variants_read
+    cerr << "[kgwas] lmm_lrt: files=" << bases.size() << " columns=" << (columns.empty() ? 1 : columns.size()) << " individuals=" << st.n_individuals << " variants_read=" << st.variants_read
          << " variants_tested=" << st.variants_tested << " eigendecompositions=" << st.eigendecompositions << " ms: eigen=" << st.eigen_ms
          << " rotate=" << st.rotate_ms << " grid=" << st.grid_ms << " refine=" << st.refine_ms << endl;
     cli_finish();

@@ -6,9 +6,12 @@
 //            every phenotype and .bed given to the handle;
 // null     : yt = U^T (y - mean y) on the host in index order, the sums without x at the grid points, the null model's maximum;
 // test_bed : per chunk of variants the raw bytes go to the device, then prep, rotate, grid and refine run in order on one stream;
+// test_bed_multi: several phenotype columns against ONE .bed. Per chunk prep, rotate and the two grid sums without y run once; the
+//            xt yt sums and the refinement run per block of LMM_PBLOCK columns. Every number has the bits of test_bed's;
 // run_files: the file layer of the lmm_lrt tool - kinship text, .fam phenotype column, .bim, .bed in, .assoc.txt and .log.txt out.
 //            Individuals without a phenotype are dropped from K, y and the .bed rows before anything else; beds that keep the
-//            same individuals share one handle, so one eigendecomposition.
+//            same individuals share one handle, so one eigendecomposition. run_file_multi: one bfile, several .fam columns with
+//            one missing set, one pass over the .bed (the shape of kmers_gwas.py:193-223).
 // No CPU fallback: the statistics need the GPU. The parsers and the formatter run without one.
 #include <algorithm>
 #include <chrono>
@@ -44,6 +47,12 @@ struct kgwas_lmm {
     DevBuf<double> d_U, d_d, d_wt, d_yt, d_HB, d_grid, d_base, d_null, d_Xt, d_G, d_lrt, d_lam, d_p;
     DevBuf<uint8_t> d_bed, d_codes;
     DevBuf<LmmVariant> d_vars;
+    // the multi-phenotype pass (allocated at its first call): per column Yt, base sums and null model; per chunk the shared grid
+    // sums; per chunk and block of LMM_PBLOCK columns the xt yt sums and the results
+    bool multi_ready = false;  // the per-chunk buffers below are allocated
+    uint32_t multi_cols = 0;
+    DevBuf<double> d_Ytm, d_basem, d_nullm, d_Gx, d_Gxy, d_lrtm, d_lamm, d_pm;
+    std::vector<double> h_outm;
     ~kgwas_lmm() {
         if (!on_device) return;
         (void)hipSetDevice(device);
@@ -110,16 +119,15 @@ void device_init(kgwas_lmm* h) {
     for (hipEvent_t& e : h->ev) KGWAS_HIP(hipEventCreate(&e));
 }
 
-void fit_null(kgwas_lmm* h, const double* y) {
+// yt[ldi] (zeroed by the caller) = U^T (y - mean y), in index order; `where` ends the message of a refused y
+void rotate_phenotype(const kgwas_lmm* h, const double* y, double* yt, const std::string& where) {
     const uint64_t n = h->n;
-    if (h->have_null && memcmp(h->y_cur.data(), y, n * sizeof(double)) == 0) return;
     double mean = 0;
     for (uint64_t k = 0; k < n; k++) {
-        if (!std::isfinite(y[k])) throw Error(KGWAS_ERR_ARG, "kgwas_lmm: a phenotype value is not finite");
+        if (!std::isfinite(y[k])) throw Error(KGWAS_ERR_ARG, "kgwas_lmm: a phenotype value is not finite" + where);
         mean += y[k];
     }
     mean /= (double)n;
-    std::vector<double> yt(h->dm.ldi, 0.0);
     bool varies = false;
     for (uint64_t k = 0; k < n; k++) {
         const double yc = y[k] - mean;
@@ -127,7 +135,14 @@ void fit_null(kgwas_lmm* h, const double* y) {
         const double* u = &h->U[k * n];
         for (uint64_t i = 0; i < n; i++) yt[i] += u[i] * yc;
     }
-    if (!varies) throw Error(KGWAS_ERR_ARG, "kgwas_lmm: the phenotype is constant");
+    if (!varies) throw Error(KGWAS_ERR_ARG, "kgwas_lmm: the phenotype is constant" + where);
+}
+
+void fit_null(kgwas_lmm* h, const double* y) {
+    const uint64_t n = h->n;
+    if (h->have_null && memcmp(h->y_cur.data(), y, n * sizeof(double)) == 0) return;
+    std::vector<double> yt(h->dm.ldi, 0.0);
+    rotate_phenotype(h, y, yt.data(), "");
     KGWAS_HIP(hipSetDevice(h->device));
     h->have_null = false;
     KGWAS_HIP(hipMemcpyAsync(h->d_yt.p, yt.data(), yt.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -177,6 +192,102 @@ void test_bed(kgwas_lmm* h, const double* y, const uint8_t* body, uint64_t nv, d
             if (n_miss) n_miss[pos + v] = vars[v].n_miss;
             if (tested) tested[pos + v] = (uint8_t)vars[v].tested;
             h->st.variants_tested += vars[v].tested;
+        }
+        h->st.variants_read += c;
+    }
+}
+
+// The multi-phenotype pass. Nothing of the single-phenotype null (y_cur, have_null, d_yt, d_base, l0) is touched.
+// multi_prepare: Y[n_pheno][n] -> Yt, the base sums and the null models of all columns on the device; logl0, lambda0 [n_pheno].
+void multi_prepare(kgwas_lmm* h, uint32_t n_pheno, const double* Y, double* logl0, double* lambda0) {
+    if (!n_pheno) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_test_bed_multi: n_pheno is 0");
+    const uint64_t n = h->n, ldi = h->dm.ldi, chunk = h->chunk;
+    std::vector<double> Yt((uint64_t)n_pheno * ldi, 0.0);
+    for (uint32_t k = 0; k < n_pheno; k++) rotate_phenotype(h, Y + k * n, &Yt[k * ldi], " (column " + std::to_string(k) + ")");
+    KGWAS_HIP(hipSetDevice(h->device));
+    if (!h->multi_ready) {
+        h->d_Gx.alloc(chunk * 2 * LMM_HB_COLS);
+        h->d_Gxy.alloc(chunk * LMM_PBLOCK * LMM_HB_COLS);
+        h->d_lrtm.alloc(chunk * LMM_PBLOCK);
+        h->d_lamm.alloc(chunk * LMM_PBLOCK);
+        h->d_pm.alloc(chunk * LMM_PBLOCK);
+        h->h_outm.resize(3 * chunk * LMM_PBLOCK);
+        h->multi_ready = true;
+    }
+    if (n_pheno > h->multi_cols) {
+        h->multi_cols = 0;
+        h->d_Ytm.alloc((uint64_t)n_pheno * ldi);
+        h->d_basem.alloc((uint64_t)n_pheno * LMM_GRID * LMM_BASE);
+        h->d_nullm.alloc(2 * (uint64_t)n_pheno);
+        h->multi_cols = n_pheno;
+    }
+    hipStream_t st = h->stream;
+    KGWAS_HIP(hipMemcpyAsync(h->d_Ytm.p, Yt.data(), Yt.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    KGWAS_HIP(launch_lmm_base_multi(h->dm, h->d_d.p, h->d_wt.p, h->d_Ytm.p, n_pheno, h->d_grid.p, h->d_basem.p, st));
+    KGWAS_HIP(launch_lmm_null_multi(h->dm, h->d_d.p, h->d_wt.p, h->d_Ytm.p, n_pheno, h->d_grid.p, h->d_basem.p, h->d_nullm.p, st));
+    std::vector<double> nulls(2 * (uint64_t)n_pheno);
+    KGWAS_HIP(hipMemcpyAsync(nulls.data(), h->d_nullm.p, nulls.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    KGWAS_HIP(hipStreamSynchronize(st));  // (Yt is read by the copy until here)
+    for (uint32_t k = 0; k < n_pheno; k++) {
+        if (logl0) logl0[k] = nulls[2 * k];
+        if (lambda0) lambda0[k] = nulls[2 * k + 1];
+    }
+}
+
+// multi_run: nv variants against the n_pheno columns multi_prepare left on the device; lrt, lam, p are [n_pheno][nv]. Per chunk
+// prep, rotate and the shared grid sums run once; the xt yt sums and the refinement per block of LMM_PBLOCK columns.
+void multi_run(kgwas_lmm* h, uint32_t n_pheno, const uint8_t* body, uint64_t nv, double maf, double miss, double* lrt, double* lam,
+               double* p, double* af, uint32_t* n_miss, uint8_t* tested) {
+    KGWAS_HIP(hipSetDevice(h->device));
+    const uint64_t ldi = h->dm.ldi, chunk = h->chunk;
+    hipStream_t st = h->stream;
+    std::vector<LmmVariant> vars;
+    for (uint64_t pos = 0; pos < nv; pos += chunk) {
+        const uint32_t c = (uint32_t)std::min<uint64_t>(chunk, nv - pos);
+        KGWAS_HIP(hipMemcpyAsync(h->d_bed.p, body + pos * h->dm.bps, (size_t)c * h->dm.bps, hipMemcpyHostToDevice, st));
+        KGWAS_HIP(hipEventRecord(h->ev[0], st));
+        KGWAS_HIP(launch_lmm_prep(h->d_bed.p, c, h->dm, maf, miss, h->d_codes.p, h->d_vars.p, st));
+        KGWAS_HIP(launch_lmm_rotate(h->d_codes.p, h->d_vars.p, c, h->dm, h->d_U.p, h->d_Xt.p, st));
+        KGWAS_HIP(hipEventRecord(h->ev[1], st));
+        KGWAS_HIP(launch_lmm_grid_shared(h->d_Xt.p, c, h->dm, h->d_wt.p, h->d_HB.p, h->d_Gx.p, st));
+        KGWAS_HIP(hipEventRecord(h->ev[2], st));
+        vars.resize(c);
+        KGWAS_HIP(hipMemcpyAsync(vars.data(), h->d_vars.p, c * sizeof(LmmVariant), hipMemcpyDeviceToHost, st));
+        KGWAS_HIP(hipStreamSynchronize(st));
+        float ms[2] = {0, 0};
+        for (int k = 0; k < 2; k++) KGWAS_HIP(hipEventElapsedTime(&ms[k], h->ev[k], h->ev[k + 1]));
+        h->st.rotate_ms += ms[0];
+        h->st.grid_ms += ms[1];
+        for (uint32_t p0 = 0; p0 < n_pheno; p0 += LMM_PBLOCK) {
+            const uint32_t pb = std::min(LMM_PBLOCK, n_pheno - p0);
+            const uint64_t cnt = (uint64_t)pb * c;
+            const double* Ytb = h->d_Ytm.p + (uint64_t)p0 * ldi;
+            KGWAS_HIP(hipEventRecord(h->ev[1], st));
+            KGWAS_HIP(launch_lmm_grid_xy(h->d_Xt.p, c, h->dm, Ytb, pb, h->d_HB.p, h->d_Gxy.p, st));
+            KGWAS_HIP(hipEventRecord(h->ev[2], st));
+            KGWAS_HIP(launch_lmm_refine_multi(h->d_Xt.p, h->d_Gx.p, h->d_Gxy.p, h->d_vars.p, c, h->dm, h->d_d.p, h->d_wt.p, Ytb, pb,
+                                              h->d_grid.p, h->d_basem.p + (uint64_t)p0 * LMM_GRID * LMM_BASE, h->d_nullm.p + 2 * (uint64_t)p0,
+                                              h->d_lrtm.p, h->d_lamm.p, h->d_pm.p, st));
+            KGWAS_HIP(hipEventRecord(h->ev[3], st));
+            double* const host[3] = {lrt, lam, p};
+            const double* const dev[3] = {h->d_lrtm.p, h->d_lamm.p, h->d_pm.p};
+            for (int a = 0; a < 3; a++)
+                if (host[a]) KGWAS_HIP(hipMemcpyAsync(&h->h_outm[a * cnt], dev[a], cnt * sizeof(double), hipMemcpyDeviceToHost, st));
+            KGWAS_HIP(hipStreamSynchronize(st));
+            for (int k = 0; k < 2; k++) KGWAS_HIP(hipEventElapsedTime(&ms[k], h->ev[k + 1], h->ev[k + 2]));
+            h->st.grid_ms += ms[0];
+            h->st.refine_ms += ms[1];
+            for (int a = 0; a < 3; a++)
+                if (host[a])
+                    for (uint32_t k = 0; k < pb; k++)
+                        memcpy(host[a] + (uint64_t)(p0 + k) * nv + pos, &h->h_outm[a * cnt + (uint64_t)k * c], c * sizeof(double));
+        }
+        h->st.chunks++;
+        for (uint32_t v = 0; v < c; v++) {
+            if (af) af[pos + v] = vars[v].af;
+            if (n_miss) n_miss[pos + v] = vars[v].n_miss;
+            if (tested) tested[pos + v] = (uint8_t)vars[v].tested;
+            h->st.variants_tested += (uint64_t)vars[v].tested * n_pheno;
         }
         h->st.variants_read += c;
     }
@@ -317,6 +428,112 @@ void add_stats(kgwas_lmm_stats& a, const kgwas_lmm_stats& b) {
     a.n_individuals = b.n_individuals;
 }
 
+// ---- what run_files and run_file_multi share ----
+
+std::vector<uint32_t> kept_lines(const std::vector<uint8_t>& keep) {
+    std::vector<uint32_t> idx;
+    for (uint64_t i = 0; i < keep.size(); i++)
+        if (keep[i]) idx.push_back((uint32_t)i);
+    return idx;
+}
+
+kgwas_lmm* create_for_kept(const std::vector<double>& Kfull, uint64_t nf, const std::vector<uint32_t>& idx, int device, double lmin,
+                           double lmax, uint64_t chunk_variants) {
+    const uint64_t n = idx.size();
+    std::vector<double> K(n * n);
+    for (uint64_t r = 0; r < n; r++)
+        for (uint64_t c = 0; c < n; c++) K[r * n + c] = Kfull[(uint64_t)idx[r] * nf + idx[c]];
+    return create(n, K.data(), device, lmin, lmax, chunk_variants);
+}
+
+// the .bim lines and the .bed body of <base>, the latter with the codes of the kept individuals idx (of nf .fam lines) alone
+void read_bim_bed(const std::string& base, uint64_t nf, const std::vector<uint32_t>& idx, std::vector<std::string>& bim,
+                  std::vector<uint8_t>& body) {
+    bim = read_lines(base + ".bim", "bim");
+    const uint64_t n = idx.size(), M = bim.size(), bps_f = (nf + 3) / 4, bps = (n + 3) / 4;
+    {
+        std::ifstream f(base + ".bed", std::ios::binary | std::ios::ate);
+        if (!f.is_open()) throw Error(KGWAS_ERR_IO, "can't open bed file: " + base + ".bed");
+        const uint64_t size = (uint64_t)f.tellg();
+        if (size != 3 + M * bps_f)
+            throw Error(KGWAS_ERR_FORMAT, base + ".bed has " + std::to_string(size) + " bytes, " + std::to_string(M) + " variants of " +
+                                              std::to_string(nf) + " individuals need " + std::to_string(3 + M * bps_f));
+        f.seekg(0);
+        uint8_t magic[3];
+        f.read((char*)magic, 3);
+        if (magic[0] != 0x6C || magic[1] != 0x1B || magic[2] != 0x01)
+            throw Error(KGWAS_ERR_FORMAT, base + ".bed: not a SNP-major PLINK .bed (magic 6C 1B 01)");
+        body.resize(M * bps_f);
+        f.read((char*)body.data(), (std::streamsize)body.size());
+        if (!f) throw Error(KGWAS_ERR_IO, "short read of " + base + ".bed");
+    }
+    if (n != nf) {  // the kept individuals' codes, packed again
+        std::vector<uint8_t> packed(M * bps, 0);
+        for (uint64_t v = 0; v < M; v++) {
+            const uint8_t* src = &body[v * bps_f];
+            uint8_t* dst = &packed[v * bps];
+            for (uint64_t r = 0; r < n; r++) dst[r >> 2] |= (uint8_t)(((src[idx[r] >> 2] >> (2 * (idx[r] & 3))) & 3) << (2 * (r & 3)));
+        }
+        body.swap(packed);
+    }
+}
+
+std::string assoc_header() {
+    std::string text(format_assoc(nullptr, "", "", 0, "", "", 0, 0, 0, nullptr, 0), '\0');
+    format_assoc(nullptr, "", "", 0, "", "", 0, 0, 0, &text[0], text.size());
+    return text;
+}
+
+// the fields of the .bim lines of the tested ones among variants first .. first + cnt (tested starts at `first`; the others stay empty)
+std::vector<std::vector<std::string>> bim_fields(const std::string& base, const std::vector<std::string>& bim, uint64_t first, uint64_t cnt,
+                                                 const uint8_t* tested) {
+    std::vector<std::vector<std::string>> fields(cnt);
+    for (uint64_t v = 0; v < cnt; v++) {
+        if (!tested[v]) continue;
+        fields[v] = split_ws(bim[first + v]);
+        if (fields[v].size() < 6)
+            throw Error(KGWAS_ERR_FORMAT, base + ".bim: line " + std::to_string(first + v + 1) + " has fewer than 6 fields");
+    }
+    return fields;
+}
+
+// appends the lines of the tested ones among fields.size() variants (all arrays start at the first of them); returns their number
+uint64_t append_assoc(std::string& text, const std::vector<std::vector<std::string>>& fields, const uint32_t* n_miss, const double* af,
+                      const double* lam, const double* p, const uint8_t* tested) {
+    uint64_t n_tested = 0;
+    for (uint64_t v = 0; v < fields.size(); v++) {
+        if (!tested[v]) continue;
+        const std::vector<std::string>& f = fields[v];
+        char line[1024];
+        const uint64_t len = format_assoc(f[0].c_str(), f[1].c_str(), f[3].c_str(), n_miss[v], f[4].c_str(), f[5].c_str(), af[v], lam[v],
+                                          p[v], line, sizeof(line));
+        text.append(line, len);
+        n_tested++;
+    }
+    return n_tested;
+}
+
+void write_text(const std::string& path, const std::string& text, const char* mode) {
+    FILE* fo = fopen(path.c_str(), mode);
+    const bool ok = fo && fwrite(text.data(), 1, text.size(), fo) == text.size();
+    if ((fo && fclose(fo) != 0) || !ok) throw Error(KGWAS_ERR_IO, "can't write " + path);
+}
+
+void write_log(const std::string& out, const std::string& base, const char* kinship_path, uint64_t nf, uint64_t n, uint64_t M,
+               uint64_t n_tested, double lambda0, double l0, double eigen_ms, double rotate_ms, double grid_ms, double refine_ms,
+               double total_ms) {
+    char log[1024];
+    const int ll = snprintf(log, sizeof(log),
+                            "lmm_lrt: ML likelihood-ratio test (-lmm 2)\nbfile\t%s\nkinship\t%s\nindividuals_in_fam\t%llu\n"
+                            "individuals_used\t%llu\nvariants_read\t%llu\nvariants_tested\t%llu\nlambda0\t%.6e\nlogl_H0\t%.6f\n"
+                            "ms: eigen=%.3f rotate=%.3f grid=%.3f refine=%.3f total=%.3f\n",
+                            base.c_str(), kinship_path, (unsigned long long)nf, (unsigned long long)n, (unsigned long long)M,
+                            (unsigned long long)n_tested, lambda0, l0, eigen_ms, rotate_ms, grid_ms, refine_ms, total_ms);
+    FILE* fl = fopen(log_path_of(out).c_str(), "wb");
+    if (!fl || ll < 0 || fwrite(log, 1, (size_t)std::min<int>(ll, sizeof(log) - 1), fl) == 0 || fclose(fl) != 0)
+        throw Error(KGWAS_ERR_IO, "can't write " + log_path_of(out));
+}
+
 void run_files(const char* kinship_path, uint64_t n_beds, const char* const* bases, const char* const* outs, uint32_t pheno_col,
                double maf, double miss, double lmin, double lmax, uint64_t chunk_variants, int device, kgwas_lmm_stats* total) {
     if (!kinship_path || (n_beds && (!bases || !outs))) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_run_files: null argument");
@@ -332,84 +549,93 @@ void run_files(const char* kinship_path, uint64_t n_beds, const char* const* bas
         read_fam(base + ".fam", pheno_col, vals, keep);
         const uint64_t nf = vals.size();
         if (Kfull.empty() || Kfull.size() != nf * nf) Kfull = read_kinship(kinship_path, nf);
-        std::vector<uint32_t> idx;
-        for (uint64_t i = 0; i < nf; i++)
-            if (keep[i]) idx.push_back((uint32_t)i);
+        const std::vector<uint32_t> idx = kept_lines(keep);
         const uint64_t n = idx.size();
         if (!h || keep != keep_cur) {
             if (h) add_stats(sum, h->st);
             h.reset();
-            std::vector<double> K(n * n), y;
-            for (uint64_t r = 0; r < n; r++)
-                for (uint64_t c = 0; c < n; c++) K[r * n + c] = Kfull[(uint64_t)idx[r] * nf + idx[c]];
-            h.reset(create(n, K.data(), device, lmin, lmax, chunk_variants));
+            h.reset(create_for_kept(Kfull, nf, idx, device, lmin, lmax, chunk_variants));
             keep_cur = keep;
         }
         std::vector<double> y(n);
         for (uint64_t r = 0; r < n; r++) y[r] = vals[idx[r]];
-        const std::vector<std::string> bim = read_lines(base + ".bim", "bim");
-        const uint64_t M = bim.size(), bps_f = (nf + 3) / 4, bps = (n + 3) / 4;
+        std::vector<std::string> bim;
         std::vector<uint8_t> body;
-        {
-            std::ifstream f(base + ".bed", std::ios::binary | std::ios::ate);
-            if (!f.is_open()) throw Error(KGWAS_ERR_IO, "can't open bed file: " + base + ".bed");
-            const uint64_t size = (uint64_t)f.tellg();
-            if (size != 3 + M * bps_f)
-                throw Error(KGWAS_ERR_FORMAT, base + ".bed has " + std::to_string(size) + " bytes, " + std::to_string(M) + " variants of " +
-                                                  std::to_string(nf) + " individuals need " + std::to_string(3 + M * bps_f));
-            f.seekg(0);
-            uint8_t magic[3];
-            f.read((char*)magic, 3);
-            if (magic[0] != 0x6C || magic[1] != 0x1B || magic[2] != 0x01)
-                throw Error(KGWAS_ERR_FORMAT, base + ".bed: not a SNP-major PLINK .bed (magic 6C 1B 01)");
-            body.resize(M * bps_f);
-            f.read((char*)body.data(), (std::streamsize)body.size());
-            if (!f) throw Error(KGWAS_ERR_IO, "short read of " + base + ".bed");
-        }
-        if (n != nf) {  // the kept individuals' codes, packed again
-            std::vector<uint8_t> packed(M * bps, 0);
-            for (uint64_t v = 0; v < M; v++) {
-                const uint8_t* src = &body[v * bps_f];
-                uint8_t* dst = &packed[v * bps];
-                for (uint64_t r = 0; r < n; r++) dst[r >> 2] |= (uint8_t)(((src[idx[r] >> 2] >> (2 * (idx[r] & 3))) & 3) << (2 * (r & 3)));
-            }
-            body.swap(packed);
-        }
+        read_bim_bed(base, nf, idx, bim, body);
+        const uint64_t M = bim.size();
         std::vector<double> lrt(M), lam(M), p(M), af(M);
         std::vector<uint32_t> n_miss(M);
         std::vector<uint8_t> tested(M);
         const kgwas_lmm_stats before = h->st;
         test_bed(h.get(), y.data(), body.data(), M, maf, miss, lrt.data(), lam.data(), p.data(), af.data(), n_miss.data(), tested.data());
-        std::string text(format_assoc(nullptr, "", "", 0, "", "", 0, 0, 0, nullptr, 0), '\0');
-        format_assoc(nullptr, "", "", 0, "", "", 0, 0, 0, &text[0], text.size());
-        uint64_t n_tested = 0;
-        for (uint64_t v = 0; v < M; v++) {
-            if (!tested[v]) continue;
-            const std::vector<std::string> f = split_ws(bim[v]);
-            if (f.size() < 6) throw Error(KGWAS_ERR_FORMAT, base + ".bim: line " + std::to_string(v + 1) + " has fewer than 6 fields");
-            char line[1024];
-            const uint64_t len = format_assoc(f[0].c_str(), f[1].c_str(), f[3].c_str(), n_miss[v], f[4].c_str(), f[5].c_str(), af[v], lam[v],
-                                              p[v], line, sizeof(line));
-            text.append(line, len);
-            n_tested++;
-        }
-        FILE* fo = fopen(out.c_str(), "wb");
-        if (!fo || fwrite(text.data(), 1, text.size(), fo) != text.size() || fclose(fo) != 0)
-            throw Error(KGWAS_ERR_IO, "can't write " + out);
-        char log[1024];
-        const int ll = snprintf(log, sizeof(log),
-                                "lmm_lrt: ML likelihood-ratio test (-lmm 2)\nbfile\t%s\nkinship\t%s\nindividuals_in_fam\t%llu\n"
-                                "individuals_used\t%llu\nvariants_read\t%llu\nvariants_tested\t%llu\nlambda0\t%.6e\nlogl_H0\t%.6f\n"
-                                "ms: eigen=%.3f rotate=%.3f grid=%.3f refine=%.3f total=%.3f\n",
-                                base.c_str(), kinship_path, (unsigned long long)nf, (unsigned long long)n, (unsigned long long)M,
-                                (unsigned long long)n_tested, h->lambda0, h->l0, h->st.eigen_ms, h->st.rotate_ms - before.rotate_ms,
-                                h->st.grid_ms - before.grid_ms, h->st.refine_ms - before.refine_ms, now_ms() - t_start);
-        FILE* fl = fopen(log_path_of(out).c_str(), "wb");
-        if (!fl || ll < 0 || fwrite(log, 1, (size_t)std::min<int>(ll, sizeof(log) - 1), fl) == 0 || fclose(fl) != 0)
-            throw Error(KGWAS_ERR_IO, "can't write " + log_path_of(out));
+        std::string text = assoc_header();
+        const uint64_t n_tested =
+            append_assoc(text, bim_fields(base, bim, 0, M, tested.data()), n_miss.data(), af.data(), lam.data(), p.data(), tested.data());
+        write_text(out, text, "wb");
+        write_log(out, base, kinship_path, nf, n, M, n_tested, h->lambda0, h->l0, h->st.eigen_ms, h->st.rotate_ms - before.rotate_ms,
+                  h->st.grid_ms - before.grid_ms, h->st.refine_ms - before.refine_ms, now_ms() - t_start);
     }
     if (h) add_stats(sum, h->st);
     if (total) *total = sum;
+}
+
+// One bfile, n_cols phenotype columns of its .fam with one missing set: the .bed, the .bim and the kinship matrix are read once,
+// K is eigendecomposed once, and every chunk of variants goes through the multi-phenotype pass. Results are written in slabs
+// of variants, so that the [column][variant] arrays stay small for a panel of millions of variants.
+void run_file_multi(const char* kinship_path, const char* bfile_base, uint32_t n_cols, const uint32_t* cols, const char* const* outs,
+                    double maf, double miss, double lmin, double lmax, uint64_t chunk_variants, int device, kgwas_lmm_stats* total) {
+    if (!kinship_path || !bfile_base || !cols || !outs) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_run_file_multi: null argument");
+    if (!n_cols) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_run_file_multi: no phenotype column given");
+    const std::string base = bfile_base;
+    const double t_start = now_ms();
+    std::vector<std::vector<double>> vals(n_cols);
+    std::vector<uint8_t> keep;
+    for (uint32_t k = 0; k < n_cols; k++) {
+        std::vector<uint8_t> keep_k;
+        read_fam(base + ".fam", cols[k], vals[k], keep_k);
+        if (k == 0)
+            keep = keep_k;
+        else if (keep_k != keep)
+            throw Error(KGWAS_ERR_FORMAT, base + ".fam: phenotype column " + std::to_string(cols[k]) + " marks other individuals as missing than column " +
+                                              std::to_string(cols[0]) + "; columns of one run must share their missing set");
+    }
+    const uint64_t nf = keep.size();
+    const std::vector<double> Kfull = read_kinship(kinship_path, nf);
+    const std::vector<uint32_t> idx = kept_lines(keep);
+    const uint64_t n = idx.size();
+    std::unique_ptr<kgwas_lmm> h(create_for_kept(Kfull, nf, idx, device, lmin, lmax, chunk_variants));
+    std::vector<double> Y((uint64_t)n_cols * n);
+    for (uint32_t k = 0; k < n_cols; k++)
+        for (uint64_t r = 0; r < n; r++) Y[k * n + r] = vals[k][idx[r]];
+    std::vector<std::string> bim;
+    std::vector<uint8_t> body;
+    read_bim_bed(base, nf, idx, bim, body);
+    const uint64_t M = bim.size(), bps = (n + 3) / 4;
+    std::vector<double> l0(n_cols), lambda0(n_cols);
+    multi_prepare(h.get(), n_cols, Y.data(), l0.data(), lambda0.data());
+    for (uint32_t k = 0; k < n_cols; k++) write_text(outs[k], assoc_header(), "wb");
+    // a slab: whole chunks, about 4 M (variant, column) pairs
+    const uint64_t slab = std::max<uint64_t>(1, (1u << 22) / ((uint64_t)n_cols * h->chunk)) * h->chunk;
+    std::vector<double> lrt(std::min(slab, M) * n_cols), lam(lrt.size()), p(lrt.size()), af(std::min(slab, M));
+    std::vector<uint32_t> n_miss(af.size());
+    std::vector<uint8_t> tested(af.size());
+    std::vector<uint64_t> n_tested(n_cols, 0);
+    for (uint64_t first = 0; first < M; first += slab) {
+        const uint64_t cnt = std::min(slab, M - first);
+        multi_run(h.get(), n_cols, body.data() + first * bps, cnt, maf, miss, lrt.data(), lam.data(), p.data(), af.data(), n_miss.data(),
+                  tested.data());
+        const std::vector<std::vector<std::string>> fields = bim_fields(base, bim, first, cnt, tested.data());  // once for all columns
+        for (uint32_t k = 0; k < n_cols; k++) {
+            std::string text;
+            n_tested[k] += append_assoc(text, fields, n_miss.data(), af.data(), &lam[k * cnt], &p[k * cnt], tested.data());
+            write_text(outs[k], text, "ab");
+        }
+    }
+    const double total_ms = now_ms() - t_start;
+    for (uint32_t k = 0; k < n_cols; k++)  // (the kernels' times are the shared pass's, the same in every column's log)
+        write_log(outs[k], base, kinship_path, nf, n, M, n_tested[k], lambda0[k], l0[k], h->st.eigen_ms, h->st.rotate_ms, h->st.grid_ms,
+                  h->st.refine_ms, total_ms);
+    if (total) *total = h->st;
 }
 
 }  // namespace
@@ -437,6 +663,24 @@ int kgwas_lmm_test_bed(kgwas_lmm* h, const double* y, const uint8_t* bed_body, u
     return guarded([&] {
         if (!h || !y || (!bed_body && n_variants)) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_test_bed: null argument");
         test_bed(h, y, bed_body, n_variants, maf, miss, lrt, lambda, p, af, n_miss, tested);
+    });
+}
+
+int kgwas_lmm_test_bed_multi(kgwas_lmm* h, uint32_t n_pheno, const double* Y, const uint8_t* bed_body, uint64_t n_variants, double maf,
+                             double miss, double* lrt, double* lambda, double* p, double* logl0, double* lambda0, double* af,
+                             uint32_t* n_miss, uint8_t* tested) {
+    return guarded([&] {
+        if (!h || (!Y && n_pheno) || (!bed_body && n_variants)) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_test_bed_multi: null argument");
+        multi_prepare(h, n_pheno, Y, logl0, lambda0);
+        multi_run(h, n_pheno, bed_body, n_variants, maf, miss, lrt, lambda, p, af, n_miss, tested);
+    });
+}
+
+int kgwas_lmm_run_file_multi(const char* kinship_path, const char* bfile_base, uint32_t n_cols, const uint32_t* pheno_cols,
+                             const char* const* out_paths, double maf, double miss, double lmin, double lmax, uint64_t chunk_variants,
+                             int32_t device, kgwas_lmm_stats* total) {
+    return guarded([&] {
+        run_file_multi(kinship_path, bfile_base, n_cols, pheno_cols, out_paths, maf, miss, lmin, lmax, chunk_variants, device, total);
     });
 }
 

@@ -11,6 +11,9 @@ constexpr uint32_t LMM_HB_COLS = 208;   // the h table's columns: h at the 101 p
 constexpr uint32_t LMM_BASE = 8;        // per grid point: sum h, sum log h, Sww, Swy, Syy, then Sww', Swy', Syy' (weights dh)
 constexpr uint32_t LMM_VTILE = 32;      // variants per wave of the rotation; chunk buffers are padded to it
 constexpr uint32_t LMM_REFINE_STEPS = 12;
+constexpr uint32_t LMM_PTILE = 4;       // phenotype columns a wave of lmm_grid_xy_kernel holds accumulators for
+constexpr uint32_t LMM_PBLOCK = 32;     // phenotype columns per launch of the multi-phenotype pass: Gxy is chunk x 32 x 208 doubles,
+                                        // 545 MB at the default chunk of 10 240 variants
 
 struct LmmVariant {  // what lmm_prep leaves per variant
     double val[4];   // value of .bed code 0..3, centred: 2 - mean, 0 (missing), 1 - mean, 0 - mean
@@ -37,12 +40,29 @@ hipError_t launch_lmm_base(LmmDims dm, const double* d, const double* wt, const 
 // G[v][3][LMM_HB_COLS]: sums over i of HB[i][c] * (xt^2, xt wt, xt yt)
 hipError_t launch_lmm_grid(const double* Xt, uint32_t nv, LmmDims dm, const double* wt, const double* yt, const double* HB, double* G,
                            hipStream_t st);
+// the same for np columns: Yt[np][ldi] -> base[np][LMM_GRID][LMM_BASE], each block with the bits of a single call
+hipError_t launch_lmm_base_multi(LmmDims dm, const double* d, const double* wt, const double* Yt, uint32_t np, const double* lambda,
+                                 double* base, hipStream_t st);
+// Gx[v][2][LMM_HB_COLS]: the xt^2 and xt wt rows of launch_lmm_grid's G, the same bits
+hipError_t launch_lmm_grid_shared(const double* Xt, uint32_t nv, LmmDims dm, const double* wt, const double* HB, double* Gx,
+                                  hipStream_t st);
+// Gxy[p][v][LMM_HB_COLS], p < np <= LMM_PBLOCK, v < nv: the xt yt row of launch_lmm_grid's G for yt = Yt[p], the same bits
+hipError_t launch_lmm_grid_xy(const double* Xt, uint32_t nv, LmmDims dm, const double* Yt, uint32_t np, const double* HB, double* Gxy,
+                              hipStream_t st);
 // the null model: out[0] = l0, out[1] = lambda0
 hipError_t launch_lmm_null(LmmDims dm, const double* d, const double* wt, const double* yt, const double* lambda, const double* base,
                            double* out, hipStream_t st);
+// the null models of np columns: out[p] = (l0, lambda0)
+hipError_t launch_lmm_null_multi(LmmDims dm, const double* d, const double* wt, const double* Yt, uint32_t np, const double* lambda,
+                                 const double* base, double* out, hipStream_t st);
 // per tested variant: lrt, lambda, p (NaN for the others)
 hipError_t launch_lmm_refine(const double* Xt, const double* G, const LmmVariant* vars, uint32_t nv, LmmDims dm, const double* d,
                              const double* wt, const double* yt, const double* lambda, const double* base, double l0, double* lrt,
                              double* lam, double* p, hipStream_t st);
+// the same per (variant, column) of a block of np <= LMM_PBLOCK columns, results at [p][v] (row stride nv); Yt, base and null
+// (pairs l0, lambda0) start at the block's first column
+hipError_t launch_lmm_refine_multi(const double* Xt, const double* Gx, const double* Gxy, const LmmVariant* vars, uint32_t nv, LmmDims dm,
+                                   const double* d, const double* wt, const double* Yt, uint32_t np, const double* lambda,
+                                   const double* base, const double* null, double* lrt, double* lam, double* p, hipStream_t st);
 
 }  // namespace kgwas

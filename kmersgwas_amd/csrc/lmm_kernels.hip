@@ -14,7 +14,10 @@
 //   lmm_base_kernel    the sums without x at the 101 grid points (one wave each);
 //   lmm_grid_kernel    G = [xt^2 | xt wt | xt yt] . HB on the same MFMA: per variant the three x sums at all grid points, with
 //                      weights h and h';
-//   lmm_null_kernel / lmm_refine_kernel   one wave per model: l and dl/dt at the grid points, then every interval where dl/dt
+//   lmm_grid_xy_kernel the xt yt sums alone, for a block of phenotype columns that share one .bed: a wave keeps its xt values and
+//                      HB operands for LMM_PTILE columns at once. Every sum is the MFMA chain of lmm_grid_kernel's third row, so
+//                      its bits are those of the single-phenotype pass; lmm_grid_kernel<2> leaves the two shared rows;
+//   lmm_null_kernel / lmm_refine_kernel / lmm_refine_multi_kernel   one wave per model: l and dl/dt at the grid points, then every interval where dl/dt
 //                      goes from + to - is refined by LMM_REFINE_STEPS bracketing steps (secant with the Illinois correction,
 //                      every third one a bisection) whose sums run over i with lanes striding and a fixed butterfly; the
 //                      evaluated point with the smallest |dl/dt| is the interval's candidate. Both ends and every such point
@@ -117,6 +120,9 @@ __global__ void __launch_bounds__(256) lmm_rotate_kernel(const uint8_t* __restri
                 Xt[(uint64_t)(v0 + 16 * m + q + 4 * j) * dm.ldi + i0 + 16 * t + r] = acc[m][t][j];
 }
 
+// NS = 3: the rows xt^2, xt wt, xt yt of G[v][3][LMM_HB_COLS]; NS = 2: the first two alone, G[v][2][LMM_HB_COLS] (yt is not read).
+// Every accumulator is a chain of its own, so a row's bits do not depend on NS.
+template <int NS>
 __global__ void __launch_bounds__(256) lmm_grid_kernel(const double* __restrict__ Xt, uint32_t nv, LmmDims dm,
                                                        const double* __restrict__ wt, const double* __restrict__ yt,
                                                        const double* __restrict__ HB, double* __restrict__ G) {
@@ -124,8 +130,8 @@ __global__ void __launch_bounds__(256) lmm_grid_kernel(const double* __restrict_
     const uint32_t v0 = (blockIdx.x * 4 + wave) * 16;
     if (v0 >= nv) return;
     const uint32_t tile0 = blockIdx.y * 4, n_tiles = LMM_HB_COLS / 16;
-    d4 acc[3][4];
-    for (int c = 0; c < 3; c++)
+    d4 acc[NS][4];
+    for (int c = 0; c < NS; c++)
         for (int t = 0; t < 4; t++) acc[c][t] = d4{0, 0, 0, 0};
     const double* xrow = Xt + (uint64_t)(v0 + r) * dm.ldi + 4 * q;  // (rows up to nv rounded up to 16 exist: LMM_VTILE padding)
     for (uint32_t i0 = 0; i0 < dm.ldi; i0 += 16) {
@@ -133,7 +139,7 @@ __global__ void __launch_bounds__(256) lmm_grid_kernel(const double* __restrict_
         for (uint32_t s = 0; s < 4; s++) {
             const uint32_t i = i0 + 4 * q + s;
             const double x = xrow[i0 + s];
-            const double axx = x * x, axw = x * wt[i], axy = x * yt[i];
+            const double axx = x * x, axw = x * wt[i], axy = NS == 3 ? x * yt[i] : 0.0;
             const double* hrow = HB + (uint64_t)i * LMM_HB_COLS + r;
 #pragma unroll
             for (uint32_t t = 0; t < 4; t++) {
@@ -141,16 +147,67 @@ __global__ void __launch_bounds__(256) lmm_grid_kernel(const double* __restrict_
                 const double b = hrow[16 * (tile0 + t)];
                 acc[0][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(axx, b, acc[0][t], 0, 0, 0);
                 acc[1][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(axw, b, acc[1][t], 0, 0, 0);
-                acc[2][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(axy, b, acc[2][t], 0, 0, 0);
+                if (NS == 3) acc[NS - 1][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(axy, b, acc[NS - 1][t], 0, 0, 0);
             }
         }
     }
     for (int j = 0; j < 4; j++) {
         const uint32_t v = v0 + q + 4 * j;
         if (v >= nv) continue;
-        for (int c = 0; c < 3; c++)
+        for (int c = 0; c < NS; c++)
             for (uint32_t t = 0; t < 4; t++)
-                if (tile0 + t < n_tiles) G[((uint64_t)v * 3 + c) * LMM_HB_COLS + 16 * (tile0 + t) + r] = acc[c][t][j];
+                if (tile0 + t < n_tiles) G[((uint64_t)v * NS + c) * LMM_HB_COLS + 16 * (tile0 + t) + r] = acc[c][t][j];
+    }
+}
+
+// Gxy[p][v][c] = sum_i HB[i][c] (xt[v][i] Yt[p][i]) for the np phenotype columns of a block, v < nv. The mapping, the order of
+// i (i0 in steps of 16, then s, lane quarter q) and the rounding of the A operand are lmm_grid_kernel's for its xt yt row: the
+// same bits. A wave owns 16 variants x 4 column tiles x LMM_PTILE columns of Yt: x and the four B operands are loaded once
+// for all of them (LMM_PTILE x 4 accumulator tiles of 4 doubles per lane).
+__global__ void __launch_bounds__(256) lmm_grid_xy_kernel(const double* __restrict__ Xt, uint32_t nv, LmmDims dm,
+                                                          const double* __restrict__ Yt, uint32_t np,
+                                                          const double* __restrict__ HB, double* __restrict__ Gxy) {
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
+    const uint32_t v0 = (blockIdx.x * 4 + wave) * 16;
+    if (v0 >= nv) return;
+    const uint32_t tile0 = blockIdx.y * 4, n_tiles = LMM_HB_COLS / 16;
+    const uint32_t p0 = blockIdx.z * LMM_PTILE, np_here = min(LMM_PTILE, np - p0);  // (the launcher gives p0 < np)
+    d4 acc[LMM_PTILE][4];
+    const double* yrow[LMM_PTILE];
+    for (uint32_t pp = 0; pp < LMM_PTILE; pp++) {
+        yrow[pp] = Yt + (uint64_t)(p0 + (pp < np_here ? pp : 0)) * dm.ldi;  // (columns past np: a valid row, never used)
+        for (int t = 0; t < 4; t++) acc[pp][t] = d4{0, 0, 0, 0};
+    }
+    const double* xrow = Xt + (uint64_t)(v0 + r) * dm.ldi + 4 * q;  // (rows up to nv rounded up to 16 exist: LMM_VTILE padding)
+    for (uint32_t i0 = 0; i0 < dm.ldi; i0 += 16) {
+#pragma unroll
+        for (uint32_t s = 0; s < 4; s++) {
+            const uint32_t i = i0 + 4 * q + s;
+            const double x = xrow[i0 + s];
+            double axy[LMM_PTILE];
+#pragma unroll
+            for (uint32_t pp = 0; pp < LMM_PTILE; pp++) axy[pp] = x * yrow[pp][i];
+            const double* hrow = HB + (uint64_t)i * LMM_HB_COLS + r;
+#pragma unroll
+            for (uint32_t t = 0; t < 4; t++) {
+                if (tile0 + t >= n_tiles) continue;
+                const double b = hrow[16 * (tile0 + t)];
+#pragma unroll
+                for (uint32_t pp = 0; pp < LMM_PTILE; pp++)
+                    if (pp < np_here) acc[pp][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(axy[pp], b, acc[pp][t], 0, 0, 0);
+            }
+        }
+    }
+    for (int j = 0; j < 4; j++) {
+        const uint32_t v = v0 + q + 4 * j;
+        if (v >= nv) continue;
+#pragma unroll
+        for (uint32_t pp = 0; pp < LMM_PTILE; pp++) {
+            if (pp >= np_here) continue;
+#pragma unroll
+            for (uint32_t t = 0; t < 4; t++)
+                if (tile0 + t < n_tiles) Gxy[((uint64_t)(p0 + pp) * nv + v) * LMM_HB_COLS + 16 * (tile0 + t) + r] = acc[pp][t][j];
+        }
     }
 }
 
@@ -158,6 +215,8 @@ __global__ void __launch_bounds__(64) lmm_base_kernel(LmmDims dm, const double* 
                                                       const double* __restrict__ yt, const double* __restrict__ grid,
                                                       double* __restrict__ base) {
     const uint32_t g = blockIdx.x, lane = threadIdx.x;
+    yt += (uint64_t)blockIdx.y * dm.ldi;  // blockIdx.y: the phenotype column (rows of Yt, blocks of base)
+    base += (uint64_t)blockIdx.y * LMM_GRID * LMM_BASE;
     const double lam = grid[g];
     double s[LMM_BASE] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (uint32_t i = lane; i < dm.n; i += 64) {
@@ -234,18 +293,20 @@ __device__ inline Sums direct_sums(double lam, uint32_t n, const double* __restr
 }
 
 // One wave (a block of 64): the maximum of l over the grid's ends and the refined interior points. grid = lambda[101], then
-// t[101] = log lambda. Gv = the variant's three rows of G (HAS_X). s_l, s_dl: LMM_GRID doubles of LDS each.
+// t[101] = log lambda. Gx = the variant's xt^2 and xt wt rows of the grid sums, Gxy = its xt yt row (HAS_X). s_l, s_dl: LMM_GRID
+// doubles of LDS each.
 template <bool HAS_X>
 __device__ void maximise(uint32_t n, const double* __restrict__ d, const double* __restrict__ wt, const double* __restrict__ yt,
-                         const double* __restrict__ xt, const double* __restrict__ Gv, const double* __restrict__ grid,
-                         const double* __restrict__ base, double* s_l, double* s_dl, double& best_l, double& best_lam) {
+                         const double* __restrict__ xt, const double* __restrict__ Gx, const double* __restrict__ Gxy,
+                         const double* __restrict__ grid, const double* __restrict__ base, double* s_l, double* s_dl, double& best_l,
+                         double& best_lam) {
     const double nd = (double)n;
     for (uint32_t g = threadIdx.x; g < LMM_GRID; g += 64) {
         const double* b = base + g * LMM_BASE;
         Sums s = {b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], 0, 0, 0, 0, 0, 0};
         if (HAS_X) {
-            s.xx = Gv[g], s.xw = Gv[LMM_HB_COLS + g], s.xy = Gv[2 * LMM_HB_COLS + g];
-            s.dxx = Gv[LMM_GRID + g], s.dxw = Gv[LMM_HB_COLS + LMM_GRID + g], s.dxy = Gv[2 * LMM_HB_COLS + LMM_GRID + g];
+            s.xx = Gx[g], s.xw = Gx[LMM_HB_COLS + g], s.xy = Gxy[g];
+            s.dxx = Gx[LMM_GRID + g], s.dxw = Gx[LMM_HB_COLS + LMM_GRID + g], s.dxy = Gxy[LMM_GRID + g];
         }
         ll_from_sums<HAS_X>(s, nd, s_l[g], s_dl[g]);
     }
@@ -300,11 +361,13 @@ __global__ void __launch_bounds__(64) lmm_null_kernel(LmmDims dm, const double* 
                                                       const double* __restrict__ yt, const double* __restrict__ grid,
                                                       const double* __restrict__ base, double* __restrict__ out) {
     __shared__ double s_l[LMM_GRID], s_dl[LMM_GRID];
+    const uint32_t col = blockIdx.x;  // the phenotype column (rows of Yt, blocks of base, pairs of out)
     double l, lam;
-    maximise<false>(dm.n, d, wt, yt, nullptr, nullptr, grid, base, s_l, s_dl, l, lam);
+    maximise<false>(dm.n, d, wt, yt + (uint64_t)col * dm.ldi, nullptr, nullptr, nullptr, grid, base + (uint64_t)col * LMM_GRID * LMM_BASE,
+                    s_l, s_dl, l, lam);
     if (threadIdx.x == 0) {
-        out[0] = l;
-        out[1] = lam;
+        out[2 * col] = l;
+        out[2 * col + 1] = lam;
     }
 }
 
@@ -321,12 +384,40 @@ __global__ void __launch_bounds__(64) lmm_refine_kernel(const double* __restrict
         return;
     }
     double l, lam;
-    maximise<true>(dm.n, d, wt, yt, Xt + (uint64_t)v * dm.ldi, G + (uint64_t)v * 3 * LMM_HB_COLS, grid, base, s_l, s_dl, l, lam);
+    const double* Gv = G + (uint64_t)v * 3 * LMM_HB_COLS;
+    maximise<true>(dm.n, d, wt, yt, Xt + (uint64_t)v * dm.ldi, Gv, Gv + 2 * LMM_HB_COLS, grid, base, s_l, s_dl, l, lam);
     if (threadIdx.x == 0) {
         const double stat = fmax(0.0, 2.0 * (l - l0));
         lrt[v] = stat;
         lam_out[v] = lam;
         p_out[v] = erfc(sqrt(0.5 * stat));
+    }
+}
+
+// The same per (variant blockIdx.x, phenotype column blockIdx.y of a block): Gx[v][2][LMM_HB_COLS] is shared by the columns,
+// Gxy[p][v][LMM_HB_COLS], Yt[p][ldi], base[p][LMM_GRID][LMM_BASE] and null[p] = (l0, lambda0) are the column's. Results at [p][v].
+__global__ void __launch_bounds__(64) lmm_refine_multi_kernel(const double* __restrict__ Xt, const double* __restrict__ Gx,
+                                                              const double* __restrict__ Gxy, const LmmVariant* __restrict__ vars,
+                                                              uint32_t nv, LmmDims dm, const double* __restrict__ d,
+                                                              const double* __restrict__ wt, const double* __restrict__ Yt,
+                                                              const double* __restrict__ grid, const double* __restrict__ base,
+                                                              const double* __restrict__ null, double* __restrict__ lrt,
+                                                              double* __restrict__ lam_out, double* __restrict__ p_out) {
+    __shared__ double s_l[LMM_GRID], s_dl[LMM_GRID];
+    const uint32_t v = blockIdx.x, col = blockIdx.y;
+    const uint64_t o = (uint64_t)col * nv + v;
+    if (!vars[v].tested) {  // (the whole block leaves)
+        if (threadIdx.x == 0) lrt[o] = lam_out[o] = p_out[o] = __builtin_nan("");
+        return;
+    }
+    double l, lam;
+    maximise<true>(dm.n, d, wt, Yt + (uint64_t)col * dm.ldi, Xt + (uint64_t)v * dm.ldi, Gx + (uint64_t)v * 2 * LMM_HB_COLS,
+                   Gxy + o * LMM_HB_COLS, grid, base + (uint64_t)col * LMM_GRID * LMM_BASE, s_l, s_dl, l, lam);
+    if (threadIdx.x == 0) {
+        const double stat = fmax(0.0, 2.0 * (l - null[2 * col]));
+        lrt[o] = stat;
+        lam_out[o] = lam;
+        p_out[o] = erfc(sqrt(0.5 * stat));
     }
 }
 
@@ -349,7 +440,13 @@ hipError_t launch_lmm_rotate(const uint8_t* codes, const LmmVariant* vars, uint3
 
 hipError_t launch_lmm_base(LmmDims dm, const double* d, const double* wt, const double* yt, const double* grid, double* base,
                            hipStream_t st) {
-    hipLaunchKernelGGL(lmm_base_kernel, dim3(LMM_GRID), dim3(64), 0, st, dm, d, wt, yt, grid, base);
+    return launch_lmm_base_multi(dm, d, wt, yt, 1, grid, base, st);
+}
+
+hipError_t launch_lmm_base_multi(LmmDims dm, const double* d, const double* wt, const double* Yt, uint32_t np, const double* grid,
+                                 double* base, hipStream_t st) {
+    if (!np) return hipSuccess;
+    hipLaunchKernelGGL(lmm_base_kernel, dim3(LMM_GRID, np), dim3(64), 0, st, dm, d, wt, Yt, grid, base);
     return hipGetLastError();
 }
 
@@ -357,13 +454,36 @@ hipError_t launch_lmm_grid(const double* Xt, uint32_t nv, LmmDims dm, const doub
                            hipStream_t st) {
     if (!nv) return hipSuccess;
     const dim3 grid((nv + 63) / 64, (LMM_HB_COLS / 16 + 3) / 4);
-    hipLaunchKernelGGL(lmm_grid_kernel, grid, dim3(256), 0, st, Xt, nv, dm, wt, yt, HB, G);
+    hipLaunchKernelGGL(lmm_grid_kernel<3>, grid, dim3(256), 0, st, Xt, nv, dm, wt, yt, HB, G);
+    return hipGetLastError();
+}
+
+hipError_t launch_lmm_grid_shared(const double* Xt, uint32_t nv, LmmDims dm, const double* wt, const double* HB, double* Gx,
+                                  hipStream_t st) {
+    if (!nv) return hipSuccess;
+    const dim3 grid((nv + 63) / 64, (LMM_HB_COLS / 16 + 3) / 4);
+    hipLaunchKernelGGL(lmm_grid_kernel<2>, grid, dim3(256), 0, st, Xt, nv, dm, wt, (const double*)nullptr, HB, Gx);
+    return hipGetLastError();
+}
+
+hipError_t launch_lmm_grid_xy(const double* Xt, uint32_t nv, LmmDims dm, const double* Yt, uint32_t np, const double* HB, double* Gxy,
+                              hipStream_t st) {
+    if (!nv || !np) return hipSuccess;
+    if (np > LMM_PBLOCK) return hipErrorInvalidValue;
+    const dim3 grid((nv + 63) / 64, (LMM_HB_COLS / 16 + 3) / 4, (np + LMM_PTILE - 1) / LMM_PTILE);
+    hipLaunchKernelGGL(lmm_grid_xy_kernel, grid, dim3(256), 0, st, Xt, nv, dm, Yt, np, HB, Gxy);
     return hipGetLastError();
 }
 
 hipError_t launch_lmm_null(LmmDims dm, const double* d, const double* wt, const double* yt, const double* grid, const double* base,
                            double* out, hipStream_t st) {
-    hipLaunchKernelGGL(lmm_null_kernel, dim3(1), dim3(64), 0, st, dm, d, wt, yt, grid, base, out);
+    return launch_lmm_null_multi(dm, d, wt, yt, 1, grid, base, out, st);
+}
+
+hipError_t launch_lmm_null_multi(LmmDims dm, const double* d, const double* wt, const double* Yt, uint32_t np, const double* grid,
+                                 const double* base, double* out, hipStream_t st) {
+    if (!np) return hipSuccess;
+    hipLaunchKernelGGL(lmm_null_kernel, dim3(np), dim3(64), 0, st, dm, d, wt, Yt, grid, base, out);
     return hipGetLastError();
 }
 
@@ -372,6 +492,16 @@ hipError_t launch_lmm_refine(const double* Xt, const double* G, const LmmVariant
                              double* lam, double* p, hipStream_t st) {
     if (!nv) return hipSuccess;
     hipLaunchKernelGGL(lmm_refine_kernel, dim3(nv), dim3(64), 0, st, Xt, G, vars, dm, d, wt, yt, grid, base, l0, lrt, lam, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_lmm_refine_multi(const double* Xt, const double* Gx, const double* Gxy, const LmmVariant* vars, uint32_t nv, LmmDims dm,
+                                   const double* d, const double* wt, const double* Yt, uint32_t np, const double* grid,
+                                   const double* base, const double* null, double* lrt, double* lam, double* p, hipStream_t st) {
+    if (!nv || !np) return hipSuccess;
+    if (np > LMM_PBLOCK) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(lmm_refine_multi_kernel, dim3(nv, np), dim3(64), 0, st, Xt, Gx, Gxy, vars, nv, dm, d, wt, Yt, grid, base, null, lrt,
+                       lam, p);
     return hipGetLastError();
 }
 

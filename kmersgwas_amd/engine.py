@@ -542,6 +542,25 @@ class LmmLrt:
                                      ptr(n_miss), ptr(tested)))
         return {"lrt": lrt, "lambda": lam, "p": p, "af": af, "n_miss": n_miss, "tested": tested.astype(bool)}
 
+    def test_bed_multi(self, Y, bed, maf: float = 0.0, miss: float = 1.0):
+        """Y: (P, n), P phenotype columns tested against one .bed body (as in test) in one pass over it. Returns a dict of
+        numpy arrays: lrt, lambda, p of shape (P, M), logl0, lambda0 of shape (P,), af, n_miss, tested of shape (M,). Every value
+        has the bits of null(Y[k]) / test(bed, Y[k])."""
+        Y = np.ascontiguousarray(Y, np.float64)
+        if Y.ndim != 2 or Y.shape[1] != self.n:
+            raise ValueError("Y must have one row per phenotype column and one value per individual")
+        bps = (self.n + 3) // 4
+        body = np.frombuffer(bed, np.uint8) if isinstance(bed, (bytes, bytearray, memoryview)) else np.ascontiguousarray(bed, np.uint8)
+        if body.size % bps:
+            raise ValueError("the .bed body is not a whole number of variants of %d bytes" % bps)
+        m, P = body.size // bps, Y.shape[0]
+        lrt, lam, p = (np.zeros((P, m)) for _ in range(3))
+        l0, lam0, af = np.zeros(P), np.zeros(P), np.zeros(m)
+        n_miss, tested = np.zeros(m, np.uint32), np.zeros(m, np.uint8)
+        check(lib.kgwas_lmm_test_bed_multi(self._h, P, ptr(Y), ptr(body), m, maf, miss, ptr(lrt), ptr(lam), ptr(p), ptr(l0), ptr(lam0),
+                                           ptr(af), ptr(n_miss), ptr(tested)))
+        return {"lrt": lrt, "lambda": lam, "p": p, "logl0": l0, "lambda0": lam0, "af": af, "n_miss": n_miss, "tested": tested.astype(bool)}
+
     def stats(self):
         st = capi.LmmStats()
         check(lib.kgwas_lmm_get_stats(self._h, C.byref(st)))

@@ -6,6 +6,13 @@ Prints one JSON line: the host eigendecomposition and the rotation / grid / refi
 101 files), the wall time, and the rotation's fp64 rate (2 n^2 flop per variant) as a fraction of the MI355X's FP64 matrix peak.
 The microarchitecture notes this project works from list no FP64 matrix figure; AMD's published 78.6 TFLOP/s is used.
 There is no GEMMA timing to set beside these numbers: GEMMA is not installed where this was measured.
+
+--columns [P] (default 101) is the SNP branch's shape instead (kmers_gwas.py:193-223): ONE synthetic .bed of 200 000 variants x 1135
+individuals and P phenotype columns (one phenotype and its permutations). It times one test_bed_multi call against P test calls
+on the same handle: a warm-up of each, then --reps timed repetitions (median, minimum and maximum are printed), checks that the two
+give the same bits, and prints the rotation / grid / refinement split of each. grid_ms of the multi pass holds both the shared
+sums and lmm_grid_xy_kernel; its rate counts the useful flop of both (2 n 202 per sum: 2 shared ones per variant, one per
+variant and column).
 """
 import argparse
 import json
@@ -21,13 +28,81 @@ import kmersgwas_amd as kg  # noqa: E402
 FP64_MATRIX_PEAK_TFLOPS = 78.6
 
 
+def bench_columns(a):
+    n, m, P = a.individuals, a.variants if a.variants != 10001 else 200000, a.columns
+    rng = np.random.default_rng(20240601)
+    rows = 2 * n
+    G = (rng.random((rows, n)) < rng.uniform(0.1, 0.9, rows)[:, None]).astype(np.float64)
+    K = 1.0 - (G.T @ (1 - G) + (1 - G).T @ G) / rows
+    d, U = np.linalg.eigh(K)
+    y = rng.standard_normal(n) + 1.5 * ((U * np.sqrt(np.clip(d, 0, None))) @ rng.standard_normal(n)) + 1.2 * G[7]
+    Y = np.stack([y] + [rng.permutation(y) for _ in range(P - 1)])
+    bps = (n + 3) // 4
+    bed = np.zeros((m, bps), np.uint8)
+    for v0 in range(0, m, 20000):  # presence: code 00, absence: code 11
+        v1 = min(m, v0 + 20000)
+        bits = rng.random((v1 - v0, bps * 4)) < rng.uniform(0.06, 0.94, v1 - v0)[:, None]
+        c = np.where(bits, 0, 3).astype(np.uint8).reshape(v1 - v0, bps, 4)
+        bed[v0:v1] = c[:, :, 0] | (c[:, :, 1] << 2) | (c[:, :, 2] << 4) | (c[:, :, 3] << 6)
+    lmm = kg.LmmLrt(K, chunk_variants=a.chunk_variants)
+
+    def timed(fn):
+        before = lmm.stats()
+        t = time.perf_counter()
+        out = fn()
+        wall = time.perf_counter() - t
+        after = lmm.stats()
+        return out, dict(wall_s=wall, **{k: after[k] - before[k] for k in ("rotate_ms", "grid_ms", "refine_ms")})
+
+    def run_multi():
+        return lmm.test_bed_multi(Y, bed, maf=0.05, miss=0.5)
+
+    def run_single():
+        return [lmm.test(bed, Y[k], maf=0.05, miss=0.5) for k in range(P)]
+
+    res = {}
+    for name, fn in (("multi", run_multi), ("single", run_single)):
+        timed(fn)  # warm-up
+        runs = []
+        for _ in range(a.reps):
+            out, t = timed(fn)
+            runs.append(t)
+        res[name] = (out, runs)
+    lmm.close()
+    mo, so = res["multi"][0], res["single"][0]
+    same = all(mo[k][j].tobytes() == so[j][k].tobytes() for k in ("lrt", "lambda", "p") for j in range(P))
+    same = same and all(mo[k].tobytes() == so[0][k].tobytes() for k in ("af", "n_miss", "tested"))
+    line = {"columns": P, "variants": m, "individuals": n, "variants_tested": int(mo["tested"].sum()), "reps": a.reps, "same_bits": bool(same)}
+    for name in ("multi", "single"):
+        runs = res[name][1]
+        for k in ("wall_s", "rotate_ms", "grid_ms", "refine_ms"):
+            v = sorted(r[k] for r in runs)
+            line["%s_%s" % (name, k)] = {"median": round(v[len(v) // 2], 3), "min": round(v[0], 3), "max": round(v[-1], 3)}
+    med = lambda name, k: line["%s_%s" % (name, k)]["median"]  # noqa: E731
+    kern = lambda name: med(name, "rotate_ms") + med(name, "grid_ms") + med(name, "refine_ms")  # noqa: E731
+    line["wall_ratio"] = round(med("single", "wall_s") / med("multi", "wall_s"), 3)
+    line["kernel_ms_ratio"] = round(kern("single") / kern("multi"), 3)
+    tf = 2.0 * n * 202 * m * (P + 2) / (med("multi", "grid_ms") * 1e-3) / 1e12
+    line["multi_grid_tflops"] = round(tf, 3)
+    line["multi_grid_fraction_of_fp64_matrix_peak"] = round(tf / FP64_MATRIX_PEAK_TFLOPS, 4)
+    tf = 2.0 * n * 202 * m * 3 * P / (med("single", "grid_ms") * 1e-3) / 1e12
+    line["single_grid_tflops"] = round(tf, 3)
+    print(json.dumps(line))
+    return 0 if same else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--beds", type=int, default=101)
     ap.add_argument("--variants", type=int, default=10001)
     ap.add_argument("--individuals", type=int, default=1135)
     ap.add_argument("--chunk_variants", type=int, default=10240)
+    ap.add_argument("--columns", type=int, nargs="?", const=101, default=None,
+                    help="time one test_bed_multi call of P columns (default 101) over one .bed of 200 000 variants against P test calls")
+    ap.add_argument("--reps", type=int, default=3, help="timed repetitions of the --columns mode")
     a = ap.parse_args()
+    if a.columns is not None:
+        sys.exit(bench_columns(a))
     n, m = a.individuals, a.variants
     rng = np.random.default_rng(20240601)
     rows = 2 * n
