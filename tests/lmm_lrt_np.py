@@ -167,6 +167,74 @@ def varying(G):
     return G[(s > 0) & (s < G.shape[1])]
 
 
+@functools.lru_cache(maxsize=None)
+def strong_fixture(n, rows, seed=1, nv=20):
+    """A panel with a causal variant, for phenotypes y(effect) = 0.3 e + 0.5 (U sqrt(d)) z + effect G[r] on fixture(n, rows, 3.0)'s
+    G and K: (K, base, g, V) with y(effect) = base + effect * g. V (nv x n, 0 / 1): the causal row g = G[r], two copies of it with
+    2 %, 10 % and 30 % of their entries flipped (at least one entry), then unrelated varying rows of G. Nothing depends on the
+    effect but y, so that the phenotypes of several effects are columns over one panel."""
+    G, K, _ = fixture(n, rows, 3.0)
+    rng = np.random.default_rng([seed, n, rows, 11])
+    d, U = np.linalg.eigh(K)
+    d = np.clip(d, 0, None)
+    e, z = rng.standard_normal(n), rng.standard_normal(n)
+    base = 0.3 * e + 0.5 * ((U * np.sqrt(d)) @ z)
+    W = varying(G)
+    r = int(rng.integers(len(W)))
+    g = W[r]
+    V = [g]
+    for frac in (0.02, 0.02, 0.1, 0.1, 0.3, 0.3):
+        c = g.copy()
+        c[rng.permutation(n)[:max(1, round(frac * n))]] ^= 1
+        V.append(c)
+    V = np.array(V + [W[k] for k in range(len(W)) if k != r][:nv - len(V)], np.uint8)
+    assert len(V) == nv and len(varying(V)) == nv
+    g = g.astype(np.float64)
+    for a in (base, g, V):
+        a.setflags(write=False)
+    return K, base, g, V
+
+
+@functools.lru_cache(maxsize=None)
+def two_peak_fixture(n, seed, rows=16):
+    """A wide-spectrum kinship, under which l(log lambda) can have two interior maxima: (K, y, X). K = sym(Q diag(d) Q^T), Q from the
+    QR of an n x n standard normal, d = exp(U(-8, 8)) with each entry set to 0 with probability 0.2, y = Q (z exp(U(-3, 3))), z
+    standard normal; X = the varying ones of `rows` Bernoulli(0.4) rows (drawn last and row by row: more rows keep the first)."""
+    rng = np.random.default_rng([seed, n, 7])
+    Q, _ = np.linalg.qr(rng.standard_normal((n, n)))
+    d = np.exp(rng.uniform(-8, 8, n))
+    d[rng.random(n) < 0.2] = 0.0
+    K = (Q * d) @ Q.T
+    K = 0.5 * (K + K.T)
+    z = rng.standard_normal(n)
+    y = Q @ (z * np.exp(rng.uniform(-3, 3, n)))
+    X = varying((rng.random((rows, n)) < 0.4).astype(np.uint8))
+    for a in (K, y, X):
+        a.setflags(write=False)
+    return K, y, X
+
+
+STRONG_EFFECTS = (3.0, 10.0, 40.0)
+STRONG_ROWS = {67: 400, 241: 600, 1135: 1400}
+# (n, seed) of two_peak_fixture with two interior maxima under H0, H1 or both (test_lmm_lrt_model.py recomputes and asserts which)
+TWO_PEAK_CASES = ((8, 18), (8, 36), (16, 69), (16, 148), (5, 12), (67, 54), (67, 56))
+
+
+def two_peak_rows(n):
+    """16 rows, and 48 more at the small sizes, so that a 16-variant and a 32-variant tile are crossed"""
+    return 64 if n <= 16 else 16
+
+
+def interior_maxima(K, y, x=None, lmin=LMIN, lmax=LMAX):
+    """The interior local maxima of model R's l on its 2001-point grid, H1 (x given) or H0: [(log lambda, l)], in grid order."""
+    d, U = eig_of(K)
+    one = np.ones(y.size)
+    X = one[:, None] if x is None else np.column_stack([one, x])
+    t = np.linspace(np.log(lmin), np.log(lmax), GRID + 1)
+    v = _loglik_R_fast(d, U.T @ y, U.T @ X, np.exp(t))
+    return [(float(t[i]), float(v[i])) for i in range(1, GRID) if v[i] > v[i - 1] and v[i] >= v[i + 1]]
+
+
 CODE_OF_DOSAGE = {2: 0, 1: 2, 0: 3, -1: 1}  # .bed codes: 00 -> 2, 10 -> 1, 11 -> 0, 01 missing
 
 
@@ -194,3 +262,92 @@ def mean_imputed(dosage):
         miss = r < 0
         r[miss] = r[~miss].mean() if (~miss).any() else 0.0
     return x
+
+
+def call_stats(D):
+    """(af, n_miss, constant) of dosage rows the way the tool counts them: af = (sum of the called dosages / their number) / 2."""
+    D = np.asarray(D)
+    called = D >= 0
+    cnt = called.sum(axis=1)
+    af = 0.5 * (np.where(called, D, 0).sum(axis=1) / np.maximum(cnt, 1))
+    constant = np.array([len(set(r[c])) < 2 for r, c in zip(D, called)])
+    return af, (~called).sum(axis=1), constant
+
+
+def expect_tested(D, maf, miss):
+    af, n_miss, constant = call_stats(D)
+    return ~constant & (np.minimum(af, 1 - af) >= maf) & (n_miss / D.shape[1] <= miss)
+
+
+@functools.lru_cache(maxsize=None)
+def codes_panel(n, rows, nv):
+    """(K, y, D): nv dosage rows over fixture(n, rows, 3.0) with heterozygous (20 %) and missing (5 %) calls, of which row nv - 2
+    has its only missing call, and row nv - 1 its only minor allele, at the last individual (the last 2-bit field of a row)."""
+    G, K, y = fixture(n, rows, 3.0)
+    rng = np.random.default_rng([5, n, nv])
+    D = 2 * varying(G)[:nv].astype(np.int64)
+    assert len(D) == nv
+    D[:nv - 2][rng.random((nv - 2, n)) < 0.2] = 1
+    D[:nv - 2][rng.random((nv - 2, n)) < 0.05] = -1
+    D[nv - 2, n - 1] = -1
+    D[nv - 1] = 0
+    D[nv - 1, n - 1] = 2
+    D.setflags(write=False)
+    return K, y, D
+
+
+DROPPED = (0, 3, 4, 33, 68, 69)  # the individuals without a phenotype in dropped_panel's columns 1, 3 and 4; column 2 also lacks 17
+
+
+@functools.lru_cache(maxsize=None)
+def dropped_panel():
+    """70 individuals of whom some have no phenotype: (K, D, pheno). K 70 x 70, D 40 x 70 dosages with heterozygous and missing
+    calls, pheno 70 x 4 (NaN = missing): columns 1, 3, 4 lack DROPPED (64 kept, a multiple of 4), column 2 lacks individual 17 as
+    well (63 kept). Rows 0..5 of D change what the filters say once the dropped are gone:
+      0  missing at the dropped and at 10: 7 / 70 of all, 1 / 64 of the kept
+      1  its carriers are the dropped and individual 20: af 0.1 of all, 1 / 64 of the kept
+      2  its carriers are the dropped alone: constant among the kept
+      3  missing at 30 kept individuals
+      4  missing at the dropped, heterozygous and homozygous calls elsewhere
+      5  heterozygous everywhere but at individual 17: constant once 17 is gone"""
+    n, nv = 70, 40
+    G, K, y = fixture(n, 400, 3.0)
+    rng = np.random.default_rng([9, n, nv])
+    D = 2 * varying(G)[:nv].astype(np.int64)
+    D[rng.random((nv, n)) < 0.2] = 1
+    D[rng.random((nv, n)) < 0.03] = -1
+    drop = list(DROPPED)
+    D[0, drop + [10]] = -1
+    D[0, [11, 12]] = 1
+    D[1] = 0
+    D[1, drop + [20]] = 2
+    D[2] = 0
+    D[2, drop] = 2
+    D[3, rng.permutation(np.setdiff1d(np.arange(n), drop))[:30]] = -1
+    D[4, drop] = -1
+    D[5] = 1
+    D[5, 17] = 2
+    pheno = np.stack([y, y + 2.5 * (D[7] > 0), rng.permutation(y), rng.permutation(y)], axis=1)
+    pheno[drop] = np.nan
+    pheno[17, 1] = np.nan
+    for a in (D, pheno):
+        a.setflags(write=False)
+    return K, D, pheno
+
+
+@functools.lru_cache(maxsize=None)
+def filter_edge_panel(n):
+    """(K, y, D) over fixture(n, 400, 3.0): 6 ordinary rows, then row 6 with one homozygous carrier (af = 1 / n), row 7 with one
+    missing call, row 8 with two, row 9 with every individual but the last one missing."""
+    G, K, y = fixture(n, 400, 3.0)
+    D = np.zeros((10, n), np.int64)
+    D[:6] = 2 * varying(G)[:6]
+    D[6, n // 2] = 2
+    D[7:9] = 2 * varying(G)[6:8]
+    D[7:9, 0], D[7:9, 2] = 2, 0  # (they vary whatever is missing)
+    D[7, 1] = -1
+    D[8, [1, n - 2]] = -1
+    D[9] = -1
+    D[9, n - 1] = 2
+    D.setflags(write=False)
+    return K, y, D

@@ -2,8 +2,9 @@
 shared eigendecompositions, boundary optima and the command-line tool.
 
 Tolerances (lmm_lrt_np.py has the models; -lmin / -lmax = e^-10 / e^10 everywhere so that tool and models search one range):
-  LRT     the two models differ by at most 2.7e-12 on the CPU fixtures (test_lmm_lrt_model.py, MEASURED_MODEL_GAP = 3e-12). The
-          tool is allowed 1000 x that gap for its different summation order and eigensolver: LRT_TOL = 3e-9 absolute (cap 1e-8).
+  LRT     the two models differ by at most 2.7e-12 on this module's CPU fixtures and by at most 7.0e-11 on those of
+          test_gpu_lmm_lrt_regimes.py, at LRT 4720 (test_lmm_lrt_model.py, MEASURED_MODEL_GAP = 7.1e-11). The tool is allowed
+          1000 x that gap for its different summation order and eigensolver, capped at 1e-8: LRT_TOL = 1e-8 absolute.
   p       against scipy.stats.chi2.sf(LRT_tool, 1). Largest relative error measured on the GPU over these tests: see
           MEASURED_P_RELERR; asserted with a 10 x margin, cap 1e-9.
   lambda  the optimum is flat (log lambda differs by up to 5e-7 between the models), so lambda is checked through the
@@ -27,7 +28,7 @@ from test_lmm_lrt_model import MEASURED_MODEL_GAP
 pytestmark = pytest.mark.gpu
 
 LRT_TOL = min(1e-8, 1000 * MEASURED_MODEL_GAP)
-MEASURED_P_RELERR = 3.2e-14  # largest |p / chi2.sf(LRT, 1) - 1| seen on the MI355X over this module's cases
+MEASURED_P_RELERR = 5.5e-14  # largest |p / chi2.sf(LRT, 1) - 1| seen on the MI355X over the lmm modules (test_gpu_lmm_lrt_regimes.py, strong, n = 241, effect 40)
 P_RTOL = min(1e-9, 10 * MEASURED_P_RELERR)
 BIN = os.path.join(os.path.dirname(os.path.abspath(capi.__file__)), "bin", "lmm_lrt")
 
