@@ -232,8 +232,9 @@ typedef struct kgwas_scan_stats {
  * Version 11: no struct changed; new entry point kgwas_list_kmers (list_kmers_found_in_multiple_samples).
  * Version 12: no struct changed; new entry points kgwas_count_kmers_files, kgwas_count_kmers_bases (count_kmers_with_strand).
  * Version 13: no struct changed; new struct kgwas_lmm_stats and entry points kgwas_sym_eigen, kgwas_lmm_* (lmm_lrt).
- * Version 14: no struct changed; new entry points kgwas_lmm_test_bed_multi, kgwas_lmm_run_file_multi (lmm_lrt --columns). */
-#define KGWAS_ABI_VERSION 14
+ * Version 14: no struct changed; new entry points kgwas_lmm_test_bed_multi, kgwas_lmm_run_file_multi (lmm_lrt --columns).
+ * Version 15: no struct changed; new entry points kgwas_lmm_test_table, kgwas_lmm_run_table (lmm_lrt --kmers_table). */
+#define KGWAS_ABI_VERSION 15
 uint32_t kgwas_abi_version(void);
 
 int kgwas_scan_create(const kgwas_scan_params* p, kgwas_scan** out);
@@ -596,6 +597,27 @@ void kgwas_snpkin_close(kgwas_snpkin* h);
  *            .bim, the .bed and the kinship matrix are read once, K is eigendecomposed once, and out_paths[k] (with its log) gets
  *            what run_files writes for column pheno_cols[k]. All columns must mark the same .fam lines as missing; otherwise
  *            KGWAS_ERR_FORMAT, naming the first column that differs from the first one.
+ * test_table (ABI version 15): the exact test of EVERY k-mer of a k-mers table, without a .bed in between, and the best best_n of
+ *            them. col[n_acc] maps the handle's individuals, in order, to table columns (kgwas_table_column_map); n_acc must be the
+ *            handle's n. A row is tested iff kgwas_table_to_bed would write it at this min_count (n_acc >= min_count, presence
+ *            count n1 >= min_count, n1 <= n_acc - min_count) AND test_bed would test its .bed row at this maf (not constant,
+ *            min(af, 1 - af) >= maf with af = (n_acc - n1) / n_acc computed as test_bed does; a table has no missing calls). The
+ *            device squeezes, counts, flags and compacts a piece of rows; only tested rows are rotated. Their lrt, lambda, p and af
+ *            have the bits that kgwas_table_to_bed followed by kgwas_lmm_test_bed gives. Kept are the best_n tested rows with the
+ *            largest lrt, ties to the smaller table row - the same set for any piece size and chunk_variants. Outputs are host
+ *            arrays of best_n entries in table row order (row: the table row index, kmer: its 2-bit word), *n_kept <= best_n of
+ *            them valid; any output may be NULL. best_n == 0, a NULL h, y, t or col, n_acc != n or a column index out of range
+ *            -> KGWAS_ERR_ARG. The table file is read on a host thread while the device works on the piece before. Stats:
+ *            variants_read counts table rows, variants_tested tested rows; rotate_ms takes the front end too. KGWAS_LMM_PIECE_ROWS
+ *            (test hook) sets the rows per piece.
+ * run_table (ABI version 15): the file layer of lmm_lrt --kmers_table. Accessions and their order are the phenotype file's
+ *            (kgwas_pheno_load; every one must be a table column), the kinship text has one row per accession, y is column
+ *            pheno_col (from 1) of the phenotype file: the loader's float, written as kgwas_table_to_bed writes it into a .fam
+ *            (ostream's default format) and parsed as read_fam parses a .fam field, so both routes see the same doubles. A value
+ *            that prints as "-9" or "NA" (missing in a .fam) is refused with KGWAS_ERR_FORMAT. min_count = kgwas_min_count(n, maf,
+ *            mac). out_path gets the header and one line per kept k-mer in table order (chr 0, rs the k-mer, ps 0, n_miss 0,
+ *            allele1 0, allele0 1, af, l_mle, p_lrt: the bytes run_files writes for that k-mer of kgwas_table_to_bed's files),
+ *            the log beside it adds rows_read, rows_tested, rows_kept and best_n.
  * read_kinship / read_fam / format_assoc: the parsers and the line formatter of run_files (no GPU). read_fam gives every line's
  *            value (NaN when missing) and keep flag, up to cap entries, and the number of lines. format_assoc returns the bytes
  *            needed and writes them if cap allows; chr == NULL gives the header line.
@@ -619,6 +641,12 @@ int kgwas_lmm_test_bed_multi(kgwas_lmm* h, uint32_t n_pheno, const double* Y, co
 int kgwas_lmm_run_file_multi(const char* kinship_path, const char* bfile_base, uint32_t n_cols, const uint32_t* pheno_cols,
                              const char* const* out_paths, double maf, double miss, double lmin, double lmax, uint64_t chunk_variants,
                              int32_t device, kgwas_lmm_stats* total);
+int kgwas_lmm_test_table(kgwas_lmm* h, const double* y, kgwas_table* t, const uint64_t* col, uint64_t n_acc, uint64_t min_count, double maf,
+                         uint64_t best_n, uint64_t* row, uint64_t* kmer, double* lrt, double* lambda, double* p, double* af,
+                         uint64_t* n_kept, uint64_t* rows_read, uint64_t* rows_tested);
+int kgwas_lmm_run_table(const char* kinship_path, const char* table_base, uint32_t kmer_len, const char* pheno_path, uint32_t pheno_col,
+                        uint64_t mac, double maf, uint64_t best_n, double lmin, double lmax, uint64_t chunk_variants, int32_t device,
+                        const char* out_path, kgwas_lmm_stats* total);
 int kgwas_lmm_get_stats(const kgwas_lmm* h, kgwas_lmm_stats* out);
 void kgwas_lmm_destroy(kgwas_lmm* h);
 int kgwas_lmm_read_kinship(const char* path, uint64_t n_expected, double* K);

@@ -43,7 +43,7 @@ SYMBOLS = [
     "kgwas_snpkin_open", "kgwas_snpkin_info", "kgwas_snpkin_feed_bed", "kgwas_snpkin_feed_file", "kgwas_snpkin_sums",
     "kgwas_snpkin_matrix", "kgwas_snpkin_format", "kgwas_snpkin_close",
     "kgwas_sym_eigen", "kgwas_lmm_create", "kgwas_lmm_null", "kgwas_lmm_test_bed", "kgwas_lmm_run_files", "kgwas_lmm_get_stats",
-    "kgwas_lmm_test_bed_multi", "kgwas_lmm_run_file_multi",
+    "kgwas_lmm_test_bed_multi", "kgwas_lmm_run_file_multi", "kgwas_lmm_test_table", "kgwas_lmm_run_table",
     "kgwas_lmm_destroy", "kgwas_lmm_read_kinship", "kgwas_lmm_read_fam", "kgwas_lmm_format_assoc",
     "kgwas_synth_rows_device", "kgwas_synth_rows_host",
 ]
@@ -156,7 +156,7 @@ lib.kgwas_version.restype = C.c_int
 lib.kgwas_device_count.argtypes = [C.POINTER(C.c_int)]
 lib.kgwas_abi_version.argtypes = []
 lib.kgwas_abi_version.restype = C.c_uint32
-ABI_VERSION = 14  # KGWAS_ABI_VERSION of include/kgwas.h this mirror was written against
+ABI_VERSION = 15  # KGWAS_ABI_VERSION of include/kgwas.h this mirror was written against
 if lib.kgwas_abi_version() != ABI_VERSION:
     raise ImportError("libkgwas.so speaks ABI version %d, kmersgwas_amd/capi.py %d: rebuild (make -C kmersgwas_amd/csrc)" % (lib.kgwas_abi_version(), ABI_VERSION))
 lib.kgwas_host_cpu_quota.argtypes = []
@@ -270,6 +270,9 @@ lib.kgwas_lmm_test_bed.argtypes = [_vp, _vp, _vp, _u64, _dbl, _dbl, _vp, _vp, _v
 lib.kgwas_lmm_run_files.argtypes = [C.c_char_p, _u64, _pstr, _pstr, _u32, _dbl, _dbl, _dbl, _dbl, _u64, _i32, C.POINTER(LmmStats)]
 lib.kgwas_lmm_test_bed_multi.argtypes = [_vp, _u32, _vp, _vp, _u64, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
 lib.kgwas_lmm_run_file_multi.argtypes = [C.c_char_p, C.c_char_p, _u32, _vp, _pstr, _dbl, _dbl, _dbl, _dbl, _u64, _i32, C.POINTER(LmmStats)]
+lib.kgwas_lmm_test_table.argtypes = [_vp, _vp, _vp, _vp, _u64, _u64, _dbl, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _pu64, _pu64, _pu64]
+lib.kgwas_lmm_run_table.argtypes = [C.c_char_p, C.c_char_p, _u32, C.c_char_p, _u32, _u64, _dbl, _u64, _dbl, _dbl, _u64, _i32, C.c_char_p,
+                                    C.POINTER(LmmStats)]
 lib.kgwas_lmm_get_stats.argtypes = [_vp, C.POINTER(LmmStats)]
 lib.kgwas_lmm_destroy.argtypes = [_vp]
 lib.kgwas_lmm_destroy.restype = None

@@ -5,7 +5,10 @@
 // and D/NAME.log.txt. Its own addition: --bfiles LIST, a file of "bfile<TAB>name" lines that all run against one
 // eigendecomposition of the kinship matrix; and --columns LIST (with -bfile), a file of "col<TAB>name" lines: the listed phenotype
 // columns of B.fam are all tested in ONE pass over B.bed (the SNP branch's 101 GEMMA runs over one panel, kmers_gwas.py:193-223),
-// output D/name.assoc.txt. Defaults of -maf, -miss, -lmin, -lmax and -outdir are GEMMA's.
+// output D/name.assoc.txt. Defaults of -maf, -miss, -lmin, -lmax and -outdir are GEMMA's. And, in place of -bfile,
+//     lmm_lrt --kmers_table T --kmers_len K -p PHENO -lmm 2 -k KINSHIP [--mac M] [-maf f] [--best N] [-n i] [-outdir D] [-o NAME]
+// the exact test of EVERY k-mer of the table T that kmers_table_to_bed (--mac M --maf f) would write and lmm_lrt (-maf f) would then
+// test, without the PLINK files in between; the best N by the test are written, in table order (kgwas_lmm_run_table).
 #include <sys/stat.h>
 
 #include <cstdlib>
@@ -33,7 +36,20 @@ static void usage(const char* prog) {
             "  -outdir D      output directory (default ./output), -o NAME output prefix (default result)\n"
             "  -n i           phenotype column of the .fam, from 1 (default 1)\n"
             "  -maf f         minor allele frequency filter (default 0.01), -miss f missingness filter (default 0.05)\n"
-            "  -lmin x, -lmax x  search range of lambda (defaults 1e-5, 1e5)\n";
+            "  -lmin x, -lmax x  search range of lambda (defaults 1e-5, 1e5)\n"
+            "or, every k-mer of a k-mers table (no PLINK files in between):\n"
+            "       " << prog
+         << " --kmers_table T --kmers_len K -p PHENO  -lmm 2  -k KINSHIP  [--mac M] [-maf f] [--best N] [-n i] [-outdir D] [-o NAME]\n"
+            "       [-lmin x] [-lmax x] [--chunk_variants c] [--device d]\n"
+            "  --kmers_table T  k-mers table base name (T.table, T.names); excludes -bfile, --bfiles and --columns\n"
+            "  --kmers_len K    length of the k-mers (10-31)\n"
+            "  -p PHENO         phenotype file: its accessions, in its order, are the individuals (each must be in the table); -k has\n"
+            "                   one row per accession; -n i picks its phenotype column, from 1 (default 1)\n"
+            "  --mac M, -maf f  a k-mer is tested iff kmers_table_to_bed --mac M --maf f would write it (presence count within\n"
+            "                   max(ceil(n f), M) of both ends) and lmm_lrt -maf f would then test it (defaults 5, 0.01); -miss is accepted\n"
+            "                   and has no effect (a table has no missing calls)\n"
+            "  --best N         the N k-mers with the largest likelihood ratio are written, in table order (default 10001)\n"
+            "  --device d       GPU ordinal (default 0)\n";
 }
 
 static double num(const string& name, const string& s) {
@@ -48,8 +64,69 @@ static double num(const string& name, const string& s) {
     }
 }
 
+static uint64_t whole(const string& name, const string& s, uint64_t lo, uint64_t hi) {
+    if (s.empty() || s.size() > 18 || s.find_first_not_of("0123456789") != string::npos || stoull(s) < lo || stoull(s) > hi) {
+        cerr << "lmm_lrt: argument '" << s << "' of " << name << " is not a whole number within " << lo << ".." << hi << endl;
+        exit(1);
+    }
+    return stoull(s);
+}
+
+// lmm_lrt --kmers_table: every check that needs no device comes before the library call
+static int table_mode(map<string, string>& a, const char* prog) {
+    if (a.count("bfile") || a.count("bfiles") || a.count("columns")) {
+        cerr << "lmm_lrt: --kmers_table excludes -bfile, --bfiles and --columns (the k-mers come from the table)" << endl;
+        return 1;
+    }
+    if (!a.count("k") || !a.count("kmers_len") || !a.count("p")) {
+        cerr << "lmm_lrt: --kmers_table needs --kmers_len, -p and -k" << endl;
+        usage(prog);
+        return 1;
+    }
+    const uint64_t klen = whole("--kmers_len", a["kmers_len"], 0, 1000);
+    if (klen > 31 || klen < 10) {
+        cerr << "kmer length has to be between 10-31" << endl;
+        return 1;
+    }
+    const uint64_t mac = a.count("mac") ? whole("--mac", a["mac"], 0, 1ull << 32) : 5;
+    const uint64_t col = a.count("n") ? whole("-n", a["n"], 1, 1000000) : 1;
+    const uint64_t chunk = a.count("chunk_variants") ? whole("--chunk_variants", a["chunk_variants"], 0, 1000000000) : 0;
+    const uint64_t device = a.count("device") ? whole("--device", a["device"], 0, 1023) : 0;
+    if (a.count("best") && a["best"].find_first_not_of("0") == string::npos) {
+        cerr << "lmm_lrt: --best 0: at least one k-mer must be kept" << endl;
+        return 1;
+    }
+    const uint64_t best = a.count("best") ? whole("--best", a["best"], 1, 1ull << 32) : 10001;
+    const double maf = a.count("maf") ? num("-maf", a["maf"]) : 0.01;
+    if (a.count("miss")) (void)num("-miss", a["miss"]);
+    const double lmin = a.count("lmin") ? num("-lmin", a["lmin"]) : 1e-5, lmax = a.count("lmax") ? num("-lmax", a["lmax"]) : 1e5;
+    for (const string& f : {a["kmers_table"] + ".names", a["kmers_table"] + ".table", a["p"], a["k"]}) {
+        ifstream probe(f);
+        if (!probe.good()) {
+            cerr << "Couldn't find file: " << f << endl;
+            return 1;
+        }
+    }
+    const string outdir = a.count("outdir") ? a["outdir"] : "./output";
+    const string out = outdir + "/" + (a.count("o") ? a["o"] : string("result")) + ".assoc.txt";
+    (void)mkdir(outdir.c_str(), 0777);
+    kgwas_lmm_stats st{};
+    const int rc = kgwas_lmm_run_table(a["k"].c_str(), a["kmers_table"].c_str(), (uint32_t)klen, a["p"].c_str(), (uint32_t)col, mac, maf, best,
+                                       lmin, lmax, chunk, (int32_t)device, out.c_str(), &st);
+    if (rc != KGWAS_OK) {
+        cerr << "lmm_lrt: " << kgwas_last_error() << endl;
+        return rc == KGWAS_ERR_DEVICE ? 3 : 1;
+    }
+    cerr << "[kgwas] lmm_lrt: kmers_table=" << a["kmers_table"] << " individuals=" << st.n_individuals << " rows_read=" << st.variants_read
+         << " rows_tested=" << st.variants_tested << " best=" << best << " eigendecompositions=" << st.eigendecompositions
+         << " ms: eigen=" << st.eigen_ms << " rotate=" << st.rotate_ms << " grid=" << st.grid_ms << " refine=" << st.refine_ms << endl;
+    cli_finish();
+    return 0;
+}
+
 int main(int argc, char* argv[]) {
-    static const char* const valued[] = {"bfile", "bfiles", "lmm", "k", "outdir", "o", "n", "maf", "miss", "lmin", "lmax", "chunk_variants", "columns"};
+    static const char* const valued[] = {"bfile", "bfiles", "lmm", "k", "outdir", "o", "n", "maf", "miss", "lmin", "lmax", "chunk_variants", "columns",
+                                         "kmers_table", "kmers_len", "p", "mac", "best", "device"};
     map<string, string> a;
     for (int i = 1; i < argc; i++) {
         string s = argv[i];
@@ -77,6 +154,12 @@ int main(int argc, char* argv[]) {
              << ": only -lmm 2, the likelihood-ratio test, is built (no Wald or score test)" << endl;
         return 1;
     }
+    if (a.count("kmers_table")) return table_mode(a, argv[0]);
+    for (const char* o : {"kmers_len", "p", "mac", "best", "device"})
+        if (a.count(o)) {
+            cerr << "lmm_lrt: option '" << o << "' needs --kmers_table" << endl;
+            return 1;
+        }
     if (a.count("columns") && (a.count("bfiles") || a.count("n") || a.count("o") || !a.count("bfile"))) {
         cerr << "lmm_lrt: --columns needs -bfile and excludes --bfiles, -n and -o (LIST names the outputs)" << endl;
         return 1;

@@ -8,6 +8,10 @@
 // test_bed : per chunk of variants the raw bytes go to the device, then prep, rotate, grid and refine run in order on one stream;
 // test_bed_multi: several phenotype columns against ONE .bed. Per chunk prep, rotate and the two grid sums without y run once; the
 //            xt yt sums and the refinement run per block of LMM_PBLOCK columns. Every number has the bits of test_bed's;
+// test_table: every row of a k-mers table, without a .bed in between. Per piece of rows the device squeezes them to phenotype
+//            order, flags the rows that kmers_table_to_bed would write AND prep would test, and compacts those into code rows
+//            and LmmVariants with prep's bits (lmm_table_kernels.hip); rotate, grid and refine then run over them unchanged. The
+//            host keeps the best N by (lrt, table row). run_table is its file layer (lmm_lrt --kmers_table);
 // run_files: the file layer of the lmm_lrt tool - kinship text, .fam phenotype column, .bim, .bed in, .assoc.txt and .log.txt out.
 //            Individuals without a phenotype are dropped from K, y and the .bed rows before anything else; beds that keep the
 //            same individuals share one handle, so one eigendecomposition. run_file_multi: one bfile, several .fam columns with
@@ -16,16 +20,21 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <condition_variable>
 #include <cstdio>
 #include <cstring>
+#include <exception>
 #include <fstream>
 #include <memory>
+#include <mutex>
 #include <sstream>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "common.h"
 #include "ingest.h"
+#include "kernels.h"
 #include "lmm_kernels.h"
 
 using namespace kgwas;
@@ -293,6 +302,200 @@ void multi_run(kgwas_lmm* h, uint32_t n_pheno, const uint8_t* body, uint64_t nv,
     }
 }
 
+// ---- the k-mers table route ----
+
+struct TableHit {  // one tested row's result
+    double lrt, lam, p, af;
+    uint64_t row, kmer;
+};
+// a ranks before b: the larger lrt, then the smaller table row (a NaN lrt ranks last). Rows are unique, so the order is total.
+bool ranks_before(const TableHit& a, const TableHit& b) {
+    const double ka = std::isnan(a.lrt) ? -INFINITY : a.lrt, kb = std::isnan(b.lrt) ? -INFINITY : b.lrt;
+    return ka != kb ? ka > kb : a.row < b.row;
+}
+
+// Every row of table t against y: the best best_n tested rows by lrt, in table row order. A reader thread fills two pinned row
+// buffers in turn while the device works on the piece before; per piece the rows are squeezed, flagged and compacted
+// (lmm_table_kernels.hip), and the compacted rows go through rotate, grid and refine in sub-chunks of at most h->chunk. The host
+// keeps a heap of best_n results with the worst on top.
+void test_table(kgwas_lmm* h, const double* y, kgwas_table* t, const uint64_t* col, uint64_t n_acc, uint64_t min_count, double maf,
+                uint64_t best_n, std::vector<TableHit>& kept, uint64_t& rows_read, uint64_t& rows_tested) {
+    if (n_acc != h->n) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_test_table: n_acc differs from the handle's number of individuals");
+    if (!best_n) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_test_table: best_n is 0");
+    uint64_t S_f = 0, n_rows = 0, W_f = 0;
+    uint32_t klen = 0;
+    if (kgwas_table_info(t, &S_f, &n_rows, &W_f, &klen) != KGWAS_OK) throw Error(KGWAS_ERR_ARG, kgwas_last_error());
+    const uint64_t S = n_acc;
+    for (uint64_t i = 0; i < S; i++)
+        if (col[i] >= S_f) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_test_table: column index out of range");
+    check_squeeze_fits("kgwas_lmm_test_table", S_f, S);  // (before any allocation)
+    fit_null(h, y);
+    KGWAS_HIP(hipSetDevice(h->device));
+    const uint32_t W_m = (uint32_t)(2 * ((S + 127) / 128));
+    const uint64_t stride = 1 + W_f, chunk = h->chunk;
+    uint64_t piece = std::max<uint64_t>(1024, std::min<uint64_t>(1u << 18, (64ull << 20) / (8 * stride)));
+    const long long forced = opt_int("KGWAS_LMM_PIECE_ROWS", 0);
+    if (forced > 0) piece = (uint64_t)std::min<long long>(forced, 1 << 20);
+    piece = std::min(piece, std::max<uint64_t>(n_rows, 1));
+    const uint64_t n_blocks = (piece + LMM_TABLE_BLOCK - 1) / LMM_TABLE_BLOCK;
+
+    std::vector<uint32_t> colmap(64ull * W_m, 0xFFFFFFFFu);
+    for (uint64_t i = 0; i < S; i++) colmap[i] = (uint32_t)col[i];
+    DevBuf<uint32_t> d_colmap, d_sq, d_n1flag, d_bcnt, d_boff, d_total;
+    DevBuf<uint64_t> d_rows, d_row, d_kmer;
+    DevBuf<uint8_t> d_codes;
+    DevBuf<LmmVariant> d_vars;
+    PinBuf<uint64_t> h_rows[2];
+    upload(d_colmap, colmap);
+    d_rows.alloc(piece * stride);
+    d_sq.alloc(piece * 2 * W_m);
+    d_n1flag.alloc(piece);
+    d_bcnt.alloc(n_blocks);
+    d_boff.alloc(n_blocks);
+    d_total.alloc(1);
+    d_codes.alloc(piece * h->dm.bpsp);
+    d_vars.alloc(piece);
+    d_row.alloc(piece);
+    d_kmer.alloc(piece);
+    for (PinBuf<uint64_t>& b : h_rows) b.alloc(piece * stride);
+    hipEvent_t fe[2] = {nullptr, nullptr};  // around a piece's front end
+    struct EventGuard {
+        hipEvent_t* e;
+        ~EventGuard() {
+            for (int k = 0; k < 2; k++)
+                if (e[k]) (void)hipEventDestroy(e[k]);
+        }
+    } eg{fe};
+    for (hipEvent_t& e : fe) KGWAS_HIP(hipEventCreate(&e));
+
+    // the reader: piece k goes into buffer k & 1 once piece k - 2 has left it
+    const uint64_t n_pieces = (n_rows + piece - 1) / piece;
+    std::mutex mu;
+    std::condition_variable cv;
+    uint64_t filled = 0, consumed = 0;
+    bool stop = false;
+    std::exception_ptr rerr;
+    std::thread reader([&] {
+        kgwas_name_this_thread("kgwas-lmm-read");
+        try {
+            for (uint64_t k = 0; k < n_pieces; k++) {
+                {
+                    std::unique_lock<std::mutex> lk(mu);
+                    cv.wait(lk, [&] { return stop || consumed + 2 > k; });
+                    if (stop) return;
+                }
+                const uint64_t pos = k * piece;
+                if (kgwas_table_read_rows(t, pos, std::min(piece, n_rows - pos), h_rows[k & 1].p) != KGWAS_OK)
+                    throw Error(KGWAS_ERR_IO, kgwas_last_error());
+                {
+                    std::unique_lock<std::mutex> lk(mu);
+                    filled = k + 1;
+                }
+                cv.notify_all();
+            }
+        } catch (...) {
+            std::unique_lock<std::mutex> lk(mu);
+            rerr = std::current_exception();
+            stop = true;
+            cv.notify_all();
+        }
+    });
+    struct ReaderJoin {
+        std::thread& t;
+        std::mutex& mu;
+        std::condition_variable& cv;
+        bool& stop;
+        ~ReaderJoin() {
+            {
+                std::unique_lock<std::mutex> lk(mu);
+                stop = true;
+            }
+            cv.notify_all();
+            if (t.joinable()) t.join();
+        }
+    } rj{reader, mu, cv, stop};
+
+    // the worst kept result on top
+    auto worse_on_top = [](const TableHit& a, const TableHit& b) { return ranks_before(a, b); };
+    std::vector<TableHit> heap;
+    heap.reserve((size_t)std::min<uint64_t>(best_n, 1u << 20));
+    std::vector<double> o_lrt(chunk), o_lam(chunk), o_p(chunk);
+    std::vector<LmmVariant> o_vars(chunk);
+    std::vector<uint64_t> o_row(chunk), o_kmer(chunk);
+    hipStream_t st = h->stream;
+    rows_read = rows_tested = 0;
+    for (uint64_t k = 0; k < n_pieces; k++) {
+        const uint64_t pos = k * piece, c = std::min(piece, n_rows - pos);
+        {
+            std::unique_lock<std::mutex> lk(mu);
+            cv.wait(lk, [&] { return stop || filled > k; });
+            if (filled <= k) break;  // (the reader failed)
+        }
+        uint32_t total = 0;
+        KGWAS_HIP(hipMemcpyAsync(d_rows.p, h_rows[k & 1].p, c * stride * 8, hipMemcpyHostToDevice, st));
+        KGWAS_HIP(hipEventRecord(fe[0], st));
+        KGWAS_HIP(launch_squeeze(d_rows.p, stride, c, d_colmap.p, W_m, (uint32_t)W_f, d_sq.p, st));
+        KGWAS_HIP(launch_lmm_table_front(d_rows.p, stride, d_sq.p, (uint32_t)c, W_m, h->dm, pos, (uint32_t)std::min<uint64_t>(min_count, 0xFFFFFFFFu),
+                                         maf, d_n1flag.p, d_bcnt.p, d_boff.p, d_total.p, d_codes.p, d_vars.p, d_row.p, d_kmer.p, st));
+        KGWAS_HIP(hipEventRecord(fe[1], st));
+        KGWAS_HIP(hipMemcpyAsync(&total, d_total.p, sizeof(total), hipMemcpyDeviceToHost, st));
+        KGWAS_HIP(hipStreamSynchronize(st));
+        {
+            std::unique_lock<std::mutex> lk(mu);  // the rows are on the device: the buffer goes back to the reader
+            consumed = k + 1;
+        }
+        cv.notify_all();
+        float fms = 0;
+        KGWAS_HIP(hipEventElapsedTime(&fms, fe[0], fe[1]));
+        h->st.rotate_ms += fms;
+        if (total > c) throw Error(KGWAS_ERR_STATE, "kgwas_lmm_test_table: the front end counted more tested rows than rows");
+        for (uint64_t sub = 0; sub < total; sub += chunk) {
+            const uint32_t cc = (uint32_t)std::min<uint64_t>(chunk, total - sub);
+            const uint8_t* codes = d_codes.p + sub * h->dm.bpsp;
+            const LmmVariant* vars = d_vars.p + sub;
+            KGWAS_HIP(hipEventRecord(h->ev[0], st));
+            KGWAS_HIP(launch_lmm_rotate(codes, vars, cc, h->dm, h->d_U.p, h->d_Xt.p, st));
+            KGWAS_HIP(hipEventRecord(h->ev[1], st));
+            KGWAS_HIP(launch_lmm_grid(h->d_Xt.p, cc, h->dm, h->d_wt.p, h->d_yt.p, h->d_HB.p, h->d_G.p, st));
+            KGWAS_HIP(hipEventRecord(h->ev[2], st));
+            KGWAS_HIP(launch_lmm_refine(h->d_Xt.p, h->d_G.p, vars, cc, h->dm, h->d_d.p, h->d_wt.p, h->d_yt.p, h->d_grid.p, h->d_base.p, h->l0,
+                                        h->d_lrt.p, h->d_lam.p, h->d_p.p, st));
+            KGWAS_HIP(hipEventRecord(h->ev[3], st));
+            KGWAS_HIP(hipMemcpyAsync(o_lrt.data(), h->d_lrt.p, cc * sizeof(double), hipMemcpyDeviceToHost, st));
+            KGWAS_HIP(hipMemcpyAsync(o_lam.data(), h->d_lam.p, cc * sizeof(double), hipMemcpyDeviceToHost, st));
+            KGWAS_HIP(hipMemcpyAsync(o_p.data(), h->d_p.p, cc * sizeof(double), hipMemcpyDeviceToHost, st));
+            KGWAS_HIP(hipMemcpyAsync(o_vars.data(), vars, cc * sizeof(LmmVariant), hipMemcpyDeviceToHost, st));
+            KGWAS_HIP(hipMemcpyAsync(o_row.data(), d_row.p + sub, cc * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+            KGWAS_HIP(hipMemcpyAsync(o_kmer.data(), d_kmer.p + sub, cc * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+            KGWAS_HIP(hipStreamSynchronize(st));
+            float ms[3] = {0, 0, 0};
+            for (int e = 0; e < 3; e++) KGWAS_HIP(hipEventElapsedTime(&ms[e], h->ev[e], h->ev[e + 1]));
+            h->st.rotate_ms += ms[0];
+            h->st.grid_ms += ms[1];
+            h->st.refine_ms += ms[2];
+            h->st.chunks++;
+            for (uint32_t v = 0; v < cc; v++) {
+                const TableHit hit{o_lrt[v], o_lam[v], o_p[v], o_vars[v].af, o_row[v], o_kmer[v]};
+                if (heap.size() < best_n) {
+                    heap.push_back(hit);
+                    std::push_heap(heap.begin(), heap.end(), worse_on_top);
+                } else if (ranks_before(hit, heap.front())) {
+                    std::pop_heap(heap.begin(), heap.end(), worse_on_top);
+                    heap.back() = hit;
+                    std::push_heap(heap.begin(), heap.end(), worse_on_top);
+                }
+            }
+        }
+        rows_read += c;
+        rows_tested += total;
+        h->st.variants_read += c;
+        h->st.variants_tested += total;
+    }
+    if (rerr) std::rethrow_exception(rerr);
+    std::sort(heap.begin(), heap.end(), [](const TableHit& a, const TableHit& b) { return a.row < b.row; });
+    kept.swap(heap);
+}
+
 kgwas_lmm* create(uint64_t n, const double* K, int device, double lmin, double lmax, uint64_t chunk_variants) {
     if (!K) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_create: null argument");
     if (n < 3 || n >= (1ull << 16)) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_create: the number of individuals must be within 3..65535");
@@ -350,10 +553,10 @@ std::vector<std::string> read_lines(const std::string& path, const char* what) {
     return lines;
 }
 
-std::vector<double> read_kinship(const std::string& path, uint64_t n_expected) {
+std::vector<double> read_kinship(const std::string& path, uint64_t n_expected, const char* counted_in = "the .fam") {
     const std::vector<std::string> lines = read_lines(path, "kinship");
     if (lines.size() != n_expected)
-        throw Error(KGWAS_ERR_FORMAT, "kinship file " + path + " has " + std::to_string(lines.size()) + " rows, the .fam has " +
+        throw Error(KGWAS_ERR_FORMAT, "kinship file " + path + " has " + std::to_string(lines.size()) + " rows, " + counted_in + " has " +
                                           std::to_string(n_expected) + " individuals");
     std::vector<double> K(n_expected * n_expected);
     for (uint64_t r = 0; r < n_expected; r++) {
@@ -638,6 +841,88 @@ void run_file_multi(const char* kinship_path, const char* bfile_base, uint32_t n
     if (total) *total = h->st;
 }
 
+// The file layer of lmm_lrt --kmers_table: the accessions and their order are the phenotype file's, y its column pheno_col (from
+// 1), the k-mers come straight from <table_base>.table. The best best_n k-mers by the exact test go to `out` in table order, with
+// the bytes run_files writes for them after kmers_table_to_bed; a log goes beside it.
+void run_table(const char* kinship_path, const char* table_base, uint32_t kmer_len, const char* pheno_path, uint32_t pheno_col,
+               uint64_t mac, double maf, uint64_t best_n, double lmin, double lmax, uint64_t chunk_variants, int device, const char* out,
+               kgwas_lmm_stats* total) {
+    if (!kinship_path || !table_base || !pheno_path || !out) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_run_table: null argument");
+    if (pheno_col < 1) throw Error(KGWAS_ERR_ARG, "the phenotype column (-n) starts at 1");
+    if (!best_n) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_run_table: best_n is 0");
+    const double t_start = now_ms();
+    struct Files {
+        kgwas_pheno* ph = nullptr;
+        kgwas_table* t = nullptr;
+        ~Files() {
+            if (t) kgwas_table_close(t);
+            if (ph) kgwas_pheno_free(ph);
+        }
+    } f;
+    auto ck = [](int rc) {
+        if (rc != KGWAS_OK) throw Error(rc, kgwas_last_error());
+    };
+    ck(kgwas_pheno_load(pheno_path, &f.ph));
+    uint64_t n_pheno = 0, S = 0;
+    ck(kgwas_pheno_info(f.ph, &n_pheno, &S));
+    if (pheno_col > n_pheno)
+        throw Error(KGWAS_ERR_FORMAT, std::string(pheno_path) + " has no phenotype column " + std::to_string(pheno_col));
+    std::vector<const char*> acc(S);
+    for (uint64_t i = 0; i < S; i++) ck(kgwas_pheno_accession(f.ph, i, &acc[i]));
+    const float* Y = nullptr;
+    ck(kgwas_pheno_values(f.ph, &Y));
+    // y as it would arrive through kmers_table_to_bed's .fam: the loader's float in ostream's default format, parsed as read_fam does
+    std::vector<double> y(S);
+    for (uint64_t i = 0; i < S; i++) {
+        std::ostringstream os;
+        os << Y[(uint64_t)(pheno_col - 1) * S + i];
+        const std::string text = os.str();
+        if (text == "-9" || text == "NA")
+            throw Error(KGWAS_ERR_FORMAT, std::string(pheno_path) + ": the phenotype of " + acc[i] + " is " + text +
+                                              ", which a .fam reads as missing; remove the accession from the phenotype file");
+        char* end = nullptr;
+        const double v = strtod(text.c_str(), &end);
+        if (end == text.c_str() || *end || !std::isfinite(v))
+            throw Error(KGWAS_ERR_FORMAT, std::string(pheno_path) + ": phenotype '" + text + "' of " + acc[i] + " is no number");
+        y[i] = v;
+    }
+    ck(kgwas_table_open(table_base, kmer_len, &f.t));
+    std::vector<uint64_t> col(S);
+    ck(kgwas_table_column_map(f.t, acc.data(), S, col.data()));
+    uint64_t S_f = 0, n_rows = 0, W_f = 0;
+    uint32_t klen = 0;
+    ck(kgwas_table_info(f.t, &S_f, &n_rows, &W_f, &klen));
+    check_squeeze_fits("lmm_lrt --kmers_table", S_f, S);
+    const std::vector<double> K = read_kinship(kinship_path, S, "the phenotype file");
+    const uint64_t min_count = kgwas_min_count(S, maf, mac);
+    std::unique_ptr<kgwas_lmm> h(create(S, K.data(), device, lmin, lmax, chunk_variants));
+    std::vector<TableHit> kept;
+    uint64_t rows_read = 0, rows_tested = 0;
+    test_table(h.get(), y.data(), f.t, col.data(), S, min_count, maf, best_n, kept, rows_read, rows_tested);
+    std::string text = assoc_header();
+    for (const TableHit& k : kept) {
+        char km[33];
+        for (uint32_t i = 0; i < klen; i++) km[i] = "ACGT"[(k.kmer >> (2 * (klen - 1 - i))) & 3];  // bits2kmer31, as kmers_table_to_bed's .bim
+        km[klen] = 0;
+        char line[1024];
+        const uint64_t len = format_assoc("0", km, "0", 0, "0", "1", k.af, k.lam, k.p, line, sizeof(line));
+        text.append(line, len);
+    }
+    write_text(out, text, "wb");
+    char log[2048];
+    const int ll = snprintf(log, sizeof(log),
+                            "lmm_lrt: ML likelihood-ratio test (-lmm 2)\nkmers_table\t%s\nphenotypes\t%s\nphenotype_column\t%u\nkinship\t%s\n"
+                            "individuals_used\t%llu\nmin_count\t%llu\nrows_read\t%llu\nrows_tested\t%llu\nrows_kept\t%llu\nbest_n\t%llu\n"
+                            "lambda0\t%.6e\nlogl_H0\t%.6f\nms: eigen=%.3f rotate=%.3f grid=%.3f refine=%.3f total=%.3f\n",
+                            table_base, pheno_path, pheno_col, kinship_path, (unsigned long long)S, (unsigned long long)min_count,
+                            (unsigned long long)rows_read, (unsigned long long)rows_tested, (unsigned long long)kept.size(),
+                            (unsigned long long)best_n, h->lambda0, h->l0, h->st.eigen_ms, h->st.rotate_ms, h->st.grid_ms, h->st.refine_ms,
+                            now_ms() - t_start);
+    if (ll < 0) throw Error(KGWAS_ERR_IO, "can't write " + log_path_of(out));
+    write_text(log_path_of(out), std::string(log, (size_t)std::min<int>(ll, sizeof(log) - 1)), "wb");
+    if (total) *total = h->st;
+}
+
 }  // namespace
 
 extern "C" {
@@ -688,6 +973,37 @@ int kgwas_lmm_run_files(const char* kinship_path, uint64_t n_beds, const char* c
                         uint32_t pheno_col, double maf, double miss, double lmin, double lmax, uint64_t chunk_variants, int32_t device,
                         kgwas_lmm_stats* total) {
     return guarded([&] { run_files(kinship_path, n_beds, bfile_bases, out_paths, pheno_col, maf, miss, lmin, lmax, chunk_variants, device, total); });
+}
+
+int kgwas_lmm_test_table(kgwas_lmm* h, const double* y, kgwas_table* t, const uint64_t* col, uint64_t n_acc, uint64_t min_count, double maf,
+                         uint64_t best_n, uint64_t* row, uint64_t* kmer, double* lrt, double* lambda, double* p, double* af,
+                         uint64_t* n_kept, uint64_t* rows_read, uint64_t* rows_tested) {
+    return guarded([&] {
+        if (!h || !y || !t || !col) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_test_table: null argument");
+        std::vector<TableHit> kept;
+        uint64_t n_read = 0, n_tested = 0;
+        test_table(h, y, t, col, n_acc, min_count, maf, best_n, kept, n_read, n_tested);
+        for (uint64_t i = 0; i < kept.size(); i++) {
+            if (row) row[i] = kept[i].row;
+            if (kmer) kmer[i] = kept[i].kmer;
+            if (lrt) lrt[i] = kept[i].lrt;
+            if (lambda) lambda[i] = kept[i].lam;
+            if (p) p[i] = kept[i].p;
+            if (af) af[i] = kept[i].af;
+        }
+        if (n_kept) *n_kept = kept.size();
+        if (rows_read) *rows_read = n_read;
+        if (rows_tested) *rows_tested = n_tested;
+    });
+}
+
+int kgwas_lmm_run_table(const char* kinship_path, const char* table_base, uint32_t kmer_len, const char* pheno_path, uint32_t pheno_col,
+                        uint64_t mac, double maf, uint64_t best_n, double lmin, double lmax, uint64_t chunk_variants, int32_t device,
+                        const char* out_path, kgwas_lmm_stats* total) {
+    return guarded([&] {
+        run_table(kinship_path, table_base, kmer_len, pheno_path, pheno_col, mac, maf, best_n, lmin, lmax, chunk_variants, device, out_path,
+                  total);
+    });
 }
 
 int kgwas_lmm_get_stats(const kgwas_lmm* h, kgwas_lmm_stats* out) {

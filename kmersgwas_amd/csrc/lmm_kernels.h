@@ -65,4 +65,16 @@ hipError_t launch_lmm_refine_multi(const double* Xt, const double* Gx, const dou
                                    const double* d, const double* wt, const double* Yt, uint32_t np, const double* lambda,
                                    const double* base, const double* null, double* lrt, double* lam, double* p, hipStream_t st);
 
+// lmm_table_kernels.hip: the front end of the k-mers table route. rows[n_rows][stride] are table rows (k-mer word, then the
+// presence words), sq[n_rows][2 W_m] their bits squeezed to phenotype order (launch_squeeze, zero past dm.n). A row is tested iff
+// dm.n >= min_count && n1 >= min_count && n1 <= dm.n - min_count (kmers_table_to_bed) and launch_lmm_prep would test its .bed
+// row at this maf. For the tested rows alone, in row order: codes[t][bpsp], vars[t] (both with the bits launch_lmm_prep leaves
+// for that .bed row), row_out[t] = first_row + row, kmer_out[t] = its k-mer word; total[0] = their number. Scratch: n1flag
+// [n_rows], block_cnt and block_off [n_rows / LMM_TABLE_BLOCK rounded up]. 0 < n_rows < 2^31.
+constexpr uint32_t LMM_TABLE_BLOCK = 256;
+hipError_t launch_lmm_table_front(const uint64_t* rows, uint64_t stride, const uint32_t* sq, uint32_t n_rows, uint32_t W_m, LmmDims dm,
+                                  uint64_t first_row, uint32_t min_count, double maf, uint32_t* n1flag, uint32_t* block_cnt,
+                                  uint32_t* block_off, uint32_t* total, uint8_t* codes, LmmVariant* vars, uint64_t* row_out,
+                                  uint64_t* kmer_out, hipStream_t st);
+
 }  // namespace kgwas

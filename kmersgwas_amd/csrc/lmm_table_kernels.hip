@@ -1,0 +1,163 @@
+// lmm_table_kernels.hip — the front end of lmm_lrt --kmers_table: rows of a k-mers table, squeezed to phenotype order
+// (squeeze_kernel, aux_kernels.hip), become what lmm_rotate_kernel / lmm_grid_kernel / lmm_refine_kernel consume - for the
+// tested rows alone, compacted ("The table front end").
+//
+// A row is tested iff kmers_table_to_bed would write it AND lmm_prep_kernel would then test it:
+//     S >= min_count && n1 >= min_count && n1 <= S - min_count                         (table_to_bed.cpp's MAC filter)
+//     mean = (double)(2 (S - n1)) / (double)S, af = 0.5 mean, not constant, fmin(af, 1 - af) >= maf   (lmm_prep_kernel, its own
+//     expressions: presence is code 11, absence code 00, so c[0] = S - n1, c[1] = c[2] = 0, c[3] = n1 and no call is missing)
+//
+//   lmm_table_flag_kernel  one lane per row: n1 (popcount of the squeezed row), the flag, and per block of 256 rows the number
+//                          of tested rows (wave ballots, then four LDS values);
+//   lmm_table_scan_kernel  one block: the exclusive prefix sum of the block counts, and the piece's total;
+//   lmm_table_emit_kernel  per block of 256 rows: a tested row's slot is its block's offset plus its rank in the block (ballot
+//                          and popcount below the lane), so slots follow the row order - the same content in every run. The row's
+//                          lane writes the LmmVariant, the table row index and the k-mer word; then the block writes the padded
+//                          2-bit code rows, one dword (16 accessions, every presence bit doubled) per lane and step.
+// No atomic, no scalar memory write: every value goes out through a vector store from plain C++.
+#include "lmm_kernels.h"
+
+namespace kgwas {
+
+namespace {
+
+constexpr uint32_t TB = LMM_TABLE_BLOCK;  // rows per block of the flag and emit kernels
+constexpr uint32_t FLAG_BIT = 0x80000000u;
+
+// 16 presence bits -> 16 two-bit codes (11 / 00), accession k of the 16 at bits 2k, 2k + 1: the bytes of bed_bytes_kernel
+__device__ inline uint32_t spread16(uint32_t x) {
+    x = (x | (x << 8)) & 0x00FF00FFu;
+    x = (x | (x << 4)) & 0x0F0F0F0Fu;
+    x = (x | (x << 2)) & 0x33333333u;
+    x = (x | (x << 1)) & 0x55555555u;
+    return x | (x << 1);
+}
+
+// the number of set flags in the block's lanes below this one; s_wave: 4 values of LDS. Every lane of the block must call it.
+__device__ inline uint32_t block_rank(bool flag, uint32_t* s_wave, uint32_t& block_total) {
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const unsigned long long mask = __ballot(flag);
+    if (lane == 0) s_wave[wave] = (uint32_t)__popcll(mask);
+    __syncthreads();
+    uint32_t before = 0, total = 0;
+    for (uint32_t w = 0; w < TB / 64; w++) {
+        before += w < wave ? s_wave[w] : 0u;
+        total += s_wave[w];
+    }
+    block_total = total;
+    return before + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+}
+
+__global__ void __launch_bounds__(TB) lmm_table_flag_kernel(const uint32_t* __restrict__ sq, uint32_t n_rows, uint32_t ndw, uint32_t S,
+                                                            uint32_t min_count, double maf, uint32_t* __restrict__ n1flag,
+                                                            uint32_t* __restrict__ block_cnt) {
+    __shared__ uint32_t s_wave[TB / 64];
+    const uint32_t r = blockIdx.x * TB + threadIdx.x;
+    bool tested = false;
+    if (r < n_rows) {
+        const uint4* row = reinterpret_cast<const uint4*>(sq + (uint64_t)r * ndw);  // (ndw is a multiple of 4: 16-byte rows)
+        uint32_t n1 = 0;
+        for (uint32_t k = 0; k < ndw / 4; k++) {
+            const uint4 w = row[k];
+            n1 += __popc(w.x) + __popc(w.y) + __popc(w.z) + __popc(w.w);
+        }
+        const bool written = S >= min_count && n1 >= min_count && n1 <= S - min_count;  // kmers_table_to_bed
+        const double mean = (double)(2u * (S - n1)) / (double)S;                          // lmm_prep_kernel: nn = S, c[2] = 0
+        const double af = 0.5 * mean;
+        const bool constant = S == 0 || n1 == 0 || n1 == S;
+        tested = written && !constant && fmin(af, 1.0 - af) >= maf;
+        n1flag[r] = n1 | (tested ? FLAG_BIT : 0u);
+    }
+    uint32_t total;
+    (void)block_rank(tested, s_wave, total);
+    if (threadIdx.x == 0) block_cnt[blockIdx.x] = total;
+}
+
+// block_off[b] = sum of block_cnt[0 .. b), total[0] = the sum of all n_blocks counts. One block of 256 lanes.
+__global__ void __launch_bounds__(256) lmm_table_scan_kernel(const uint32_t* __restrict__ block_cnt, uint32_t n_blocks,
+                                                             uint32_t* __restrict__ block_off, uint32_t* __restrict__ total) {
+    __shared__ uint32_t s_wave[4];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    uint32_t carry = 0;
+    for (uint32_t b0 = 0; b0 < n_blocks; b0 += 256) {
+        const uint32_t b = b0 + threadIdx.x;
+        const uint32_t v = b < n_blocks ? block_cnt[b] : 0u;
+        uint32_t incl = v;  // inclusive scan within the wave
+#pragma unroll
+        for (uint32_t d = 1; d < 64; d <<= 1) {
+            const uint32_t o = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += o;
+        }
+        if (lane == 63) s_wave[wave] = incl;
+        __syncthreads();
+        uint32_t before = carry, tile = 0;
+        for (uint32_t w = 0; w < 4; w++) {
+            before += w < wave ? s_wave[w] : 0u;
+            tile += s_wave[w];
+        }
+        if (b < n_blocks) block_off[b] = before + incl - v;
+        carry += tile;
+        __syncthreads();  // (s_wave is written again in the next round)
+    }
+    if (threadIdx.x == 0) total[0] = carry;
+}
+
+__global__ void __launch_bounds__(TB) lmm_table_emit_kernel(const uint64_t* __restrict__ rows, uint64_t stride,
+                                                            const uint32_t* __restrict__ sq, uint32_t n_rows, uint32_t ndw, uint32_t S,
+                                                            uint64_t first_row, const uint32_t* __restrict__ n1flag,
+                                                            const uint32_t* __restrict__ block_off, uint32_t bpsp,
+                                                            uint32_t* __restrict__ codes, LmmVariant* __restrict__ vars,
+                                                            uint64_t* __restrict__ row_out, uint64_t* __restrict__ kmer_out) {
+    __shared__ uint32_t s_wave[TB / 64];
+    __shared__ uint32_t s_slot[TB];
+    const uint32_t row0 = blockIdx.x * TB, r = row0 + threadIdx.x;
+    const uint32_t nf = r < n_rows ? n1flag[r] : 0u;
+    const bool tested = (nf & FLAG_BIT) != 0u;
+    uint32_t total;
+    const uint32_t slot = block_off[blockIdx.x] + block_rank(tested, s_wave, total);
+    s_slot[threadIdx.x] = tested ? slot : 0xFFFFFFFFu;
+    if (tested) {
+        const uint32_t n1 = nf & ~FLAG_BIT;
+        const double mean = (double)(2u * (S - n1)) / (double)S;  // as lmm_prep_kernel: (2 c[0] + c[2]) / nn
+        LmmVariant o;
+        o.val[0] = 2.0 - mean;
+        o.val[1] = 0.0;
+        o.val[2] = 1.0 - mean;
+        o.val[3] = 0.0 - mean;
+        o.af = 0.5 * mean;
+        o.n_miss = 0;
+        o.tested = 1;
+        vars[slot] = o;
+        row_out[slot] = first_row + r;
+        kmer_out[slot] = rows[(uint64_t)r * stride];
+    }
+    __syncthreads();
+    if (total == 0) return;  // (block-uniform)
+    const uint32_t ndc = bpsp / 4;  // code dwords per row; dword j holds accessions 16 j .. 16 j + 15 (zero past S: the squeeze pads)
+    for (uint32_t e = threadIdx.x; e < TB * ndc; e += TB) {
+        const uint32_t rr = e / ndc, j = e - rr * ndc;
+        const uint32_t s = s_slot[rr];
+        if (s == 0xFFFFFFFFu) continue;
+        const uint32_t bits = (sq[(uint64_t)(row0 + rr) * ndw + (j >> 1)] >> (16u * (j & 1u))) & 0xFFFFu;
+        codes[(uint64_t)s * ndc + j] = spread16(bits);
+    }
+}
+
+}  // namespace
+
+hipError_t launch_lmm_table_front(const uint64_t* rows, uint64_t stride, const uint32_t* sq, uint32_t n_rows, uint32_t W_m, LmmDims dm,
+                                  uint64_t first_row, uint32_t min_count, double maf, uint32_t* n1flag, uint32_t* block_cnt,
+                                  uint32_t* block_off, uint32_t* total, uint8_t* codes, LmmVariant* vars, uint64_t* row_out,
+                                  uint64_t* kmer_out, hipStream_t st) {
+    if (!n_rows) return hipErrorInvalidValue;  // (total would stay unwritten)
+    const uint32_t ndw = 2u * W_m, n_blocks = (n_rows + TB - 1) / TB;
+    // the squeezed row must hold every accession the code row covers, and be read in 16-byte steps
+    if (ndw % 4u || dm.bpsp % 4u || (uint64_t)ndw * 32u < (uint64_t)dm.bpsp * 4u || dm.n > 32u * ndw) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(lmm_table_flag_kernel, dim3(n_blocks), dim3(TB), 0, st, sq, n_rows, ndw, dm.n, min_count, maf, n1flag, block_cnt);
+    hipLaunchKernelGGL(lmm_table_scan_kernel, dim3(1), dim3(256), 0, st, block_cnt, n_blocks, block_off, total);
+    hipLaunchKernelGGL(lmm_table_emit_kernel, dim3(n_blocks), dim3(TB), 0, st, rows, stride, sq, n_rows, ndw, dm.n, first_row, n1flag,
+                       block_off, dm.bpsp, reinterpret_cast<uint32_t*>(codes), vars, row_out, kmer_out);
+    return hipGetLastError();
+}
+
+}  // namespace kgwas

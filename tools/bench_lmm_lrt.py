@@ -13,11 +13,21 @@ on the same handle: a warm-up of each, then --reps timed repetitions (median, mi
 give the same bits, and prints the rotation / grid / refinement split of each. grid_ms of the multi pass holds both the shared
 sums and lmm_grid_xy_kernel; its rate counts the useful flop of both (2 n 202 per sum: 2 shared ones per variant, one per
 variant and column).
+
+--table [ROWS] (default 4 000 000) times lmm_lrt --kmers_table: a synthetic k-mers table of ROWS rows x 1135 accessions (the seeded
+generator of the other benchmarks, written to a temporary directory), one phenotype, --mac 5 -maf 0.05 --best 10001. A warm-up and
+--reps timed runs of the tool (median, minimum, maximum of the wall time; the kernels' split and the counts come from its log),
+and beside them, on the same files, the wall time of the route that needs the PLINK files: kmers_table_to_bed, then lmm_lrt
+-bfile (files in the page cache, the output of the first removed before every run). Both routes eigendecompose K once per run;
+eigen_ms is printed so that it can be taken off.
 """
 import argparse
 import json
 import os
+import shutil
+import subprocess
 import sys
+import tempfile
 import time
 
 import numpy as np
@@ -91,6 +101,88 @@ def bench_columns(a):
     return 0 if same else 1
 
 
+def bench_table(a):
+    n, rows = a.individuals, a.table
+    bindir = os.path.join(os.path.dirname(os.path.abspath(kg.__file__)), "bin")
+    rng = np.random.default_rng(20240601)
+    g_rows = 2 * n
+    G = (rng.random((g_rows, n)) < rng.uniform(0.1, 0.9, g_rows)[:, None]).astype(np.float64)
+    K = 1.0 - (G.T @ (1 - G) + (1 - G).T @ G) / g_rows
+    d, U = np.linalg.eigh(K)
+    y = rng.standard_normal(n) + 1.5 * ((U * np.sqrt(np.clip(d, 0, None))) @ rng.standard_normal(n)) + 1.2 * G[7]
+    tmp = tempfile.mkdtemp(prefix="bench_lmm_table_")
+    try:
+        base = os.path.join(tmp, "t")
+        hdr = np.uint32(0xDDCCBBAA).tobytes() + np.uint64(n).tobytes() + np.uint32(31).tobytes()
+        with open(base + ".table", "wb") as f:
+            f.write(hdr)
+            for r0 in range(0, rows, 1_000_000):
+                kg.synth_rows_host(r0, min(1_000_000, rows - r0), n, 20240601).tofile(f)
+        names = ["s%d" % i for i in range(n)]
+        open(base + ".names", "w").write("".join(x + "\n" for x in names))
+        ph = os.path.join(tmp, "ph.tsv")
+        open(ph, "w").write("accession_id\tv\n" + "".join("%s\t%.6f\n" % (x, v) for x, v in zip(names, y)))
+        kin = os.path.join(tmp, "ph.kinship")
+        open(kin, "w").write("\n".join("\t".join("%.17g" % v for v in r) for r in K) + "\n")
+        out = os.path.join(tmp, "out")
+
+        def tool(cmd):
+            t = time.perf_counter()
+            r = subprocess.run(cmd, capture_output=True, text=True)
+            if r.returncode != 0:
+                sys.exit("%s failed: %s" % (cmd[0], r.stderr[-2000:]))
+            return time.perf_counter() - t
+
+        def log_of(name):
+            log = {}
+            for l in open(os.path.join(out, name + ".log.txt")).read().split("\n"):
+                if "\t" in l:
+                    k, v = l.split("\t", 1)
+                    log[k] = v
+                elif l.startswith("ms: "):
+                    log.update((kv.split("=")[0], float(kv.split("=")[1])) for kv in l[4:].split())
+            return log
+
+        def table_route():
+            wall = tool([os.path.join(bindir, "lmm_lrt"), "--kmers_table", base, "--kmers_len", "31", "-p", ph, "-lmm", "2", "-k", kin,
+                         "--mac", "5", "-maf", "0.05", "--best", "10001", "-outdir", out, "-o", "table",
+                         "--chunk_variants", str(a.chunk_variants)])
+            return dict(wall_s=wall, **log_of("table"))
+
+        def bed_route():
+            for f in os.listdir(tmp):
+                if f.startswith("plink."):
+                    os.remove(os.path.join(tmp, f))
+            t1 = tool([os.path.join(bindir, "kmers_table_to_bed"), "-t", base, "-k", "31", "-p", ph, "--maf", "0.05", "--mac", "5",
+                       "-b", str(rows + 1), "-o", os.path.join(tmp, "plink")])
+            t2 = tool([os.path.join(bindir, "lmm_lrt"), "-bfile", os.path.join(tmp, "plink.0"), "-lmm", "2", "-k", kin, "-maf", "0.05",
+                       "-outdir", out, "-o", "bed", "--chunk_variants", str(a.chunk_variants)])
+            return dict(wall_s=t1 + t2, table_to_bed_s=t1, lmm_lrt_s=t2, **log_of("bed"))
+
+        line = {"table_rows": rows, "individuals": n, "best": 10001, "reps": a.reps}
+        for name, fn in (("table", table_route), ("bed", bed_route)):
+            fn()  # warm-up
+            runs = [fn() for _ in range(a.reps)]
+            keys = ["wall_s", "eigen", "rotate", "grid", "refine"] + (["table_to_bed_s", "lmm_lrt_s"] if name == "bed" else [])
+            for k in keys:
+                v = sorted(float(r[k]) for r in runs)
+                line["%s_%s" % (name, k if k.endswith("_s") else k + "_ms")] = {"median": round(v[len(v) // 2], 3), "min": round(v[0], 3), "max": round(v[-1], 3)}
+            if name == "table":
+                line["rows_tested"], line["rows_kept"] = int(runs[0]["rows_tested"]), int(runs[0]["rows_kept"])
+            else:
+                line["bed_variants_tested"] = int(runs[0]["variants_tested"])
+        wall = line["table_wall_s"]["median"]
+        line["rows_per_s"] = round(rows / wall)
+        line["tested_rows_per_s"] = round(line["rows_tested"] / wall)
+        kern = sum(line["table_%s_ms" % k]["median"] for k in ("rotate", "grid", "refine"))
+        line["kernel_ms_per_million_tested"] = round(kern / max(line["rows_tested"], 1) * 1e6, 3)
+        line["wall_ratio_bed_over_table"] = round(line["bed_wall_s"]["median"] / wall, 3)
+        print(json.dumps(line))
+        return 0 if line["rows_tested"] == line["bed_variants_tested"] else 1
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--beds", type=int, default=101)
@@ -99,8 +191,12 @@ def main():
     ap.add_argument("--chunk_variants", type=int, default=10240)
     ap.add_argument("--columns", type=int, nargs="?", const=101, default=None,
                     help="time one test_bed_multi call of P columns (default 101) over one .bed of 200 000 variants against P test calls")
-    ap.add_argument("--reps", type=int, default=3, help="timed repetitions of the --columns mode")
+    ap.add_argument("--reps", type=int, default=3, help="timed repetitions of the --columns and --table modes")
+    ap.add_argument("--table", type=int, nargs="?", const=4_000_000, default=None,
+                    help="time lmm_lrt --kmers_table over a synthetic table of ROWS rows (default 4 000 000) against kmers_table_to_bed + lmm_lrt -bfile")
     a = ap.parse_args()
+    if a.table is not None:
+        sys.exit(bench_table(a))
     if a.columns is not None:
         sys.exit(bench_columns(a))
     n, m = a.individuals, a.variants
