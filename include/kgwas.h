@@ -233,7 +233,8 @@ typedef struct kgwas_scan_stats {
  * Version 12: no struct changed; new entry points kgwas_count_kmers_files, kgwas_count_kmers_bases (count_kmers_with_strand).
  * Version 13: no struct changed; new struct kgwas_lmm_stats and entry points kgwas_sym_eigen, kgwas_lmm_* (lmm_lrt).
  * Version 14: no struct changed; new entry points kgwas_lmm_test_bed_multi, kgwas_lmm_run_file_multi (lmm_lrt --columns).
- * Version 15: no struct changed; new entry points kgwas_lmm_test_table, kgwas_lmm_run_table (lmm_lrt --kmers_table). */
+ * Version 15: no struct changed; new entry points kgwas_lmm_test_table, kgwas_lmm_run_table (lmm_lrt --kmers_table), and later,
+ * without a new version number, kgwas_lmm_test_table_multi, kgwas_lmm_run_table_multi (lmm_lrt --kmers_table --pheno_columns). */
 #define KGWAS_ABI_VERSION 15
 uint32_t kgwas_abi_version(void);
 
@@ -618,6 +619,26 @@ void kgwas_snpkin_close(kgwas_snpkin* h);
  *            mac). out_path gets the header and one line per kept k-mer in table order (chr 0, rs the k-mer, ps 0, n_miss 0,
  *            allele1 0, allele0 1, af, l_mle, p_lrt: the bytes run_files writes for that k-mer of kgwas_table_to_bed's files),
  *            the log beside it adds rows_read, rows_tested, rows_kept and best_n.
+ * test_table_multi (ABI version 15): test_table for n_pheno columns Y[n_pheno][n] in ONE pass over the table - the phenotype and
+ *            its permutations, whose best p-values give the pipeline its threshold (kmers_gwas.py:245-253). A piece is read,
+ *            squeezed, flagged, compacted and rotated once; the grid sums without y run once per sub-chunk; the sums with y, the
+ *            refinement and a select kernel run per block of 32 columns. The select kernel hands the host only the (column, row)
+ *            pairs that can still enter the column's best best_n: all while the column's heap is not full, then those whose lrt
+ *            is larger than the lrt of the heap's worst hit as the host knew it before the launch (rows arrive in increasing order,
+ *            so a later row with an equal lrt ranks after the kept one). The host heaps still decide. row, kmer, lrt, lambda, p,
+ *            af are [n_pheno][best_n] (column k's entries start at k best_n, in table row order, n_kept[k] of them valid); n_kept,
+ *            logl0, lambda0 [n_pheno]; any output may be NULL. Column k's kept rows and numbers have the bits kgwas_lmm_test_table
+ *            gives for Y[k] alone, and logl0 / lambda0 those of kgwas_lmm_null, for any piece size, chunk_variants and order of the
+ *            columns. *pairs_shipped: the records the device handed to the host, at most rows_tested x n_pheno. Errors as
+ *            test_table, and n_pheno == 0, a non-finite value or a constant column -> KGWAS_ERR_ARG (the message names the column,
+ *            from 0), all before any device work; the handle stays usable and the phenotype cached by kgwas_lmm_null stays
+ *            untouched. Stats: variants_read counts table rows, variants_tested a tested row once per column; rotate_ms takes the
+ *            front end and the rotation, grid_ms the shared and the per-column sums, refine_ms the refinement and the select
+ *            kernel. The selection's buffers (32 chunk_variants records of 56 bytes on the device and pinned on the host) are
+ *            allocated at the first such call. KGWAS_LMM_TABLE_SELECT=0 (test hook) lets every pair through; the results are the same.
+ * run_table_multi (ABI version 15): run_table for n_cols columns of the phenotype file (pheno_cols, from 1) in one pass: the
+ *            phenotype file, the table and the kinship text are read once, K is eigendecomposed once, and out_paths[k] with its
+ *            log gets what run_table writes for column pheno_cols[k] (the kernels' times in the logs are the shared pass's).
  * read_kinship / read_fam / format_assoc: the parsers and the line formatter of run_files (no GPU). read_fam gives every line's
  *            value (NaN when missing) and keep flag, up to cap entries, and the number of lines. format_assoc returns the bytes
  *            needed and writes them if cap allows; chr == NULL gives the header line.
@@ -647,6 +668,13 @@ int kgwas_lmm_test_table(kgwas_lmm* h, const double* y, kgwas_table* t, const ui
 int kgwas_lmm_run_table(const char* kinship_path, const char* table_base, uint32_t kmer_len, const char* pheno_path, uint32_t pheno_col,
                         uint64_t mac, double maf, uint64_t best_n, double lmin, double lmax, uint64_t chunk_variants, int32_t device,
                         const char* out_path, kgwas_lmm_stats* total);
+int kgwas_lmm_test_table_multi(kgwas_lmm* h, uint32_t n_pheno, const double* Y, kgwas_table* t, const uint64_t* col, uint64_t n_acc,
+                               uint64_t min_count, double maf, uint64_t best_n, uint64_t* row, uint64_t* kmer, double* lrt, double* lambda,
+                               double* p, double* af, uint64_t* n_kept, double* logl0, double* lambda0, uint64_t* rows_read,
+                               uint64_t* rows_tested, uint64_t* pairs_shipped);
+int kgwas_lmm_run_table_multi(const char* kinship_path, const char* table_base, uint32_t kmer_len, const char* pheno_path, uint32_t n_cols,
+                              const uint32_t* pheno_cols, const char* const* out_paths, uint64_t mac, double maf, uint64_t best_n,
+                              double lmin, double lmax, uint64_t chunk_variants, int32_t device, kgwas_lmm_stats* total);
 int kgwas_lmm_get_stats(const kgwas_lmm* h, kgwas_lmm_stats* out);
 void kgwas_lmm_destroy(kgwas_lmm* h);
 int kgwas_lmm_read_kinship(const char* path, uint64_t n_expected, double* K);

@@ -44,6 +44,7 @@ SYMBOLS = [
     "kgwas_snpkin_matrix", "kgwas_snpkin_format", "kgwas_snpkin_close",
     "kgwas_sym_eigen", "kgwas_lmm_create", "kgwas_lmm_null", "kgwas_lmm_test_bed", "kgwas_lmm_run_files", "kgwas_lmm_get_stats",
     "kgwas_lmm_test_bed_multi", "kgwas_lmm_run_file_multi", "kgwas_lmm_test_table", "kgwas_lmm_run_table",
+    "kgwas_lmm_test_table_multi", "kgwas_lmm_run_table_multi",
     "kgwas_lmm_destroy", "kgwas_lmm_read_kinship", "kgwas_lmm_read_fam", "kgwas_lmm_format_assoc",
     "kgwas_synth_rows_device", "kgwas_synth_rows_host",
 ]
@@ -273,6 +274,10 @@ lib.kgwas_lmm_run_file_multi.argtypes = [C.c_char_p, C.c_char_p, _u32, _vp, _pst
 lib.kgwas_lmm_test_table.argtypes = [_vp, _vp, _vp, _vp, _u64, _u64, _dbl, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _pu64, _pu64, _pu64]
 lib.kgwas_lmm_run_table.argtypes = [C.c_char_p, C.c_char_p, _u32, C.c_char_p, _u32, _u64, _dbl, _u64, _dbl, _dbl, _u64, _i32, C.c_char_p,
                                     C.POINTER(LmmStats)]
+lib.kgwas_lmm_test_table_multi.argtypes = [_vp, _u32, _vp, _vp, _vp, _u64, _u64, _dbl, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _pu64,
+                                           _pu64, _pu64]
+lib.kgwas_lmm_run_table_multi.argtypes = [C.c_char_p, C.c_char_p, _u32, C.c_char_p, _u32, _vp, _pstr, _u64, _dbl, _u64, _dbl, _dbl, _u64,
+                                          _i32, C.POINTER(LmmStats)]
 lib.kgwas_lmm_get_stats.argtypes = [_vp, C.POINTER(LmmStats)]
 lib.kgwas_lmm_destroy.argtypes = [_vp]
 lib.kgwas_lmm_destroy.restype = None

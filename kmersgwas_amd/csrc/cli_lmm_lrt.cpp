@@ -8,7 +8,10 @@
 // output D/name.assoc.txt. Defaults of -maf, -miss, -lmin, -lmax and -outdir are GEMMA's. And, in place of -bfile,
 //     lmm_lrt --kmers_table T --kmers_len K -p PHENO -lmm 2 -k KINSHIP [--mac M] [-maf f] [--best N] [-n i] [-outdir D] [-o NAME]
 // the exact test of EVERY k-mer of the table T that kmers_table_to_bed (--mac M --maf f) would write and lmm_lrt (-maf f) would then
-// test, without the PLINK files in between; the best N by the test are written, in table order (kgwas_lmm_run_table).
+// test, without the PLINK files in between; the best N by the test are written, in table order (kgwas_lmm_run_table). With
+//     --pheno_columns LIST   (a file of "col<TAB>name" lines, in place of -n and -o)
+// the listed columns of PHENO - the phenotype and its permutations - are all tested in ONE pass over the table, the best N of each
+// to D/name.assoc.txt with a log (kgwas_lmm_run_table_multi): what calc_best_pvals / get_threshold_from_perm read.
 #include <sys/stat.h>
 
 #include <cstdlib>
@@ -39,7 +42,8 @@ static void usage(const char* prog) {
             "  -lmin x, -lmax x  search range of lambda (defaults 1e-5, 1e5)\n"
             "or, every k-mer of a k-mers table (no PLINK files in between):\n"
             "       " << prog
-         << " --kmers_table T --kmers_len K -p PHENO  -lmm 2  -k KINSHIP  [--mac M] [-maf f] [--best N] [-n i] [-outdir D] [-o NAME]\n"
+         << " --kmers_table T --kmers_len K -p PHENO  -lmm 2  -k KINSHIP  [--mac M] [-maf f] [--best N] [-n i | --pheno_columns LIST]\n"
+            "       [-outdir D] [-o NAME]\n"
             "       [-lmin x] [-lmax x] [--chunk_variants c] [--device d]\n"
             "  --kmers_table T  k-mers table base name (T.table, T.names); excludes -bfile, --bfiles and --columns\n"
             "  --kmers_len K    length of the k-mers (10-31)\n"
@@ -49,6 +53,8 @@ static void usage(const char* prog) {
             "                   max(ceil(n f), M) of both ends) and lmm_lrt -maf f would then test it (defaults 5, 0.01); -miss is accepted\n"
             "                   and has no effect (a table has no missing calls)\n"
             "  --best N         the N k-mers with the largest likelihood ratio are written, in table order (default 10001)\n"
+            "  --pheno_columns LIST  file of 'col<TAB>name' lines: every listed phenotype column of PHENO (from 1) is tested in one pass\n"
+            "                   over the table, the best N of each to D/name.assoc.txt (no -n, no -o)\n"
             "  --device d       GPU ordinal (default 0)\n";
 }
 
@@ -72,6 +78,42 @@ static uint64_t whole(const string& name, const string& s, uint64_t lo, uint64_t
     return stoull(s);
 }
 
+// LIST of --columns and --pheno_columns: 'col<TAB>name' lines -> the columns (from 1) and the outputs outdir/name.assoc.txt
+static bool read_column_list(const string& path, const string& outdir, vector<uint32_t>& columns, vector<string>& outs) {
+    ifstream f(path);
+    if (!f.is_open()) {
+        cerr << "lmm_lrt: can't open " << path << endl;
+        return false;
+    }
+    set<string> names;
+    for (string line; getline(f, line);) {
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.empty()) continue;
+        const size_t tab = line.find('\t');
+        const string col = line.substr(0, tab == string::npos ? 0 : tab), name = tab == string::npos ? string() : line.substr(tab + 1);
+        if (col.empty() || col.size() > 6 || col.find_first_not_of("0123456789") != string::npos || name.empty() ||
+            name.find('\t') != string::npos) {
+            cerr << "lmm_lrt: " << path << ": a line is not 'col<TAB>name': " << line << endl;
+            return false;
+        }
+        if (stoul(col) < 1) {
+            cerr << "lmm_lrt: " << path << ": phenotype columns start at 1: " << line << endl;
+            return false;
+        }
+        if (!names.insert(name).second) {
+            cerr << "lmm_lrt: " << path << ": the name '" << name << "' is given twice" << endl;
+            return false;
+        }
+        columns.push_back((uint32_t)stoul(col));
+        outs.push_back(outdir + "/" + name + ".assoc.txt");
+    }
+    if (columns.empty()) {
+        cerr << "lmm_lrt: " << path << " lists no column" << endl;
+        return false;
+    }
+    return true;
+}
+
 // lmm_lrt --kmers_table: every check that needs no device comes before the library call
 static int table_mode(map<string, string>& a, const char* prog) {
     if (a.count("bfile") || a.count("bfiles") || a.count("columns")) {
@@ -81,6 +123,10 @@ static int table_mode(map<string, string>& a, const char* prog) {
     if (!a.count("k") || !a.count("kmers_len") || !a.count("p")) {
         cerr << "lmm_lrt: --kmers_table needs --kmers_len, -p and -k" << endl;
         usage(prog);
+        return 1;
+    }
+    if (a.count("pheno_columns") && (a.count("n") || a.count("o"))) {
+        cerr << "lmm_lrt: --pheno_columns excludes -n and -o (LIST names the columns and the outputs)" << endl;
         return 1;
     }
     const uint64_t klen = whole("--kmers_len", a["kmers_len"], 0, 1000);
@@ -108,16 +154,28 @@ static int table_mode(map<string, string>& a, const char* prog) {
         }
     }
     const string outdir = a.count("outdir") ? a["outdir"] : "./output";
-    const string out = outdir + "/" + (a.count("o") ? a["o"] : string("result")) + ".assoc.txt";
+    vector<uint32_t> columns;
+    vector<string> outs;
+    if (a.count("pheno_columns")) {
+        if (!read_column_list(a["pheno_columns"], outdir, columns, outs)) return 1;
+    } else {
+        outs.push_back(outdir + "/" + (a.count("o") ? a["o"] : string("result")) + ".assoc.txt");
+    }
     (void)mkdir(outdir.c_str(), 0777);
+    vector<const char*> op;
+    for (const string& o : outs) op.push_back(o.c_str());
     kgwas_lmm_stats st{};
-    const int rc = kgwas_lmm_run_table(a["k"].c_str(), a["kmers_table"].c_str(), (uint32_t)klen, a["p"].c_str(), (uint32_t)col, mac, maf, best,
-                                       lmin, lmax, chunk, (int32_t)device, out.c_str(), &st);
+    const int rc = columns.empty() ? kgwas_lmm_run_table(a["k"].c_str(), a["kmers_table"].c_str(), (uint32_t)klen, a["p"].c_str(), (uint32_t)col,
+                                                         mac, maf, best, lmin, lmax, chunk, (int32_t)device, op[0], &st)
+                                   : kgwas_lmm_run_table_multi(a["k"].c_str(), a["kmers_table"].c_str(), (uint32_t)klen, a["p"].c_str(),
+                                                               (uint32_t)columns.size(), columns.data(), op.data(), mac, maf, best, lmin,
+                                                               lmax, chunk, (int32_t)device, &st);
     if (rc != KGWAS_OK) {
         cerr << "lmm_lrt: " << kgwas_last_error() << endl;
         return rc == KGWAS_ERR_DEVICE ? 3 : 1;
     }
-    cerr << "[kgwas] lmm_lrt: kmers_table=" << a["kmers_table"] << " individuals=" << st.n_individuals << " rows_read=" << st.variants_read
+    cerr << "[kgwas] lmm_lrt: kmers_table=" << a["kmers_table"] << " columns=" << (columns.empty() ? 1 : columns.size())
+         << " individuals=" << st.n_individuals << " rows_read=" << st.variants_read
          << " rows_tested=" << st.variants_tested << " best=" << best << " eigendecompositions=" << st.eigendecompositions
          << " ms: eigen=" << st.eigen_ms << " rotate=" << st.rotate_ms << " grid=" << st.grid_ms << " refine=" << st.refine_ms << endl;
     cli_finish();
@@ -126,7 +184,7 @@ static int table_mode(map<string, string>& a, const char* prog) {
 
 int main(int argc, char* argv[]) {
     static const char* const valued[] = {"bfile", "bfiles", "lmm", "k", "outdir", "o", "n", "maf", "miss", "lmin", "lmax", "chunk_variants", "columns",
-                                         "kmers_table", "kmers_len", "p", "mac", "best", "device"};
+                                         "kmers_table", "kmers_len", "p", "mac", "best", "device", "pheno_columns"};
     map<string, string> a;
     for (int i = 1; i < argc; i++) {
         string s = argv[i];
@@ -155,7 +213,7 @@ int main(int argc, char* argv[]) {
         return 1;
     }
     if (a.count("kmers_table")) return table_mode(a, argv[0]);
-    for (const char* o : {"kmers_len", "p", "mac", "best", "device"})
+    for (const char* o : {"kmers_len", "p", "mac", "best", "device", "pheno_columns"})
         if (a.count(o)) {
             cerr << "lmm_lrt: option '" << o << "' needs --kmers_table" << endl;
             return 1;
@@ -173,37 +231,7 @@ int main(int argc, char* argv[]) {
     vector<string> bases, outs;
     vector<uint32_t> columns;
     if (a.count("columns")) {
-        ifstream f(a["columns"]);
-        if (!f.is_open()) {
-            cerr << "lmm_lrt: can't open " << a["columns"] << endl;
-            return 1;
-        }
-        set<string> names;
-        for (string line; getline(f, line);) {
-            if (!line.empty() && line.back() == '\r') line.pop_back();
-            if (line.empty()) continue;
-            const size_t tab = line.find('\t');
-            const string col = line.substr(0, tab == string::npos ? 0 : tab), name = tab == string::npos ? string() : line.substr(tab + 1);
-            if (col.empty() || col.size() > 6 || col.find_first_not_of("0123456789") != string::npos || name.empty() ||
-                name.find('\t') != string::npos) {
-                cerr << "lmm_lrt: " << a["columns"] << ": a line is not 'col<TAB>name': " << line << endl;
-                return 1;
-            }
-            if (stoul(col) < 1) {
-                cerr << "lmm_lrt: " << a["columns"] << ": phenotype columns start at 1: " << line << endl;
-                return 1;
-            }
-            if (!names.insert(name).second) {
-                cerr << "lmm_lrt: " << a["columns"] << ": the name '" << name << "' is given twice" << endl;
-                return 1;
-            }
-            columns.push_back((uint32_t)stoul(col));
-            outs.push_back(outdir + "/" + name + ".assoc.txt");
-        }
-        if (columns.empty()) {
-            cerr << "lmm_lrt: " << a["columns"] << " lists no column" << endl;
-            return 1;
-        }
+        if (!read_column_list(a["columns"], outdir, columns, outs)) return 1;
         bases.push_back(a["bfile"]);
     } else if (a.count("bfile")) {
         bases.push_back(a["bfile"]);

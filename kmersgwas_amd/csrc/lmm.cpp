@@ -12,6 +12,10 @@
 //            order, flags the rows that kmers_table_to_bed would write AND prep would test, and compacts those into code rows
 //            and LmmVariants with prep's bits (lmm_table_kernels.hip); rotate, grid and refine then run over them unchanged. The
 //            host keeps the best N by (lrt, table row). run_table is its file layer (lmm_lrt --kmers_table);
+// test_table_multi: several phenotype columns against ONE table in one pass (the phenotype and its permutations). The front end and
+//            the rotation run once per row, the xt yt sums and the refinement per block of LMM_PBLOCK columns, and a select kernel
+//            hands the host only the (column, row) pairs that can still enter a column's best N. Every kept row and number has the
+//            bits of test_table's for that column. run_table_multi is its file layer (lmm_lrt --kmers_table --pheno_columns);
 // run_files: the file layer of the lmm_lrt tool - kinship text, .fam phenotype column, .bim, .bed in, .assoc.txt and .log.txt out.
 //            Individuals without a phenotype are dropped from K, y and the .bed rows before anything else; beds that keep the
 //            same individuals share one handle, so one eigendecomposition. run_file_multi: one bfile, several .fam columns with
@@ -62,6 +66,13 @@ struct kgwas_lmm {
     uint32_t multi_cols = 0;
     DevBuf<double> d_Ytm, d_basem, d_nullm, d_Gx, d_Gxy, d_lrtm, d_lamm, d_pm;
     std::vector<double> h_outm;
+    // the selection of the multi-phenotype table pass (allocated at its first call): per block of 256 pairs the counts and offsets,
+    // the survivors' number, the block's thresholds, and the records on the device and in pinned host memory
+    bool select_ready = false;
+    DevBuf<uint32_t> d_sel_cnt, d_sel_off, d_sel_total;
+    DevBuf<LmmSelectCol> d_sel_cols;
+    DevBuf<LmmTableRecord> d_sel_rec;
+    PinBuf<LmmTableRecord> h_sel_rec;
     ~kgwas_lmm() {
         if (!on_device) return;
         (void)hipSetDevice(device);
@@ -208,8 +219,9 @@ void test_bed(kgwas_lmm* h, const double* y, const uint8_t* body, uint64_t nv, d
 
 // The multi-phenotype pass. Nothing of the single-phenotype null (y_cur, have_null, d_yt, d_base, l0) is touched.
 // multi_prepare: Y[n_pheno][n] -> Yt, the base sums and the null models of all columns on the device; logl0, lambda0 [n_pheno].
-void multi_prepare(kgwas_lmm* h, uint32_t n_pheno, const double* Y, double* logl0, double* lambda0) {
-    if (!n_pheno) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_test_bed_multi: n_pheno is 0");
+void multi_prepare(kgwas_lmm* h, uint32_t n_pheno, const double* Y, double* logl0, double* lambda0,
+                   const char* who = "kgwas_lmm_test_bed_multi") {
+    if (!n_pheno) throw Error(KGWAS_ERR_ARG, std::string(who) + ": n_pheno is 0");
     const uint64_t n = h->n, ldi = h->dm.ldi, chunk = h->chunk;
     std::vector<double> Yt((uint64_t)n_pheno * ldi, 0.0);
     for (uint32_t k = 0; k < n_pheno; k++) rotate_phenotype(h, Y + k * n, &Yt[k * ldi], " (column " + std::to_string(k) + ")");
@@ -314,25 +326,44 @@ bool ranks_before(const TableHit& a, const TableHit& b) {
     return ka != kb ? ka > kb : a.row < b.row;
 }
 
-// Every row of table t against y: the best best_n tested rows by lrt, in table row order. A reader thread fills two pinned row
+// offers a result to a heap of at most best_n with the worst kept result on top
+void heap_offer(std::vector<TableHit>& heap, uint64_t best_n, const TableHit& hit) {
+    auto worse_on_top = [](const TableHit& a, const TableHit& b) { return ranks_before(a, b); };
+    if (heap.size() < best_n) {
+        heap.push_back(hit);
+        std::push_heap(heap.begin(), heap.end(), worse_on_top);
+    } else if (ranks_before(hit, heap.front())) {
+        std::pop_heap(heap.begin(), heap.end(), worse_on_top);
+        heap.back() = hit;
+        std::push_heap(heap.begin(), heap.end(), worse_on_top);
+    }
+}
+
+void sort_by_row(std::vector<TableHit>& heap) {
+    std::sort(heap.begin(), heap.end(), [](const TableHit& a, const TableHit& b) { return a.row < b.row; });
+}
+
+// What test_table and test_table_multi share: the checks, the pieces and the front end. A reader thread fills two pinned row
 // buffers in turn while the device works on the piece before; per piece the rows are squeezed, flagged and compacted
-// (lmm_table_kernels.hip), and the compacted rows go through rotate, grid and refine in sub-chunks of at most h->chunk. The host
-// keeps a heap of best_n results with the worst on top.
-void test_table(kgwas_lmm* h, const double* y, kgwas_table* t, const uint64_t* col, uint64_t n_acc, uint64_t min_count, double maf,
-                uint64_t best_n, std::vector<TableHit>& kept, uint64_t& rows_read, uint64_t& rows_tested) {
-    if (n_acc != h->n) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_test_table: n_acc differs from the handle's number of individuals");
-    if (!best_n) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_test_table: best_n is 0");
+// (lmm_table_kernels.hip). prepare() runs after the checks and before any device work (the null models); per_piece(total, codes,
+// vars, row, kmer) gets a piece's compacted tested rows on the device, total > 0 of them, and is done with them when it returns.
+// `who` starts the messages; a tested row counts `weight` times in the stats' variants_tested.
+template <class Prepare, class PerPiece>
+void table_pass(kgwas_lmm* h, kgwas_table* t, const uint64_t* col, uint64_t n_acc, uint64_t min_count, double maf, uint64_t best_n,
+                const std::string& who, uint64_t weight, Prepare prepare, PerPiece per_piece, uint64_t& rows_read, uint64_t& rows_tested) {
+    if (n_acc != h->n) throw Error(KGWAS_ERR_ARG, who + ": n_acc differs from the handle's number of individuals");
+    if (!best_n) throw Error(KGWAS_ERR_ARG, who + ": best_n is 0");
     uint64_t S_f = 0, n_rows = 0, W_f = 0;
     uint32_t klen = 0;
     if (kgwas_table_info(t, &S_f, &n_rows, &W_f, &klen) != KGWAS_OK) throw Error(KGWAS_ERR_ARG, kgwas_last_error());
     const uint64_t S = n_acc;
     for (uint64_t i = 0; i < S; i++)
-        if (col[i] >= S_f) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_test_table: column index out of range");
-    check_squeeze_fits("kgwas_lmm_test_table", S_f, S);  // (before any allocation)
-    fit_null(h, y);
+        if (col[i] >= S_f) throw Error(KGWAS_ERR_ARG, who + ": column index out of range");
+    check_squeeze_fits(who.c_str(), S_f, S);  // (before any allocation)
+    prepare();
     KGWAS_HIP(hipSetDevice(h->device));
     const uint32_t W_m = (uint32_t)(2 * ((S + 127) / 128));
-    const uint64_t stride = 1 + W_f, chunk = h->chunk;
+    const uint64_t stride = 1 + W_f;
     uint64_t piece = std::max<uint64_t>(1024, std::min<uint64_t>(1u << 18, (64ull << 20) / (8 * stride)));
     const long long forced = opt_int("KGWAS_LMM_PIECE_ROWS", 0);
     if (forced > 0) piece = (uint64_t)std::min<long long>(forced, 1 << 20);
@@ -415,13 +446,6 @@ void test_table(kgwas_lmm* h, const double* y, kgwas_table* t, const uint64_t* c
         }
     } rj{reader, mu, cv, stop};
 
-    // the worst kept result on top
-    auto worse_on_top = [](const TableHit& a, const TableHit& b) { return ranks_before(a, b); };
-    std::vector<TableHit> heap;
-    heap.reserve((size_t)std::min<uint64_t>(best_n, 1u << 20));
-    std::vector<double> o_lrt(chunk), o_lam(chunk), o_p(chunk);
-    std::vector<LmmVariant> o_vars(chunk);
-    std::vector<uint64_t> o_row(chunk), o_kmer(chunk);
     hipStream_t st = h->stream;
     rows_read = rows_tested = 0;
     for (uint64_t k = 0; k < n_pieces; k++) {
@@ -448,11 +472,36 @@ void test_table(kgwas_lmm* h, const double* y, kgwas_table* t, const uint64_t* c
         float fms = 0;
         KGWAS_HIP(hipEventElapsedTime(&fms, fe[0], fe[1]));
         h->st.rotate_ms += fms;
-        if (total > c) throw Error(KGWAS_ERR_STATE, "kgwas_lmm_test_table: the front end counted more tested rows than rows");
+        if (total > c) throw Error(KGWAS_ERR_STATE, who + ": the front end counted more tested rows than rows");
+        if (total) per_piece(total, (const uint8_t*)d_codes.p, (const LmmVariant*)d_vars.p, (const uint64_t*)d_row.p, (const uint64_t*)d_kmer.p);
+        rows_read += c;
+        rows_tested += total;
+        h->st.variants_read += c;
+        h->st.variants_tested += total * weight;
+    }
+    if (rerr) std::rethrow_exception(rerr);
+}
+
+// Every row of table t against y: the best best_n tested rows by lrt, in table row order. The compacted rows of a piece go
+// through rotate, grid and refine in sub-chunks of at most h->chunk. The host keeps a heap of best_n results with the worst on top.
+void test_table(kgwas_lmm* h, const double* y, kgwas_table* t, const uint64_t* col, uint64_t n_acc, uint64_t min_count, double maf,
+                uint64_t best_n, std::vector<TableHit>& kept, uint64_t& rows_read, uint64_t& rows_tested) {
+    const uint64_t chunk = h->chunk;
+    std::vector<TableHit> heap;
+    std::vector<double> o_lrt, o_lam, o_p;
+    std::vector<LmmVariant> o_vars;
+    std::vector<uint64_t> o_row, o_kmer;
+    auto prepare = [&] {
+        fit_null(h, y);
+        heap.reserve((size_t)std::min<uint64_t>(best_n, 1u << 20));
+        o_lrt.resize(chunk), o_lam.resize(chunk), o_p.resize(chunk), o_vars.resize(chunk), o_row.resize(chunk), o_kmer.resize(chunk);
+    };
+    auto per_piece = [&](uint32_t total, const uint8_t* d_codes, const LmmVariant* d_vars, const uint64_t* d_row, const uint64_t* d_kmer) {
+        hipStream_t st = h->stream;
         for (uint64_t sub = 0; sub < total; sub += chunk) {
             const uint32_t cc = (uint32_t)std::min<uint64_t>(chunk, total - sub);
-            const uint8_t* codes = d_codes.p + sub * h->dm.bpsp;
-            const LmmVariant* vars = d_vars.p + sub;
+            const uint8_t* codes = d_codes + sub * h->dm.bpsp;
+            const LmmVariant* vars = d_vars + sub;
             KGWAS_HIP(hipEventRecord(h->ev[0], st));
             KGWAS_HIP(launch_lmm_rotate(codes, vars, cc, h->dm, h->d_U.p, h->d_Xt.p, st));
             KGWAS_HIP(hipEventRecord(h->ev[1], st));
@@ -465,8 +514,8 @@ void test_table(kgwas_lmm* h, const double* y, kgwas_table* t, const uint64_t* c
             KGWAS_HIP(hipMemcpyAsync(o_lam.data(), h->d_lam.p, cc * sizeof(double), hipMemcpyDeviceToHost, st));
             KGWAS_HIP(hipMemcpyAsync(o_p.data(), h->d_p.p, cc * sizeof(double), hipMemcpyDeviceToHost, st));
             KGWAS_HIP(hipMemcpyAsync(o_vars.data(), vars, cc * sizeof(LmmVariant), hipMemcpyDeviceToHost, st));
-            KGWAS_HIP(hipMemcpyAsync(o_row.data(), d_row.p + sub, cc * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-            KGWAS_HIP(hipMemcpyAsync(o_kmer.data(), d_kmer.p + sub, cc * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+            KGWAS_HIP(hipMemcpyAsync(o_row.data(), d_row + sub, cc * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+            KGWAS_HIP(hipMemcpyAsync(o_kmer.data(), d_kmer + sub, cc * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
             KGWAS_HIP(hipStreamSynchronize(st));
             float ms[3] = {0, 0, 0};
             for (int e = 0; e < 3; e++) KGWAS_HIP(hipEventElapsedTime(&ms[e], h->ev[e], h->ev[e + 1]));
@@ -474,26 +523,112 @@ void test_table(kgwas_lmm* h, const double* y, kgwas_table* t, const uint64_t* c
             h->st.grid_ms += ms[1];
             h->st.refine_ms += ms[2];
             h->st.chunks++;
-            for (uint32_t v = 0; v < cc; v++) {
-                const TableHit hit{o_lrt[v], o_lam[v], o_p[v], o_vars[v].af, o_row[v], o_kmer[v]};
-                if (heap.size() < best_n) {
-                    heap.push_back(hit);
-                    std::push_heap(heap.begin(), heap.end(), worse_on_top);
-                } else if (ranks_before(hit, heap.front())) {
-                    std::pop_heap(heap.begin(), heap.end(), worse_on_top);
-                    heap.back() = hit;
-                    std::push_heap(heap.begin(), heap.end(), worse_on_top);
-                }
-            }
+            for (uint32_t v = 0; v < cc; v++) heap_offer(heap, best_n, TableHit{o_lrt[v], o_lam[v], o_p[v], o_vars[v].af, o_row[v], o_kmer[v]});
         }
-        rows_read += c;
-        rows_tested += total;
-        h->st.variants_read += c;
-        h->st.variants_tested += total;
-    }
-    if (rerr) std::rethrow_exception(rerr);
-    std::sort(heap.begin(), heap.end(), [](const TableHit& a, const TableHit& b) { return a.row < b.row; });
+    };
+    table_pass(h, t, col, n_acc, min_count, maf, best_n, "kgwas_lmm_test_table", 1, prepare, per_piece, rows_read, rows_tested);
+    sort_by_row(heap);
     kept.swap(heap);
+}
+
+// The same for n_pheno columns Y[n_pheno][n] in one pass over the table: the best best_n per column, each with the rows and the
+// bits test_table gives for that column alone. Per sub-chunk the rotation and the grid sums without y run once; per block of
+// LMM_PBLOCK columns the xt yt sums, the refinement and the select kernel, which hands the host only the (column, row) pairs that
+// can still enter the column's heap: all of them while the heap is not full, then those with lrt above the heap's worst as the
+// host knew it before the launch. The heaps still decide; the per-row arrays stay on the device.
+void test_table_multi(kgwas_lmm* h, uint32_t n_pheno, const double* Y, kgwas_table* t, const uint64_t* col, uint64_t n_acc,
+                      uint64_t min_count, double maf, uint64_t best_n, std::vector<std::vector<TableHit>>& kept, double* logl0,
+                      double* lambda0, uint64_t& rows_read, uint64_t& rows_tested, uint64_t& pairs_shipped) {
+    const std::string who = "kgwas_lmm_test_table_multi";
+    if (!n_pheno) throw Error(KGWAS_ERR_ARG, who + ": n_pheno is 0");  // (before the table's checks)
+    const uint64_t chunk = h->chunk, ldi = h->dm.ldi, cap = (uint64_t)LMM_PBLOCK * chunk;
+    const bool select = opt_int("KGWAS_LMM_TABLE_SELECT", 1) != 0;
+    std::vector<std::vector<TableHit>> heaps(n_pheno);
+    hipEvent_t se[3] = {nullptr, nullptr, nullptr};  // around a sub-chunk's rotation and shared grid sums
+    struct EventGuard {
+        hipEvent_t* e;
+        ~EventGuard() {
+            for (int k = 0; k < 3; k++)
+                if (e[k]) (void)hipEventDestroy(e[k]);
+        }
+    } eg{se};
+    pairs_shipped = 0;
+    auto prepare = [&] {
+        multi_prepare(h, n_pheno, Y, logl0, lambda0, who.c_str());
+        if (!h->select_ready) {
+            const uint64_t n_blocks = (cap + LMM_TABLE_BLOCK - 1) / LMM_TABLE_BLOCK;
+            h->d_sel_cnt.alloc(n_blocks);
+            h->d_sel_off.alloc(n_blocks);
+            h->d_sel_total.alloc(1);
+            h->d_sel_cols.alloc(LMM_PBLOCK);
+            h->d_sel_rec.alloc(cap);
+            h->h_sel_rec.alloc(cap);
+            h->select_ready = true;
+        }
+        for (hipEvent_t& e : se) KGWAS_HIP(hipEventCreate(&e));
+        for (std::vector<TableHit>& hp : heaps) hp.reserve((size_t)std::min<uint64_t>(best_n, 1u << 14));
+    };
+    auto per_piece = [&](uint32_t total, const uint8_t* d_codes, const LmmVariant* d_vars, const uint64_t* d_row, const uint64_t* d_kmer) {
+        hipStream_t st = h->stream;
+        for (uint64_t sub = 0; sub < total; sub += chunk) {
+            const uint32_t cc = (uint32_t)std::min<uint64_t>(chunk, total - sub);
+            const LmmVariant* vars = d_vars + sub;
+            KGWAS_HIP(hipEventRecord(se[0], st));
+            KGWAS_HIP(launch_lmm_rotate(d_codes + sub * h->dm.bpsp, vars, cc, h->dm, h->d_U.p, h->d_Xt.p, st));
+            KGWAS_HIP(hipEventRecord(se[1], st));
+            KGWAS_HIP(launch_lmm_grid_shared(h->d_Xt.p, cc, h->dm, h->d_wt.p, h->d_HB.p, h->d_Gx.p, st));
+            KGWAS_HIP(hipEventRecord(se[2], st));
+            for (uint32_t p0 = 0; p0 < n_pheno; p0 += LMM_PBLOCK) {
+                const uint32_t pb = std::min(LMM_PBLOCK, n_pheno - p0);
+                const double* Ytb = h->d_Ytm.p + (uint64_t)p0 * ldi;
+                // what the host knows of the block's heaps now; a NaN lrt ranks as -inf (ranks_before)
+                LmmSelectCol sc[LMM_PBLOCK];
+                for (uint32_t k = 0; k < pb; k++) {
+                    const std::vector<TableHit>& hp = heaps[p0 + k];
+                    const bool open = !select || hp.size() < best_n;
+                    const double worst = open ? 0.0 : hp.front().lrt;
+                    sc[k] = LmmSelectCol{std::isnan(worst) ? -INFINITY : worst, open ? 1u : 0u, 0u};
+                }
+                KGWAS_HIP(hipMemcpyAsync(h->d_sel_cols.p, sc, pb * sizeof(LmmSelectCol), hipMemcpyHostToDevice, st));
+                KGWAS_HIP(hipEventRecord(h->ev[1], st));
+                KGWAS_HIP(launch_lmm_grid_xy(h->d_Xt.p, cc, h->dm, Ytb, pb, h->d_HB.p, h->d_Gxy.p, st));
+                KGWAS_HIP(hipEventRecord(h->ev[2], st));
+                KGWAS_HIP(launch_lmm_refine_multi(h->d_Xt.p, h->d_Gx.p, h->d_Gxy.p, vars, cc, h->dm, h->d_d.p, h->d_wt.p, Ytb, pb, h->d_grid.p,
+                                                  h->d_basem.p + (uint64_t)p0 * LMM_GRID * LMM_BASE, h->d_nullm.p + 2 * (uint64_t)p0,
+                                                  h->d_lrtm.p, h->d_lamm.p, h->d_pm.p, st));
+                KGWAS_HIP(launch_lmm_table_select(h->d_lrtm.p, h->d_lamm.p, h->d_pm.p, cc, pb, vars, d_row + sub, d_kmer + sub, h->d_sel_cols.p,
+                                                  h->d_sel_cnt.p, h->d_sel_off.p, h->d_sel_total.p, h->d_sel_rec.p, (uint32_t)cap, st));
+                KGWAS_HIP(hipEventRecord(h->ev[3], st));
+                uint32_t count = 0;
+                KGWAS_HIP(hipMemcpyAsync(&count, h->d_sel_total.p, sizeof(count), hipMemcpyDeviceToHost, st));
+                KGWAS_HIP(hipStreamSynchronize(st));  // (sc is read by the copy until here)
+                if (count > (uint64_t)pb * cc) throw Error(KGWAS_ERR_STATE, who + ": the select kernel counted more survivors than pairs");
+                if (count) {
+                    KGWAS_HIP(hipMemcpyAsync(h->h_sel_rec.p, h->d_sel_rec.p, count * sizeof(LmmTableRecord), hipMemcpyDeviceToHost, st));
+                    KGWAS_HIP(hipStreamSynchronize(st));
+                }
+                float ms[2] = {0, 0};
+                if (p0 == 0) {
+                    for (int e = 0; e < 2; e++) KGWAS_HIP(hipEventElapsedTime(&ms[e], se[e], se[e + 1]));
+                    h->st.rotate_ms += ms[0];
+                    h->st.grid_ms += ms[1];
+                }
+                for (int e = 0; e < 2; e++) KGWAS_HIP(hipEventElapsedTime(&ms[e], h->ev[e + 1], h->ev[e + 2]));
+                h->st.grid_ms += ms[0];
+                h->st.refine_ms += ms[1];
+                for (uint32_t r = 0; r < count; r++) {
+                    const LmmTableRecord& o = h->h_sel_rec.p[r];
+                    if (o.col >= pb) throw Error(KGWAS_ERR_STATE, who + ": a survivor record names a column outside its block");
+                    heap_offer(heaps[p0 + o.col], best_n, TableHit{o.lrt, o.lam, o.p, o.af, o.row, o.kmer});
+                }
+                pairs_shipped += count;
+            }
+            h->st.chunks++;
+        }
+    };
+    table_pass(h, t, col, n_acc, min_count, maf, best_n, who, n_pheno, prepare, per_piece, rows_read, rows_tested);
+    for (std::vector<TableHit>& hp : heaps) sort_by_row(hp);
+    kept.swap(heaps);
 }
 
 kgwas_lmm* create(uint64_t n, const double* K, int device, double lmin, double lmax, uint64_t chunk_variants) {
@@ -841,69 +976,77 @@ void run_file_multi(const char* kinship_path, const char* bfile_base, uint32_t n
     if (total) *total = h->st;
 }
 
-// The file layer of lmm_lrt --kmers_table: the accessions and their order are the phenotype file's, y its column pheno_col (from
-// 1), the k-mers come straight from <table_base>.table. The best best_n k-mers by the exact test go to `out` in table order, with
-// the bytes run_files writes for them after kmers_table_to_bed; a log goes beside it.
-void run_table(const char* kinship_path, const char* table_base, uint32_t kmer_len, const char* pheno_path, uint32_t pheno_col,
-               uint64_t mac, double maf, uint64_t best_n, double lmin, double lmax, uint64_t chunk_variants, int device, const char* out,
-               kgwas_lmm_stats* total) {
-    if (!kinship_path || !table_base || !pheno_path || !out) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_run_table: null argument");
-    if (pheno_col < 1) throw Error(KGWAS_ERR_ARG, "the phenotype column (-n) starts at 1");
-    if (!best_n) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_run_table: best_n is 0");
-    const double t_start = now_ms();
-    struct Files {
-        kgwas_pheno* ph = nullptr;
-        kgwas_table* t = nullptr;
-        ~Files() {
-            if (t) kgwas_table_close(t);
-            if (ph) kgwas_pheno_free(ph);
-        }
-    } f;
-    auto ck = [](int rc) {
-        if (rc != KGWAS_OK) throw Error(rc, kgwas_last_error());
-    };
-    ck(kgwas_pheno_load(pheno_path, &f.ph));
-    uint64_t n_pheno = 0, S = 0;
-    ck(kgwas_pheno_info(f.ph, &n_pheno, &S));
-    if (pheno_col > n_pheno)
-        throw Error(KGWAS_ERR_FORMAT, std::string(pheno_path) + " has no phenotype column " + std::to_string(pheno_col));
-    std::vector<const char*> acc(S);
-    for (uint64_t i = 0; i < S; i++) ck(kgwas_pheno_accession(f.ph, i, &acc[i]));
-    const float* Y = nullptr;
-    ck(kgwas_pheno_values(f.ph, &Y));
-    // y as it would arrive through kmers_table_to_bed's .fam: the loader's float in ostream's default format, parsed as read_fam does
-    std::vector<double> y(S);
-    for (uint64_t i = 0; i < S; i++) {
-        std::ostringstream os;
-        os << Y[(uint64_t)(pheno_col - 1) * S + i];
-        const std::string text = os.str();
-        if (text == "-9" || text == "NA")
-            throw Error(KGWAS_ERR_FORMAT, std::string(pheno_path) + ": the phenotype of " + acc[i] + " is " + text +
-                                              ", which a .fam reads as missing; remove the accession from the phenotype file");
-        char* end = nullptr;
-        const double v = strtod(text.c_str(), &end);
-        if (end == text.c_str() || *end || !std::isfinite(v))
-            throw Error(KGWAS_ERR_FORMAT, std::string(pheno_path) + ": phenotype '" + text + "' of " + acc[i] + " is no number");
-        y[i] = v;
-    }
-    ck(kgwas_table_open(table_base, kmer_len, &f.t));
-    std::vector<uint64_t> col(S);
-    ck(kgwas_table_column_map(f.t, acc.data(), S, col.data()));
-    uint64_t S_f = 0, n_rows = 0, W_f = 0;
+// ---- what run_table and run_table_multi share ----
+
+// The inputs of lmm_lrt --kmers_table, each read once: the phenotype file (its accessions, in its order, are the individuals), the
+// open table with its column map, the kinship text.
+struct TableRun {
+    kgwas_pheno* ph = nullptr;
+    kgwas_table* t = nullptr;
+    std::string pheno_path;
+    uint64_t n_pheno = 0, S = 0, min_count = 0;
     uint32_t klen = 0;
-    ck(kgwas_table_info(f.t, &S_f, &n_rows, &W_f, &klen));
-    check_squeeze_fits("lmm_lrt --kmers_table", S_f, S);
-    const std::vector<double> K = read_kinship(kinship_path, S, "the phenotype file");
-    const uint64_t min_count = kgwas_min_count(S, maf, mac);
-    std::unique_ptr<kgwas_lmm> h(create(S, K.data(), device, lmin, lmax, chunk_variants));
-    std::vector<TableHit> kept;
-    uint64_t rows_read = 0, rows_tested = 0;
-    test_table(h.get(), y.data(), f.t, col.data(), S, min_count, maf, best_n, kept, rows_read, rows_tested);
+    std::vector<const char*> acc;
+    const float* Y = nullptr;
+    std::vector<uint64_t> col;
+    std::vector<double> K;
+    ~TableRun() {
+        if (t) kgwas_table_close(t);
+        if (ph) kgwas_pheno_free(ph);
+    }
+    static void ck(int rc) {
+        if (rc != KGWAS_OK) throw Error(rc, kgwas_last_error());
+    }
+    void load_pheno(const char* path) {
+        pheno_path = path;
+        ck(kgwas_pheno_load(path, &ph));
+        ck(kgwas_pheno_info(ph, &n_pheno, &S));
+    }
+    void need_column(uint32_t pheno_col) const {
+        if (pheno_col > n_pheno) throw Error(KGWAS_ERR_FORMAT, pheno_path + " has no phenotype column " + std::to_string(pheno_col));
+    }
+    void load_values() {
+        acc.resize(S);
+        for (uint64_t i = 0; i < S; i++) ck(kgwas_pheno_accession(ph, i, &acc[i]));
+        ck(kgwas_pheno_values(ph, &Y));
+    }
+    // y as it would arrive through kmers_table_to_bed's .fam: the loader's float in ostream's default format, parsed as read_fam does
+    void column(uint32_t pheno_col, double* y) const {
+        for (uint64_t i = 0; i < S; i++) {
+            std::ostringstream os;
+            os << Y[(uint64_t)(pheno_col - 1) * S + i];
+            const std::string text = os.str();
+            if (text == "-9" || text == "NA")
+                throw Error(KGWAS_ERR_FORMAT, pheno_path + ": the phenotype of " + acc[i] + " is " + text +
+                                                  ", which a .fam reads as missing; remove the accession from the phenotype file");
+            char* end = nullptr;
+            const double v = strtod(text.c_str(), &end);
+            if (end == text.c_str() || *end || !std::isfinite(v))
+                throw Error(KGWAS_ERR_FORMAT, pheno_path + ": phenotype '" + text + "' of " + acc[i] + " is no number");
+            y[i] = v;
+        }
+    }
+    void open_table(const char* table_base, uint32_t kmer_len, const char* kinship_path, double maf, uint64_t mac) {
+        ck(kgwas_table_open(table_base, kmer_len, &t));
+        col.resize(S);
+        ck(kgwas_table_column_map(t, acc.data(), S, col.data()));
+        uint64_t S_f = 0, n_rows = 0, W_f = 0;
+        ck(kgwas_table_info(t, &S_f, &n_rows, &W_f, &klen));
+        check_squeeze_fits("lmm_lrt --kmers_table", S_f, S);
+        K = read_kinship(kinship_path, S, "the phenotype file");
+        min_count = kgwas_min_count(S, maf, mac);
+    }
+};
+
+// one column's kept k-mers to `out` in table order, with the bytes run_files writes for them after kmers_table_to_bed, and the log
+void write_table_result(const std::string& out, const std::vector<TableHit>& kept, const TableRun& r, const char* table_base,
+                        uint32_t pheno_col, const char* kinship_path, uint64_t rows_read, uint64_t rows_tested, uint64_t best_n,
+                        double lambda0, double l0, const kgwas_lmm_stats& st, double total_ms) {
     std::string text = assoc_header();
     for (const TableHit& k : kept) {
         char km[33];
-        for (uint32_t i = 0; i < klen; i++) km[i] = "ACGT"[(k.kmer >> (2 * (klen - 1 - i))) & 3];  // bits2kmer31, as kmers_table_to_bed's .bim
-        km[klen] = 0;
+        for (uint32_t i = 0; i < r.klen; i++) km[i] = "ACGT"[(k.kmer >> (2 * (r.klen - 1 - i))) & 3];  // bits2kmer31, as kmers_table_to_bed's .bim
+        km[r.klen] = 0;
         char line[1024];
         const uint64_t len = format_assoc("0", km, "0", 0, "0", "1", k.af, k.lam, k.p, line, sizeof(line));
         text.append(line, len);
@@ -914,12 +1057,70 @@ void run_table(const char* kinship_path, const char* table_base, uint32_t kmer_l
                             "lmm_lrt: ML likelihood-ratio test (-lmm 2)\nkmers_table\t%s\nphenotypes\t%s\nphenotype_column\t%u\nkinship\t%s\n"
                             "individuals_used\t%llu\nmin_count\t%llu\nrows_read\t%llu\nrows_tested\t%llu\nrows_kept\t%llu\nbest_n\t%llu\n"
                             "lambda0\t%.6e\nlogl_H0\t%.6f\nms: eigen=%.3f rotate=%.3f grid=%.3f refine=%.3f total=%.3f\n",
-                            table_base, pheno_path, pheno_col, kinship_path, (unsigned long long)S, (unsigned long long)min_count,
+                            table_base, r.pheno_path.c_str(), pheno_col, kinship_path, (unsigned long long)r.S, (unsigned long long)r.min_count,
                             (unsigned long long)rows_read, (unsigned long long)rows_tested, (unsigned long long)kept.size(),
-                            (unsigned long long)best_n, h->lambda0, h->l0, h->st.eigen_ms, h->st.rotate_ms, h->st.grid_ms, h->st.refine_ms,
-                            now_ms() - t_start);
+                            (unsigned long long)best_n, lambda0, l0, st.eigen_ms, st.rotate_ms, st.grid_ms, st.refine_ms, total_ms);
     if (ll < 0) throw Error(KGWAS_ERR_IO, "can't write " + log_path_of(out));
     write_text(log_path_of(out), std::string(log, (size_t)std::min<int>(ll, sizeof(log) - 1)), "wb");
+}
+
+// The file layer of lmm_lrt --kmers_table: the accessions and their order are the phenotype file's, y its column pheno_col (from
+// 1), the k-mers come straight from <table_base>.table. The best best_n k-mers by the exact test go to `out` in table order, with
+// the bytes run_files writes for them after kmers_table_to_bed; a log goes beside it.
+void run_table(const char* kinship_path, const char* table_base, uint32_t kmer_len, const char* pheno_path, uint32_t pheno_col,
+               uint64_t mac, double maf, uint64_t best_n, double lmin, double lmax, uint64_t chunk_variants, int device, const char* out,
+               kgwas_lmm_stats* total) {
+    if (!kinship_path || !table_base || !pheno_path || !out) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_run_table: null argument");
+    if (pheno_col < 1) throw Error(KGWAS_ERR_ARG, "the phenotype column (-n) starts at 1");
+    if (!best_n) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_run_table: best_n is 0");
+    const double t_start = now_ms();
+    TableRun r;
+    r.load_pheno(pheno_path);
+    r.need_column(pheno_col);
+    r.load_values();
+    std::vector<double> y(r.S);
+    r.column(pheno_col, y.data());
+    r.open_table(table_base, kmer_len, kinship_path, maf, mac);
+    std::unique_ptr<kgwas_lmm> h(create(r.S, r.K.data(), device, lmin, lmax, chunk_variants));
+    std::vector<TableHit> kept;
+    uint64_t rows_read = 0, rows_tested = 0;
+    test_table(h.get(), y.data(), r.t, r.col.data(), r.S, r.min_count, maf, best_n, kept, rows_read, rows_tested);
+    write_table_result(out, kept, r, table_base, pheno_col, kinship_path, rows_read, rows_tested, best_n, h->lambda0, h->l0, h->st,
+                       now_ms() - t_start);
+    if (total) *total = h->st;
+}
+
+// The same for n_cols columns of the phenotype file (pheno_cols, from 1) in ONE pass over the table: the files are read once, K is
+// eigendecomposed once, and outs[k] with its log gets what run_table writes for column pheno_cols[k] (the kernels' times are the
+// shared pass's, the same in every column's log).
+void run_table_multi(const char* kinship_path, const char* table_base, uint32_t kmer_len, const char* pheno_path, uint32_t n_cols,
+                     const uint32_t* cols, const char* const* outs, uint64_t mac, double maf, uint64_t best_n, double lmin, double lmax,
+                     uint64_t chunk_variants, int device, kgwas_lmm_stats* total) {
+    if (!kinship_path || !table_base || !pheno_path || !cols || !outs) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_run_table_multi: null argument");
+    if (!n_cols) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_run_table_multi: no phenotype column given");
+    for (uint32_t k = 0; k < n_cols; k++) {
+        if (!outs[k]) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_run_table_multi: null argument");
+        if (cols[k] < 1) throw Error(KGWAS_ERR_ARG, "phenotype columns start at 1");
+    }
+    if (!best_n) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_run_table_multi: best_n is 0");
+    const double t_start = now_ms();
+    TableRun r;
+    r.load_pheno(pheno_path);
+    for (uint32_t k = 0; k < n_cols; k++) r.need_column(cols[k]);
+    r.load_values();
+    std::vector<double> Y((uint64_t)n_cols * r.S);
+    for (uint32_t k = 0; k < n_cols; k++) r.column(cols[k], &Y[k * r.S]);
+    r.open_table(table_base, kmer_len, kinship_path, maf, mac);
+    std::unique_ptr<kgwas_lmm> h(create(r.S, r.K.data(), device, lmin, lmax, chunk_variants));
+    std::vector<std::vector<TableHit>> kept;
+    std::vector<double> l0(n_cols), lambda0(n_cols);
+    uint64_t rows_read = 0, rows_tested = 0, shipped = 0;
+    test_table_multi(h.get(), n_cols, Y.data(), r.t, r.col.data(), r.S, r.min_count, maf, best_n, kept, l0.data(), lambda0.data(), rows_read,
+                     rows_tested, shipped);
+    const double total_ms = now_ms() - t_start;
+    for (uint32_t k = 0; k < n_cols; k++)
+        write_table_result(outs[k], kept[k], r, table_base, cols[k], kinship_path, rows_read, rows_tested, best_n, lambda0[k], l0[k], h->st,
+                           total_ms);
     if (total) *total = h->st;
 }
 
@@ -1003,6 +1204,42 @@ int kgwas_lmm_run_table(const char* kinship_path, const char* table_base, uint32
     return guarded([&] {
         run_table(kinship_path, table_base, kmer_len, pheno_path, pheno_col, mac, maf, best_n, lmin, lmax, chunk_variants, device, out_path,
                   total);
+    });
+}
+
+int kgwas_lmm_test_table_multi(kgwas_lmm* h, uint32_t n_pheno, const double* Y, kgwas_table* t, const uint64_t* col, uint64_t n_acc,
+                               uint64_t min_count, double maf, uint64_t best_n, uint64_t* row, uint64_t* kmer, double* lrt, double* lambda,
+                               double* p, double* af, uint64_t* n_kept, double* logl0, double* lambda0, uint64_t* rows_read,
+                               uint64_t* rows_tested, uint64_t* pairs_shipped) {
+    return guarded([&] {
+        if (!h || (!Y && n_pheno) || !t || !col) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_test_table_multi: null argument");
+        std::vector<std::vector<TableHit>> kept;
+        uint64_t n_read = 0, n_tested = 0, n_shipped = 0;
+        test_table_multi(h, n_pheno, Y, t, col, n_acc, min_count, maf, best_n, kept, logl0, lambda0, n_read, n_tested, n_shipped);
+        for (uint32_t k = 0; k < n_pheno; k++) {
+            const uint64_t at = (uint64_t)k * best_n;
+            for (uint64_t i = 0; i < kept[k].size(); i++) {
+                if (row) row[at + i] = kept[k][i].row;
+                if (kmer) kmer[at + i] = kept[k][i].kmer;
+                if (lrt) lrt[at + i] = kept[k][i].lrt;
+                if (lambda) lambda[at + i] = kept[k][i].lam;
+                if (p) p[at + i] = kept[k][i].p;
+                if (af) af[at + i] = kept[k][i].af;
+            }
+            if (n_kept) n_kept[k] = kept[k].size();
+        }
+        if (rows_read) *rows_read = n_read;
+        if (rows_tested) *rows_tested = n_tested;
+        if (pairs_shipped) *pairs_shipped = n_shipped;
+    });
+}
+
+int kgwas_lmm_run_table_multi(const char* kinship_path, const char* table_base, uint32_t kmer_len, const char* pheno_path, uint32_t n_cols,
+                              const uint32_t* pheno_cols, const char* const* out_paths, uint64_t mac, double maf, uint64_t best_n,
+                              double lmin, double lmax, uint64_t chunk_variants, int32_t device, kgwas_lmm_stats* total) {
+    return guarded([&] {
+        run_table_multi(kinship_path, table_base, kmer_len, pheno_path, n_cols, pheno_cols, out_paths, mac, maf, best_n, lmin, lmax,
+                        chunk_variants, device, total);
     });
 }
 

@@ -77,4 +77,23 @@ hipError_t launch_lmm_table_front(const uint64_t* rows, uint64_t stride, const u
                                   uint32_t* block_off, uint32_t* total, uint8_t* codes, LmmVariant* vars, uint64_t* row_out,
                                   uint64_t* kmer_out, hipStream_t st);
 
+// lmm_table_kernels.hip: the first stage of the selection of the multi-phenotype table pass. After launch_lmm_refine_multi over a
+// sub-chunk of cc compacted tested rows and a block of pb <= LMM_PBLOCK columns (lrt, lam, p at [column][row], row stride cc), the
+// pair (column c, row v) survives iff cols[c].open != 0 (the column's host heap is not full) or lrt[c][v] > cols[c].thr (the lrt of
+// the worst hit that heap kept when the host last looked; a NaN lrt never passes it). Survivors become records in (column, row)
+// order, the same content in every run: count[0] = their number, rec[0 .. count). No store goes past rec[cap). Scratch: block_cnt
+// and block_off [pb cc / LMM_TABLE_BLOCK rounded up]. cc > 0, pb cc < 2^31.
+struct LmmSelectCol {  // per column of the block
+    double thr;
+    uint32_t open, pad;
+};
+struct LmmTableRecord {  // everything the host heap needs of one surviving (column, row) pair
+    double lrt, lam, p, af;
+    uint64_t row, kmer;  // the table row index and its k-mer word
+    uint32_t col, pad;   // the column within the block; pad = 0
+};
+hipError_t launch_lmm_table_select(const double* lrt, const double* lam, const double* p, uint32_t cc, uint32_t pb, const LmmVariant* vars,
+                                   const uint64_t* row, const uint64_t* kmer, const LmmSelectCol* cols, uint32_t* block_cnt,
+                                   uint32_t* block_off, uint32_t* count, LmmTableRecord* rec, uint32_t cap, hipStream_t st);
+
 }  // namespace kgwas

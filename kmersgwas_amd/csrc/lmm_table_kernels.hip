@@ -14,6 +14,12 @@
 //                          and popcount below the lane), so slots follow the row order - the same content in every run. The row's
 //                          lane writes the LmmVariant, the table row index and the k-mer word; then the block writes the padded
 //                          2-bit code rows, one dword (16 accessions, every presence bit doubled) per lane and step.
+// And the first stage of the selection of the multi-phenotype pass (kgwas_lmm_test_table_multi), by the same scheme:
+//   lmm_table_select_count_kernel  one lane per (column, row) pair of a refined block: does it pass its column's threshold; per
+//                                  block of 256 pairs the number that do;
+//   lmm_table_scan_kernel          as above: the offsets and the number of survivors;
+//   lmm_table_select_kernel        a surviving pair's lane writes its record at offset + rank, so records follow the (column, row)
+//                                  order and are the same in every run.
 // No atomic, no scalar memory write: every value goes out through a vector store from plain C++.
 #include "lmm_kernels.h"
 
@@ -143,7 +149,65 @@ __global__ void __launch_bounds__(TB) lmm_table_emit_kernel(const uint64_t* __re
     }
 }
 
+// ---- the selection's first stage of the multi-phenotype pass ("The multi-phenotype table pass") ----
+// Element e = c cc + v is the pair (column c of the block, compacted row v), so the element order is the (column, row) order.
+
+// does element e < n survive? The comparison is false for a NaN lrt, which therefore survives only into an open heap.
+__device__ inline bool select_survives(const double* __restrict__ lrt, const LmmSelectCol* __restrict__ cols, uint32_t cc, uint32_t e,
+                                       uint32_t n) {
+    if (e >= n) return false;
+    const LmmSelectCol sc = cols[e / cc];
+    return sc.open != 0u || lrt[e] > sc.thr;
+}
+
+__global__ void __launch_bounds__(TB) lmm_table_select_count_kernel(const double* __restrict__ lrt, const LmmSelectCol* __restrict__ cols,
+                                                                    uint32_t cc, uint32_t n, uint32_t* __restrict__ block_cnt) {
+    __shared__ uint32_t s_wave[TB / 64];
+    const bool keep = select_survives(lrt, cols, cc, blockIdx.x * TB + threadIdx.x, n);
+    uint32_t total;
+    (void)block_rank(keep, s_wave, total);
+    if (threadIdx.x == 0) block_cnt[blockIdx.x] = total;
+}
+
+// a survivor's slot is its block's offset plus its rank in the block: slots follow the element order. Its lane writes the record.
+__global__ void __launch_bounds__(TB) lmm_table_select_kernel(const double* __restrict__ lrt, const double* __restrict__ lam,
+                                                              const double* __restrict__ p, const LmmSelectCol* __restrict__ cols,
+                                                              uint32_t cc, uint32_t n, const LmmVariant* __restrict__ vars,
+                                                              const uint64_t* __restrict__ row, const uint64_t* __restrict__ kmer,
+                                                              const uint32_t* __restrict__ block_off, LmmTableRecord* __restrict__ rec,
+                                                              uint32_t cap) {
+    __shared__ uint32_t s_wave[TB / 64];
+    const uint32_t e = blockIdx.x * TB + threadIdx.x;
+    const bool keep = select_survives(lrt, cols, cc, e, n);
+    uint32_t total;
+    const uint32_t slot = block_off[blockIdx.x] + block_rank(keep, s_wave, total);
+    if (!keep || slot >= cap) return;
+    const uint32_t c = e / cc, v = e - c * cc;
+    LmmTableRecord o;
+    o.lrt = lrt[e];
+    o.lam = lam[e];
+    o.p = p[e];
+    o.af = vars[v].af;
+    o.row = row[v];
+    o.kmer = kmer[v];
+    o.col = c;
+    o.pad = 0;
+    rec[slot] = o;
+}
+
 }  // namespace
+
+hipError_t launch_lmm_table_select(const double* lrt, const double* lam, const double* p, uint32_t cc, uint32_t pb, const LmmVariant* vars,
+                                   const uint64_t* row, const uint64_t* kmer, const LmmSelectCol* cols, uint32_t* block_cnt,
+                                   uint32_t* block_off, uint32_t* count, LmmTableRecord* rec, uint32_t cap, hipStream_t st) {
+    if (!cc || !pb || pb > LMM_PBLOCK || (uint64_t)pb * cc >= (1ull << 31)) return hipErrorInvalidValue;  // (count would stay unwritten)
+    const uint32_t n = pb * cc, n_blocks = (n + TB - 1) / TB;
+    hipLaunchKernelGGL(lmm_table_select_count_kernel, dim3(n_blocks), dim3(TB), 0, st, lrt, cols, cc, n, block_cnt);
+    hipLaunchKernelGGL(lmm_table_scan_kernel, dim3(1), dim3(256), 0, st, block_cnt, n_blocks, block_off, count);
+    hipLaunchKernelGGL(lmm_table_select_kernel, dim3(n_blocks), dim3(TB), 0, st, lrt, lam, p, cols, cc, n, vars, row, kmer, block_off, rec,
+                       cap);
+    return hipGetLastError();
+}
 
 hipError_t launch_lmm_table_front(const uint64_t* rows, uint64_t stride, const uint32_t* sq, uint32_t n_rows, uint32_t W_m, LmmDims dm,
                                   uint64_t first_row, uint32_t min_count, double maf, uint32_t* n1flag, uint32_t* block_cnt,

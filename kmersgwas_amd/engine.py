@@ -576,6 +576,31 @@ class LmmLrt:
         return {"row": row[:k], "kmer": kmer[:k], "lrt": lrt[:k], "lambda": lam[:k], "p": p[:k], "af": af[:k],
                 "rows_read": n_read.value, "rows_tested": n_tested.value}
 
+    def test_table_multi(self, table: "KmersTable", col, Y, min_count: int, maf: float = 0.0, best_n: int = 10001):
+        """test_table for the P columns Y (P, n) in one pass over the table: the phenotype and its permutations. Returns a dict:
+        columns, a list of P dicts shaped like test_table's (each with the rows and the bits test_table(.., Y[k], ..) gives);
+        logl0 and lambda0 of shape (P,) with the bits of null(Y[k]); rows_read, rows_tested; and pairs_shipped, the number of
+        (column, row) records the device's selection handed to the host (at most rows_tested * P)."""
+        col = np.ascontiguousarray(col, np.uint64)
+        Y = np.ascontiguousarray(Y, np.float64)
+        if Y.ndim != 2 or Y.shape[1] != self.n:
+            raise ValueError("Y must have one row per phenotype column and one value per individual")
+        P = Y.shape[0]
+        row, kmer = np.zeros((P, best_n), np.uint64), np.zeros((P, best_n), np.uint64)
+        lrt, lam, p, af = (np.zeros((P, best_n)) for _ in range(4))
+        kept, l0, lam0 = np.zeros(P, np.uint64), np.zeros(P), np.zeros(P)
+        n_read, n_tested, shipped = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        check(lib.kgwas_lmm_test_table_multi(self._h, P, ptr(Y), table._h, ptr(col), len(col), min_count, maf, best_n, ptr(row), ptr(kmer),
+                                             ptr(lrt), ptr(lam), ptr(p), ptr(af), ptr(kept), ptr(l0), ptr(lam0), C.byref(n_read),
+                                             C.byref(n_tested), C.byref(shipped)))
+        cols = []
+        for j in range(P):
+            k = int(kept[j])
+            cols.append({"row": row[j, :k].copy(), "kmer": kmer[j, :k].copy(), "lrt": lrt[j, :k].copy(), "lambda": lam[j, :k].copy(),
+                         "p": p[j, :k].copy(), "af": af[j, :k].copy(), "rows_read": n_read.value, "rows_tested": n_tested.value})
+        return {"columns": cols, "logl0": l0, "lambda0": lam0, "rows_read": n_read.value, "rows_tested": n_tested.value,
+                "pairs_shipped": shipped.value}
+
     def stats(self):
         st = capi.LmmStats()
         check(lib.kgwas_lmm_get_stats(self._h, C.byref(st)))

@@ -20,6 +20,14 @@ generator of the other benchmarks, written to a temporary directory), one phenot
 and beside them, on the same files, the wall time of the route that needs the PLINK files: kmers_table_to_bed, then lmm_lrt
 -bfile (files in the page cache, the output of the first removed before every run). Both routes eigendecompose K once per run;
 eigen_ms is printed so that it can be taken off.
+
+--table [ROWS] --pheno_columns [P] (default 101) times the phenotype and its P - 1 permutations over the same synthetic table,
+--mac 5 -maf 0.05 --best 10001, a warm-up and --reps timed runs of each (median, minimum, maximum of the wall time):
+(a) ONE lmm_lrt --kmers_table --pheno_columns run of the P columns; (b) the way without it, one --kmers_table -n i run per column,
+measured on --subset columns (default 3: the first, the middle and the last one) and scaled to P, the subset is printed; (c) run (a)
+with KGWAS_LMM_TABLE_SELECT=0, the device's selection switched off. It prints the ratios (b)/(a) and (c)/(a), the kernels' split
+of (a) and (c), and the share of (column, row) pairs the selection handed to the host (from the library, on the same files). The
+outputs of (a) and of the measured columns of (b) are compared byte for byte.
 """
 import argparse
 import json
@@ -183,6 +191,98 @@ def bench_table(a):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+def bench_table_multi(a):
+    n, rows, P = a.individuals, a.table, a.pheno_columns
+    bindir = os.path.join(os.path.dirname(os.path.abspath(kg.__file__)), "bin")
+    rng = np.random.default_rng(20240601)
+    g_rows = 2 * n
+    G = (rng.random((g_rows, n)) < rng.uniform(0.1, 0.9, g_rows)[:, None]).astype(np.float64)
+    K = 1.0 - (G.T @ (1 - G) + (1 - G).T @ G) / g_rows
+    d, U = np.linalg.eigh(K)
+    y = rng.standard_normal(n) + 1.5 * ((U * np.sqrt(np.clip(d, 0, None))) @ rng.standard_normal(n)) + 1.2 * G[7]
+    Y = np.stack([y] + [rng.permutation(y) for _ in range(P - 1)])
+    tmp = tempfile.mkdtemp(prefix="bench_lmm_table_multi_")
+    try:
+        base = os.path.join(tmp, "t")
+        hdr = np.uint32(0xDDCCBBAA).tobytes() + np.uint64(n).tobytes() + np.uint32(31).tobytes()
+        with open(base + ".table", "wb") as f:
+            f.write(hdr)
+            for r0 in range(0, rows, 1_000_000):
+                kg.synth_rows_host(r0, min(1_000_000, rows - r0), n, 20240601).tofile(f)
+        names = ["s%d" % i for i in range(n)]
+        open(base + ".names", "w").write("".join(x + "\n" for x in names))
+        ph = os.path.join(tmp, "ph.tsv")
+        open(ph, "w").write("accession_id\t" + "\t".join("P%d" % k for k in range(P)) + "\n"
+                            + "".join(names[i] + "".join("\t%.6f" % Y[k, i] for k in range(P)) + "\n" for i in range(n)))
+        kin = os.path.join(tmp, "ph.kinship")
+        open(kin, "w").write("\n".join("\t".join("%.17g" % v for v in r) for r in K) + "\n")
+        lst = os.path.join(tmp, "cols.txt")
+        open(lst, "w").write("".join("%d\tP%d\n" % (k + 1, k) for k in range(P)))
+        common = [os.path.join(bindir, "lmm_lrt"), "--kmers_table", base, "--kmers_len", "31", "-p", ph, "-lmm", "2", "-k", kin, "--mac", "5",
+                  "-maf", "0.05", "--best", "10001", "--chunk_variants", str(a.chunk_variants)]
+
+        def tool(args, env=None):
+            t = time.perf_counter()
+            r = subprocess.run(common + args, capture_output=True, text=True, env=env)
+            if r.returncode != 0:
+                sys.exit("lmm_lrt failed: %s" % r.stderr[-2000:])
+            return time.perf_counter() - t
+
+        def log_of(outdir, name):
+            log = {}
+            for l in open(os.path.join(outdir, name + ".log.txt")).read().split("\n"):
+                if "\t" in l:
+                    k, v = l.split("\t", 1)
+                    log[k] = v
+                elif l.startswith("ms: "):
+                    log.update((kv.split("=")[0], float(kv.split("=")[1])) for kv in l[4:].split())
+            return log
+
+        subset = sorted(set(np.linspace(0, P - 1, max(1, min(a.subset, P))).astype(int).tolist()))
+        out_a, out_b, out_c = (os.path.join(tmp, d) for d in ("multi", "single", "noselect"))
+        off = dict(os.environ, KGWAS_LMM_TABLE_SELECT="0")
+
+        def run_a():
+            return dict(wall_s=tool(["-outdir", out_a, "--pheno_columns", lst]), **log_of(out_a, "P0"))
+
+        def run_c():
+            return dict(wall_s=tool(["-outdir", out_c, "--pheno_columns", lst], env=off), **log_of(out_c, "P0"))
+
+        def run_b():
+            walls = [tool(["-outdir", out_b, "-n", str(k + 1), "-o", "P%d" % k]) for k in subset]
+            return dict(wall_s=sum(walls) * P / len(subset), measured_s=sum(walls), **log_of(out_b, "P%d" % subset[0]))
+
+        line = {"table_rows": rows, "individuals": n, "columns": P, "best": 10001, "reps": a.reps, "single_subset": [k + 1 for k in subset]}
+        for name, fn in (("multi", run_a), ("single_scaled", run_b), ("multi_noselect", run_c)):
+            fn()  # warm-up
+            runs = [fn() for _ in range(a.reps)]
+            for k in ("wall_s", "eigen", "rotate", "grid", "refine"):
+                v = sorted(float(r[k]) for r in runs)
+                line["%s_%s" % (name, k if k.endswith("_s") else k + "_ms")] = {"median": round(v[len(v) // 2], 3), "min": round(v[0], 3), "max": round(v[-1], 3)}
+            if name == "multi":
+                line["rows_tested"] = int(runs[0]["rows_tested"])
+        same = all(open(os.path.join(d, "P%d.assoc.txt" % k), "rb").read() == open(os.path.join(out_a, "P%d.assoc.txt" % k), "rb").read()
+                   for d, ks in ((out_b, subset), (out_c, range(P))) for k in ks)
+        line["same_bytes"] = bool(same)
+        med = lambda name: line[name + "_wall_s"]["median"]  # noqa: E731
+        line["wall_ratio_single_over_multi"] = round(med("single_scaled") / med("multi"), 3)
+        line["wall_ratio_noselect_over_multi"] = round(med("multi_noselect") / med("multi"), 3)
+        # the selection's share, from the library on the same files (one more pass, not timed)
+        tbl = kg.KmersTable(base, 31)
+        lmm = kg.LmmLrt(K, chunk_variants=a.chunk_variants)
+        # the values the tool tests: the file's "%.6f" text as the loader's float32, printed with six significant digits, parsed again
+        Yt = np.array([[float("%g" % np.float32(float("%.6f" % v))) for v in row] for row in Y])
+        res = lmm.test_table_multi(tbl, np.arange(n, dtype=np.uint64), Yt, kg.min_count(n, 0.05, 5), 0.05, 10001)
+        lmm.close()
+        tbl.close()
+        line["pairs_shipped"], line["pairs"] = int(res["pairs_shipped"]), int(res["rows_tested"]) * P
+        line["pairs_shipped_share"] = round(res["pairs_shipped"] / max(res["rows_tested"] * P, 1), 6)
+        print(json.dumps(line))
+        return 0 if same else 1
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--beds", type=int, default=101)
@@ -194,7 +294,15 @@ def main():
     ap.add_argument("--reps", type=int, default=3, help="timed repetitions of the --columns and --table modes")
     ap.add_argument("--table", type=int, nargs="?", const=4_000_000, default=None,
                     help="time lmm_lrt --kmers_table over a synthetic table of ROWS rows (default 4 000 000) against kmers_table_to_bed + lmm_lrt -bfile")
+    ap.add_argument("--pheno_columns", type=int, nargs="?", const=101, default=None,
+                    help="with --table: time one --pheno_columns run of P columns (default 101) against P runs of --kmers_table -n i "
+                         "(measured on --subset columns and scaled) and against the same run without the device's selection")
+    ap.add_argument("--subset", type=int, default=3, help="columns of the --pheno_columns mode's one-run-per-column route that are measured")
     a = ap.parse_args()
+    if a.pheno_columns is not None:
+        if a.table is None:
+            sys.exit("--pheno_columns needs --table")
+        sys.exit(bench_table_multi(a))
     if a.table is not None:
         sys.exit(bench_table(a))
     if a.columns is not None:
