@@ -1,0 +1,567 @@
+// lmm_files.cpp — the file layer of the lmm_lrt tool over the passes of lmm.cpp and lmm_table.cpp: the parsers,
+// the .assoc.txt formatter and the writers. It makes no HIP call of its own; the parsers and the formatter run without a GPU.
+//
+// run_files: kinship text, .fam phenotype column, .bim, .bed in, .assoc.txt and .log.txt out. Individuals without a phenotype are
+//            dropped from K, y and the .bed rows before anything else; beds that keep the same individuals share one handle, so
+//            one eigendecomposition;
+// run_file_multi: one bfile, several .fam columns with one missing set, one pass over the .bed (the shape of
+//            kmers_gwas.py:193-223);
+// run_table, run_table_multi: lmm_lrt --kmers_table, with -n and with --pheno_columns.
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <fstream>
+#include <sstream>
+#include <string>
+#include <vector>
+
+#include "kernels.h"
+#include "lmm_internal.h"
+
+using namespace kgwas;
+using namespace kgwas::lmm;
+
+namespace {
+
+std::vector<std::string> split_ws(const std::string& line) {
+    std::vector<std::string> f;
+    size_t i = 0;
+    while (i < line.size()) {
+        while (i < line.size() && (line[i] == ' ' || line[i] == '\t' || line[i] == '\r')) i++;
+        size_t j = i;
+        while (j < line.size() && line[j] != ' ' && line[j] != '\t' && line[j] != '\r') j++;
+        if (j > i) f.push_back(line.substr(i, j - i));
+        i = j;
+    }
+    return f;
+}
+
+std::vector<std::string> read_lines(const std::string& path, const char* what) {
+    std::ifstream f(path);
+    if (!f.is_open()) throw Error(KGWAS_ERR_IO, std::string("can't open ") + what + " file: " + path);
+    std::vector<std::string> lines;
+    for (std::string l; std::getline(f, l);)
+        if (l.find_first_not_of(" \t\r") != std::string::npos) lines.push_back(l);
+    return lines;
+}
+
+}  // namespace
+
+std::vector<double> kgwas::lmm::read_kinship(const std::string& path, uint64_t n_expected, const char* counted_in) {
+    const std::vector<std::string> lines = read_lines(path, "kinship");
+    if (lines.size() != n_expected)
+        throw Error(KGWAS_ERR_FORMAT, "kinship file " + path + " has " + std::to_string(lines.size()) + " rows, " + counted_in + " has " +
+                                          std::to_string(n_expected) + " individuals");
+    std::vector<double> K(n_expected * n_expected);
+    for (uint64_t r = 0; r < n_expected; r++) {
+        const char* s = lines[r].c_str();
+        uint64_t c = 0;
+        for (;; c++) {
+            char* end = nullptr;
+            const double v = strtod(s, &end);
+            if (end == s) break;
+            if (c < n_expected) K[r * n_expected + c] = v;
+            s = end;
+        }
+        while (*s == ' ' || *s == '\t' || *s == '\r') s++;
+        if (*s) throw Error(KGWAS_ERR_FORMAT, "kinship file " + path + ": row " + std::to_string(r + 1) + " holds text that is no number");
+        if (c != n_expected)
+            throw Error(KGWAS_ERR_FORMAT, "kinship file " + path + ": row " + std::to_string(r + 1) + " has " + std::to_string(c) +
+                                              " values, expected " + std::to_string(n_expected));
+    }
+    return K;
+}
+
+namespace {
+
+// a phenotype field as a .fam gives it: "-9" and "NA" are missing, anything else must be one finite number
+enum class Pheno { missing, number, no_number };
+Pheno parse_phenotype(const std::string& t, double& v) {
+    if (t == "-9" || t == "NA") return Pheno::missing;
+    char* end = nullptr;
+    v = strtod(t.c_str(), &end);
+    return end == t.c_str() || *end || !std::isfinite(v) ? Pheno::no_number : Pheno::number;
+}
+
+// values[i] and keep[i] of every .fam line; the phenotype is field 5 + pheno_col (1-based)
+void read_fam(const std::string& path, uint32_t pheno_col, std::vector<double>& values, std::vector<uint8_t>& keep) {
+    if (pheno_col < 1) throw Error(KGWAS_ERR_ARG, "the phenotype column (-n) starts at 1");
+    const std::vector<std::string> lines = read_lines(path, "fam");
+    values.assign(lines.size(), std::nan(""));
+    keep.assign(lines.size(), 0);
+    for (size_t i = 0; i < lines.size(); i++) {
+        const std::vector<std::string> f = split_ws(lines[i]);
+        if (f.size() < 5u + pheno_col)
+            throw Error(KGWAS_ERR_FORMAT, path + ": line " + std::to_string(i + 1) + " has no phenotype column " + std::to_string(pheno_col));
+        const std::string& t = f[4 + pheno_col];
+        double v = 0;
+        const Pheno kind = parse_phenotype(t, v);
+        if (kind == Pheno::missing) continue;
+        if (kind == Pheno::no_number)
+            throw Error(KGWAS_ERR_FORMAT, path + ": line " + std::to_string(i + 1) + ": phenotype '" + t + "' is no number");
+        values[i] = v;
+        keep[i] = 1;
+    }
+}
+
+uint64_t format_assoc(const char* chr, const char* rs, const char* ps, uint32_t n_miss, const char* a1, const char* a0, double af,
+                      double l_mle, double p, char* out, uint64_t cap) {
+    char buf[1024];
+    int len;
+    if (!chr)
+        len = snprintf(buf, sizeof(buf), "chr\trs\tps\tn_miss\tallele1\tallele0\taf\tl_mle\tp_lrt\n");
+    else
+        len = snprintf(buf, sizeof(buf), "%s\t%s\t%s\t%u\t%s\t%s\t%.3f\t%.6e\t%.6e\n", chr, rs, ps, n_miss, a1, a0, af, l_mle, p);
+    if (len < 0 || (size_t)len >= sizeof(buf)) throw Error(KGWAS_ERR_FORMAT, "a .bim line is too long");
+    if (out && cap >= (uint64_t)len) memcpy(out, buf, (size_t)len);
+    return (uint64_t)len;
+}
+
+std::string log_path_of(const std::string& out) {
+    const std::string suf = ".assoc.txt";
+    if (out.size() >= suf.size() && out.compare(out.size() - suf.size(), suf.size(), suf) == 0)
+        return out.substr(0, out.size() - suf.size()) + ".log.txt";
+    return out + ".log.txt";
+}
+
+void add_stats(kgwas_lmm_stats& a, const kgwas_lmm_stats& b) {
+    a.eigen_ms += b.eigen_ms;
+    a.rotate_ms += b.rotate_ms;
+    a.grid_ms += b.grid_ms;
+    a.refine_ms += b.refine_ms;
+    a.variants_read += b.variants_read;
+    a.variants_tested += b.variants_tested;
+    a.chunks += b.chunks;
+    a.eigendecompositions += b.eigendecompositions;
+    a.n_individuals = b.n_individuals;
+}
+
+// ---- what run_files and run_file_multi share ----
+
+std::vector<uint32_t> kept_lines(const std::vector<uint8_t>& keep) {
+    std::vector<uint32_t> idx;
+    for (uint64_t i = 0; i < keep.size(); i++)
+        if (keep[i]) idx.push_back((uint32_t)i);
+    return idx;
+}
+
+kgwas_lmm* create_for_kept(const std::vector<double>& Kfull, uint64_t nf, const std::vector<uint32_t>& idx, int device, double lmin,
+                           double lmax, uint64_t chunk_variants) {
+    const uint64_t n = idx.size();
+    std::vector<double> K(n * n);
+    for (uint64_t r = 0; r < n; r++)
+        for (uint64_t c = 0; c < n; c++) K[r * n + c] = Kfull[(uint64_t)idx[r] * nf + idx[c]];
+    return create(n, K.data(), device, lmin, lmax, chunk_variants);
+}
+
+// the .bim lines and the .bed body of <base>, the latter with the codes of the kept individuals idx (of nf .fam lines) alone
+void read_bim_bed(const std::string& base, uint64_t nf, const std::vector<uint32_t>& idx, std::vector<std::string>& bim,
+                  std::vector<uint8_t>& body) {
+    bim = read_lines(base + ".bim", "bim");
+    const uint64_t n = idx.size(), M = bim.size(), bps_f = (nf + 3) / 4, bps = (n + 3) / 4;
+    {
+        std::ifstream f(base + ".bed", std::ios::binary | std::ios::ate);
+        if (!f.is_open()) throw Error(KGWAS_ERR_IO, "can't open bed file: " + base + ".bed");
+        const uint64_t size = (uint64_t)f.tellg();
+        if (size != 3 + M * bps_f)
+            throw Error(KGWAS_ERR_FORMAT, base + ".bed has " + std::to_string(size) + " bytes, " + std::to_string(M) + " variants of " +
+                                              std::to_string(nf) + " individuals need " + std::to_string(3 + M * bps_f));
+        f.seekg(0);
+        uint8_t magic[3];
+        f.read((char*)magic, 3);
+        if (magic[0] != 0x6C || magic[1] != 0x1B || magic[2] != 0x01)
+            throw Error(KGWAS_ERR_FORMAT, base + ".bed: not a SNP-major PLINK .bed (magic 6C 1B 01)");
+        body.resize(M * bps_f);
+        f.read((char*)body.data(), (std::streamsize)body.size());
+        if (!f) throw Error(KGWAS_ERR_IO, "short read of " + base + ".bed");
+    }
+    if (n != nf) {  // the kept individuals' codes, packed again
+        std::vector<uint8_t> packed(M * bps, 0);
+        for (uint64_t v = 0; v < M; v++) {
+            const uint8_t* src = &body[v * bps_f];
+            uint8_t* dst = &packed[v * bps];
+            for (uint64_t r = 0; r < n; r++) dst[r >> 2] |= (uint8_t)(((src[idx[r] >> 2] >> (2 * (idx[r] & 3))) & 3) << (2 * (r & 3)));
+        }
+        body.swap(packed);
+    }
+}
+
+std::string assoc_header() {
+    std::string text(format_assoc(nullptr, "", "", 0, "", "", 0, 0, 0, nullptr, 0), '\0');
+    format_assoc(nullptr, "", "", 0, "", "", 0, 0, 0, &text[0], text.size());
+    return text;
+}
+
+// the fields of the .bim lines of the tested ones among variants first .. first + cnt (tested starts at `first`; the others stay empty)
+std::vector<std::vector<std::string>> bim_fields(const std::string& base, const std::vector<std::string>& bim, uint64_t first, uint64_t cnt,
+                                                 const uint8_t* tested) {
+    std::vector<std::vector<std::string>> fields(cnt);
+    for (uint64_t v = 0; v < cnt; v++) {
+        if (!tested[v]) continue;
+        fields[v] = split_ws(bim[first + v]);
+        if (fields[v].size() < 6)
+            throw Error(KGWAS_ERR_FORMAT, base + ".bim: line " + std::to_string(first + v + 1) + " has fewer than 6 fields");
+    }
+    return fields;
+}
+
+// appends the lines of the tested ones among fields.size() variants (all arrays start at the first of them); returns their number
+uint64_t append_assoc(std::string& text, const std::vector<std::vector<std::string>>& fields, const uint32_t* n_miss, const double* af,
+                      const double* lam, const double* p, const uint8_t* tested) {
+    uint64_t n_tested = 0;
+    for (uint64_t v = 0; v < fields.size(); v++) {
+        if (!tested[v]) continue;
+        const std::vector<std::string>& f = fields[v];
+        char line[1024];
+        const uint64_t len = format_assoc(f[0].c_str(), f[1].c_str(), f[3].c_str(), n_miss[v], f[4].c_str(), f[5].c_str(), af[v], lam[v],
+                                          p[v], line, sizeof(line));
+        text.append(line, len);
+        n_tested++;
+    }
+    return n_tested;
+}
+
+void write_text(const std::string& path, const std::string& text, const char* mode) {
+    FILE* fo = fopen(path.c_str(), mode);
+    const bool ok = fo && fwrite(text.data(), 1, text.size(), fo) == text.size();
+    if ((fo && fclose(fo) != 0) || !ok) throw Error(KGWAS_ERR_IO, "can't write " + path);
+}
+
+// the log beside `out`: what snprintf left in log[cap], ll being its return value
+void write_log_text(const std::string& out, const char* log, size_t cap, int ll) {
+    if (ll < 0) throw Error(KGWAS_ERR_IO, "can't write " + log_path_of(out));
+    write_text(log_path_of(out), std::string(log, std::min((size_t)ll, cap - 1)), "wb");
+}
+
+void write_log(const std::string& out, const std::string& base, const char* kinship_path, uint64_t nf, uint64_t n, uint64_t M,
+               uint64_t n_tested, double lambda0, double l0, double eigen_ms, double rotate_ms, double grid_ms, double refine_ms,
+               double total_ms) {
+    char log[1024];
+    const int ll = snprintf(log, sizeof(log),
+                            "lmm_lrt: ML likelihood-ratio test (-lmm 2)\nbfile\t%s\nkinship\t%s\nindividuals_in_fam\t%llu\n"
+                            "individuals_used\t%llu\nvariants_read\t%llu\nvariants_tested\t%llu\nlambda0\t%.6e\nlogl_H0\t%.6f\n"
+                            "ms: eigen=%.3f rotate=%.3f grid=%.3f refine=%.3f total=%.3f\n",
+                            base.c_str(), kinship_path, (unsigned long long)nf, (unsigned long long)n, (unsigned long long)M,
+                            (unsigned long long)n_tested, lambda0, l0, eigen_ms, rotate_ms, grid_ms, refine_ms, total_ms);
+    write_log_text(out, log, sizeof(log), ll);
+}
+
+void run_files(const char* kinship_path, uint64_t n_beds, const char* const* bases, const char* const* outs, uint32_t pheno_col,
+               double maf, double miss, double lmin, double lmax, uint64_t chunk_variants, int device, kgwas_lmm_stats* total) {
+    if (!kinship_path || (n_beds && (!bases || !outs))) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_run_files: null argument");
+    kgwas_lmm_stats sum{};
+    std::vector<double> Kfull;
+    Handle h;
+    std::vector<uint8_t> keep_cur;
+    for (uint64_t b = 0; b < n_beds; b++) {
+        const std::string base = bases[b], out = outs[b];
+        const double t_start = now_ms();
+        std::vector<double> vals;
+        std::vector<uint8_t> keep;
+        read_fam(base + ".fam", pheno_col, vals, keep);
+        const uint64_t nf = vals.size();
+        if (Kfull.empty() || Kfull.size() != nf * nf) Kfull = read_kinship(kinship_path, nf);
+        const std::vector<uint32_t> idx = kept_lines(keep);
+        const uint64_t n = idx.size();
+        if (!h || keep != keep_cur) {
+            if (h) add_stats(sum, h->st);
+            h.reset();
+            h.reset(create_for_kept(Kfull, nf, idx, device, lmin, lmax, chunk_variants));
+            keep_cur = keep;
+        }
+        std::vector<double> y(n);
+        for (uint64_t r = 0; r < n; r++) y[r] = vals[idx[r]];
+        std::vector<std::string> bim;
+        std::vector<uint8_t> body;
+        read_bim_bed(base, nf, idx, bim, body);
+        const uint64_t M = bim.size();
+        std::vector<double> lrt(M), lam(M), p(M), af(M);
+        std::vector<uint32_t> n_miss(M);
+        std::vector<uint8_t> tested(M);
+        const kgwas_lmm_stats before = h->st;
+        test_bed(h.get(), y.data(), body.data(), M, maf, miss, lrt.data(), lam.data(), p.data(), af.data(), n_miss.data(), tested.data());
+        std::string text = assoc_header();
+        const uint64_t n_tested =
+            append_assoc(text, bim_fields(base, bim, 0, M, tested.data()), n_miss.data(), af.data(), lam.data(), p.data(), tested.data());
+        write_text(out, text, "wb");
+        write_log(out, base, kinship_path, nf, n, M, n_tested, h->lambda0, h->l0, h->st.eigen_ms, h->st.rotate_ms - before.rotate_ms,
+                  h->st.grid_ms - before.grid_ms, h->st.refine_ms - before.refine_ms, now_ms() - t_start);
+    }
+    if (h) add_stats(sum, h->st);
+    if (total) *total = sum;
+}
+
+// One bfile, n_cols phenotype columns of its .fam with one missing set: the .bed, the .bim and the kinship matrix are read once,
+// K is eigendecomposed once, and every chunk of variants goes through the multi-phenotype pass. Results are written in slabs
+// of variants, so that the [column][variant] arrays stay small for a panel of millions of variants.
+void run_file_multi(const char* kinship_path, const char* bfile_base, uint32_t n_cols, const uint32_t* cols, const char* const* outs,
+                    double maf, double miss, double lmin, double lmax, uint64_t chunk_variants, int device, kgwas_lmm_stats* total) {
+    if (!kinship_path || !bfile_base || !cols || !outs) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_run_file_multi: null argument");
+    if (!n_cols) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_run_file_multi: no phenotype column given");
+    const std::string base = bfile_base;
+    const double t_start = now_ms();
+    std::vector<std::vector<double>> vals(n_cols);
+    std::vector<uint8_t> keep;
+    for (uint32_t k = 0; k < n_cols; k++) {
+        std::vector<uint8_t> keep_k;
+        read_fam(base + ".fam", cols[k], vals[k], keep_k);
+        if (k == 0)
+            keep = keep_k;
+        else if (keep_k != keep)
+            throw Error(KGWAS_ERR_FORMAT, base + ".fam: phenotype column " + std::to_string(cols[k]) + " marks other individuals as missing than column " +
+                                              std::to_string(cols[0]) + "; columns of one run must share their missing set");
+    }
+    const uint64_t nf = keep.size();
+    const std::vector<double> Kfull = read_kinship(kinship_path, nf);
+    const std::vector<uint32_t> idx = kept_lines(keep);
+    const uint64_t n = idx.size();
+    Handle h(create_for_kept(Kfull, nf, idx, device, lmin, lmax, chunk_variants));
+    std::vector<double> Y((uint64_t)n_cols * n);
+    for (uint32_t k = 0; k < n_cols; k++)
+        for (uint64_t r = 0; r < n; r++) Y[k * n + r] = vals[k][idx[r]];
+    std::vector<std::string> bim;
+    std::vector<uint8_t> body;
+    read_bim_bed(base, nf, idx, bim, body);
+    const uint64_t M = bim.size(), bps = (n + 3) / 4;
+    std::vector<double> l0(n_cols), lambda0(n_cols);
+    multi_prepare(h.get(), n_cols, Y.data(), l0.data(), lambda0.data());
+    for (uint32_t k = 0; k < n_cols; k++) write_text(outs[k], assoc_header(), "wb");
+    // a slab: whole chunks, about 4 M (variant, column) pairs
+    const uint64_t slab = std::max<uint64_t>(1, (1u << 22) / ((uint64_t)n_cols * h->chunk)) * h->chunk;
+    std::vector<double> lrt(std::min(slab, M) * n_cols), lam(lrt.size()), p(lrt.size()), af(std::min(slab, M));
+    std::vector<uint32_t> n_miss(af.size());
+    std::vector<uint8_t> tested(af.size());
+    std::vector<uint64_t> n_tested(n_cols, 0);
+    for (uint64_t first = 0; first < M; first += slab) {
+        const uint64_t cnt = std::min(slab, M - first);
+        multi_run(h.get(), n_cols, body.data() + first * bps, cnt, maf, miss, lrt.data(), lam.data(), p.data(), af.data(), n_miss.data(),
+                  tested.data());
+        const std::vector<std::vector<std::string>> fields = bim_fields(base, bim, first, cnt, tested.data());  // once for all columns
+        for (uint32_t k = 0; k < n_cols; k++) {
+            std::string text;
+            n_tested[k] += append_assoc(text, fields, n_miss.data(), af.data(), &lam[k * cnt], &p[k * cnt], tested.data());
+            write_text(outs[k], text, "ab");
+        }
+    }
+    const double total_ms = now_ms() - t_start;
+    for (uint32_t k = 0; k < n_cols; k++)  // (the kernels' times are the shared pass's, the same in every column's log)
+        write_log(outs[k], base, kinship_path, nf, n, M, n_tested[k], lambda0[k], l0[k], h->st.eigen_ms, h->st.rotate_ms, h->st.grid_ms,
+                  h->st.refine_ms, total_ms);
+    if (total) *total = h->st;
+}
+
+// ---- what run_table and run_table_multi share ----
+
+// The inputs of lmm_lrt --kmers_table, each read once: the phenotype file (its accessions, in its order, are the individuals), the
+// open table with its column map, the kinship text.
+struct TableRun {
+    kgwas_pheno* ph = nullptr;
+    kgwas_table* t = nullptr;
+    std::string pheno_path;
+    uint64_t n_pheno = 0, S = 0, min_count = 0;
+    uint32_t klen = 0;
+    std::vector<const char*> acc;
+    const float* Y = nullptr;
+    std::vector<uint64_t> col;
+    std::vector<double> K;
+    ~TableRun() {
+        if (t) kgwas_table_close(t);
+        if (ph) kgwas_pheno_free(ph);
+    }
+    static void ck(int rc) {
+        if (rc != KGWAS_OK) throw Error(rc, kgwas_last_error());
+    }
+    void load_pheno(const char* path) {
+        pheno_path = path;
+        ck(kgwas_pheno_load(path, &ph));
+        ck(kgwas_pheno_info(ph, &n_pheno, &S));
+    }
+    void need_column(uint32_t pheno_col) const {
+        if (pheno_col > n_pheno) throw Error(KGWAS_ERR_FORMAT, pheno_path + " has no phenotype column " + std::to_string(pheno_col));
+    }
+    void load_values() {
+        acc.resize(S);
+        for (uint64_t i = 0; i < S; i++) ck(kgwas_pheno_accession(ph, i, &acc[i]));
+        ck(kgwas_pheno_values(ph, &Y));
+    }
+    // y as it would arrive through kmers_table_to_bed's .fam: the loader's float in ostream's default format, parsed as read_fam does
+    void column(uint32_t pheno_col, double* y) const {
+        for (uint64_t i = 0; i < S; i++) {
+            std::ostringstream os;
+            os << Y[(uint64_t)(pheno_col - 1) * S + i];
+            const std::string text = os.str();
+            const Pheno kind = parse_phenotype(text, y[i]);
+            if (kind == Pheno::missing)
+                throw Error(KGWAS_ERR_FORMAT, pheno_path + ": the phenotype of " + acc[i] + " is " + text +
+                                                  ", which a .fam reads as missing; remove the accession from the phenotype file");
+            if (kind == Pheno::no_number)
+                throw Error(KGWAS_ERR_FORMAT, pheno_path + ": phenotype '" + text + "' of " + acc[i] + " is no number");
+        }
+    }
+    void open_table(const char* table_base, uint32_t kmer_len, const char* kinship_path, double maf, uint64_t mac) {
+        ck(kgwas_table_open(table_base, kmer_len, &t));
+        col.resize(S);
+        ck(kgwas_table_column_map(t, acc.data(), S, col.data()));
+        uint64_t S_f = 0, n_rows = 0, W_f = 0;
+        ck(kgwas_table_info(t, &S_f, &n_rows, &W_f, &klen));
+        check_squeeze_fits("lmm_lrt --kmers_table", S_f, S);
+        K = read_kinship(kinship_path, S, "the phenotype file");
+        min_count = kgwas_min_count(S, maf, mac);
+    }
+};
+
+// one column's kept k-mers to `out` in table order, with the bytes run_files writes for them after kmers_table_to_bed, and the log
+void write_table_result(const std::string& out, const std::vector<TableHit>& kept, const TableRun& r, const char* table_base,
+                        uint32_t pheno_col, const char* kinship_path, uint64_t rows_read, uint64_t rows_tested, uint64_t best_n,
+                        double lambda0, double l0, const kgwas_lmm_stats& st, double total_ms) {
+    std::string text = assoc_header();
+    for (const TableHit& k : kept) {
+        char km[33];
+        for (uint32_t i = 0; i < r.klen; i++) km[i] = "ACGT"[(k.kmer >> (2 * (r.klen - 1 - i))) & 3];  // bits2kmer31, as kmers_table_to_bed's .bim
+        km[r.klen] = 0;
+        char line[1024];
+        const uint64_t len = format_assoc("0", km, "0", 0, "0", "1", k.af, k.lam, k.p, line, sizeof(line));
+        text.append(line, len);
+    }
+    write_text(out, text, "wb");
+    char log[2048];
+    const int ll = snprintf(log, sizeof(log),
+                            "lmm_lrt: ML likelihood-ratio test (-lmm 2)\nkmers_table\t%s\nphenotypes\t%s\nphenotype_column\t%u\nkinship\t%s\n"
+                            "individuals_used\t%llu\nmin_count\t%llu\nrows_read\t%llu\nrows_tested\t%llu\nrows_kept\t%llu\nbest_n\t%llu\n"
+                            "lambda0\t%.6e\nlogl_H0\t%.6f\nms: eigen=%.3f rotate=%.3f grid=%.3f refine=%.3f total=%.3f\n",
+                            table_base, r.pheno_path.c_str(), pheno_col, kinship_path, (unsigned long long)r.S, (unsigned long long)r.min_count,
+                            (unsigned long long)rows_read, (unsigned long long)rows_tested, (unsigned long long)kept.size(),
+                            (unsigned long long)best_n, lambda0, l0, st.eigen_ms, st.rotate_ms, st.grid_ms, st.refine_ms, total_ms);
+    write_log_text(out, log, sizeof(log), ll);
+}
+
+// The file layer of lmm_lrt --kmers_table: the accessions and their order are the phenotype file's, y its column pheno_col (from
+// 1), the k-mers come straight from <table_base>.table. The best best_n k-mers by the exact test go to `out` in table order, with
+// the bytes run_files writes for them after kmers_table_to_bed; a log goes beside it.
+void run_table(const char* kinship_path, const char* table_base, uint32_t kmer_len, const char* pheno_path, uint32_t pheno_col,
+               uint64_t mac, double maf, uint64_t best_n, double lmin, double lmax, uint64_t chunk_variants, int device, const char* out,
+               kgwas_lmm_stats* total) {
+    if (!kinship_path || !table_base || !pheno_path || !out) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_run_table: null argument");
+    if (pheno_col < 1) throw Error(KGWAS_ERR_ARG, "the phenotype column (-n) starts at 1");
+    if (!best_n) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_run_table: best_n is 0");
+    const double t_start = now_ms();
+    TableRun r;
+    r.load_pheno(pheno_path);
+    r.need_column(pheno_col);
+    r.load_values();
+    std::vector<double> y(r.S);
+    r.column(pheno_col, y.data());
+    r.open_table(table_base, kmer_len, kinship_path, maf, mac);
+    Handle h(create(r.S, r.K.data(), device, lmin, lmax, chunk_variants));
+    std::vector<TableHit> kept;
+    uint64_t rows_read = 0, rows_tested = 0;
+    test_table(h.get(), y.data(), r.t, r.col.data(), r.S, r.min_count, maf, best_n, kept, rows_read, rows_tested);
+    write_table_result(out, kept, r, table_base, pheno_col, kinship_path, rows_read, rows_tested, best_n, h->lambda0, h->l0, h->st,
+                       now_ms() - t_start);
+    if (total) *total = h->st;
+}
+
+// The same for n_cols columns of the phenotype file (pheno_cols, from 1) in ONE pass over the table: the files are read once, K is
+// eigendecomposed once, and outs[k] with its log gets what run_table writes for column pheno_cols[k] (the kernels' times are the
+// shared pass's, the same in every column's log).
+void run_table_multi(const char* kinship_path, const char* table_base, uint32_t kmer_len, const char* pheno_path, uint32_t n_cols,
+                     const uint32_t* cols, const char* const* outs, uint64_t mac, double maf, uint64_t best_n, double lmin, double lmax,
+                     uint64_t chunk_variants, int device, kgwas_lmm_stats* total) {
+    if (!kinship_path || !table_base || !pheno_path || !cols || !outs) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_run_table_multi: null argument");
+    if (!n_cols) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_run_table_multi: no phenotype column given");
+    for (uint32_t k = 0; k < n_cols; k++) {
+        if (!outs[k]) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_run_table_multi: null argument");
+        if (cols[k] < 1) throw Error(KGWAS_ERR_ARG, "phenotype columns start at 1");
+    }
+    if (!best_n) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_run_table_multi: best_n is 0");
+    const double t_start = now_ms();
+    TableRun r;
+    r.load_pheno(pheno_path);
+    for (uint32_t k = 0; k < n_cols; k++) r.need_column(cols[k]);
+    r.load_values();
+    std::vector<double> Y((uint64_t)n_cols * r.S);
+    for (uint32_t k = 0; k < n_cols; k++) r.column(cols[k], &Y[k * r.S]);
+    r.open_table(table_base, kmer_len, kinship_path, maf, mac);
+    Handle h(create(r.S, r.K.data(), device, lmin, lmax, chunk_variants));
+    std::vector<std::vector<TableHit>> kept;
+    std::vector<double> l0(n_cols), lambda0(n_cols);
+    uint64_t rows_read = 0, rows_tested = 0, shipped = 0;
+    test_table_multi(h.get(), n_cols, Y.data(), r.t, r.col.data(), r.S, r.min_count, maf, best_n, kept, l0.data(), lambda0.data(), rows_read,
+                     rows_tested, shipped);
+    const double total_ms = now_ms() - t_start;
+    for (uint32_t k = 0; k < n_cols; k++)
+        write_table_result(outs[k], kept[k], r, table_base, cols[k], kinship_path, rows_read, rows_tested, best_n, lambda0[k], l0[k], h->st,
+                           total_ms);
+    if (total) *total = h->st;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kgwas_lmm_run_files(const char* kinship_path, uint64_t n_beds, const char* const* bfile_bases, const char* const* out_paths,
+                        uint32_t pheno_col, double maf, double miss, double lmin, double lmax, uint64_t chunk_variants, int32_t device,
+                        kgwas_lmm_stats* total) {
+    return guarded([&] { run_files(kinship_path, n_beds, bfile_bases, out_paths, pheno_col, maf, miss, lmin, lmax, chunk_variants, device, total); });
+}
+
+int kgwas_lmm_run_file_multi(const char* kinship_path, const char* bfile_base, uint32_t n_cols, const uint32_t* pheno_cols,
+                             const char* const* out_paths, double maf, double miss, double lmin, double lmax, uint64_t chunk_variants,
+                             int32_t device, kgwas_lmm_stats* total) {
+    return guarded([&] {
+        run_file_multi(kinship_path, bfile_base, n_cols, pheno_cols, out_paths, maf, miss, lmin, lmax, chunk_variants, device, total);
+    });
+}
+
+int kgwas_lmm_run_table(const char* kinship_path, const char* table_base, uint32_t kmer_len, const char* pheno_path, uint32_t pheno_col,
+                        uint64_t mac, double maf, uint64_t best_n, double lmin, double lmax, uint64_t chunk_variants, int32_t device,
+                        const char* out_path, kgwas_lmm_stats* total) {
+    return guarded([&] {
+        run_table(kinship_path, table_base, kmer_len, pheno_path, pheno_col, mac, maf, best_n, lmin, lmax, chunk_variants, device, out_path,
+                  total);
+    });
+}
+
+int kgwas_lmm_run_table_multi(const char* kinship_path, const char* table_base, uint32_t kmer_len, const char* pheno_path, uint32_t n_cols,
+                              const uint32_t* pheno_cols, const char* const* out_paths, uint64_t mac, double maf, uint64_t best_n,
+                              double lmin, double lmax, uint64_t chunk_variants, int32_t device, kgwas_lmm_stats* total) {
+    return guarded([&] {
+        run_table_multi(kinship_path, table_base, kmer_len, pheno_path, n_cols, pheno_cols, out_paths, mac, maf, best_n, lmin, lmax,
+                        chunk_variants, device, total);
+    });
+}
+
+int kgwas_lmm_read_kinship(const char* path, uint64_t n_expected, double* K) {
+    return guarded([&] {
+        if (!path || !K) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_read_kinship: null argument");
+        const std::vector<double> k = read_kinship(path, n_expected);
+        memcpy(K, k.data(), k.size() * sizeof(double));
+    });
+}
+
+int kgwas_lmm_read_fam(const char* path, uint32_t pheno_col, uint64_t cap, double* values, uint8_t* keep, uint64_t* n_lines) {
+    return guarded([&] {
+        if (!path || !n_lines) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_read_fam: null argument");
+        std::vector<double> v;
+        std::vector<uint8_t> k;
+        read_fam(path, pheno_col, v, k);
+        *n_lines = v.size();
+        for (uint64_t i = 0; i < std::min<uint64_t>(cap, v.size()); i++) {
+            if (values) values[i] = v[i];
+            if (keep) keep[i] = k[i];
+        }
+    });
+}
+
+uint64_t kgwas_lmm_format_assoc(const char* chr, const char* rs, const char* ps, uint32_t n_miss, const char* allele1, const char* allele0,
+                                double af, double l_mle, double p_lrt, char* out, uint64_t cap) {
+    uint64_t need = 0;
+    guarded([&] {
+        if (chr && (!rs || !ps || !allele1 || !allele0)) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_format_assoc: null argument");
+        need = format_assoc(chr, rs, ps, n_miss, allele1, allele0, af, l_mle, p_lrt, out, cap);
+    });
+    return need;
+}
+
+}  // extern "C"

@@ -1,0 +1,117 @@
+// lmm_internal.h — what lmm.cpp (the device session, the .bed passes and the back-end steps), lmm_table.cpp (the k-mers table
+// route) and lmm_files.cpp (the file layer) share: the handle and what they call in each other. Nothing else includes it.
+#pragma once
+#include <chrono>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "common.h"
+#include "ingest.h"
+#include "lmm_kernels.h"
+
+// Times the stages of the work on the handle's stream into the buckets of kgwas_lmm_stats. begin() opens an interval, end(bucket)
+// closes it into that bucket and opens the next one; once the stream is synchronised collect() adds every closed interval to its
+// bucket and forgets them all. Copies stay outside: they are issued before begin() or after the last end().
+class LmmStageTimer {
+  public:
+    using Bucket = double kgwas_lmm_stats::*;
+    LmmStageTimer() = default;
+    LmmStageTimer(const LmmStageTimer&) = delete;
+    LmmStageTimer& operator=(const LmmStageTimer&) = delete;
+    ~LmmStageTimer();
+    void begin(hipStream_t st) { stamp(st); }
+    void end(Bucket bucket, hipStream_t st) {
+        stamp(st);
+        closed.push_back({used - 2, bucket});
+    }
+    void collect(kgwas_lmm_stats& stats);
+
+  private:
+    struct Interval {
+        size_t from;  // events[from] .. events[from + 1]
+        Bucket bucket;
+    };
+    void stamp(hipStream_t st);
+    std::vector<hipEvent_t> events;  // created when first needed, reused after every collect()
+    size_t used = 0;
+    std::vector<Interval> closed;
+};
+
+struct kgwas_lmm {
+    int device = 0;
+    uint64_t n = 0;
+    kgwas::LmmDims dm{};
+    double lmin = 0, lmax = 0;
+    uint32_t chunk = 0;
+    std::vector<double> U, d;
+    std::vector<double> y_cur;
+    bool have_null = false;
+    double l0 = 0, lambda0 = 0;
+    kgwas_lmm_stats st{};
+    bool on_device = false;
+    hipStream_t stream = nullptr;
+    LmmStageTimer timer;
+    kgwas::DevBuf<double> d_U, d_d, d_wt, d_yt, d_HB, d_grid, d_base, d_null, d_Xt, d_G, d_lrt, d_lam, d_p;
+    kgwas::DevBuf<uint8_t> d_bed, d_codes;
+    kgwas::DevBuf<kgwas::LmmVariant> d_vars;
+    // The buffers below are allocated by the first pass that needs them.
+    // ensure_multi_chunk: per chunk the shared grid sums, per chunk and block of LMM_PBLOCK columns the xt yt sums and the results
+    bool have_multi_chunk = false;
+    kgwas::DevBuf<double> d_Gx, d_Gxy, d_lrtm, d_lamm, d_pm;
+    std::vector<double> h_outm;
+    void ensure_multi_chunk();
+    // ensure_multi_cols: per phenotype column Yt, the base sums and the null model
+    uint32_t multi_cols = 0;
+    kgwas::DevBuf<double> d_Ytm, d_basem, d_nullm;
+    void ensure_multi_cols(uint32_t n_pheno);
+    // ensure_select, the selection of the multi-phenotype table pass: per block of 256 pairs the counts and offsets, the
+    // survivors' number, the block's thresholds, and the records on the device and in pinned host memory
+    bool have_select = false;
+    kgwas::DevBuf<uint32_t> d_sel_cnt, d_sel_off, d_sel_total;
+    kgwas::DevBuf<kgwas::LmmSelectCol> d_sel_cols;
+    kgwas::DevBuf<kgwas::LmmTableRecord> d_sel_rec;
+    kgwas::PinBuf<kgwas::LmmTableRecord> h_sel_rec;
+    void ensure_select();
+    ~kgwas_lmm();
+};
+
+namespace kgwas {
+namespace lmm {
+
+struct TableHit {  // one tested row's result
+    double lrt, lam, p, af;
+    uint64_t row, kmer;
+};
+
+struct Destroy {
+    void operator()(kgwas_lmm* h) const { kgwas_lmm_destroy(h); }
+};
+using Handle = std::unique_ptr<kgwas_lmm, Destroy>;
+
+inline double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// ---- lmm.cpp: the session and the .bed passes (what each does stands at its definition) ----
+kgwas_lmm* create(uint64_t n, const double* K, int device, double lmin, double lmax, uint64_t chunk_variants);
+void fit_null(kgwas_lmm* h, const double* y);
+void test_bed(kgwas_lmm* h, const double* y, const uint8_t* body, uint64_t nv, double maf, double miss, double* lrt, double* lam,
+              double* p, double* af, uint32_t* n_miss, uint8_t* tested);
+void multi_prepare(kgwas_lmm* h, uint32_t n_pheno, const double* Y, double* logl0, double* lambda0,
+                   const char* who = "kgwas_lmm_test_bed_multi");
+void multi_run(kgwas_lmm* h, uint32_t n_pheno, const uint8_t* body, uint64_t nv, double maf, double miss, double* lrt, double* lam,
+               double* p, double* af, uint32_t* n_miss, uint8_t* tested);
+// ---- lmm.cpp: the back-end steps the .bed passes share with the table route ----
+void single_backend(kgwas_lmm* h, const uint8_t* codes, const LmmVariant* vars, uint32_t cc);
+void multi_front(kgwas_lmm* h, const uint8_t* codes, const LmmVariant* vars, uint32_t cc);
+void multi_block(kgwas_lmm* h, const LmmVariant* vars, uint32_t cc, uint32_t p0, uint32_t pb);
+// ---- lmm_table.cpp ----
+void test_table(kgwas_lmm* h, const double* y, kgwas_table* t, const uint64_t* col, uint64_t n_acc, uint64_t min_count, double maf,
+                uint64_t best_n, std::vector<TableHit>& kept, uint64_t& rows_read, uint64_t& rows_tested);
+void test_table_multi(kgwas_lmm* h, uint32_t n_pheno, const double* Y, kgwas_table* t, const uint64_t* col, uint64_t n_acc,
+                      uint64_t min_count, double maf, uint64_t best_n, std::vector<std::vector<TableHit>>& kept, double* logl0,
+                      double* lambda0, uint64_t& rows_read, uint64_t& rows_tested, uint64_t& pairs_shipped);
+// ---- lmm_files.cpp ----
+std::vector<double> read_kinship(const std::string& path, uint64_t n_expected, const char* counted_in = "the .fam");
+
+}  // namespace lmm
+}  // namespace kgwas

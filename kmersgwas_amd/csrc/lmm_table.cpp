@@ -1,0 +1,345 @@
+// lmm_table.cpp — the k-mers table route of kgwas_lmm_* (lmm_lrt --kmers_table): every row of a k-mers table goes
+// through the mixed-model test without a .bed in between.
+//
+// test_table: per piece of rows the device squeezes them to phenotype order, flags the rows that kmers_table_to_bed would write
+//            AND prep would test, and compacts those into code rows and LmmVariants with prep's bits (lmm_table_kernels.hip);
+//            rotate, grid and refine then run over them unchanged (lmm.cpp's single_backend). The host keeps the best N by
+//            (lrt, table row);
+// test_table_multi: several phenotype columns against ONE table in one pass (the phenotype and its permutations). The front end and
+//            the rotation run once per row, the xt yt sums and the refinement per block of LMM_PBLOCK columns (lmm.cpp's
+//            multi_front and multi_block), and a select kernel hands the host only the (column, row) pairs that can still enter a
+//            column's best N. Every kept row and number has the bits of test_table's for that column.
+#include <algorithm>
+#include <cmath>
+#include <condition_variable>
+#include <exception>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "kernels.h"
+#include "lmm_internal.h"
+
+using namespace kgwas;
+using namespace kgwas::lmm;
+
+namespace {
+
+// a ranks before b: the larger lrt, then the smaller table row (a NaN lrt ranks last). Rows are unique, so the order is total.
+bool ranks_before(const TableHit& a, const TableHit& b) {
+    const double ka = std::isnan(a.lrt) ? -INFINITY : a.lrt, kb = std::isnan(b.lrt) ? -INFINITY : b.lrt;
+    return ka != kb ? ka > kb : a.row < b.row;
+}
+
+// offers a result to a heap of at most best_n with the worst kept result on top
+void heap_offer(std::vector<TableHit>& heap, uint64_t best_n, const TableHit& hit) {
+    auto worse_on_top = [](const TableHit& a, const TableHit& b) { return ranks_before(a, b); };
+    if (heap.size() < best_n) {
+        heap.push_back(hit);
+        std::push_heap(heap.begin(), heap.end(), worse_on_top);
+    } else if (ranks_before(hit, heap.front())) {
+        std::pop_heap(heap.begin(), heap.end(), worse_on_top);
+        heap.back() = hit;
+        std::push_heap(heap.begin(), heap.end(), worse_on_top);
+    }
+}
+
+void sort_by_row(std::vector<TableHit>& heap) {
+    std::sort(heap.begin(), heap.end(), [](const TableHit& a, const TableHit& b) { return a.row < b.row; });
+}
+
+// The reader of table_pass: its thread fills two pinned row buffers in turn, piece k going into buffer k & 1 once piece k - 2
+// has left it, while the device works on the piece before. The consumer takes piece k with wait(k), which rethrows what a failed
+// read threw, and hands its buffer back with release(k). The destructor stops the thread and joins it.
+class PieceReader {
+  public:
+    PieceReader(kgwas_table* t, uint64_t n_rows, uint64_t piece, uint64_t stride) : t_(t), n_rows_(n_rows), piece_(piece) {
+        for (PinBuf<uint64_t>& b : rows_) b.alloc(piece * stride);
+        thread_ = std::thread([this] { fill(); });
+    }
+    ~PieceReader() {
+        {
+            std::unique_lock<std::mutex> lk(mu_);
+            stop_ = true;
+        }
+        cv_.notify_all();
+        if (thread_.joinable()) thread_.join();
+    }
+    const uint64_t* wait(uint64_t k) {
+        std::unique_lock<std::mutex> lk(mu_);
+        cv_.wait(lk, [&] { return stop_ || filled_ > k; });
+        if (filled_ <= k) std::rethrow_exception(err_);  // (only the reader's failure stops it before the consumer is done)
+        return rows_[k & 1].p;
+    }
+    void release(uint64_t k) {
+        {
+            std::unique_lock<std::mutex> lk(mu_);
+            consumed_ = k + 1;
+        }
+        cv_.notify_all();
+    }
+
+  private:
+    void fill() {
+        kgwas_name_this_thread("kgwas-lmm-read");
+        try {
+            for (uint64_t k = 0; k * piece_ < n_rows_; k++) {
+                {
+                    std::unique_lock<std::mutex> lk(mu_);
+                    cv_.wait(lk, [&] { return stop_ || consumed_ + 2 > k; });
+                    if (stop_) return;
+                }
+                const uint64_t pos = k * piece_;
+                if (kgwas_table_read_rows(t_, pos, std::min(piece_, n_rows_ - pos), rows_[k & 1].p) != KGWAS_OK)
+                    throw Error(KGWAS_ERR_IO, kgwas_last_error());
+                {
+                    std::unique_lock<std::mutex> lk(mu_);
+                    filled_ = k + 1;
+                }
+                cv_.notify_all();
+            }
+        } catch (...) {
+            std::unique_lock<std::mutex> lk(mu_);
+            err_ = std::current_exception();
+            stop_ = true;
+            cv_.notify_all();
+        }
+    }
+    kgwas_table* const t_;
+    const uint64_t n_rows_, piece_;
+    PinBuf<uint64_t> rows_[2];
+    std::mutex mu_;
+    std::condition_variable cv_;
+    uint64_t filled_ = 0, consumed_ = 0;
+    bool stop_ = false;
+    std::exception_ptr err_;
+    std::thread thread_;
+};
+
+// What test_table and test_table_multi share: the checks, the pieces and the front end. Per piece the rows are squeezed, flagged
+// and compacted (lmm_table_kernels.hip). prepare() runs after the checks and before any device work (the null models);
+// per_piece(total, codes, vars, row, kmer) gets a piece's compacted tested rows on the device, total > 0 of them, and is done
+// with them when it returns. `who` starts the messages; a tested row counts `weight` times in the stats' variants_tested.
+template <class Prepare, class PerPiece>
+void table_pass(kgwas_lmm* h, kgwas_table* t, const uint64_t* col, uint64_t n_acc, uint64_t min_count, double maf, uint64_t best_n,
+                const std::string& who, uint64_t weight, Prepare prepare, PerPiece per_piece, uint64_t& rows_read, uint64_t& rows_tested) {
+    if (n_acc != h->n) throw Error(KGWAS_ERR_ARG, who + ": n_acc differs from the handle's number of individuals");
+    if (!best_n) throw Error(KGWAS_ERR_ARG, who + ": best_n is 0");
+    uint64_t S_f = 0, n_rows = 0, W_f = 0;
+    uint32_t klen = 0;
+    if (kgwas_table_info(t, &S_f, &n_rows, &W_f, &klen) != KGWAS_OK) throw Error(KGWAS_ERR_ARG, kgwas_last_error());
+    const uint64_t S = n_acc;
+    for (uint64_t i = 0; i < S; i++)
+        if (col[i] >= S_f) throw Error(KGWAS_ERR_ARG, who + ": column index out of range");
+    check_squeeze_fits(who.c_str(), S_f, S);  // (before any allocation)
+    prepare();
+    KGWAS_HIP(hipSetDevice(h->device));
+    const uint32_t W_m = (uint32_t)(2 * ((S + 127) / 128));
+    const uint64_t stride = 1 + W_f;
+    uint64_t piece = std::max<uint64_t>(1024, std::min<uint64_t>(1u << 18, (64ull << 20) / (8 * stride)));
+    const long long forced = opt_int("KGWAS_LMM_PIECE_ROWS", 0);
+    if (forced > 0) piece = (uint64_t)std::min<long long>(forced, 1 << 20);
+    piece = std::min(piece, std::max<uint64_t>(n_rows, 1));
+    const uint64_t n_blocks = (piece + LMM_TABLE_BLOCK - 1) / LMM_TABLE_BLOCK;
+
+    std::vector<uint32_t> colmap(64ull * W_m, 0xFFFFFFFFu);
+    for (uint64_t i = 0; i < S; i++) colmap[i] = (uint32_t)col[i];
+    DevBuf<uint32_t> d_colmap, d_sq, d_n1flag, d_bcnt, d_boff, d_total;
+    DevBuf<uint64_t> d_rows, d_row, d_kmer;
+    DevBuf<uint8_t> d_codes;
+    DevBuf<LmmVariant> d_vars;
+    d_colmap.alloc(colmap.size());
+    KGWAS_HIP(hipMemcpy(d_colmap.p, colmap.data(), colmap.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    d_rows.alloc(piece * stride);
+    d_sq.alloc(piece * 2 * W_m);
+    d_n1flag.alloc(piece);
+    d_bcnt.alloc(n_blocks);
+    d_boff.alloc(n_blocks);
+    d_total.alloc(1);
+    d_codes.alloc(piece * h->dm.bpsp);
+    d_vars.alloc(piece);
+    d_row.alloc(piece);
+    d_kmer.alloc(piece);
+    PieceReader reader(t, n_rows, piece, stride);
+
+    hipStream_t st = h->stream;
+    rows_read = rows_tested = 0;
+    for (uint64_t k = 0, pos = 0; pos < n_rows; k++, pos += piece) {
+        const uint64_t c = std::min(piece, n_rows - pos);
+        const uint64_t* h_rows = reader.wait(k);
+        uint32_t total = 0;
+        KGWAS_HIP(hipMemcpyAsync(d_rows.p, h_rows, c * stride * 8, hipMemcpyHostToDevice, st));
+        h->timer.begin(st);
+        KGWAS_HIP(launch_squeeze(d_rows.p, stride, c, d_colmap.p, W_m, (uint32_t)W_f, d_sq.p, st));
+        KGWAS_HIP(launch_lmm_table_front(d_rows.p, stride, d_sq.p, (uint32_t)c, W_m, h->dm, pos, (uint32_t)std::min<uint64_t>(min_count, 0xFFFFFFFFu),
+                                         maf, d_n1flag.p, d_bcnt.p, d_boff.p, d_total.p, d_codes.p, d_vars.p, d_row.p, d_kmer.p, st));
+        h->timer.end(&kgwas_lmm_stats::rotate_ms, st);
+        KGWAS_HIP(hipMemcpyAsync(&total, d_total.p, sizeof(total), hipMemcpyDeviceToHost, st));
+        KGWAS_HIP(hipStreamSynchronize(st));
+        reader.release(k);  // the rows are on the device: the buffer goes back to the reader
+        h->timer.collect(h->st);
+        if (total > c) throw Error(KGWAS_ERR_STATE, who + ": the front end counted more tested rows than rows");
+        if (total) per_piece(total, (const uint8_t*)d_codes.p, (const LmmVariant*)d_vars.p, (const uint64_t*)d_row.p, (const uint64_t*)d_kmer.p);
+        rows_read += c;
+        rows_tested += total;
+        h->st.variants_read += c;
+        h->st.variants_tested += total * weight;
+    }
+}
+
+// copies kept into the optional output arrays of the C ABI, from their element `at` on
+void copy_hits(const std::vector<TableHit>& kept, uint64_t at, uint64_t* row, uint64_t* kmer, double* lrt, double* lambda, double* p,
+               double* af) {
+    for (uint64_t i = 0; i < kept.size(); i++) {
+        if (row) row[at + i] = kept[i].row;
+        if (kmer) kmer[at + i] = kept[i].kmer;
+        if (lrt) lrt[at + i] = kept[i].lrt;
+        if (lambda) lambda[at + i] = kept[i].lam;
+        if (p) p[at + i] = kept[i].p;
+        if (af) af[at + i] = kept[i].af;
+    }
+}
+
+}  // namespace
+
+// Every row of table t against y: the best best_n tested rows by lrt, in table row order. The compacted rows of a piece go
+// through rotate, grid and refine in sub-chunks of at most h->chunk. The host keeps a heap of best_n results with the worst on top.
+void kgwas::lmm::test_table(kgwas_lmm* h, const double* y, kgwas_table* t, const uint64_t* col, uint64_t n_acc, uint64_t min_count,
+                            double maf, uint64_t best_n, std::vector<TableHit>& kept, uint64_t& rows_read, uint64_t& rows_tested) {
+    const uint64_t chunk = h->chunk;
+    std::vector<TableHit> heap;
+    std::vector<double> o_lrt, o_lam, o_p;
+    std::vector<LmmVariant> o_vars;
+    std::vector<uint64_t> o_row, o_kmer;
+    auto prepare = [&] {
+        fit_null(h, y);
+        heap.reserve((size_t)std::min<uint64_t>(best_n, 1u << 20));
+        o_lrt.resize(chunk), o_lam.resize(chunk), o_p.resize(chunk), o_vars.resize(chunk), o_row.resize(chunk), o_kmer.resize(chunk);
+    };
+    auto per_piece = [&](uint32_t total, const uint8_t* d_codes, const LmmVariant* d_vars, const uint64_t* d_row, const uint64_t* d_kmer) {
+        hipStream_t st = h->stream;
+        for (uint64_t sub = 0; sub < total; sub += chunk) {
+            const uint32_t cc = (uint32_t)std::min<uint64_t>(chunk, total - sub);
+            const LmmVariant* vars = d_vars + sub;
+            h->timer.begin(st);
+            single_backend(h, d_codes + sub * h->dm.bpsp, vars, cc);
+            KGWAS_HIP(hipMemcpyAsync(o_lrt.data(), h->d_lrt.p, cc * sizeof(double), hipMemcpyDeviceToHost, st));
+            KGWAS_HIP(hipMemcpyAsync(o_lam.data(), h->d_lam.p, cc * sizeof(double), hipMemcpyDeviceToHost, st));
+            KGWAS_HIP(hipMemcpyAsync(o_p.data(), h->d_p.p, cc * sizeof(double), hipMemcpyDeviceToHost, st));
+            KGWAS_HIP(hipMemcpyAsync(o_vars.data(), vars, cc * sizeof(LmmVariant), hipMemcpyDeviceToHost, st));
+            KGWAS_HIP(hipMemcpyAsync(o_row.data(), d_row + sub, cc * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+            KGWAS_HIP(hipMemcpyAsync(o_kmer.data(), d_kmer + sub, cc * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+            KGWAS_HIP(hipStreamSynchronize(st));
+            h->timer.collect(h->st);
+            h->st.chunks++;
+            for (uint32_t v = 0; v < cc; v++) heap_offer(heap, best_n, TableHit{o_lrt[v], o_lam[v], o_p[v], o_vars[v].af, o_row[v], o_kmer[v]});
+        }
+    };
+    table_pass(h, t, col, n_acc, min_count, maf, best_n, "kgwas_lmm_test_table", 1, prepare, per_piece, rows_read, rows_tested);
+    sort_by_row(heap);
+    kept.swap(heap);
+}
+
+// The same for n_pheno columns Y[n_pheno][n] in one pass over the table: the best best_n per column, each with the rows and the
+// bits test_table gives for that column alone. Per sub-chunk the rotation and the grid sums without y run once; per block of
+// LMM_PBLOCK columns the xt yt sums, the refinement and the select kernel, which hands the host only the (column, row) pairs that
+// can still enter the column's heap: all of them while the heap is not full, then those with lrt above the heap's worst as the
+// host knew it before the launch. The heaps still decide; the per-row arrays stay on the device.
+void kgwas::lmm::test_table_multi(kgwas_lmm* h, uint32_t n_pheno, const double* Y, kgwas_table* t, const uint64_t* col, uint64_t n_acc,
+                                  uint64_t min_count, double maf, uint64_t best_n, std::vector<std::vector<TableHit>>& kept,
+                                  double* logl0, double* lambda0, uint64_t& rows_read, uint64_t& rows_tested, uint64_t& pairs_shipped) {
+    const std::string who = "kgwas_lmm_test_table_multi";
+    if (!n_pheno) throw Error(KGWAS_ERR_ARG, who + ": n_pheno is 0");  // (before the table's checks)
+    const uint64_t chunk = h->chunk, cap = (uint64_t)LMM_PBLOCK * chunk;
+    const bool select = opt_int("KGWAS_LMM_TABLE_SELECT", 1) != 0;
+    std::vector<std::vector<TableHit>> heaps(n_pheno);
+    pairs_shipped = 0;
+    auto prepare = [&] {
+        multi_prepare(h, n_pheno, Y, logl0, lambda0, who.c_str());
+        h->ensure_select();
+        for (std::vector<TableHit>& hp : heaps) hp.reserve((size_t)std::min<uint64_t>(best_n, 1u << 14));
+    };
+    auto per_piece = [&](uint32_t total, const uint8_t* d_codes, const LmmVariant* d_vars, const uint64_t* d_row, const uint64_t* d_kmer) {
+        hipStream_t st = h->stream;
+        for (uint64_t sub = 0; sub < total; sub += chunk) {
+            const uint32_t cc = (uint32_t)std::min<uint64_t>(chunk, total - sub);
+            const LmmVariant* vars = d_vars + sub;
+            h->timer.begin(st);
+            multi_front(h, d_codes + sub * h->dm.bpsp, vars, cc);
+            for (uint32_t p0 = 0; p0 < n_pheno; p0 += LMM_PBLOCK) {
+                const uint32_t pb = std::min(LMM_PBLOCK, n_pheno - p0);
+                // what the host knows of the block's heaps now; a NaN lrt ranks as -inf (ranks_before)
+                LmmSelectCol sc[LMM_PBLOCK];
+                for (uint32_t k = 0; k < pb; k++) {
+                    const std::vector<TableHit>& hp = heaps[p0 + k];
+                    const bool open = !select || hp.size() < best_n;
+                    const double worst = open ? 0.0 : hp.front().lrt;
+                    sc[k] = LmmSelectCol{std::isnan(worst) ? -INFINITY : worst, open ? 1u : 0u, 0u};
+                }
+                KGWAS_HIP(hipMemcpyAsync(h->d_sel_cols.p, sc, pb * sizeof(LmmSelectCol), hipMemcpyHostToDevice, st));
+                multi_block(h, vars, cc, p0, pb);
+                KGWAS_HIP(launch_lmm_table_select(h->d_lrtm.p, h->d_lamm.p, h->d_pm.p, cc, pb, vars, d_row + sub, d_kmer + sub, h->d_sel_cols.p,
+                                                  h->d_sel_cnt.p, h->d_sel_off.p, h->d_sel_total.p, h->d_sel_rec.p, (uint32_t)cap, st));
+                h->timer.end(&kgwas_lmm_stats::refine_ms, st);  // (the select kernels are timed with the refinement)
+                uint32_t count = 0;
+                KGWAS_HIP(hipMemcpyAsync(&count, h->d_sel_total.p, sizeof(count), hipMemcpyDeviceToHost, st));
+                KGWAS_HIP(hipStreamSynchronize(st));  // (sc is read by the copy until here)
+                h->timer.collect(h->st);
+                if (count > (uint64_t)pb * cc) throw Error(KGWAS_ERR_STATE, who + ": the select kernel counted more survivors than pairs");
+                if (count) {
+                    KGWAS_HIP(hipMemcpyAsync(h->h_sel_rec.p, h->d_sel_rec.p, count * sizeof(LmmTableRecord), hipMemcpyDeviceToHost, st));
+                    KGWAS_HIP(hipStreamSynchronize(st));
+                }
+                for (uint32_t r = 0; r < count; r++) {
+                    const LmmTableRecord& o = h->h_sel_rec.p[r];
+                    if (o.col >= pb) throw Error(KGWAS_ERR_STATE, who + ": a survivor record names a column outside its block");
+                    heap_offer(heaps[p0 + o.col], best_n, TableHit{o.lrt, o.lam, o.p, o.af, o.row, o.kmer});
+                }
+                pairs_shipped += count;
+            }
+            h->st.chunks++;
+        }
+    };
+    table_pass(h, t, col, n_acc, min_count, maf, best_n, who, n_pheno, prepare, per_piece, rows_read, rows_tested);
+    for (std::vector<TableHit>& hp : heaps) sort_by_row(hp);
+    kept.swap(heaps);
+}
+
+extern "C" {
+
+int kgwas_lmm_test_table(kgwas_lmm* h, const double* y, kgwas_table* t, const uint64_t* col, uint64_t n_acc, uint64_t min_count, double maf,
+                         uint64_t best_n, uint64_t* row, uint64_t* kmer, double* lrt, double* lambda, double* p, double* af,
+                         uint64_t* n_kept, uint64_t* rows_read, uint64_t* rows_tested) {
+    return guarded([&] {
+        if (!h || !y || !t || !col) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_test_table: null argument");
+        std::vector<TableHit> kept;
+        uint64_t n_read = 0, n_tested = 0;
+        test_table(h, y, t, col, n_acc, min_count, maf, best_n, kept, n_read, n_tested);
+        copy_hits(kept, 0, row, kmer, lrt, lambda, p, af);
+        if (n_kept) *n_kept = kept.size();
+        if (rows_read) *rows_read = n_read;
+        if (rows_tested) *rows_tested = n_tested;
+    });
+}
+
+int kgwas_lmm_test_table_multi(kgwas_lmm* h, uint32_t n_pheno, const double* Y, kgwas_table* t, const uint64_t* col, uint64_t n_acc,
+                               uint64_t min_count, double maf, uint64_t best_n, uint64_t* row, uint64_t* kmer, double* lrt, double* lambda,
+                               double* p, double* af, uint64_t* n_kept, double* logl0, double* lambda0, uint64_t* rows_read,
+                               uint64_t* rows_tested, uint64_t* pairs_shipped) {
+    return guarded([&] {
+        if (!h || (!Y && n_pheno) || !t || !col) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_test_table_multi: null argument");
+        std::vector<std::vector<TableHit>> kept;
+        uint64_t n_read = 0, n_tested = 0, n_shipped = 0;
+        test_table_multi(h, n_pheno, Y, t, col, n_acc, min_count, maf, best_n, kept, logl0, lambda0, n_read, n_tested, n_shipped);
+        for (uint32_t k = 0; k < n_pheno; k++) {
+            copy_hits(kept[k], (uint64_t)k * best_n, row, kmer, lrt, lambda, p, af);
+            if (n_kept) n_kept[k] = kept[k].size();
+        }
+        if (rows_read) *rows_read = n_read;
+        if (rows_tested) *rows_tested = n_tested;
+        if (pairs_shipped) *pairs_shipped = n_shipped;
+    });
+}
+
+}  // extern "C"
