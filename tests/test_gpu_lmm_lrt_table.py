@@ -33,8 +33,9 @@ def write_case(tmp_path, rows, S_f, pick, name="tab"):
     return base, [names[i] for i in pick]
 
 
-def bed_route(tmp_path, base, rows, pick, acc, K, y, min_count, maf, lmin=1e-5, lmax=1e5):
-    """The yardstick: (table rows of the tested variants, dict of their lrt, lambda, p, af), in table order."""
+def bed_route(tmp_path, base, rows, pick, acc, K, y, min_count, maf, lmin=1e-5, lmax=1e5, chunk=10240, m=None):
+    """The yardstick: (table rows of the tested variants, dict of their lrt, lambda, p, af), in table order. m: an open LmmLrt of K
+    to use instead of a new one of chunk_variants = chunk."""
     out = str(tmp_path / "yard")
     tbl = kg.KmersTable(base, T.K_LEN)
     nb, nw = kg.table_to_bed(out, tbl, np.asarray(pick, np.uint64), acc, y.astype(np.float32), min_count, max(len(rows), 1), False)
@@ -43,23 +44,36 @@ def bed_route(tmp_path, base, rows, pick, acc, K, y, min_count, maf, lmin=1e-5, 
     body = np.frombuffer(open(out + ".0.bed", "rb").read(), np.uint8)[3:]
     bim = [l.split("\t")[1] for l in open(out + ".0.bim").read().split("\n") if l]
     assert len(bim) == nw
-    row_of = {T.kmer_text(w): r for r, w in enumerate(rows[:, 0])}
-    bim_rows = np.array([row_of[k] for k in bim], np.uint64)
-    m = kg.LmmLrt(K, lmin=lmin, lmax=lmax, chunk_variants=10240)
-    res = m.test(body, y, maf=maf, miss=1.0) if nw else {k: np.zeros(0) for k in FIELDS + ("tested",)}
-    m.close()
+    # the table row of every .bim line, by its k-mer (table_from_bits: the k-mer words are ascending and unique)
+    words = T.kmer_words(bim)
+    bim_rows = np.searchsorted(rows[:, 0], words).astype(np.uint64)
+    assert (bim_rows < len(rows)).all() and (rows[bim_rows.astype(np.int64), 0] == words).all(), "a .bim k-mer that is not in the table"
+    own = m is None
+    if own:
+        m = kg.LmmLrt(K, lmin=lmin, lmax=lmax, chunk_variants=chunk)
+    try:
+        res = m.test(body, y, maf=maf, miss=1.0) if nw else {k: np.zeros(0) for k in FIELDS + ("tested",)}
+    finally:
+        if own:
+            m.close()
     t = np.asarray(res["tested"], bool)
     return bim_rows[t], {k: res[k][t] for k in FIELDS}
 
 
-def table_route(base, pick, K, y, min_count, maf, best_n, chunk, lmin=1e-5, lmax=1e5):
+def table_route(base, pick, K, y, min_count, maf, best_n, chunk, lmin=1e-5, lmax=1e5, m=None):
+    """m: an open LmmLrt of K to use instead of a new one of chunk_variants = chunk; res["stats"] then counts this call alone too."""
     tbl = kg.KmersTable(base, T.K_LEN)
-    m = kg.LmmLrt(K, lmin=lmin, lmax=lmax, chunk_variants=chunk)
+    own = m is None
+    if own:
+        m = kg.LmmLrt(K, lmin=lmin, lmax=lmax, chunk_variants=chunk)
     try:
+        before = m.stats()
         res = m.test_table(tbl, np.asarray(pick, np.uint64), y, min_count, maf, best_n)
-        res["stats"] = m.stats()
+        after = m.stats()
+        res["stats"] = {k: after[k] - before[k] for k in ("variants_read", "variants_tested", "chunks")}
     finally:
-        m.close()
+        if own:
+            m.close()
         tbl.close()
     return res
 
@@ -99,28 +113,36 @@ def test_equals_the_bed_route(tmp_path, monkeypatch, S, S_f):
 
 
 # ---- 2. the edges of the tested set --------------------------------------------------------------------------------------------
+def edges_case(tmp_path, S, maf, mac, chunk=64):
+    """Presence counts at and beside every edge of both rules, and every count 0 .. S: the table route against the .bed route and
+    the numpy rule. Returns (counts, rule)."""
+    mc = kg.min_count(S, maf, mac)
+    counts = [0, S, 1, S - 1, mc - 1, mc, mc + 1, S - mc - 1, S - mc, S - mc + 1] * 3 + list(range(0, S + 1))
+    bits = T.bits_with_counts(counts, S, S)
+    K, y = T.kinship_and_phenotype(S)
+    pick = np.random.default_rng(S).permutation(S)
+    rows = T.table_from_bits(bits, S, pick, 9)
+    d = tmp_path / ("S%d_%g" % (S, maf))
+    d.mkdir()
+    base, acc = write_case(d, rows, S, pick)
+    rows_exp, exp = bed_route(d, base, rows, pick, acc, K, y, mc, maf)
+    rule = T.tested_rule(counts, S, mc, maf)
+    assert rows_exp.tolist() == np.flatnonzero(rule).tolist()
+    res = table_route(base, pick, K, y, mc, maf, len(counts), chunk)
+    assert_same(res, rows_exp, exp, "S=%d maf=%g" % (S, maf))
+    return np.asarray(counts), rule
+
+
 def test_tested_set_edges(tmp_path, monkeypatch):
     monkeypatch.setenv("KGWAS_LMM_PIECE_ROWS", "64")
     # S = 50, maf = 0.1: ceil(S maf) = 5 carriers pass the MAC rule, but 1 - af = 1 - 0.9 = 0.09999999999999998 < 0.1 at n1 = 5
     # (while af = 0.1 passes at n1 = 45): the two rules disagree by one count at one end
     for S, maf, mac in ((50, 0.1, 1), (67, 0.05, 5), (67, 0.0, 7)):
-        mc = kg.min_count(S, maf, mac)
-        counts = [0, S, 1, S - 1, mc - 1, mc, mc + 1, S - mc - 1, S - mc, S - mc + 1] * 3 + list(range(0, S + 1))
-        bits = T.bits_with_counts(counts, S, S)
-        K, y = T.kinship_and_phenotype(S)
-        pick = np.random.default_rng(S).permutation(S)
-        rows = T.table_from_bits(bits, S, pick, 9)
-        d = tmp_path / ("S%d_%g" % (S, maf))
-        d.mkdir()
-        base, acc = write_case(d, rows, S, pick)
-        rows_exp, exp = bed_route(d, base, rows, pick, acc, K, y, mc, maf)
-        rule = T.tested_rule(counts, S, mc, maf)
-        assert rows_exp.tolist() == np.flatnonzero(rule).tolist()
+        counts, rule = edges_case(tmp_path, S, maf, mac)
         if S == 50:
-            mac_only = (np.asarray(counts) >= mc) & (np.asarray(counts) <= S - mc)
-            assert (mac_only & ~rule).any() and set(np.asarray(counts)[mac_only & ~rule]) == {5}, "the fixture's rules do not disagree"
-        res = table_route(base, pick, K, y, mc, maf, len(counts), 64)
-        assert_same(res, rows_exp, exp, "S=%d maf=%g" % (S, maf))
+            mc = kg.min_count(S, maf, mac)
+            mac_only = (counts >= mc) & (counts <= S - mc)
+            assert (mac_only & ~rule).any() and set(counts[mac_only & ~rule]) == {5}, "the fixture's rules do not disagree"
 
 
 def test_no_row_tested(tmp_path):

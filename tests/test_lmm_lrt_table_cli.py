@@ -1,6 +1,7 @@
 """lmm_lrt --kmers_table without a GPU: the refusals of the tool (each a non-zero exit, its message, and no output file), the
-device error of a well-formed command line on a machine without a GPU, the new entry points, and the model gap of the fixture
-that test_gpu_lmm_lrt_table.py checks against model E."""
+device error of a well-formed command line on a machine without a GPU, the new entry points, the model gap of the fixture
+that test_gpu_lmm_lrt_table.py checks against model E, and the geometry of the fixtures of test_gpu_lmm_lrt_table_scale.py: which
+blocks and scan rounds (lmm_table_scan_kernel) their pieces and select launches reach."""
 import os
 import subprocess
 
@@ -193,3 +194,106 @@ def test_tested_rule_edges():
     assert not t[5] and t[6] and t[45] and not t[46] and not t[0] and not t[50]
     t = T.tested_rule(np.arange(68), 67, 5, 0.05)
     assert list(np.flatnonzero(t)) == list(range(5, 63))
+
+
+# ---- the fixtures of test_gpu_lmm_lrt_table_scale.py: numpy only ----------------------------------------------------------------
+def test_kmer_words_inverts_kmer_text():
+    words = np.array([0, 1, (1 << 62) - 1, 0x2AAAAAAAAAAAAAAA, 123456789012345], np.uint64)
+    assert T.kmer_words([T.kmer_text(w) for w in words]).tolist() == words.tolist()
+    assert T.kmer_words([]).shape == (0,)
+
+
+def test_block_fixture_kinds():
+    """The block-structured table holds every kind of block, the rows that must not be tested come from both sides of the rule
+    and are mostly not empty, and the table's words hold the bits."""
+    bits, pick, rows, rule = T.scale_fixture()
+    n_rows, S, mc = T.SCALE_ROWS, T.SCALE_S, T.SCALE_MIN_COUNT
+    assert bits.shape == (n_rows, S) and rows.shape == (n_rows, 3) and n_rows == (1 << 18) + (1 << 16) + 77
+    assert (np.diff(rows[:, 0].astype(np.int64)) > 0).all()
+    sample = np.r_[0:300, 65500:65600, n_rows - 100:n_rows]
+    got = np.array([[(int(rows[r, 1 + int(c) // 64]) >> (int(c) % 64)) & 1 for c in pick] for r in sample], bool)
+    assert (got == bits[sample]).all()
+    n1 = bits.sum(axis=1)
+    for count in (0, S, mc - 1, S - mc + 1):
+        assert ((n1 == count) & ~rule).sum() > n_rows // 8, "few untested rows with %d carriers" % count
+    kinds = T.scale_kinds()
+    (blocks,) = [r for p in T.scan_geometry(rule, n_rows) for r in [np.concatenate(p)]]
+    assert len(blocks) == len(kinds) == 1281
+    assert (blocks[kinds == T.FULL][:-1] == 256).all() and blocks[-1] == 77 and (blocks[kinds == T.EMPTY] == 0).all()
+    for kind, at in ((T.FIRST, 0), (T.LAST, 255)):
+        b = np.flatnonzero(kinds == kind)
+        assert len(b) > 100 and (blocks[b] == 1).all() and rule[b * 256 + at].all()
+    rnd = blocks[kinds == T.RANDOM]
+    assert len(rnd) > 400 and 2 < rnd.mean() < 40 and rnd.max() < 256
+
+
+@pytest.mark.parametrize("forced", T.SCALE_PIECES)
+def test_block_fixture_geometry(forced):
+    """What lmm_table_scan_kernel meets in test_pieces_beyond_one_scan_round at this KGWAS_LMM_PIECE_ROWS."""
+    bits, pick, rows, rule = T.scale_fixture()
+    n_rows = T.SCALE_ROWS
+    piece = T.piece_rows(n_rows, forced, rows.shape[1])
+    geo = T.scan_geometry(rule, piece)
+    sizes = [min(piece, n_rows - pos) for pos in range(0, n_rows, piece)]
+    print("KGWAS_LMM_PIECE_ROWS %s: pieces of %s rows, rounds x blocks %s" % (forced, sizes, [[len(r) for r in p] for p in geo]))
+    # a lost carry shows in the very next round: no round without a tested row
+    assert all(r.sum() > 0 for p in geo for r in p)
+    later = [r for p in geo for r in p[1:]]
+    if forced is None:
+        assert sizes == [1 << 18, 65613] and [[len(r) for r in p] for p in geo] == [[256] * 4, [256, 1]]
+    elif forced == T.MAX_PIECE:
+        assert sizes == [n_rows] and [len(r) for r in geo[0]] == [256] * 5 + [1]
+    elif forced == 65536:
+        assert sizes == [65536] * 5 + [77] and [[len(r) for r in p] for p in geo] == [[256]] * 5 + [[1]]
+    else:
+        assert sizes == [65537] * 5 + [72] and [[len(r) for r in p] for p in geo] == [[256, 1]] * 5 + [[1]]
+        assert all(p[1].tolist() == [1] for p in geo[:5]), "the second round's one row is not tested"
+    if forced in (None, T.MAX_PIECE):
+        # a full, an empty and a single-row block (the row first and last in its block) in a round other than the first
+        assert any((r == 256).any() for r in later) and any((r == 0).any() for r in later) and any((r == 1).any() for r in later)
+        flags = np.concatenate([np.r_[rule[pos:pos + piece], np.zeros(-len(rule[pos:pos + piece]) % 256, bool)].reshape(-1, 256)[256:]
+                                for pos in range(0, n_rows, piece)])
+        alone = flags[flags.sum(axis=1) == 1]
+        assert alone[:, 0].any() and alone[:, 255].any()
+        # a partial last round and a partial last block
+        assert any(len(p[-1]) < 256 for p in geo) and any(s % 256 for s in sizes)
+
+
+def test_sub_chunk_and_select_fixture_geometry():
+    """The tables of the sub-chunk and select tests: one piece each, the tested rows they need, and the scan rounds of their
+    select launches (256 pairs per block, 256 blocks per round)."""
+    for n_rows, least, ties in ((T.CHUNK_ROWS, T.CHUNK_MIN_TESTED, False), (T.SELECT_OPEN_ROWS, T.SELECT_OPEN_MIN_TESTED, False),
+                                (T.SELECT_ROWS, T.SELECT_MIN_TESTED, False), (T.SELECT_ROWS, T.SELECT_MIN_TESTED, True)):
+        tested = int(T.scale_tested(T.scale_bits(n_rows, ties)).sum())
+        assert least <= tested < n_rows and T.piece_rows(n_rows, None, 3) == n_rows
+        assert len(T.scan_geometry(np.ones(n_rows, bool), n_rows)[0]) == 1, "the front end of these tables has one round"
+    tested = int(T.scale_tested(T.scale_bits(T.CHUNK_ROWS)).sum())
+    assert -(-tested // 10240) == 3 and tested % 10240 and tested <= 65536
+    # open heaps: one launch of 32 x tested pairs, two rounds, the second partial
+    tested = int(T.scale_tested(T.scale_bits(T.SELECT_OPEN_ROWS)).sum())
+    (launch,) = T.scan_geometry(np.ones(32 * tested, bool), 32 * tested)
+    assert 32 * tested > 65536 and tested <= 10240 and [len(r) for r in launch] == [256, -(-32 * tested // 256) - 256]
+    # closed heaps: launches of 32 x 3008 pairs = 376 blocks, two rounds, then the rest; the repeated rows a sub-chunk apart
+    (launch,) = T.scan_geometry(np.ones(32 * T.SELECT_CHUNK, bool), 32 * T.SELECT_CHUNK)
+    assert [len(r) for r in launch] == [256, 120]
+    rule = T.scale_tested(T.scale_bits(T.SELECT_ROWS, True))
+    assert int(rule.sum()) > 2 * T.SELECT_CHUNK
+    place = np.cumsum(rule) - 1
+    a, b = np.arange(T.TIE_FROM, T.TIE_FROM + T.TIE_COUNT), np.arange(T.TIE_TO, T.TIE_TO + T.TIE_COUNT)
+    assert (T.scale_bits(T.SELECT_ROWS, True)[a] == T.scale_bits(T.SELECT_ROWS, True)[b]).all() and rule[a].sum() >= 40
+    assert (place[a] // T.SELECT_CHUNK == 0).all() and (place[b] // T.SELECT_CHUNK == 1).all()
+
+
+def test_scan_kernel_guards_its_lds_between_rounds():
+    """lmm_table_scan_kernel writes s_wave once per round of 256 blocks and every wave reads all of it: a barrier must stand between
+    the write and the reads, and one between the reads and the end of the round, or a wave that is a round ahead overwrites what a
+    slower wave still reads. The outputs do not show the second one missing (without it the kernel passed every table test on an
+    MI355X: the window is shorter than the next round's global load), so the source is read here."""
+    src = open(os.path.join(os.path.dirname(os.path.abspath(capi.__file__)), "csrc", "lmm_table_kernels.hip")).read()
+    src = "\n".join(l.split("//")[0] for l in src.split("\n"))
+    body = src[src.index("lmm_table_scan_kernel("):]
+    body = body[body.index("for (uint32_t b0"):body.index("total[0] = carry")]
+    write, first_read, last_read = body.index("s_wave[wave] ="), body.index("s_wave[w]"), body.rindex("s_wave[w]")
+    assert write < first_read
+    assert "__syncthreads()" in body[write:first_read], "no barrier between the write of s_wave and its reads"
+    assert "__syncthreads()" in body[last_read:], "no barrier between the reads of s_wave and the next round's write"
