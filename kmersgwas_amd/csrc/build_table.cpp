@@ -21,7 +21,7 @@
 #include <vector>
 
 #include "common.h"
-#include "ingest.h"
+#include "device.h"
 #include "kernels.h"
 #include "sorted_file_io.h"
 
@@ -42,7 +42,7 @@ struct Builder {
     unsigned n_threads = 1;
     int dev = 0;
 
-    uint64_t window_of(uint64_t x) const { return x == 0 ? 1 : (x - 1) / step + 1; }  // max(1, ceil(x / step))
+    uint64_t window_of(uint64_t x) const { return kgwas::window_of(x, step); }
 
     // The reference's loop over the windows of one piece on the host: A[0, n) masked all-k-mers words (windows from their
     // running maximum), every accession's slice read from pos[c] by the reference's rule with threshold thr. rows: n x stride,
@@ -62,27 +62,19 @@ struct Builder {
             std::vector<uint64_t> buf(block_words);
             for (uint64_t wd; (wd = next.fetch_add(1)) < W;) {
                 for (uint64_t c = wd * 64; c < std::min(S, wd * 64 + 64); c++) {
-                    Fd f;
-                    open_input(f, paths[c]);
                     const uint64_t bit = 1ull << (c % 64);
-                    uint64_t p = pos[c], m = 0;
-                    bool end = false;
-                    while (!end && p < words[c]) {
-                        const uint64_t cnt = std::min(block_words, words[c] - p);
-                        read_words(f.fd, buf.data(), p, cnt, paths[c]);
-                        const uint64_t e = first_above(buf.data(), cnt, thr);
-                        end = e < cnt;
+                    uint64_t m = 0;
+                    pos[c] = walk_slice(paths[c], pos[c], words[c], block_words, thr, [&] { return buf.data(); }, [&](const uint64_t* h, uint64_t e) {
                         for (uint64_t i = 0; i < e; i++) {
-                            const uint64_t x = buf[i] & KEY_MASK;
+                            const uint64_t x = h[i] & KEY_MASK;
                             m = std::max(m, x);
                             const uint64_t w = window_of(m);
                             if (w < w0 || w > w1) continue;
                             auto it = maps[w - w0].find(x);
                             if (it != maps[w - w0].end()) rows[it->second * stride + 1 + wd] |= bit;
                         }
-                        p += e;
-                    }
-                    pos[c] = p;
+                        return true;
+                    }).pos;
                 }
             }
         });
@@ -100,8 +92,7 @@ void build_run(const char* all_kmers_path, const char* const* kmer_paths, const 
     if (names) {  // (src/build_kmers_table.cpp:80-91)
         const std::string np = base + ".names";
         Fd f;
-        f.fd = ::open(np.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
-        if (f.fd < 0) throw Error(KGWAS_ERR_IO, "can't open output file " + np + ": " + std::strerror(errno));
+        open_output(f, np);
         std::string text;
         for (uint64_t i = 0; i < n_acc; i++) text += std::string(names[i]) + "\n";
         write_all(f.fd, text.data(), text.size(), np);
@@ -113,7 +104,7 @@ void build_run(const char* all_kmers_path, const char* const* kmer_paths, const 
     b.S = n_acc;
     b.W = (n_acc + 63) / 64;
     b.stride = 1 + b.W;
-    b.step = ((1ull << (2ull * kmer_len)) - 1ull) / TOTAL_ITER + 1;  // kmers_step_to_threshold (src/kmer_general.cpp:255-258)
+    b.step = kmers_step_to_threshold(TOTAL_ITER, kmer_len);
     const uint64_t last_thr = b.step * (TOTAL_ITER + 1);
     // the member initialiser opens the all-k-mers file first, the constructor's body the accessions' in order
     b.a_words = words_in_file(b.all_path);
@@ -122,11 +113,7 @@ void build_run(const char* all_kmers_path, const char* const* kmer_paths, const 
     b.pos.assign(n_acc, 0);
     for (uint64_t c = 0; c < n_acc; c++) b.words[c] = words_in_file(b.paths[c]);
     // (every guard of the reference is through: only now is the device touched)
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        throw Error(KGWAS_ERR_DEVICE, "no HIP device available: libkgwas has no CPU fallback");
-    if (device < 0 || device >= ndev) throw Error(KGWAS_ERR_ARG, "device ordinal out of range");
-    KGWAS_HIP(hipSetDevice(device));
+    use_device(device);
     b.n_threads = std::max(2u, std::min(8u, kgwas_host_cpu_quota() / 2));
     b.block_words = (uint64_t)std::max<long long>(1, std::min<long long>(opt_int("KGWAS_BUILD_BLOCK_WORDS", 1 << 16), 1 << 24));
     // rows of a piece: 256 MiB of rows on the device (pieces small enough that writing one overlaps matching the next)
@@ -135,8 +122,7 @@ void build_run(const char* all_kmers_path, const char* const* kmer_paths, const 
         if (e > 0) budget = std::min<uint64_t>((uint64_t)e, 1ull << 26);
 
     Fd out;
-    out.fd = ::open(table_path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
-    if (out.fd < 0) throw Error(KGWAS_ERR_IO, "can't open output file " + table_path + ": " + std::strerror(errno));
+    open_output(out, table_path);
     {
         char head[16] = {(char)0xAA, (char)0xBB, (char)0xCC, (char)0xDD};
         const uint64_t acc = n_acc;
@@ -160,42 +146,19 @@ void build_run(const char* all_kmers_path, const char* const* kmer_paths, const 
     h_A.alloc(cap);
     h_spl.alloc(FK_SPLITTERS);
     h_flag.alloc(1);
-    hipStream_t st = nullptr;
-    KGWAS_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    // one lane of the slice readers: its stream and two blocks each of pinned and device memory
+    Stream st;
+    st.create(hipStreamNonBlocking);
+    // one lane of the slice readers: its upload lane and a device block for each of the lane's two
     struct Lane {
-        hipStream_t st = nullptr;
-        PinBuf<uint64_t> h[2];
         DevBuf<uint64_t> d[2];
-        hipEvent_t ev[2] = {nullptr, nullptr};
-        uint64_t turn = 0;
+        UploadLane<uint64_t> up;
     };
     std::vector<Lane> lanes(b.n_threads);
-    struct Cleanup {
-        hipStream_t& st;
-        std::vector<Lane>& lanes;
-        std::future<void>& pending;
-        ~Cleanup() {
-            if (pending.valid()) pending.wait();  // (the writer reads a pinned buffer that goes away after this)
-            for (auto& l : lanes) {
-                if (l.st) (void)hipStreamSynchronize(l.st), (void)hipStreamDestroy(l.st);
-                for (auto& e : l.ev)
-                    if (e) (void)hipEventDestroy(e);
-            }
-            (void)hipStreamSynchronize(st);
-            (void)hipStreamDestroy(st);
-        }
-    };
-    std::future<void> pending;  // the rows of the last piece being written
-    Cleanup cleanup{st, lanes, pending};
     for (auto& l : lanes) {
-        KGWAS_HIP(hipStreamCreateWithFlags(&l.st, hipStreamNonBlocking));
-        for (int i = 0; i < 2; i++) {
-            l.h[i].alloc(b.block_words);
-            l.d[i].alloc(b.block_words);
-            KGWAS_HIP(hipEventCreateWithFlags(&l.ev[i], hipEventDisableTiming | hipEventBlockingSync));
-        }
+        l.up.create(b.block_words);
+        for (auto& d : l.d) d.alloc(b.block_words);
     }
+    std::future<void> pending;  // the rows of the last piece being written (after h_out: its destructor waits for the writer)
 
     std::vector<uint64_t> big_A, host_rows;  // a window above the budget; rows made on the host
     uint64_t total_rows = 0, handed = 0;
@@ -275,35 +238,23 @@ void build_run(const char* all_kmers_path, const char* const* kmer_paths, const 
             kgwas_run_on_threads((unsigned)std::min<uint64_t>(b.n_threads, std::max<uint64_t>(1, b.S)), "kgwas-build", [&] {
                 KGWAS_HIP(hipSetDevice(b.dev));
                 Lane& l = lanes[next_lane.fetch_add(1)];
-                struct Sync {  // whatever happens, nothing of this lane is in flight when the thread ends
-                    hipStream_t s;
-                    ~Sync() { (void)hipStreamSynchronize(s); }
-                } sync{l.st};
                 for (uint64_t c; (c = next.fetch_add(1)) < b.S;) {
-                    Fd f;
-                    open_input(f, b.paths[c]);
-                    uint64_t p = b.pos[c], carry = 0;
-                    bool end = false, has_prev = false;
-                    while (!end && p < b.words[c]) {
-                        const int i = (int)(l.turn++ & 1);
-                        KGWAS_HIP(hipEventSynchronize(l.ev[i]));  // (the block copied out of this buffer two turns ago)
-                        const uint64_t c2 = std::min(b.block_words, b.words[c] - p);
-                        read_words(f.fd, l.h[i].p, p, c2, b.paths[c]);
-                        const uint64_t e = first_above(l.h[i].p, c2, thr);
-                        end = e < c2;
+                    uint64_t carry = 0;
+                    bool has_prev = false;
+                    b.pos[c] = walk_slice(b.paths[c], b.pos[c], b.words[c], b.block_words, thr, [&] { return l.up.take(); }, [&](const uint64_t* h, uint64_t e) {
                         if (e) {
-                            KGWAS_HIP(hipMemcpyAsync(l.d[i].p, l.h[i].p, e * 8, hipMemcpyHostToDevice, l.st));
-                            KGWAS_HIP(launch_bt_match(d_A.p, n, d_spl.p, (uint32_t)ns, B, l.d[i].p, (uint32_t)e, carry, has_prev, d_rows.p,
-                                                      b.stride, c, d_flag.p, l.st));
-                            KGWAS_HIP(hipEventRecord(l.ev[i], l.st));
-                            carry = l.h[i].p[e - 1] & KEY_MASK;
+                            uint64_t* d = l.d[l.up.cur].p;
+                            KGWAS_HIP(hipMemcpyAsync(d, h, e * 8, hipMemcpyHostToDevice, l.up.st));
+                            KGWAS_HIP(launch_bt_match(d_A.p, n, d_spl.p, (uint32_t)ns, B, d, (uint32_t)e, carry, has_prev, d_rows.p, b.stride, c,
+                                                      d_flag.p, l.up.st));
+                            l.up.sent();
+                            carry = h[e - 1] & KEY_MASK;
                             has_prev = true;
                         }
-                        p += e;
-                    }
-                    b.pos[c] = p;
+                        return true;
+                    }).pos;
                 }
-                KGWAS_HIP(hipStreamSynchronize(l.st));
+                KGWAS_HIP(hipStreamSynchronize(l.up.st));
             });
             KGWAS_HIP(hipMemcpyAsync(h_flag.p, d_flag.p, 4, hipMemcpyDeviceToHost, st));
             KGWAS_HIP(hipStreamSynchronize(st));
@@ -333,9 +284,7 @@ void build_run(const char* all_kmers_path, const char* const* kmer_paths, const 
         total_rows += n;
     }
     if (pending.valid()) pending.get();
-    const int rc = ::close(out.fd);
-    out.fd = -1;
-    if (rc != 0) throw Error(KGWAS_ERR_IO, "write error on " + table_path + ": " + std::strerror(errno));
+    close_output(out, table_path);
     if (n_rows_out) *n_rows_out = total_rows;
 }
 

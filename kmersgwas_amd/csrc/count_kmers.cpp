@@ -25,7 +25,7 @@
 #include <vector>
 
 #include "common.h"
-#include "ingest.h"
+#include "device.h"
 #include "kernels.h"
 #include "sorted_file_io.h"
 
@@ -40,21 +40,17 @@ double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock:
 
 // ---- the resident base stream ---------------------------------------------------------------------------------------------------------
 struct Segment {
-    uint8_t* p = nullptr;
+    DevBuf<uint8_t> own;   // the segment's memory, unless it is the caller's
+    uint8_t* p = nullptr;  // own.p, or the caller's memory
     uint64_t cap = 0, used = 0;
-    bool owned = true;
 };
 
-struct Stream {
+struct BaseStream {
     std::mutex mu;
     std::vector<Segment> segs;
     uint64_t seg_bytes = 256ull << 20;  // room of a new segment (more for a single claim above it)
     uint64_t min_pass_bytes = 0;        // what one pass of the smallest size needs beside the stream
 
-    ~Stream() {
-        for (auto& s : segs)
-            if (s.owned && s.p) (void)hipFree(s.p);
-    }
     uint64_t bytes() const {
         uint64_t b = 0;
         for (auto& s : segs) b += s.used;
@@ -63,7 +59,7 @@ struct Stream {
     // room for n bytes in one piece of device memory
     uint8_t* claim(uint64_t n) {
         std::lock_guard<std::mutex> lk(mu);
-        if (segs.empty() || !segs.back().owned || segs.back().used + n > segs.back().cap) {
+        if (segs.empty() || !segs.back().own.p || segs.back().used + n > segs.back().cap) {
             const uint64_t cap = (std::max(seg_bytes, n) + 255) / 256 * 256;
             size_t free_b = 0, total_b = 0;
             KGWAS_HIP(hipMemGetInfo(&free_b, &total_b));
@@ -75,9 +71,10 @@ struct Stream {
                                                std::to_string(free_b) + " bytes of device memory free beside the bases so far");
             }
             Segment s;
-            KGWAS_HIP(hipMalloc((void**)&s.p, cap));
+            s.own.alloc(cap);
+            s.p = s.own.p;
             s.cap = cap;
-            segs.push_back(s);
+            segs.push_back(std::move(s));
         }
         Segment& s = segs.back();
         uint8_t* at = s.p + s.used;
@@ -86,35 +83,24 @@ struct Stream {
     }
 };
 
-// One parser thread's way to the device: two pinned pieces, a stream of its own.
+// One parser thread's way to the device: an upload lane of two pinned pieces.
 struct Uploader {
-    Stream& out;
+    BaseStream& out;
     uint64_t P;
     uint32_t k;
-    hipStream_t st = nullptr;
-    PinBuf<uint8_t> h[2];
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    int cur = 0;
+    UploadLane<uint8_t> lane;
+    uint8_t* piece = nullptr;  // the piece in hand
     uint64_t fill = 0;
 
-    Uploader(Stream& o, uint64_t piece, uint32_t kmer_len) : out(o), P(piece), k(kmer_len) {
-        KGWAS_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        for (int i = 0; i < 2; i++) {
-            h[i].alloc(P);
-            KGWAS_HIP(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming | hipEventBlockingSync));
-        }
-    }
-    ~Uploader() {
-        if (st) (void)hipStreamSynchronize(st), (void)hipStreamDestroy(st);  // (nothing reads the pinned pieces after this)
-        for (auto& e : ev)
-            if (e) (void)hipEventDestroy(e);
+    Uploader(BaseStream& o, uint64_t piece_size, uint32_t kmer_len) : out(o), P(piece_size), k(kmer_len) {
+        lane.create(P);
+        piece = lane.take();
     }
     // the piece in hand goes to `dst`; the other one is in hand once its last copy is through
     void send(uint8_t* dst, uint64_t n) {
-        KGWAS_HIP(hipMemcpyAsync(dst, h[cur].p, n, hipMemcpyHostToDevice, st));
-        KGWAS_HIP(hipEventRecord(ev[cur], st));
-        cur ^= 1;
-        KGWAS_HIP(hipEventSynchronize(ev[cur]));
+        KGWAS_HIP(hipMemcpyAsync(dst, piece, n, hipMemcpyHostToDevice, lane.st));
+        lane.sent();
+        piece = lane.take();
         fill = 0;
     }
     void flush() {
@@ -125,16 +111,16 @@ struct Uploader {
         const uint64_t len = n + (sep ? 1 : 0);
         if (fill + len > P) flush();
         if (len <= P) {
-            memcpy(h[cur].p + fill, p, n);
-            if (sep) h[cur].p[fill + n] = SEP;
+            memcpy(piece + fill, p, n);
+            if (sep) piece[fill + n] = SEP;
             fill += len;
             return;
         }
         uint8_t* dst = out.claim(len);
         for (uint64_t o = 0; o < len; o += P) {
             const uint64_t part = std::min(P, len - o), from_p = std::min(part, n - std::min(n, o));
-            memcpy(h[cur].p, p + o, from_p);
-            if (from_p < part) h[cur].p[from_p] = SEP;
+            memcpy(piece, p + o, from_p);
+            if (from_p < part) piece[from_p] = SEP;
             send(dst + o, part);
         }
     }
@@ -143,7 +129,7 @@ struct Uploader {
     }
     void finish() {
         flush();
-        KGWAS_HIP(hipStreamSynchronize(st));
+        KGWAS_HIP(hipStreamSynchronize(lane.st));
     }
 };
 
@@ -231,7 +217,7 @@ void convert(Chunk& c, Uploader& up) {
 
 struct Parser {
     std::vector<Source>& src;
-    Stream& out;
+    BaseStream& out;
     uint64_t piece, block;
     uint32_t k;
     int dev;
@@ -358,12 +344,11 @@ struct Parser {
 
 // ---- the passes -----------------------------------------------------------------------------------------------------------------------
 struct Counter {
-    Stream& in;
+    BaseStream& in;
     uint32_t k;
     uint64_t ci, cx;
     int out_fd;
     const std::string& out_path;
-    hipStream_t st = nullptr;
     uint64_t C = 0;
     DevBuf<uint64_t> d_a, d_b;  // a: the pass's words, then the runs' results; b: the sorted words, then the kept words
     DevBuf<uint32_t> d_heads, d_blk, d_off;
@@ -371,14 +356,11 @@ struct Counter {
     DevBuf<char> d_temp;
     PinBuf<uint64_t> h_out[2];
     PinBuf<unsigned long long> h_ctr;
+    Stream st;  // (after the buffers its work reads and writes: it goes first)
     size_t temp_bytes = 0;
     uint64_t host_counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t passes = 0, splits = 0, big_keys = 0;
     std::vector<uint64_t> sample_;  // the sampled canonical keys, sorted
-
-    ~Counter() {
-        if (st) (void)hipStreamSynchronize(st), (void)hipStreamDestroy(st);
-    }
 
     static uint64_t pass_bytes(uint64_t c, size_t temp) { return c * 20 + 2 * 4 * (uint64_t)ck_blocks(c) + temp + (1 << 20); }
 
@@ -397,7 +379,7 @@ struct Counter {
         C = c;
         temp_bytes = ck_temp_bytes(C, max_sample, k);
         if (!temp_bytes) throw Error(KGWAS_ERR_DEVICE, "kgwas_count_kmers: hipcub temporary-storage query failed");
-        KGWAS_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        st.create(hipStreamNonBlocking);
         d_a.alloc(C);
         d_b.alloc(C);
         d_heads.alloc(C);
@@ -532,26 +514,15 @@ void check_args(const char* who, uint32_t kmer_len, uint64_t ci, uint64_t cx, co
     if (ci > cx) throw Error(KGWAS_ERR_ARG, std::string(who) + ": the minimum count " + std::to_string(ci) + " is above the maximum count " + std::to_string(cx));
 }
 
-void use_device(int32_t device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        throw Error(KGWAS_ERR_DEVICE, "no HIP device available: libkgwas has no CPU fallback");
-    if (device < 0 || device >= ndev) throw Error(KGWAS_ERR_ARG, "device ordinal out of range");
-    KGWAS_HIP(hipSetDevice(device));
-}
-
 uint64_t piece_bytes() { return (uint64_t)std::max<long long>(16, std::min<long long>(opt_int("KGWAS_COUNT_PIECE_BYTES", 8 << 20), 1 << 28)); }
 
-void count_stream(Stream& in, uint32_t kmer_len, uint64_t ci, uint64_t cx, const char* out_path, uint64_t counts[8], double t0, double t_in) {
+void count_stream(BaseStream& in, uint32_t kmer_len, uint64_t ci, uint64_t cx, const char* out_path, uint64_t counts[8], double t0, double t_in) {
     const std::string out(out_path);
     Fd f;
-    f.fd = ::open(out.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
-    if (f.fd < 0) throw Error(KGWAS_ERR_IO, "can't open output file " + out + ": " + std::strerror(errno));
+    open_output(f, out);
     Counter c{in, kmer_len, ci, cx, f.fd, out};
     c.run();
-    const int rc = ::close(f.fd);
-    f.fd = -1;
-    if (rc != 0) throw Error(KGWAS_ERR_IO, "write error on " + out + ": " + std::strerror(errno));
+    close_output(f, out);
     if (counts)
         for (int i = 0; i < 8; i++) counts[i] = c.host_counts[i];
     if (opt_set("KGWAS_TRACE"))
@@ -581,7 +552,7 @@ void files_run(const char* const* paths, uint64_t n, uint32_t kmer_len, uint64_t
             all_known = false;
     }
     use_device(device);
-    Stream in;
+    BaseStream in;
     const bool hooked = opt_set("KGWAS_COUNT_PIECE_BYTES");
     const uint64_t piece = piece_bytes();
     // (a read takes no more room in the stream than its record in the file)
@@ -605,14 +576,13 @@ void bases_run(const void* bases, uint64_t n_bytes, int on_device, uint32_t kmer
     check_args("kgwas_count_kmers_bases", kmer_len, ci, cx, out_path);
     if (!bases && n_bytes) throw Error(KGWAS_ERR_ARG, "kgwas_count_kmers_bases: null argument");
     use_device(device);
-    Stream in;
+    BaseStream in;
     in.min_pass_bytes = min_pass_bytes(kmer_len);
     if (on_device) {
         Segment s;
         s.p = const_cast<uint8_t*>(static_cast<const uint8_t*>(bases));
         s.cap = s.used = n_bytes;
-        s.owned = false;
-        if (n_bytes) in.segs.push_back(s);
+        if (n_bytes) in.segs.push_back(std::move(s));
     } else if (n_bytes) {
         in.seg_bytes = n_bytes;
         Uploader up(in, std::min<uint64_t>(piece_bytes(), std::max<uint64_t>(n_bytes, 16)), kmer_len);

@@ -18,22 +18,14 @@
 #include <vector>
 
 #include "common.h"
+#include "device.h"
 #include "ingest.h"
 #include "kernels.h"
+#include "sorted_file_io.h"
 
 using namespace kgwas;
 
 namespace {
-
-void write_all(int fd, const char* d, size_t n, const std::string& path) {
-    while (n) {
-        const ssize_t w = ::write(fd, d, n);
-        if (w < 0 && errno == EINTR) continue;
-        if (w <= 0) throw Error(KGWAS_ERR_IO, "write error on " + path + ": " + std::strerror(w < 0 ? errno : EIO));
-        d += w;
-        n -= (size_t)w;
-    }
-}
 
 // Text output budget of a piece: pieces are cut so that their emitted lines fit (every row of a piece may be emitted).
 constexpr uint64_t TEXT_BUDGET = 256ull << 20;
@@ -41,11 +33,7 @@ constexpr uint64_t TEXT_BUDGET = 256ull << 20;
 void filter_run(kgwas_table* t, const uint64_t* codes, uint64_t n, int32_t device, const char* out_path, uint64_t* file_rows,
                 uint64_t* rows_out, uint64_t* n_found) {
     if (!t || (!codes && n)) throw Error(KGWAS_ERR_ARG, "kgwas_filter_kmers: null argument");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        throw Error(KGWAS_ERR_DEVICE, "no HIP device available: libkgwas has no CPU fallback");
-    if (device < 0 || device >= ndev) throw Error(KGWAS_ERR_ARG, "device ordinal out of range");
-    KGWAS_HIP(hipSetDevice(device));
+    use_device(device);
     uint64_t S_f = 0, n_rows = 0, W_f = 0;
     uint32_t klen = 0;
     if (kgwas_table_info(t, &S_f, &n_rows, &W_f, &klen) != KGWAS_OK) throw Error(KGWAS_ERR_ARG, kgwas_last_error());
@@ -56,17 +44,10 @@ void filter_run(kgwas_table* t, const uint64_t* codes, uint64_t n, int32_t devic
     std::vector<uint64_t> L(codes, codes + n);
     std::sort(L.begin(), L.end());
 
-    int fd = -1;
-    struct FdClose {
-        int& fd;
-        ~FdClose() {
-            if (fd >= 0) ::close(fd);
-        }
-    } fdc{fd};
+    Fd f;
     const std::string path = out_path ? out_path : "";
     if (out_path) {
-        fd = ::open(out_path, O_WRONLY | O_CREAT | O_TRUNC, 0666);
-        if (fd < 0) throw Error(KGWAS_ERR_IO, "can't open output file " + path + ": " + std::strerror(errno));
+        open_output(f, path);
         std::string head = "kmer";  // src/filter_kmers.cpp:144-147
         for (uint64_t i = 0; i < S_f; i++) {
             const char* nm = nullptr;
@@ -75,7 +56,7 @@ void filter_run(kgwas_table* t, const uint64_t* codes, uint64_t n, int32_t devic
             head += nm;
         }
         head += '\n';
-        write_all(fd, head.data(), head.size(), path);
+        write_all(f.fd, head.data(), head.size(), path);
     }
     uint64_t found = 0;
     if (n > 0 && n_rows > 0) {
@@ -96,15 +77,8 @@ void filter_run(kgwas_table* t, const uint64_t* codes, uint64_t n, int32_t devic
         PinBuf<char> h_text[2];
         h_small.alloc(5);
         std::vector<uint32_t> h_sel;
-        hipStream_t st = nullptr;
-        KGWAS_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        struct StreamGuard {
-            hipStream_t s;
-            ~StreamGuard() {
-                (void)hipStreamSynchronize(s);
-                (void)hipStreamDestroy(s);
-            }
-        } sg{st};
+        Stream st;
+        st.create(hipStreamNonBlocking);
 
         uint64_t max_piece = ~0ull;  // (the rows-only call: Ingest's own piece size)
         if (out_path) {
@@ -116,7 +90,7 @@ void filter_run(kgwas_table* t, const uint64_t* codes, uint64_t n, int32_t devic
         // merge-join state: parallel rule (carry of the last piece's last run) until the first descent, then the host's p
         bool has_prev = false, host_mode = false, done = false;
         uint64_t carry_key = 0, carry_run = 0, p = 0, handed = 0;
-        std::future<void> pending;  // the text of the last piece being written
+        std::future<void> pending;  // the text of the last piece being written (after h_text: its destructor waits for the writer)
 
         Ingest ingest;
         ingest.file_feed_ = true;
@@ -210,7 +184,7 @@ void filter_run(kgwas_table* t, const uint64_t* codes, uint64_t n, int32_t devic
                     KGWAS_HIP(hipMemcpyAsync(h, d_text.p, bytes, hipMemcpyDeviceToHost, st));
                     KGWAS_HIP(hipStreamSynchronize(st));
                     if (pending.valid()) pending.get();  // (the piece before this one: its buffer is the other one)
-                    pending = std::async(std::launch::async, [&fd, &path, h, bytes] { write_all(fd, h, bytes, path); });
+                    pending = std::async(std::launch::async, [&f, &path, h, bytes] { write_all(f.fd, h, bytes, path); });
                     handed++;
                 } else {
                     if (rows_out) {
@@ -226,11 +200,7 @@ void filter_run(kgwas_table* t, const uint64_t* codes, uint64_t n, int32_t devic
             });
         if (pending.valid()) pending.get();
     }
-    if (fd >= 0) {
-        const int rc = ::close(fd);
-        fd = -1;
-        if (rc != 0) throw Error(KGWAS_ERR_IO, "write error on " + path + ": " + std::strerror(errno));
-    }
+    if (f.fd >= 0) close_output(f, path);
     if (n_found) *n_found = found;
 }
 

@@ -12,8 +12,6 @@
 // with most of them idle behind its last sub-piece). The consumer sees the rows in order, so results do not depend
 // on any of these sizes.
 #pragma once
-#include <sys/mman.h>
-
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
@@ -28,115 +26,9 @@
 #include <vector>
 
 #include "common.h"
+#include "device.h"
 
 namespace kgwas {
-
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n) {
-        o.p = nullptr;
-        o.n = 0;
-    }
-    void alloc(size_t count) {
-        release();
-        if (count) KGWAS_HIP(hipMalloc((void**)&p, count * sizeof(T)));
-        n = count;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-    ~DevBuf() { release(); }
-};
-// Pinned, device-mapped host memory. hipHostMalloc costs 0.16 s per GiB (it faults and zeroes 4 KiB pages one by one; a
-// fresh `associate_kmers` spent 0.17 of its 0.52 s there): large buffers are mapped with MADV_HUGEPAGE, touched by a few
-// threads and registered instead - 5 ms per 512 MiB where transparent huge pages are available (16x), ~45 ms where they
-// are not - and fall back to hipHostMalloc if any step fails (KGWAS_PIN_PLAIN=1 forces that).
-struct PinRegion {
-    void* p = nullptr;       // what the caller uses
-    void* map = nullptr;     // the mapping it lies in (registered memory), nullptr: hipHostMalloc
-    size_t map_bytes = 0;
-    static constexpr size_t HUGE = 2u << 20;
-    void alloc(size_t bytes) {
-        release();
-        if (!bytes) return;
-        static const bool plain = opt_set("KGWAS_PIN_PLAIN");
-        if (!plain && bytes >= (8u << 20)) {
-            const size_t len = (bytes + HUGE - 1) / HUGE * HUGE;
-            void* m = mmap(nullptr, len + HUGE, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-            if (m != MAP_FAILED) {
-                char* al = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(m) + HUGE - 1) & ~(uintptr_t)(HUGE - 1));
-                (void)madvise(al, len, MADV_HUGEPAGE);
-                {
-                    // touched in segments of 32 MiB by up to 8 threads (this one among them; fewer if no more are to be had)
-                    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-                    const size_t seg = 32u << 20, n_seg = (len + seg - 1) / seg;
-                    const unsigned nt = (unsigned)std::min<size_t>(std::min<size_t>(8, hw), n_seg);
-                    std::atomic<size_t> next(0);
-                    kgwas_run_on_threads(nt, "kgwas-touch", [&] {
-                        for (size_t i; (i = next.fetch_add(1, std::memory_order_relaxed)) < n_seg;)
-                            for (size_t o = i * seg, b = std::min(len, (i + 1) * seg); o < b; o += 4096) al[o] = 0;
-                    });
-                }
-                if (hipHostRegister(al, len, hipHostRegisterMapped) == hipSuccess) {
-                    p = al;
-                    map = m;
-                    map_bytes = len + HUGE;
-                    return;
-                }
-                (void)hipGetLastError();  // (not sticky: the plain allocation below is the answer)
-                munmap(m, len + HUGE);
-            }
-        }
-        KGWAS_HIP(hipHostMalloc(&p, bytes, hipHostMallocMapped));
-    }
-    void release() {
-        if (map) {
-            (void)hipHostUnregister(p);
-            munmap(map, map_bytes);
-        } else if (p)
-            (void)hipHostFree(p);
-        p = map = nullptr;
-        map_bytes = 0;
-    }
-};
-template <class T>
-struct PinBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    PinRegion r;
-    PinBuf() = default;
-    PinBuf(const PinBuf&) = delete;
-    PinBuf& operator=(const PinBuf&) = delete;
-    PinBuf(PinBuf&& o) noexcept : p(o.p), n(o.n), r(o.r) {
-        o.p = nullptr;
-        o.n = 0;
-        o.r = PinRegion();
-    }
-    void alloc(size_t count) {
-        release();
-        r.alloc(count * sizeof(T));
-        p = static_cast<T*>(r.p);
-        n = count;
-    }
-    T* dev() const {
-        T* d = nullptr;
-        if (p) KGWAS_HIP(hipHostGetDevicePointer((void**)&d, p, 0));
-        return d;
-    }
-    void release() {
-        r.release();
-        p = nullptr;
-        n = 0;
-    }
-    ~PinBuf() { release(); }
-};
 
 class Ingest {
 public:
@@ -146,8 +38,6 @@ public:
     // consume(d_rows, row_off, cnt): work on a device piece; `stream` already waits for its copy. Must return with
     // the work on the piece complete (the device buffer is reused device_pieces_ pieces later).
     using Consume = std::function<void(const uint64_t*, uint64_t, uint64_t)>;
-
-    ~Ingest() { drop(); }
 
     // stride = 64-bit words per row; max_piece_rows bounds a piece (the consumer's own chunk limit).
     void run(uint64_t stride, uint64_t n_rows, uint64_t max_piece_rows, hipStream_t stream, const Fill& fill,
@@ -164,16 +54,16 @@ public:
                 if (atoi(e) >= 2 && atoi(e) <= 64) device_pieces_ = (unsigned)atoi(e);
             try {
                 h_.resize(pinned_pieces_);
-                ev_h_.assign(pinned_pieces_, nullptr);
+                ev_h_.resize(pinned_pieces_);
                 for (auto& h : h_) h.alloc(pr * stride);
                 // (blocking: a producer that has to wait for a copy sleeps; the replay workers share its CPU)
-                for (auto& e : ev_h_) KGWAS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventBlockingSync));
+                for (auto& e : ev_h_) e.create(hipEventDisableTiming | hipEventBlockingSync);
                 // (the device pieces themselves are allocated below, as many as the feed at hand has pieces: a session that is
                 // fed a few small host buffers and then device-resident tables does not hold ten 128 MiB pieces of HBM)
                 d_.resize(device_pieces_);
-                ev_.assign(device_pieces_, nullptr);
-                KGWAS_HIP(hipStreamCreateWithFlags(&copy_stream_, hipStreamNonBlocking));
-                for (auto& e : ev_) KGWAS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+                ev_.resize(device_pieces_);
+                copy_stream_.create(hipStreamNonBlocking);
+                for (auto& e : ev_) e.create(hipEventDisableTiming);
             } catch (...) {
                 drop();  // (a later run starts over instead of finding half of the buffers)
                 throw;
@@ -343,24 +233,19 @@ public:
 
 private:
     void drop() {
-        for (auto& e : ev_)
-            if (e) (void)hipEventDestroy(e);
-        for (auto& e : ev_h_)
-            if (e) (void)hipEventDestroy(e);
+        copy_stream_.release();
         ev_.clear();
         ev_h_.clear();
-        if (copy_stream_) (void)hipStreamDestroy(copy_stream_);
-        copy_stream_ = nullptr;
         h_.clear();
         d_.clear();
         device_ready_ = 0;
         piece_rows_ = 0;
     }
     std::vector<PinBuf<uint64_t>> h_;
-    std::vector<hipEvent_t> ev_h_;  // per pinned piece: its copy to the device has completed
+    std::vector<Event> ev_h_;  // per pinned piece: its copy to the device has completed
     std::vector<DevBuf<uint64_t>> d_;
-    hipStream_t copy_stream_ = nullptr;
-    std::vector<hipEvent_t> ev_;  // per device piece: its copy has completed
+    Stream copy_stream_;     // (after the pieces its copies read and write: it goes first)
+    std::vector<Event> ev_;  // per device piece: its copy has completed
     uint64_t piece_rows_ = 0;
 
 public:

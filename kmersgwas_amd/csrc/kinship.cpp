@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "common.h"
+#include "device.h"
 #include "ingest.h"
 #include "kernels.h"
 #include "synth.h"
@@ -21,34 +22,19 @@ struct kgwas_kinship {
     uint64_t S_f = 0, W_f = 0, min_count = 0;
     uint32_t S_pad = 0;
     uint64_t chunk_rows = 0, n_rw_cap = 0;
-    hipStream_t stream = nullptr, stream_tr = nullptr;  // Gram accumulation / bit transposes
-    hipEvent_t ev_user = nullptr, ev0 = nullptr, ev1 = nullptr;
-    hipEvent_t ev_tr[2] = {nullptr, nullptr}, ev_gram[2] = {nullptr, nullptr};
     bool gram_pending[2] = {false, false};
-    uint32_t* d_T2[2] = {nullptr, nullptr};  // sample-major bit planes of two chunks
-    unsigned long long* d_H = nullptr;
-    void* d_part = nullptr;  // partial tiles of a chunk's row slices (kin_gram_scratch_bytes)
+    DevBuf<uint32_t> d_T2[2];  // sample-major bit planes of two chunks
+    DevBuf<unsigned long long> d_H;
+    DevBuf<char> d_part;  // partial tiles of a chunk's row slices (kin_gram_scratch_bytes)
     size_t part_bytes = 0;
-    unsigned long long* d_n = nullptr;
+    DevBuf<unsigned long long> d_n;
     Ingest ingest;  // host / file feeds: pinned and device piece rings, a copy stream (ingest.h)
+    Stream stream, stream_tr;  // Gram accumulation / bit transposes (behind the buffers: they go first)
+    Event ev_user, ev0, ev1;
+    Event ev_tr[2], ev_gram[2];
     double kernel_ms = 0;
     uint64_t launches = 0, rows_fed = 0;
-    ~kgwas_kinship() {
-        (void)hipSetDevice(device);
-        for (int b = 0; b < 2; b++) {
-            if (d_T2[b]) (void)hipFree(d_T2[b]);
-            if (ev_tr[b]) (void)hipEventDestroy(ev_tr[b]);
-            if (ev_gram[b]) (void)hipEventDestroy(ev_gram[b]);
-        }
-        if (stream_tr) (void)hipStreamDestroy(stream_tr);
-        if (d_part) (void)hipFree(d_part);
-        if (d_H) (void)hipFree(d_H);
-        if (d_n) (void)hipFree(d_n);
-        if (ev_user) (void)hipEventDestroy(ev_user);
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
+    ~kgwas_kinship() { (void)hipSetDevice(device); }  // (before any member is released)
 };
 
 // Chunks of 2^20 rows: the transpose of chunk i + 1 (memory- and LDS-bound) runs on its own stream beside the Gram
@@ -68,11 +54,11 @@ static void kin_feed(kgwas_kinship* k, const uint64_t* d_rows, uint64_t n_rows) 
         static const bool no_tr = exp_set("KGWAS_KIN_NO_TR");  // experiments: the Gram kernel alone (wrong results)
         if (!no_tr || i < 2)
         KGWAS_HIP(launch_kin_transpose(d_rows + pos * stride, stride, c, (uint32_t)k->S_f, k->S_pad,
-                                       (uint32_t)std::min<uint64_t>(k->min_count, 0xFFFFFFFFull), k->d_T2[b], n_rw, k->d_n,
+                                       (uint32_t)std::min<uint64_t>(k->min_count, 0xFFFFFFFFull), k->d_T2[b].p, n_rw, k->d_n.p,
                                        k->stream_tr));
         KGWAS_HIP(hipEventRecord(k->ev_tr[b], k->stream_tr));
         KGWAS_HIP(hipStreamWaitEvent(k->stream, k->ev_tr[b], 0));
-        KGWAS_HIP(launch_kin_gram(k->d_T2[b], n_rw, k->S_pad, k->d_H, k->d_part, k->part_bytes, k->stream));
+        KGWAS_HIP(launch_kin_gram(k->d_T2[b].p, n_rw, k->S_pad, k->d_H.p, k->d_part.p, k->part_bytes, k->stream));
         KGWAS_HIP(hipEventRecord(k->ev_gram[b], k->stream));
         k->gram_pending[b] = true;
         k->launches++;
@@ -92,12 +78,7 @@ extern "C" {
 int kgwas_kinship_create(int32_t device, uint64_t n_acc_file, uint64_t min_count, kgwas_kinship** out) {
     return guarded([&] {
         if (!out || n_acc_file == 0 || n_acc_file >= (1ull << 31)) throw Error(KGWAS_ERR_ARG, "kgwas_kinship_create: bad argument");
-        int n = 0;
-        hipError_t e = hipGetDeviceCount(&n);
-        if (e != hipSuccess || n <= 0)
-            throw Error(KGWAS_ERR_DEVICE, "no HIP device available: libkgwas has no CPU fallback");
-        if (device < 0 || device >= n) throw Error(KGWAS_ERR_ARG, "device ordinal out of range");
-        KGWAS_HIP(hipSetDevice(device));
+        use_device(device);
         std::unique_ptr<kgwas_kinship> k(new kgwas_kinship);
         k->device = device;
         k->S_f = n_acc_file;
@@ -109,22 +90,22 @@ int kgwas_kinship_create(int32_t device, uint64_t n_acc_file, uint64_t min_count
                                            " accessions exceed what the bit-transpose kernel can stage in LDS (at most 10112)");
         k->chunk_rows = 1ull << 20;  // the reference's own batch size (src/emma_kinship_kmers.cpp:89)
         k->n_rw_cap = (k->chunk_rows + 511) / 512 * 16;
-        KGWAS_HIP(hipStreamCreateWithFlags(&k->stream, hipStreamNonBlocking));
-        KGWAS_HIP(hipEventCreate(&k->ev_user));
-        KGWAS_HIP(hipEventCreate(&k->ev0));
-        KGWAS_HIP(hipEventCreate(&k->ev1));
-        KGWAS_HIP(hipStreamCreateWithFlags(&k->stream_tr, hipStreamNonBlocking));
+        k->stream.create(hipStreamNonBlocking);
+        k->ev_user.create();
+        k->ev0.create();
+        k->ev1.create();
+        k->stream_tr.create(hipStreamNonBlocking);
         for (int b = 0; b < 2; b++) {
-            KGWAS_HIP(hipMalloc((void**)&k->d_T2[b], (size_t)k->S_pad * k->n_rw_cap * 4));
-            KGWAS_HIP(hipEventCreateWithFlags(&k->ev_tr[b], hipEventDisableTiming));
-            KGWAS_HIP(hipEventCreateWithFlags(&k->ev_gram[b], hipEventDisableTiming));
+            k->d_T2[b].alloc((size_t)k->S_pad * k->n_rw_cap);
+            k->ev_tr[b].create(hipEventDisableTiming);
+            k->ev_gram[b].create(hipEventDisableTiming);
         }
-        KGWAS_HIP(hipMalloc((void**)&k->d_H, (size_t)k->S_pad * k->S_pad * 8));
+        k->d_H.alloc((size_t)k->S_pad * k->S_pad);
         k->part_bytes = kin_gram_scratch_bytes(k->S_pad);
-        KGWAS_HIP(hipMalloc(&k->d_part, k->part_bytes));
-        KGWAS_HIP(hipMalloc((void**)&k->d_n, TESTED_SHARDS * 8));
-        KGWAS_HIP(hipMemset(k->d_H, 0, (size_t)k->S_pad * k->S_pad * 8));
-        KGWAS_HIP(hipMemset(k->d_n, 0, TESTED_SHARDS * 8));
+        k->d_part.alloc(k->part_bytes);
+        k->d_n.alloc(TESTED_SHARDS);
+        KGWAS_HIP(hipMemset(k->d_H.p, 0, (size_t)k->S_pad * k->S_pad * 8));
+        KGWAS_HIP(hipMemset(k->d_n.p, 0, TESTED_SHARDS * 8));
         // (hipMemset runs on the null stream, which the session's non-blocking streams do not wait for: without this the
         // zeroing could land after the first feed's kernels and wipe its counts)
         KGWAS_HIP(hipStreamSynchronize(nullptr));
@@ -183,11 +164,11 @@ int kgwas_kinship_partials(kgwas_kinship* k, uint64_t* hamming, uint64_t* n_used
         // ~60 ms - a fifth of an `emma_kinship_kmers` run on 40 M rows -, and the copy into pageable memory is staged anyway)
         PinBuf<unsigned long long> Hp;
         Hp.alloc((size_t)k->S_pad * k->S_pad);
-        KGWAS_HIP(launch_copy_to_host(k->d_H, Hp.dev(), Hp.n * 8, k->stream));
+        KGWAS_HIP(launch_copy_to_host(k->d_H.p, Hp.dev(), Hp.n * 8, k->stream));
         KGWAS_HIP(hipStreamSynchronize(k->stream));
         const unsigned long long* H = Hp.p;
         unsigned long long n = 0, shards[TESTED_SHARDS];
-        KGWAS_HIP(hipMemcpy(shards, k->d_n, sizeof(shards), hipMemcpyDeviceToHost));
+        KGWAS_HIP(hipMemcpy(shards, k->d_n.p, sizeof(shards), hipMemcpyDeviceToHost));
         for (unsigned long long v : shards) n += v;
         // d_H holds the Gram counts c_ij = sum_rows g_i g_j (tiles on or above the diagonal of the 128-sample tiling);
         // Hamming(i, j) = c_ii + c_jj - 2 c_ij
@@ -223,8 +204,7 @@ int kgwas_synth_rows_device(void* d_rows, uint64_t first_row, uint64_t n_rows, u
                             void* hip_stream) {
     return guarded([&] {
         if ((!d_rows && n_rows) || n_acc == 0) throw Error(KGWAS_ERR_ARG, "kgwas_synth_rows_device: bad argument");
-        int n = 0;
-        if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) throw Error(KGWAS_ERR_DEVICE, "no HIP device available");
+        (void)device_count("");
         KGWAS_HIP(launch_synth(reinterpret_cast<uint64_t*>(d_rows), first_row, n_rows, n_acc, seed, (hipStream_t)hip_stream));
     });
 }

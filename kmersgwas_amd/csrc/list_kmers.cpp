@@ -23,7 +23,7 @@
 #include <vector>
 
 #include "common.h"
-#include "ingest.h"
+#include "device.h"
 #include "kernels.h"
 #include "sorted_file_io.h"
 
@@ -72,8 +72,12 @@ struct Lister {
     unsigned n_threads = 1;
     int dev = 0;
 
-    uint64_t window_of(uint64_t x) const { return x == 0 ? 1 : (x - 1) / step + 1; }  // max(1, ceil(x / step))
+    uint64_t window_of(uint64_t x) const { return kgwas::window_of(x, step); }
     bool file_has(uint64_t c, uint64_t thr) const { return pos[c] < words[c] && head[c] <= thr; }
+    void ended(uint64_t c, const SliceEnd& r) {  // file c's slice of a piece has been walked
+        pos[c] = r.pos;
+        if (r.above) head[c] = r.head;
+    }
 
     [[noreturn]] void flag_zero(uint64_t c) const {
         throw Error(KGWAS_ERR_FORMAT, "a k-mer word without strand flags (flag 0) in: " + paths[c]);
@@ -113,17 +117,10 @@ struct Lister {
         uint64_t zero_window = ~0ull, zero_file = 0;  // the flag-0 word the reference meets first: lowest window, then first file
         for (uint64_t c = 0; c < N; c++) {
             if (!file_has(c, thr)) continue;
-            Fd f;
-            open_input(f, paths[c]);
-            uint64_t p = pos[c], m = 0;
-            bool end = false;
-            while (!end && p < words[c]) {
-                const uint64_t cnt = std::min(block_words, words[c] - p);
-                read_words(f.fd, buf.data(), p, cnt, paths[c]);
-                const uint64_t e = first_above(buf.data(), cnt, thr);
-                end = e < cnt;
+            uint64_t m = 0;
+            ended(c, walk_slice(paths[c], pos[c], words[c], block_words, thr, [&] { return buf.data(); }, [&](const uint64_t* h, uint64_t e) {
                 for (uint64_t i = 0; i < e; i++) {
-                    const uint64_t x = buf[i] & KEY_MASK, flag = buf[i] >> 62;
+                    const uint64_t x = h[i] & KEY_MASK, flag = h[i] >> 62;
                     m = std::max(m, x);
                     const uint64_t w = std::min(std::max(window_of(m), w0), w1);
                     if (flag == 0) {
@@ -135,10 +132,8 @@ struct Lister {
                     n.canon += flag == 1;
                     n.non += flag == 2;
                 }
-                if (end) head[c] = buf[e] & KEY_MASK;
-                p += e;
-            }
-            pos[c] = p;
+                return true;
+            }));
         }
         std::vector<uint64_t> keys;
         for (auto& map : maps) {
@@ -154,12 +149,9 @@ struct Lister {
 
 void write_text_file(const std::string& path, const std::string& text) {
     Fd f;
-    f.fd = ::open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
-    if (f.fd < 0) throw Error(KGWAS_ERR_IO, "can't open output file " + path + ": " + std::strerror(errno));
+    open_output(f, path);
     write_all(f.fd, text.data(), text.size(), path);
-    const int rc = ::close(f.fd);
-    f.fd = -1;
-    if (rc != 0) throw Error(KGWAS_ERR_IO, "write error on " + path + ": " + std::strerror(errno));
+    close_output(f, path);
 }
 
 void list_run(const char* const* kmer_paths, uint64_t n_files, uint32_t kmer_len, uint64_t mac, double min_strand_percent, int32_t device,
@@ -178,7 +170,7 @@ void list_run(const char* const* kmer_paths, uint64_t n_files, uint32_t kmer_len
     b.NN = b.N1 * b.N1;
     b.k = kmer_len;
     b.mac = mac;
-    b.step = ((1ull << (2ull * kmer_len)) - 1ull) / STEPS + 1;
+    b.step = kmers_step_to_threshold(STEPS, kmer_len);
     b.paths.assign(kmer_paths, kmer_paths + n_files);
     b.words.resize(n_files);
     b.pos.assign(n_files, 0);
@@ -188,11 +180,7 @@ void list_run(const char* const* kmer_paths, uint64_t n_files, uint32_t kmer_len
         b.head[c] &= KEY_MASK;
     }
     // (every guard of the reference is through: only now is the device touched)
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        throw Error(KGWAS_ERR_DEVICE, "no HIP device available: libkgwas has no CPU fallback");
-    if (device < 0 || device >= ndev) throw Error(KGWAS_ERR_ARG, "device ordinal out of range");
-    KGWAS_HIP(hipSetDevice(device));
+    use_device(device);
 
     // need[all]: ceil(p * all) is an integer, an infinity or NaN, so (double)m >= it is m >= it in integers
     b.need.resize(b.N1);
@@ -213,10 +201,8 @@ void list_run(const char* const* kmer_paths, uint64_t n_files, uint32_t kmer_len
 
     const std::string out(out_path), np_path = out + ".no_pass_kmers";
     Fd f_out, f_np;
-    f_out.fd = ::open(out.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
-    if (f_out.fd < 0) throw Error(KGWAS_ERR_IO, "can't open output file " + out + ": " + std::strerror(errno));
-    f_np.fd = ::open(np_path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
-    if (f_np.fd < 0) throw Error(KGWAS_ERR_IO, "can't open output file " + np_path + ": " + std::strerror(errno));
+    open_output(f_out, out);
+    open_output(f_np, np_path);
     {
         const std::string h = "kmer\tcount_all\tcanonical\tnon-canonical\tboth\n";
         write_all(f_np.fd, h.data(), h.size(), np_path);
@@ -232,7 +218,6 @@ void list_run(const char* const* kmer_paths, uint64_t n_files, uint32_t kmer_len
     const size_t temp_bytes = ll_temp_bytes(max_m, max_nb);
     if (!temp_bytes) throw Error(KGWAS_ERR_DEVICE, "kgwas_list_kmers: hipcub temporary-storage query failed");
     const uint64_t n_dev_stats = n_stats + TESTED_SHARDS;
-    hipStream_t st = nullptr;
     if (b.N) {
         d_words.alloc(cap);
         for (auto& d : d_stage) d.alloc(cap);
@@ -253,40 +238,16 @@ void list_run(const char* const* kmer_paths, uint64_t n_files, uint32_t kmer_len
         KGWAS_HIP(hipMemset(d_piece_stats.p, 0, n_dev_stats * 8));
         KGWAS_HIP(hipMemset(d_total_stats.p, 0, n_dev_stats * 8));
     }
-    KGWAS_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    // one lane of the slice readers: its stream and two pinned blocks
+    Stream st;
+    st.create(hipStreamNonBlocking);
+    // one lane of the slice readers: its upload lane and what it put into the piece
     struct Lane {
-        hipStream_t st = nullptr;
-        PinBuf<uint64_t> h[2];
-        hipEvent_t ev[2] = {nullptr, nullptr};
-        uint64_t turn = 0;
+        UploadLane<uint64_t> up;
         std::vector<uint32_t> segs;  // (offset, length) of the blocks it put into the piece
     };
     std::vector<Lane> lanes(b.N ? b.n_threads : 0);
-    struct Cleanup {
-        hipStream_t& st;
-        std::vector<Lane>& lanes;
-        std::future<void>& pending;
-        ~Cleanup() {
-            if (pending.valid()) pending.wait();  // (the writer reads a pinned buffer that goes away after this)
-            for (auto& l : lanes) {
-                if (l.st) (void)hipStreamSynchronize(l.st), (void)hipStreamDestroy(l.st);
-                for (auto& e : l.ev)
-                    if (e) (void)hipEventDestroy(e);
-            }
-            (void)hipStreamSynchronize(st);
-            (void)hipStreamDestroy(st);
-        }
-    };
-    std::future<void> pending;  // the outputs of the last device piece being written
-    Cleanup cleanup{st, lanes, pending};
-    for (auto& l : lanes) {
-        KGWAS_HIP(hipStreamCreateWithFlags(&l.st, hipStreamNonBlocking));
-        for (int i = 0; i < 2; i++) {
-            l.h[i].alloc(b.block_words);
-            KGWAS_HIP(hipEventCreateWithFlags(&l.ev[i], hipEventDisableTiming | hipEventBlockingSync));
-        }
-    }
+    for (auto& l : lanes) l.up.create(b.block_words);
+    std::future<void> pending;  // the outputs of the last device piece being written (after h_out: its destructor waits for the writer)
 
     // windows per piece, from the file sizes: three quarters of the budget if every window held the same number of words
     uint64_t all_words = 0;
@@ -320,43 +281,31 @@ void list_run(const char* const* kmer_paths, uint64_t n_files, uint32_t kmer_len
         kgwas_run_on_threads((unsigned)std::min<uint64_t>(b.n_threads, b.N), "kgwas-list", [&] {
             KGWAS_HIP(hipSetDevice(b.dev));
             Lane& l = lanes[next_lane.fetch_add(1)];
-            struct Sync {  // whatever happens, nothing of this lane is in flight when the thread ends
-                hipStream_t s;
-                ~Sync() { (void)hipStreamSynchronize(s); }
-            } sync{l.st};
             for (uint64_t c; !no_fit.load() && (c = next.fetch_add(1)) < b.N;) {
                 if (!b.file_has(c, thr)) continue;
-                Fd f;
-                open_input(f, b.paths[c]);
-                uint64_t p = b.pos[c], carry = 0;
-                bool end = false, has_prev = false;
-                while (!end && p < b.words[c] && !no_fit.load()) {
-                    const int i = (int)(l.turn++ & 1);
-                    KGWAS_HIP(hipEventSynchronize(l.ev[i]));  // (the block copied out of this buffer two turns ago)
-                    const uint64_t c2 = std::min(b.block_words, b.words[c] - p);
-                    read_words(f.fd, l.h[i].p, p, c2, b.paths[c]);
-                    const uint64_t e = first_above(l.h[i].p, c2, thr);
-                    end = e < c2;
+                uint64_t carry = 0;
+                bool has_prev = false;
+                // (a piece that does not fit stops every walk: its files are rewound below, whatever the walks leave behind)
+                b.ended(c, walk_slice(b.paths[c], b.pos[c], b.words[c], b.block_words, thr, [&] { return l.up.take(); }, [&](const uint64_t* h, uint64_t e) {
+                    if (no_fit.load()) return false;
                     if (e) {
                         const uint64_t off = total.fetch_add(e);
                         if (off + e > cap) {
                             no_fit.store(true);
-                            break;
+                            return false;
                         }
-                        KGWAS_HIP(hipMemcpyAsync(d_words.p + off, l.h[i].p, e * 8, hipMemcpyHostToDevice, l.st));
-                        KGWAS_HIP(launch_ll_check(d_words.p + off, (uint32_t)e, carry, has_prev, (uint32_t)c, d_flags.p, l.st));
-                        KGWAS_HIP(hipEventRecord(l.ev[i], l.st));
+                        KGWAS_HIP(hipMemcpyAsync(d_words.p + off, h, e * 8, hipMemcpyHostToDevice, l.up.st));
+                        KGWAS_HIP(launch_ll_check(d_words.p + off, (uint32_t)e, carry, has_prev, (uint32_t)c, d_flags.p, l.up.st));
+                        l.up.sent();
                         l.segs.push_back((uint32_t)off);
                         l.segs.push_back((uint32_t)e);
-                        carry = l.h[i].p[e - 1] & KEY_MASK;
+                        carry = h[e - 1] & KEY_MASK;
                         has_prev = true;
                     }
-                    if (end) b.head[c] = l.h[i].p[e] & KEY_MASK;
-                    p += e;
-                }
-                b.pos[c] = p;
+                    return true;
+                }));
             }
-            KGWAS_HIP(hipStreamSynchronize(l.st));
+            KGWAS_HIP(hipStreamSynchronize(l.up.st));
         });
         const auto rewind = [&] { b.pos = start_pos, b.head = start_head; };
         if (no_fit.load()) {
@@ -475,11 +424,8 @@ void list_run(const char* const* kmer_paths, uint64_t n_files, uint32_t kmer_len
     if (opt_set("KGWAS_TRACE"))
         fprintf(stderr, "[kgwas] list: device_pieces=%llu host_pieces=%llu reread=%llu device_words=%llu\n", (unsigned long long)handed,
                 (unsigned long long)host_pieces, (unsigned long long)reread, (unsigned long long)words_used);
-    for (auto* f : {&f_out, &f_np}) {
-        const int rc = ::close(f->fd);
-        f->fd = -1;
-        if (rc != 0) throw Error(KGWAS_ERR_IO, std::string("write error on ") + (f == &f_out ? out : np_path) + ": " + std::strerror(errno));
-    }
+    close_output(f_out, out);
+    close_output(f_np, np_path);
     if (b.N) {  // the device's statistics to the host's
         std::vector<unsigned long long> dev_stats(n_dev_stats);
         KGWAS_HIP(hipMemcpy(dev_stats.data(), d_total_stats.p, n_dev_stats * 8, hipMemcpyDeviceToHost));

@@ -26,8 +26,8 @@ using namespace kgwas::lmm;
 
 void LmmStageTimer::stamp(hipStream_t st) {
     if (used == events.size()) {
-        events.push_back(nullptr);
-        KGWAS_HIP(hipEventCreate(&events.back()));
+        events.emplace_back();
+        events.back().create();
     }
     KGWAS_HIP(hipEventRecord(events[used++], st));
 }
@@ -40,11 +40,6 @@ void LmmStageTimer::collect(kgwas_lmm_stats& stats) {
     }
     closed.clear();
     used = 0;
-}
-
-LmmStageTimer::~LmmStageTimer() {
-    for (hipEvent_t e : events)
-        if (e) (void)hipEventDestroy(e);
 }
 
 void kgwas_lmm::ensure_multi_chunk() {
@@ -80,13 +75,6 @@ void kgwas_lmm::ensure_select() {
     have_select = true;
 }
 
-kgwas_lmm::~kgwas_lmm() {
-    if (!on_device) return;
-    (void)hipSetDevice(device);
-    if (stream) (void)hipStreamSynchronize(stream);
-    if (stream) (void)hipStreamDestroy(stream);
-}
-
 namespace {
 
 template <class T>
@@ -96,10 +84,7 @@ void upload(DevBuf<T>& b, const std::vector<T>& v) {
 }
 
 void device_init(kgwas_lmm* h) {
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) throw Error(KGWAS_ERR_DEVICE, "no HIP device available: libkgwas has no CPU fallback");
-    if (h->device < 0 || h->device >= nd) throw Error(KGWAS_ERR_ARG, "device ordinal out of range");
-    KGWAS_HIP(hipSetDevice(h->device));
+    use_device(h->device);
     h->on_device = true;
     const uint64_t n = h->n, ldi = h->dm.ldi, n16 = h->dm.n16;
     std::vector<double> Up(n16 * ldi, 0.0), dp(ldi, 0.0), wt(ldi, 0.0), HB(ldi * LMM_HB_COLS, 0.0), grid(2 * LMM_GRID);
@@ -137,7 +122,7 @@ void device_init(kgwas_lmm* h) {
     h->d_bed.alloc(c * h->dm.bps);
     h->d_codes.alloc(c * h->dm.bpsp);
     h->d_vars.alloc(c);
-    KGWAS_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    h->stream.create(hipStreamNonBlocking);
 }
 
 // yt[ldi] (zeroed by the caller) = U^T (y - mean y), in index order; `where` ends the message of a refused y

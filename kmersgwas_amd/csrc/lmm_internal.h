@@ -7,7 +7,7 @@
 #include <vector>
 
 #include "common.h"
-#include "ingest.h"
+#include "device.h"
 #include "lmm_kernels.h"
 
 // Times the stages of the work on the handle's stream into the buckets of kgwas_lmm_stats. begin() opens an interval, end(bucket)
@@ -16,10 +16,6 @@
 class LmmStageTimer {
   public:
     using Bucket = double kgwas_lmm_stats::*;
-    LmmStageTimer() = default;
-    LmmStageTimer(const LmmStageTimer&) = delete;
-    LmmStageTimer& operator=(const LmmStageTimer&) = delete;
-    ~LmmStageTimer();
     void begin(hipStream_t st) { stamp(st); }
     void end(Bucket bucket, hipStream_t st) {
         stamp(st);
@@ -33,7 +29,7 @@ class LmmStageTimer {
         Bucket bucket;
     };
     void stamp(hipStream_t st);
-    std::vector<hipEvent_t> events;  // created when first needed, reused after every collect()
+    std::vector<kgwas::Event> events;  // created when first needed, reused after every collect()
     size_t used = 0;
     std::vector<Interval> closed;
 };
@@ -50,7 +46,6 @@ struct kgwas_lmm {
     double l0 = 0, lambda0 = 0;
     kgwas_lmm_stats st{};
     bool on_device = false;
-    hipStream_t stream = nullptr;
     LmmStageTimer timer;
     kgwas::DevBuf<double> d_U, d_d, d_wt, d_yt, d_HB, d_grid, d_base, d_null, d_Xt, d_G, d_lrt, d_lam, d_p;
     kgwas::DevBuf<uint8_t> d_bed, d_codes;
@@ -73,7 +68,10 @@ struct kgwas_lmm {
     kgwas::DevBuf<kgwas::LmmTableRecord> d_sel_rec;
     kgwas::PinBuf<kgwas::LmmTableRecord> h_sel_rec;
     void ensure_select();
-    ~kgwas_lmm();
+    kgwas::Stream stream;  // (behind the buffers its work reads and writes: it goes first)
+    ~kgwas_lmm() {
+        if (on_device) (void)hipSetDevice(device);  // (before any member is released)
+    }
 };
 
 namespace kgwas {

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "common.h"
+#include "device.h"
 
 using namespace kgwas;
 
@@ -236,17 +237,16 @@ int kgwas_multiscan_finish(kgwas_multiscan* m) {
             m->patterns = 0;
             if (total) {
                 KGWAS_HIP(hipSetDevice(dv[0]));
-                uint64_t* all = nullptr;
-                KGWAS_HIP(hipMalloc((void**)&all, total * sizeof(uint64_t)));
+                DevBuf<uint64_t> all;
+                all.alloc(total);
                 uint64_t off = 0;
                 hipError_t e = hipSuccess;
                 for (size_t g = 0; g < G && e == hipSuccess; g++) {
-                    if (n[g]) e = hipMemcpyPeer(all + off, dv[0], src[g], dv[g], n[g] * sizeof(uint64_t));
+                    if (n[g]) e = hipMemcpyPeer(all.p + off, dv[0], src[g], dv[g], n[g] * sizeof(uint64_t));
                     off += n[g];
                 }
                 uint64_t distinct = 0;
-                if (e == hipSuccess) e = count_distinct_u64(all, total, &distinct, nullptr);
-                (void)hipFree(all);
+                if (e == hipSuccess) e = count_distinct_u64(all.p, total, &distinct, nullptr);
                 KGWAS_HIP(e);
                 m->patterns = distinct;
             }

@@ -75,18 +75,18 @@ static std::unique_ptr<kgwas_scan> new_session(const kgwas_scan_params* p, ScanS
 }
 
 static void create_streams(kgwas_scan* s, const CreateTrace& tcreate) {
-    KGWAS_HIP(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+    s->stream.create(hipStreamNonBlocking);
     tcreate("stream created (HIP context up)");
     // (Round 4 tried a side thread here that loaded the library's code objects and exercised the stream's first launch, copy
     // and cross-stream wait while this thread went on: ~20 ms of a fresh process. A fuzz run then hung INSIDE this function -
     // one helper thread spinning, this thread blocked - about once per 3 500 s of randomised sessions, never before that
     // thread existed: two threads driving the HIP runtime's allocation / registration / synchronisation paths at once is
     // not worth 20 ms. The first uses are paid where they occur.)
-    KGWAS_HIP(hipEventCreate(&s->ev_user));
-    KGWAS_HIP(hipEventCreate(&s->ev_ds));
-    KGWAS_HIP(hipEventCreateWithFlags(&s->ev_dcopy, hipEventDisableTiming));
-    KGWAS_HIP(hipEventCreate(&s->ev_d0));
-    KGWAS_HIP(hipEventCreate(&s->ev_d1));
+    s->ev_user.create();
+    s->ev_ds.create();
+    s->ev_dcopy.create(hipEventDisableTiming);
+    s->ev_d0.create();
+    s->ev_d1.create();
     tcreate("events created");
 }
 
@@ -211,7 +211,7 @@ static void alloc_filter_buffers(kgwas_scan* s) {
     int least = 0, greatest = 0;
     KGWAS_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
     const bool hi = !(exp_int("KGWAS_COPY_PRIO", 1) == 0);
-    KGWAS_HIP(hipStreamCreateWithPriority(&s->copy_stream, hipStreamNonBlocking, hi ? greatest : least));
+    s->copy_stream.create_with_priority(hipStreamNonBlocking, hi ? greatest : least);
     s->row_key_bits = 1;
     while (s->row_key_bits < 32 && (1ull << s->row_key_bits) < s->chunk_max) s->row_key_bits++;
 }
@@ -257,7 +257,7 @@ static void alloc_slots(kgwas_scan* s, const CreateTrace& tcreate) {
             memset(sl.h_meta.p, 0, (2 * P + 4) * sizeof(uint32_t));
             sl.h_meta_dev = sl.h_meta.dev();
             sl.h_thr_dev = sl.h_thr.dev();
-            KGWAS_HIP(hipEventCreateWithFlags(&sl.ev_counts, hipEventBlockingSync));
+            sl.ev_counts.create(hipEventBlockingSync);
         } else {
             sl.cand.alloc((uint64_t)s->cap * P);
             sl.d_cand = sl.cand.dev();
@@ -267,12 +267,12 @@ static void alloc_slots(kgwas_scan* s, const CreateTrace& tcreate) {
         sl.d_tested.alloc(TESTED_SHARDS);
         sl.h_tested.alloc(TESTED_SHARDS);
         sl.h_tested_dev = sl.h_tested.dev();
-        KGWAS_HIP(hipEventCreate(&sl.ev_sq0));
-        KGWAS_HIP(hipEventCreate(&sl.ev_k0));
-        KGWAS_HIP(hipEventCreate(&sl.ev_k1));
+        sl.ev_sq0.create();
+        sl.ev_k0.create();
+        sl.ev_k1.create();
         // (blocking wait: the control thread sleeps instead of spinning beside the replay workers)
-        KGWAS_HIP(hipEventCreateWithFlags(&sl.ev_done, hipEventBlockingSync));
-        KGWAS_HIP(hipEventCreate(&sl.ev_mid));
+        sl.ev_done.create(hipEventBlockingSync);
+        sl.ev_mid.create();
     }
     s->d_dense.alloc(P * s->dense_rows);
     s->h_dense.alloc(P * s->dense_rows);

@@ -46,6 +46,7 @@
 
 #include "common.h"
 #include "heap.h"
+#include "device.h"
 #include "ingest.h"
 #include "kernels.h"
 
@@ -414,10 +415,10 @@ struct Slot {
     PinBuf<double> h_thr;  // the device's thresholds behind this chunk (columns in select mode prune their pools with them, scan_lazy.cpp)
     bool tie_check = false;          // columns in select mode look at their pools for ties after this chunk (scan_lazy.cpp)
     bool tested_in_meta = false;     // the chunk's MAC-passing rows came in h_meta (narrow scans), not in h_tested
-    hipEvent_t ev_counts = nullptr;  // compute stream: compaction done, h_meta copied
+    Event ev_counts;                 // compute stream: compaction done, h_meta copied
     DevBuf<unsigned long long> d_tested;
     PinBuf<unsigned long long> h_tested;
-    hipEvent_t ev_sq0 = nullptr, ev_k0 = nullptr, ev_k1 = nullptr, ev_done = nullptr, ev_mid = nullptr;
+    Event ev_sq0, ev_k0, ev_k1, ev_done, ev_mid;
     bool used_coarse = false;
     int coarse_mode = 0;
     double cand_est = 0;  // candidates the chunk was planned for (sum of topn x rows / rows before it)
@@ -444,10 +445,7 @@ struct kgwas_scan {
     uint64_t max_topn = 0;
     uint32_t nb_full = 0;  // leading 128-sample blocks the MFMA scorer may read unmasked
 
-    hipStream_t stream = nullptr, copy_stream = nullptr;  // copy_stream: candidate records HBM -> host
-    hipEvent_t ev_user = nullptr, ev_ds = nullptr, ev_d0 = nullptr, ev_d1 = nullptr;  // caller sync + dense-chunk timing
-    hipEvent_t ev_dcopy = nullptr;     // the dense start's scores are in host memory (their copy runs on copy_stream, run_dense)
-    bool dense_copy_pending = false;   // ... and nobody has waited for it yet (wait_dense_copy)
+    bool dense_copy_pending = false;   // the dense start's scores are on their way to host memory and nobody has waited for ev_dcopy yet (wait_dense_copy)
     DevBuf<uint32_t> d_dmask, d_colmap, d_sq;
     DevBuf<float> d_Yperm, d_Ymfma, d_sums;
     DevBuf<double> d_thr;
@@ -553,6 +551,10 @@ struct kgwas_scan {
     // thread, two device pieces, a copy stream; piece k+1 is read and copied while piece k is scored and replayed
     DevBuf<uint64_t> d_stage;  // kgwas_scan_scores_dense staging
     Ingest ingest;
+    // (behind every buffer their work reads and writes: the streams go first, idle)
+    Stream stream, copy_stream;             // copy_stream: candidate records HBM -> host
+    Event ev_user, ev_ds, ev_d0, ev_d1;     // caller sync + dense-chunk timing
+    Event ev_dcopy;                         // the dense start's scores are in host memory (their copy runs on copy_stream, run_dense)
 
     // all heaps' arrays in one 2 MB-aligned, MADV_HUGEPAGE arena (make_heaps); declared before the heaps: destroyed after
     struct HugeArena {
@@ -644,26 +646,7 @@ struct kgwas_scan {
     std::vector<std::vector<uint64_t>> res_kmer, res_row;
     std::vector<std::vector<double>> res_score;
 
-    ~kgwas_scan() {
-        (void)hipSetDevice(device);
-        auto drop_events = [](Slot& s) {
-            if (s.ev_sq0) (void)hipEventDestroy(s.ev_sq0);
-            if (s.ev_k0) (void)hipEventDestroy(s.ev_k0);
-            if (s.ev_k1) (void)hipEventDestroy(s.ev_k1);
-            if (s.ev_done) (void)hipEventDestroy(s.ev_done);
-            if (s.ev_mid) (void)hipEventDestroy(s.ev_mid);
-            if (s.ev_counts) (void)hipEventDestroy(s.ev_counts);
-        };
-        for (auto& s : slot) drop_events(s);
-        drop_events(redo);
-        if (ev_user) (void)hipEventDestroy(ev_user);
-        if (ev_ds) (void)hipEventDestroy(ev_ds);
-        if (ev_dcopy) (void)hipEventDestroy(ev_dcopy);
-        if (ev_d0) (void)hipEventDestroy(ev_d0);
-        if (ev_d1) (void)hipEventDestroy(ev_d1);
-        if (stream) (void)hipStreamDestroy(stream);
-        if (copy_stream) (void)hipStreamDestroy(copy_stream);
-    }
+    ~kgwas_scan() { (void)hipSetDevice(device); }  // (before any member is released)
 };
 
 namespace kgwas {

@@ -18,7 +18,7 @@
 #include <vector>
 
 #include "common.h"
-#include "ingest.h"
+#include "device.h"
 #include "kernels.h"
 
 using namespace kgwas;
@@ -30,8 +30,6 @@ struct kgwas_snpkin {
     uint32_t chunk = 0;  // SNPs per launch pair
     int rows_per_wave = 4;
     uint32_t n_tiles = 0;
-    hipStream_t stream = nullptr, copy = nullptr;
-    hipEvent_t ev_copied[2] = {nullptr, nullptr}, ev_used[2] = {nullptr, nullptr};
     bool copied_pending[2] = {false, false}, used_pending[2] = {false, false};
     int slot = 0;
     DevBuf<uint8_t> d_bed[2];
@@ -40,18 +38,11 @@ struct kgwas_snpkin {
     DevBuf<uint2> d_tiles;
     DevBuf<double> d_sums;
     DevBuf<unsigned long long> d_n;
+    Stream stream, copy;  // (behind the buffers their work reads and writes: they go first)
+    Event ev_copied[2], ev_used[2];
     bool on_device = false;
     ~kgwas_snpkin() {
-        if (!on_device) return;
-        (void)hipSetDevice(device);
-        if (stream) (void)hipStreamSynchronize(stream);
-        if (copy) (void)hipStreamSynchronize(copy);
-        for (int b = 0; b < 2; b++) {
-            if (ev_copied[b]) (void)hipEventDestroy(ev_copied[b]);
-            if (ev_used[b]) (void)hipEventDestroy(ev_used[b]);
-        }
-        if (copy) (void)hipStreamDestroy(copy);
-        if (stream) (void)hipStreamDestroy(stream);
+        if (on_device) (void)hipSetDevice(device);  // (before any member is released)
     }
 };
 
@@ -89,10 +80,7 @@ std::vector<uint2> make_tiles(uint32_t S, uint32_t rw) {
 }
 
 void device_init(kgwas_snpkin* h) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) throw Error(KGWAS_ERR_DEVICE, "no HIP device available: libkgwas has no CPU fallback");
-    if (h->device < 0 || h->device >= n) throw Error(KGWAS_ERR_ARG, "device ordinal out of range");
-    KGWAS_HIP(hipSetDevice(h->device));
+    use_device(h->device);
     h->on_device = true;
     const uint32_t S = (uint32_t)h->S;
     // 8 rows per wave where that still puts 2 waves on each of the MI355X's 1024 SIMDs, else 4 (S = 1135: 2 664 waves)
@@ -109,11 +97,11 @@ void device_init(kgwas_snpkin* h) {
     const long long forced = opt_int("KGWAS_SNPKIN_CHUNK_SNPS", 0);
     if (forced > 0) chunk = (uint64_t)std::min<long long>(forced, 1 << 20);
     h->chunk = (uint32_t)chunk;
-    KGWAS_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    KGWAS_HIP(hipStreamCreateWithFlags(&h->copy, hipStreamNonBlocking));
+    h->stream.create(hipStreamNonBlocking);
+    h->copy.create(hipStreamNonBlocking);
     for (int b = 0; b < 2; b++) {
-        KGWAS_HIP(hipEventCreateWithFlags(&h->ev_copied[b], hipEventDisableTiming));
-        KGWAS_HIP(hipEventCreateWithFlags(&h->ev_used[b], hipEventDisableTiming));
+        h->ev_copied[b].create(hipEventDisableTiming);
+        h->ev_used[b].create(hipEventDisableTiming);
         h->d_bed[b].alloc(chunk * h->bps);
         h->h_bed[b].alloc(chunk * h->bps);
     }

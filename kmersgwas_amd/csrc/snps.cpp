@@ -41,31 +41,15 @@ using namespace kgwas;
 
 namespace {
 
-template <class T>
-struct DevArr {
-    T* p = nullptr;
-    void alloc(size_t n) { KGWAS_HIP(hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T))); }
-    ~DevArr() {
-        if (p) (void)hipFree(p);
-    }
-};
-
-void need_device(int device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        throw Error(KGWAS_ERR_DEVICE, "no HIP device available: libkgwas has no CPU fallback");
-    KGWAS_HIP(hipSetDevice(device));
-}
-
 // Scores of SNPs [first, first + c) for all columns into out[p * out_stride + i], i = 0..c-1.
 struct SnpScorer {
     const kgwas_snps* s;
     uint64_t S, P, W_m, L, ndw, chunk;
-    DevArr<uint8_t> d_bed;
-    DevArr<uint32_t> d_bidx, d_shift, d_planes;
-    DevArr<float> d_Y;
-    DevArr<double> d_scores;
-    hipStream_t st = nullptr;
+    DevBuf<uint8_t> d_bed;
+    DevBuf<uint32_t> d_bidx, d_shift, d_planes;
+    DevBuf<float> d_Y;
+    DevBuf<double> d_scores;
+    Stream st;
     SnpScorer(const kgwas_snps* s_, const float* Y, uint64_t n_pheno) : s(s_) {
         S = s->samples.size();
         P = n_pheno;
@@ -85,18 +69,15 @@ struct SnpScorer {
                     for (uint64_t l = 0; l < 4; l++) Yperm[j * L + 128 * b + 4 * sx + l] = V[128 * b + 32 * l + 31 - sx];
         }
         d_bed.alloc(chunk * s->bytes_per_snp);
-        d_bidx.alloc(S);
-        d_shift.alloc(S);
-        d_planes.alloc(chunk * 3 * ndw);
-        d_Y.alloc(P * L);
+        d_bidx.alloc(std::max<uint64_t>(S, 1));  // (no sample at all: still something to point at)
+        d_shift.alloc(std::max<uint64_t>(S, 1));
+        d_planes.alloc(std::max<uint64_t>(chunk * 3 * ndw, 1));
+        d_Y.alloc(std::max<uint64_t>(P * L, 1));
         d_scores.alloc(P * chunk);
         KGWAS_HIP(hipMemcpy(d_bidx.p, s->byte_idx.data(), S * 4, hipMemcpyHostToDevice));
         KGWAS_HIP(hipMemcpy(d_shift.p, s->shift.data(), S * 4, hipMemcpyHostToDevice));
         KGWAS_HIP(hipMemcpy(d_Y.p, Yperm.data(), Yperm.size() * 4, hipMemcpyHostToDevice));
-        KGWAS_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));  // (last: a constructor that throws runs no destructor)
-    }
-    ~SnpScorer() {
-        if (st) (void)hipStreamDestroy(st);
+        st.create(hipStreamNonBlocking);
     }
     void run(uint64_t first, uint64_t c, double mac, double* out, uint64_t out_stride) {
         KGWAS_HIP(hipMemcpyAsync(d_bed.p, s->bed.data() + first * s->bytes_per_snp, c * s->bytes_per_snp, hipMemcpyHostToDevice, st));
@@ -173,7 +154,7 @@ int kgwas_snps_info(const kgwas_snps* s, uint64_t* n_snps, uint64_t* n_samples_f
 int kgwas_snps_scores(kgwas_snps* s, const float* Y, uint64_t n_pheno, double mac, int device, double* scores) {
     return guarded([&] {
         if (!s || (n_pheno && (!Y || !scores))) throw Error(KGWAS_ERR_ARG, "kgwas_snps_scores: null argument");
-        need_device(device);
+        use_device(device);
         if (n_pheno == 0 || s->n_snps == 0) return;
         SnpScorer sc(s, Y, n_pheno);
         for (uint64_t pos = 0; pos < s->n_snps; pos += sc.chunk) {
@@ -187,7 +168,7 @@ int kgwas_snps_best(kgwas_snps* s, const float* Y, uint64_t n_pheno, uint64_t to
                     uint64_t* indices) {
     return guarded([&] {
         if (!s || (n_pheno && (!Y || !counts || !indices))) throw Error(KGWAS_ERR_ARG, "kgwas_snps_best: null argument");
-        need_device(device);
+        use_device(device);
         require_heap_emulation();
         std::vector<BestHeap> heaps;
         for (uint64_t j = 0; j < n_pheno; j++) heaps.emplace_back((size_t)topn);

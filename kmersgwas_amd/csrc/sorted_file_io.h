@@ -39,6 +39,19 @@ inline void write_all(int fd, const void* data, size_t n, const std::string& pat
     }
 }
 
+inline void open_output(Fd& f, const std::string& path) {
+    f.reset();
+    f.fd = ::open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
+    if (f.fd < 0) throw Error(KGWAS_ERR_IO, "can't open output file " + path + ": " + std::strerror(errno));
+}
+
+// closes a file that was written, and reports a close that fails
+inline void close_output(Fd& f, const std::string& path) {
+    const int rc = ::close(f.fd);
+    f.fd = -1;
+    if (rc != 0) throw Error(KGWAS_ERR_IO, "write error on " + path + ": " + std::strerror(errno));
+}
+
 inline void open_input(Fd& f, const std::string& path) {
     f.reset();
     f.fd = ::open(path.c_str(), O_RDONLY);
@@ -82,6 +95,42 @@ inline uint64_t first_above(const uint64_t* h, uint64_t cnt, uint64_t thr) {
                 if ((h[i] & SORTED_KEY_MASK) > thr) return i;
     }
     return cnt;
+}
+
+// kmers_step_to_threshold (src/kmer_general.cpp:255-258): the width of one of `steps` key windows for k-mers of kmer_len bases
+inline uint64_t kmers_step_to_threshold(uint64_t steps, uint32_t kmer_len) { return ((1ull << (2ull * kmer_len)) - 1ull) / steps + 1; }
+
+// The window of key x, windows counted from 1: max(1, ceil(x / step)).
+inline uint64_t window_of(uint64_t x, uint64_t step) { return x == 0 ? 1 : (x - 1) / step + 1; }
+
+// Where a walk over one file's slice ended: the words handed over so far, and, when a word above the threshold ended it, that
+// word's masked key.
+struct SliceEnd {
+    uint64_t pos = 0;
+    bool above = false;
+    uint64_t head = 0;
+};
+
+// The reference's rule for one accession's slice (KmersSingleDataBaseSortedFile::load_kmers_upto_x, :153-177): words are read from
+// `pos` in blocks of at most block_words, up to the first one whose masked value is above thr or to the end of the file.
+// take() gives the block to read into (room for block_words words); use(block, e) is handed the block and the e words of it that
+// belong to the slice, and returns false to stop the walk, in which case these e words do not count as handed over.
+template <class Take, class Use>
+SliceEnd walk_slice(const std::string& path, uint64_t pos, uint64_t words, uint64_t block_words, uint64_t thr, Take&& take, Use&& use) {
+    Fd f;
+    open_input(f, path);
+    SliceEnd r;
+    r.pos = pos;
+    while (!r.above && r.pos < words) {
+        uint64_t* h = take();
+        const uint64_t cnt = std::min(block_words, words - r.pos);
+        read_words(f.fd, h, r.pos, cnt, path);
+        const uint64_t e = first_above(h, cnt, thr);
+        if (!use(h, e)) break;
+        if (e < cnt) r.above = true, r.head = h[e] & SORTED_KEY_MASK;
+        r.pos += e;
+    }
+    return r;
 }
 
 }  // namespace kgwas

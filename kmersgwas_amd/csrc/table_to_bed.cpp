@@ -17,21 +17,10 @@
 #include <vector>
 
 #include "common.h"
-#include "ingest.h"
+#include "device.h"
 #include "kernels.h"
 
 namespace kgwas {
-namespace {
-
-template <class T>
-struct Dev {
-    T* p = nullptr;
-    void alloc(size_t n) { KGWAS_HIP(hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T))); }
-    ~Dev() {
-        if (p) (void)hipFree(p);
-    }
-};
-}  // namespace
 
 void check_squeeze_fits(const char* who, uint64_t S_f, uint64_t S) {
     const uint64_t W_f = (S_f + 63) / 64, W_m = 2 * ((S + 127) / 128);
@@ -50,10 +39,7 @@ extern "C" int kgwas_table_to_bed(kgwas_table* t, const uint64_t* col, uint64_t 
                                   const char* out_base, int device, uint64_t* n_batches, uint64_t* n_written) {
     return guarded([&] {
         if (!t || !col || !acc_names || !y || !out_base) throw Error(KGWAS_ERR_ARG, "kgwas_table_to_bed: null argument");
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-            throw Error(KGWAS_ERR_DEVICE, "no HIP device available: libkgwas has no CPU fallback");
-        KGWAS_HIP(hipSetDevice(device));
+        use_device(device);
         uint64_t S_f = 0, n_rows = 0, W_f = 0;
         uint32_t klen = 0;
         if (kgwas_table_info(t, &S_f, &n_rows, &W_f, &klen) != KGWAS_OK) throw Error(KGWAS_ERR_ARG, kgwas_last_error());
@@ -70,9 +56,9 @@ extern "C" int kgwas_table_to_bed(kgwas_table* t, const uint64_t* col, uint64_t 
 
         std::vector<uint32_t> colmap(64ull * W_m, 0xFFFFFFFFu);
         for (uint64_t i = 0; i < S; i++) colmap[i] = (uint32_t)col[i];
-        Dev<uint32_t> d_colmap, d_sq, d_n1;
-        Dev<uint64_t> d_rows, d_hash;
-        Dev<uint8_t> d_bed;
+        DevBuf<uint32_t> d_colmap, d_sq, d_n1;
+        DevBuf<uint64_t> d_rows, d_hash;
+        DevBuf<uint8_t> d_bed;
         // Two sets of host buffers: piece k + 1 is read, copied and processed on the GPU (this thread) while piece k's kept rows
         // are written (the writer thread below: batches, the pattern set and the files are its alone, pieces in order).
         struct HostSet {
@@ -80,31 +66,28 @@ extern "C" int kgwas_table_to_bed(kgwas_table* t, const uint64_t* col, uint64_t 
             PinBuf<uint32_t> n1;
             PinBuf<uint8_t> bed;
         } hs[2];
-        d_colmap.alloc(colmap.size());
+        d_colmap.alloc(std::max<size_t>(colmap.size(), 1));  // (no accession at all: still something to point at)
         KGWAS_HIP(hipMemcpy(d_colmap.p, colmap.data(), colmap.size() * 4, hipMemcpyHostToDevice));
         d_rows.alloc(piece * stride);
-        d_sq.alloc(piece * 2 * W_m);
+        d_sq.alloc(std::max<uint64_t>(piece * 2 * W_m, 1));
         d_n1.alloc(piece);
         d_hash.alloc(piece);
-        d_bed.alloc(piece * bpr);
+        d_bed.alloc(std::max<uint64_t>(piece * bpr, 1));
         for (HostSet& h : hs) {
             h.rows.alloc(piece * stride);
             h.n1.alloc(piece);
             h.hash.alloc(piece);
             h.bed.alloc(piece * bpr);
         }
-        hipStream_t st = nullptr;
-        KGWAS_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        struct StreamGuard {
-            hipStream_t s;
-            ~StreamGuard() { (void)hipStreamDestroy(s); }
-        } sg{st};
+        Stream st;
+        st.create(hipStreamNonBlocking);
 
         std::unordered_set<uint64_t> seen;  // pa_patterns_counter (src/kmers_table_to_bed.cpp:107-108)
         std::ofstream bed, bim;
         bool open = false;
         uint64_t batch = 0, kept = 0, written = 0;
-        std::future<void> bed_pending;  // the .bed bytes of the last run, written beside the formatting of the next run's .bim lines
+        // the .bed bytes of the last run, written beside the formatting of the next run's .bim lines
+        std::future<void> bed_pending;  // (after hs and bed, which its writer uses: its destructor waits for the writer)
         auto bed_wait = [&] {
             if (bed_pending.valid()) bed_pending.get();
         };
