@@ -234,7 +234,10 @@ typedef struct kgwas_scan_stats {
  * Version 13: no struct changed; new struct kgwas_lmm_stats and entry points kgwas_sym_eigen, kgwas_lmm_* (lmm_lrt).
  * Version 14: no struct changed; new entry points kgwas_lmm_test_bed_multi, kgwas_lmm_run_file_multi (lmm_lrt --columns).
  * Version 15: no struct changed; new entry points kgwas_lmm_test_table, kgwas_lmm_run_table (lmm_lrt --kmers_table), and later,
- * without a new version number, kgwas_lmm_test_table_multi, kgwas_lmm_run_table_multi (lmm_lrt --kmers_table --pheno_columns). */
+ * without a new version number, kgwas_lmm_test_table_multi, kgwas_lmm_run_table_multi (lmm_lrt --kmers_table --pheno_columns), and
+ * kgwas_lmm_null_reml, kgwas_lmm_test_bed_all, kgwas_lmm_run_files_all, kgwas_lmm_format_assoc4, kgwas_fdist_tail (lmm_lrt -lmm 4).
+ * Those came after version 15 without a bump: a caller that may meet an older version-15 library probes for them by symbol
+ * (dlsym, or hasattr on a ctypes handle). */
 #define KGWAS_ABI_VERSION 15
 uint32_t kgwas_abi_version(void);
 
@@ -642,6 +645,28 @@ void kgwas_snpkin_close(kgwas_snpkin* h);
  * read_kinship / read_fam / format_assoc: the parsers and the line formatter of run_files (no GPU). read_fam gives every line's
  *            value (NaN when missing) and keep flag, up to cap entries, and the number of lines. format_assoc returns the bytes
  *            needed and writes them if cap allows; chr == NULL gives the header line.
+ *
+ * -lmm 4 (after ABI version 15, no bump: probe by symbol). Beside the LRT: the REML effect estimate with its standard error, the
+ * Wald test and the score test - the forms GEMMA documents for -lmm 1 / 3 / 4, not checked against a GEMMA run. With the rotated,
+ * centred vectors, h_i = 1 / (lambda d_i + 1), the h-weighted sums ww .. xy and a.w the Schur complement after w:
+ *     lR(lambda) = df/2 (log(df / 2 pi) - 1) + 1/2 sum log h_i - 1/2 (log ww + log xx.w) - df/2 log RSS1,  df = n - 2,
+ * l_remle its maximiser over [lmin, lmax] by the procedure that finds l_mle (a boundary optimum is lmin or lmax exactly);
+ *     beta = xy.w / xx.w, se = sqrt(RSS1 / (df xx.w)), F_wald = (yy.w - RSS1) df / RSS1 = (beta / se)^2 at l_remle,
+ *     F_score = n xy.w^2 / (xx.w yy.w) at lambda0, the null model's ML lambda (kgwas_lmm_null),
+ * p_wald and p_score their F(1, df) tails. beta is per unit of the decoded dosage (code 00 -> 2): the allele that af counts.
+ * null_reml: the null model by REML, lR0(lambda) = df0/2 (log(df0 / 2 pi) - 1) + 1/2 sum log h - 1/2 log ww - df0/2 log yy.w with
+ *            df0 = n - 1, the same maximisation; ve = yy.w / df0 and vg = lambda ve at the maximiser (emma.REMLE's ve and vg, delta =
+ *            1 / lambda). Any output may be NULL. The phenotype is cached as kgwas_lmm_null caches it.
+ * test_bed_all: test_bed with five more outputs (any may be NULL). An untested variant has NaN in all eight statistics. lrt,
+ *            lambda_mle, p_lrt, af, n_miss and tested have the bits of kgwas_lmm_test_bed, and all eight are bit-identical from run
+ *            to run, in any variant order and for any chunk_variants.
+ * run_files_all: run_files writing the -lmm 4 file: chr rs ps n_miss allele1 allele0 af beta se l_remle l_mle p_wald p_lrt p_score
+ *            (columns 1-7, l_mle and p_lrt with the bytes of the -lmm 2 file); the log has the -lmm 2 log's lines under its own
+ *            title and, behind logl_H0, lambda0_remle, logl_remle_H0, vg and ve.
+ * format_assoc4: format_assoc for that file; af as %.3f, the seven numbers as %.6e (a p below the normal doubles prints as a
+ *            subnormal or 0, which parses back).
+ * fdist_tail: Q(F; 1, df) = I_x(df / 2, 1 / 2), x = df / (df + F): the tail both tests use, the host instance of the function the
+ *            kernel calls (no GPU). F <= 0 -> 1; relative error below 1e-9 for df <= 65533 also where p is tiny.
  * ---------------------------------------------------------------------------------- */
 typedef struct kgwas_lmm kgwas_lmm;
 typedef struct kgwas_lmm_stats {
@@ -681,6 +706,17 @@ int kgwas_lmm_read_kinship(const char* path, uint64_t n_expected, double* K);
 int kgwas_lmm_read_fam(const char* path, uint32_t pheno_col, uint64_t cap, double* values, uint8_t* keep, uint64_t* n_lines);
 uint64_t kgwas_lmm_format_assoc(const char* chr, const char* rs, const char* ps, uint32_t n_miss, const char* allele1, const char* allele0,
                                 double af, double l_mle, double p_lrt, char* out, uint64_t cap);
+int kgwas_lmm_null_reml(kgwas_lmm* h, const double* y, double* logl0_reml, double* lambda0_reml, double* vg, double* ve);
+int kgwas_lmm_test_bed_all(kgwas_lmm* h, const double* y, const uint8_t* bed_body, uint64_t n_variants, double maf, double miss, double* lrt,
+                           double* lambda_mle, double* p_lrt, double* beta, double* se, double* lambda_remle, double* p_wald,
+                           double* p_score, double* af, uint32_t* n_miss, uint8_t* tested);
+int kgwas_lmm_run_files_all(const char* kinship_path, uint64_t n_beds, const char* const* bfile_bases, const char* const* out_paths,
+                            uint32_t pheno_col, double maf, double miss, double lmin, double lmax, uint64_t chunk_variants, int32_t device,
+                            kgwas_lmm_stats* total);
+uint64_t kgwas_lmm_format_assoc4(const char* chr, const char* rs, const char* ps, uint32_t n_miss, const char* allele1, const char* allele0,
+                                 double af, double beta, double se, double l_remle, double l_mle, double p_wald, double p_lrt, double p_score,
+                                 char* out, uint64_t cap);
+double kgwas_fdist_tail(double F, double df);
 
 /* ------------------------------------------------------------------------------------
  * Seeded synthetic table rows: kmer = row + 1, per-row frequency q/256 with

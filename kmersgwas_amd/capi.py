@@ -46,6 +46,7 @@ SYMBOLS = [
     "kgwas_lmm_test_bed_multi", "kgwas_lmm_run_file_multi", "kgwas_lmm_test_table", "kgwas_lmm_run_table",
     "kgwas_lmm_test_table_multi", "kgwas_lmm_run_table_multi",
     "kgwas_lmm_destroy", "kgwas_lmm_read_kinship", "kgwas_lmm_read_fam", "kgwas_lmm_format_assoc",
+    "kgwas_lmm_null_reml", "kgwas_lmm_test_bed_all", "kgwas_lmm_run_files_all", "kgwas_lmm_format_assoc4", "kgwas_fdist_tail",
     "kgwas_synth_rows_device", "kgwas_synth_rows_host",
 ]
 
@@ -285,6 +286,14 @@ lib.kgwas_lmm_read_kinship.argtypes = [C.c_char_p, _u64, _vp]
 lib.kgwas_lmm_read_fam.argtypes = [C.c_char_p, _u32, _u64, _vp, _vp, _pu64]
 lib.kgwas_lmm_format_assoc.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, _u32, C.c_char_p, C.c_char_p, _dbl, _dbl, _dbl, C.c_char_p, _u64]
 lib.kgwas_lmm_format_assoc.restype = _u64
+# -lmm 4: added after ABI version 15 without a bump
+lib.kgwas_lmm_null_reml.argtypes = [_vp, _vp, _pdbl, _pdbl, _pdbl, _pdbl]
+lib.kgwas_lmm_test_bed_all.argtypes = [_vp, _vp, _vp, _u64, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+lib.kgwas_lmm_run_files_all.argtypes = lib.kgwas_lmm_run_files.argtypes
+lib.kgwas_lmm_format_assoc4.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, _u32, C.c_char_p, C.c_char_p] + [_dbl] * 8 + [C.c_char_p, _u64]
+lib.kgwas_lmm_format_assoc4.restype = _u64
+lib.kgwas_fdist_tail.argtypes = [_dbl, _dbl]
+lib.kgwas_fdist_tail.restype = _dbl
 lib.kgwas_synth_rows_device.argtypes = [_vp, _u64, _u64, _u64, _u64, _vp]
 lib.kgwas_synth_rows_host.argtypes = [_vp, _u64, _u64, _u64, _u64]
 

@@ -12,6 +12,8 @@
 //     --pheno_columns LIST   (a file of "col<TAB>name" lines, in place of -n and -o)
 // the listed columns of PHENO - the phenotype and its permutations - are all tested in ONE pass over the table, the best N of each
 // to D/name.assoc.txt with a log (kgwas_lmm_run_table_multi): what calc_best_pvals / get_threshold_from_perm read.
+// -lmm 4 (with -bfile or --bfiles only) writes chr rs ps n_miss allele1 allele0 af beta se l_remle l_mle p_wald p_lrt p_score: the
+// REML effect estimate, its standard error, the Wald and the score test beside the LRT (kgwas_lmm_run_files_all).
 #include <sys/stat.h>
 
 #include <cstdlib>
@@ -29,12 +31,15 @@ using namespace std;
 
 static void usage(const char* prog) {
     cerr << "usage: " << prog
-         << " -bfile B [--columns LIST] | --bfiles LIST  -lmm 2  -k KINSHIP  [-outdir D] [-o NAME] [-n i] [-maf f] [-miss f] [-lmin x] [-lmax x]\n"
+         << " -bfile B [--columns LIST] | --bfiles LIST  -lmm 2|4  -k KINSHIP  [-outdir D] [-o NAME] [-n i] [-maf f] [-miss f] [-lmin x] [-lmax x]\n"
             "  -bfile B       PLINK base name (B.bed, B.bim, B.fam)\n"
             "  --bfiles LIST  file of 'bfile<TAB>name' lines: every bfile is tested, output D/name.assoc.txt\n"
             "  --columns LIST file of 'col<TAB>name' lines, with -bfile: every listed phenotype column of B.fam (from 1) is tested in\n"
             "                 one pass over B.bed, output D/name.assoc.txt (no -n, no -o); the columns must share their missing individuals\n"
-            "  -lmm 2         the likelihood-ratio test (the only test built)\n"
+            "  -lmm 2         the likelihood-ratio test: columns l_mle and p_lrt\n"
+            "  -lmm 4         that, and the REML effect size, the Wald test and the score test: columns beta se l_remle l_mle p_wald p_lrt\n"
+            "                 p_score (with -bfile or --bfiles; not with --columns, --kmers_table or --pheno_columns). -lmm 1 and -lmm 3\n"
+            "                 are not built as formats of their own: their columns are in the -lmm 4 file\n"
             "  -k FILE        kinship matrix, text, one row per .fam line\n"
             "  -outdir D      output directory (default ./output), -o NAME output prefix (default result)\n"
             "  -n i           phenotype column of the .fam, from 1 (default 1)\n"
@@ -207,10 +212,20 @@ int main(int argc, char* argv[]) {
         }
         a[name] = argv[++i];
     }
-    if (!a.count("lmm") || a["lmm"] != "2") {
+    if (!a.count("lmm") || (a["lmm"] != "2" && a["lmm"] != "4")) {
         cerr << "lmm_lrt: -lmm " << (a.count("lmm") ? a["lmm"] : string("(missing)"))
-             << ": only -lmm 2, the likelihood-ratio test, is built (no Wald or score test)" << endl;
+             << ": only -lmm 2 and -lmm 4 are built; -lmm 4 writes the Wald and score columns too" << endl;
         return 1;
+    }
+    const bool all_tests = a["lmm"] == "4";
+    if (all_tests) {  // (before any file is opened)
+        string given;
+        for (const char* o : {"columns", "kmers_table", "pheno_columns"})
+            if (a.count(o)) given += string(given.empty() ? "" : ", ") + "--" + o;
+        if (!given.empty()) {
+            cerr << "lmm_lrt: -lmm 4 is not built for " << given << ": it takes -bfile or --bfiles (-lmm 2 runs with them)" << endl;
+            return 1;
+        }
     }
     if (a.count("kmers_table")) return table_mode(a, argv[0]);
     for (const char* o : {"kmers_len", "p", "mac", "best", "device", "pheno_columns"})
@@ -266,9 +281,11 @@ int main(int argc, char* argv[]) {
     for (const string& b : bases) bp.push_back(b.c_str());
     for (const string& o : outs) op.push_back(o.c_str());
     kgwas_lmm_stats st{};
-    const int rc = columns.empty() ? kgwas_lmm_run_files(a["k"].c_str(), bases.size(), bp.data(), op.data(), (uint32_t)col, maf, miss, lmin,
-                                                         lmax, (uint64_t)chunk, 0, &st)
-                                   : kgwas_lmm_run_file_multi(a["k"].c_str(), bp[0], (uint32_t)columns.size(), columns.data(), op.data(), maf,
+    const int rc = all_tests       ? kgwas_lmm_run_files_all(a["k"].c_str(), bases.size(), bp.data(), op.data(), (uint32_t)col, maf, miss, lmin,
+                                                             lmax, (uint64_t)chunk, 0, &st)
+                   : columns.empty() ? kgwas_lmm_run_files(a["k"].c_str(), bases.size(), bp.data(), op.data(), (uint32_t)col, maf, miss, lmin,
+                                                           lmax, (uint64_t)chunk, 0, &st)
+                                     : kgwas_lmm_run_file_multi(a["k"].c_str(), bp[0], (uint32_t)columns.size(), columns.data(), op.data(), maf,
                                                               miss, lmin, lmax, (uint64_t)chunk, 0, &st);
     if (rc != KGWAS_OK) {
         cerr << "lmm_lrt: " << kgwas_last_error() << endl;

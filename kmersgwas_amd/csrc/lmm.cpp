@@ -9,6 +9,8 @@
 // test_bed : per chunk of variants the raw bytes go to the device, then prep, rotate, grid and refine run in order on one stream;
 // test_bed_multi: several phenotype columns against ONE .bed. Per chunk prep, rotate and the two grid sums without y run once; the
 //            xt yt sums and the refinement run per block of LMM_PBLOCK columns. Every number has the bits of test_bed's.
+// -lmm 4  : null_reml fits the REML null model (vg, ve) on the sums null left; test_bed_all is test_bed with the other refinement
+//            kernel, which adds beta, se, l_remle and the Wald and score p-values and leaves lrt, lambda and p their bits.
 // No CPU fallback: the statistics need the GPU.
 #include <algorithm>
 #include <cmath>
@@ -73,6 +75,13 @@ void kgwas_lmm::ensure_select() {
     d_sel_rec.alloc(cap);
     h_sel_rec.alloc(cap);
     have_select = true;
+}
+
+void kgwas_lmm::ensure_wald() {
+    if (have_wald) return;
+    d_wald.alloc(5 * (uint64_t)chunk);
+    d_null_reml.alloc(4);
+    have_wald = true;
 }
 
 namespace {
@@ -199,7 +208,7 @@ void kgwas::lmm::fit_null(kgwas_lmm* h, const double* y) {
     std::vector<double> yt(h->dm.ldi, 0.0);
     rotate_phenotype(h, y, yt.data(), "");
     KGWAS_HIP(hipSetDevice(h->device));
-    h->have_null = false;
+    h->have_null = h->have_null_reml = false;
     KGWAS_HIP(hipMemcpyAsync(h->d_yt.p, yt.data(), yt.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     KGWAS_HIP(launch_lmm_base(h->dm, h->d_d.p, h->d_wt.p, h->d_yt.p, h->d_grid.p, h->d_base.p, h->stream));
     KGWAS_HIP(launch_lmm_null(h->dm, h->d_d.p, h->d_wt.p, h->d_yt.p, h->d_grid.p, h->d_base.p, h->d_null.p, h->stream));
@@ -212,19 +221,40 @@ void kgwas::lmm::fit_null(kgwas_lmm* h, const double* y) {
     h->have_null = true;
 }
 
+// The REML null model of y on what fit_null left on the device (yt and the base sums): l0_reml, lambda0_reml, vg, ve.
+void kgwas::lmm::fit_null_reml(kgwas_lmm* h, const double* y) {
+    fit_null(h, y);
+    if (h->have_null_reml) return;
+    KGWAS_HIP(hipSetDevice(h->device));
+    h->ensure_wald();
+    KGWAS_HIP(launch_lmm_null_reml(h->dm, h->d_d.p, h->d_wt.p, h->d_yt.p, h->d_grid.p, h->d_base.p, h->d_null_reml.p, h->stream));
+    double out[4];
+    KGWAS_HIP(hipMemcpyAsync(out, h->d_null_reml.p, sizeof(out), hipMemcpyDeviceToHost, h->stream));
+    KGWAS_HIP(hipStreamSynchronize(h->stream));
+    h->l0_reml = out[0];
+    h->lambda0_reml = out[1];
+    h->vg = out[2];
+    h->ve = out[3];
+    h->have_null_reml = true;
+}
+
 // ---- the back-end steps. They launch on the handle's stream and time their stages; the caller issues the copies, synchronises
 // the stream and collects the times (h->timer.collect). ----
 
 // The single-phenotype back end over cc variants: rotate -> grid -> refine against the null model fit_null left; codes and vars
 // are on the device. Leaves d_lrt, d_lam, d_p. The caller has opened the rotation's interval (test_bed's prep falls into it).
-void kgwas::lmm::single_backend(kgwas_lmm* h, const uint8_t* codes, const LmmVariant* vars, uint32_t cc) {
+void kgwas::lmm::single_backend(kgwas_lmm* h, const uint8_t* codes, const LmmVariant* vars, uint32_t cc, bool wald) {
     hipStream_t st = h->stream;
     KGWAS_HIP(launch_lmm_rotate(codes, vars, cc, h->dm, h->d_U.p, h->d_Xt.p, st));
     h->timer.end(&kgwas_lmm_stats::rotate_ms, st);
     KGWAS_HIP(launch_lmm_grid(h->d_Xt.p, cc, h->dm, h->d_wt.p, h->d_yt.p, h->d_HB.p, h->d_G.p, st));
     h->timer.end(&kgwas_lmm_stats::grid_ms, st);
-    KGWAS_HIP(launch_lmm_refine(h->d_Xt.p, h->d_G.p, vars, cc, h->dm, h->d_d.p, h->d_wt.p, h->d_yt.p, h->d_grid.p, h->d_base.p, h->l0,
-                                h->d_lrt.p, h->d_lam.p, h->d_p.p, st));
+    if (wald)  // -lmm 4 (the caller has called ensure_wald): d_wald too
+        KGWAS_HIP(launch_lmm_refine_all(h->d_Xt.p, h->d_G.p, vars, cc, h->dm, h->d_d.p, h->d_wt.p, h->d_yt.p, h->d_grid.p, h->d_base.p, h->l0,
+                                        h->lambda0, h->d_lrt.p, h->d_lam.p, h->d_p.p, h->wald_out(), st));
+    else
+        KGWAS_HIP(launch_lmm_refine(h->d_Xt.p, h->d_G.p, vars, cc, h->dm, h->d_d.p, h->d_wt.p, h->d_yt.p, h->d_grid.p, h->d_base.p, h->l0,
+                                    h->d_lrt.p, h->d_lam.p, h->d_p.p, st));
     h->timer.end(&kgwas_lmm_stats::refine_ms, st);
 }
 
@@ -255,9 +285,10 @@ void kgwas::lmm::multi_block(kgwas_lmm* h, const LmmVariant* vars, uint32_t cc, 
 // ---- the .bed passes ----
 
 void kgwas::lmm::test_bed(kgwas_lmm* h, const double* y, const uint8_t* body, uint64_t nv, double maf, double miss, double* lrt,
-                          double* lam, double* p, double* af, uint32_t* n_miss, uint8_t* tested) {
+                          double* lam, double* p, double* af, uint32_t* n_miss, uint8_t* tested, const WaldArrays* wald) {
     fit_null(h, y);
     KGWAS_HIP(hipSetDevice(h->device));
+    if (wald) h->ensure_wald();
     hipStream_t st = h->stream;
     std::vector<LmmVariant> vars;
     for (uint64_t pos = 0; pos < nv; pos += h->chunk) {
@@ -265,7 +296,13 @@ void kgwas::lmm::test_bed(kgwas_lmm* h, const double* y, const uint8_t* body, ui
         KGWAS_HIP(hipMemcpyAsync(h->d_bed.p, body + pos * h->dm.bps, (size_t)c * h->dm.bps, hipMemcpyHostToDevice, st));
         h->timer.begin(st);
         KGWAS_HIP(launch_lmm_prep(h->d_bed.p, c, h->dm, maf, miss, h->d_codes.p, h->d_vars.p, st));
-        single_backend(h, h->d_codes.p, h->d_vars.p, c);
+        single_backend(h, h->d_codes.p, h->d_vars.p, c, wald != nullptr);
+        if (wald) {
+            double* const host[5] = {wald->beta, wald->se, wald->lam_remle, wald->p_wald, wald->p_score};
+            for (int a = 0; a < 5; a++)
+                if (host[a])
+                    KGWAS_HIP(hipMemcpyAsync(host[a] + pos, h->d_wald.p + (uint64_t)a * h->chunk, c * sizeof(double), hipMemcpyDeviceToHost, st));
+        }
         if (lrt) KGWAS_HIP(hipMemcpyAsync(lrt + pos, h->d_lrt.p, c * sizeof(double), hipMemcpyDeviceToHost, st));
         if (lam) KGWAS_HIP(hipMemcpyAsync(lam + pos, h->d_lam.p, c * sizeof(double), hipMemcpyDeviceToHost, st));
         if (p) KGWAS_HIP(hipMemcpyAsync(p + pos, h->d_p.p, c * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -360,6 +397,27 @@ int kgwas_lmm_test_bed(kgwas_lmm* h, const double* y, const uint8_t* bed_body, u
     return guarded([&] {
         if (!h || !y || (!bed_body && n_variants)) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_test_bed: null argument");
         test_bed(h, y, bed_body, n_variants, maf, miss, lrt, lambda, p, af, n_miss, tested);
+    });
+}
+
+int kgwas_lmm_null_reml(kgwas_lmm* h, const double* y, double* logl0_reml, double* lambda0_reml, double* vg, double* ve) {
+    return guarded([&] {
+        if (!h || !y) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_null_reml: null argument");
+        fit_null_reml(h, y);
+        if (logl0_reml) *logl0_reml = h->l0_reml;
+        if (lambda0_reml) *lambda0_reml = h->lambda0_reml;
+        if (vg) *vg = h->vg;
+        if (ve) *ve = h->ve;
+    });
+}
+
+int kgwas_lmm_test_bed_all(kgwas_lmm* h, const double* y, const uint8_t* bed_body, uint64_t n_variants, double maf, double miss, double* lrt,
+                           double* lambda_mle, double* p_lrt, double* beta, double* se, double* lambda_remle, double* p_wald,
+                           double* p_score, double* af, uint32_t* n_miss, uint8_t* tested) {
+    return guarded([&] {
+        if (!h || !y || (!bed_body && n_variants)) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_test_bed_all: null argument");
+        const WaldArrays w = {beta, se, lambda_remle, p_wald, p_score};
+        test_bed(h, y, bed_body, n_variants, maf, miss, lrt, lambda_mle, p_lrt, af, n_miss, tested, &w);
     });
 }
 

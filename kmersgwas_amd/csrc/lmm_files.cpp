@@ -7,6 +7,7 @@
 // run_file_multi: one bfile, several .fam columns with one missing set, one pass over the .bed (the shape of
 //            kmers_gwas.py:193-223);
 // run_table, run_table_multi: lmm_lrt --kmers_table, with -n and with --pheno_columns.
+// -lmm 4   : run_files with all_tests writes the 14-column file (format_assoc4) and four more lines in the log.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -16,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "fdist_tail.h"
 #include "kernels.h"
 #include "lmm_internal.h"
 
@@ -113,6 +115,22 @@ uint64_t format_assoc(const char* chr, const char* rs, const char* ps, uint32_t 
         len = snprintf(buf, sizeof(buf), "chr\trs\tps\tn_miss\tallele1\tallele0\taf\tl_mle\tp_lrt\n");
     else
         len = snprintf(buf, sizeof(buf), "%s\t%s\t%s\t%u\t%s\t%s\t%.3f\t%.6e\t%.6e\n", chr, rs, ps, n_miss, a1, a0, af, l_mle, p);
+    if (len < 0 || (size_t)len >= sizeof(buf)) throw Error(KGWAS_ERR_FORMAT, "a .bim line is too long");
+    if (out && cap >= (uint64_t)len) memcpy(out, buf, (size_t)len);
+    return (uint64_t)len;
+}
+
+// the -lmm 4 line: columns 1-7, l_mle and p_lrt with the bytes of format_assoc's
+uint64_t format_assoc4(const char* chr, const char* rs, const char* ps, uint32_t n_miss, const char* a1, const char* a0, double af,
+                       double beta, double se, double l_remle, double l_mle, double p_wald, double p_lrt, double p_score, char* out,
+                       uint64_t cap) {
+    char buf[1280];
+    int len;
+    if (!chr)
+        len = snprintf(buf, sizeof(buf), "chr\trs\tps\tn_miss\tallele1\tallele0\taf\tbeta\tse\tl_remle\tl_mle\tp_wald\tp_lrt\tp_score\n");
+    else
+        len = snprintf(buf, sizeof(buf), "%s\t%s\t%s\t%u\t%s\t%s\t%.3f\t%.6e\t%.6e\t%.6e\t%.6e\t%.6e\t%.6e\t%.6e\n", chr, rs, ps, n_miss, a1, a0,
+                       af, beta, se, l_remle, l_mle, p_wald, p_lrt, p_score);
     if (len < 0 || (size_t)len >= sizeof(buf)) throw Error(KGWAS_ERR_FORMAT, "a .bim line is too long");
     if (out && cap >= (uint64_t)len) memcpy(out, buf, (size_t)len);
     return (uint64_t)len;
@@ -222,6 +240,28 @@ uint64_t append_assoc(std::string& text, const std::vector<std::vector<std::stri
     return n_tested;
 }
 
+// -lmm 4: the header and the lines of the tested ones among fields.size() variants; returns their number
+struct WaldColumns {
+    std::vector<double> beta, se, lam, p_wald, p_score;
+    explicit WaldColumns(uint64_t m) : beta(m), se(m), lam(m), p_wald(m), p_score(m) {}
+    WaldArrays arrays() { return {beta.data(), se.data(), lam.data(), p_wald.data(), p_score.data()}; }
+};
+uint64_t append_assoc4(std::string& text, const std::vector<std::vector<std::string>>& fields, const uint32_t* n_miss, const double* af,
+                       const double* lam, const double* p, const WaldColumns& w, const uint8_t* tested) {
+    char line[1280];
+    text.append(line, format_assoc4(nullptr, "", "", 0, "", "", 0, 0, 0, 0, 0, 0, 0, 0, line, sizeof(line)));
+    uint64_t n_tested = 0;
+    for (uint64_t v = 0; v < fields.size(); v++) {
+        if (!tested[v]) continue;
+        const std::vector<std::string>& f = fields[v];
+        const uint64_t len = format_assoc4(f[0].c_str(), f[1].c_str(), f[3].c_str(), n_miss[v], f[4].c_str(), f[5].c_str(), af[v], w.beta[v],
+                                           w.se[v], w.lam[v], lam[v], w.p_wald[v], p[v], w.p_score[v], line, sizeof(line));
+        text.append(line, len);
+        n_tested++;
+    }
+    return n_tested;
+}
+
 void write_text(const std::string& path, const std::string& text, const char* mode) {
     FILE* fo = fopen(path.c_str(), mode);
     const bool ok = fo && fwrite(text.data(), 1, text.size(), fo) == text.size();
@@ -247,9 +287,26 @@ void write_log(const std::string& out, const std::string& base, const char* kins
     write_log_text(out, log, sizeof(log), ll);
 }
 
+// the log of -lmm 4: write_log's lines under its own title, with the REML null model's four behind logl_H0
+void write_log4(const std::string& out, const std::string& base, const char* kinship_path, uint64_t nf, uint64_t n, uint64_t M,
+                uint64_t n_tested, const kgwas_lmm* h, double rotate_ms, double grid_ms, double refine_ms, double total_ms) {
+    char log[1280];
+    const int ll = snprintf(log, sizeof(log),
+                            "lmm_lrt: ML likelihood-ratio test, REML Wald test and score test (-lmm 4)\nbfile\t%s\nkinship\t%s\n"
+                            "individuals_in_fam\t%llu\nindividuals_used\t%llu\nvariants_read\t%llu\nvariants_tested\t%llu\nlambda0\t%.6e\n"
+                            "logl_H0\t%.6f\nlambda0_remle\t%.6e\nlogl_remle_H0\t%.6f\nvg\t%.6e\nve\t%.6e\n"
+                            "ms: eigen=%.3f rotate=%.3f grid=%.3f refine=%.3f total=%.3f\n",
+                            base.c_str(), kinship_path, (unsigned long long)nf, (unsigned long long)n, (unsigned long long)M,
+                            (unsigned long long)n_tested, h->lambda0, h->l0, h->lambda0_reml, h->l0_reml, h->vg, h->ve, h->st.eigen_ms, rotate_ms,
+                            grid_ms, refine_ms, total_ms);
+    write_log_text(out, log, sizeof(log), ll);
+}
+
 void run_files(const char* kinship_path, uint64_t n_beds, const char* const* bases, const char* const* outs, uint32_t pheno_col,
-               double maf, double miss, double lmin, double lmax, uint64_t chunk_variants, int device, kgwas_lmm_stats* total) {
-    if (!kinship_path || (n_beds && (!bases || !outs))) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_run_files: null argument");
+               double maf, double miss, double lmin, double lmax, uint64_t chunk_variants, int device, kgwas_lmm_stats* total,
+               bool all_tests = false) {
+    if (!kinship_path || (n_beds && (!bases || !outs)))
+        throw Error(KGWAS_ERR_ARG, std::string(all_tests ? "kgwas_lmm_run_files_all" : "kgwas_lmm_run_files") + ": null argument");
     kgwas_lmm_stats sum{};
     std::vector<double> Kfull;
     Handle h;
@@ -280,6 +337,19 @@ void run_files(const char* kinship_path, uint64_t n_beds, const char* const* bas
         std::vector<uint32_t> n_miss(M);
         std::vector<uint8_t> tested(M);
         const kgwas_lmm_stats before = h->st;
+        if (all_tests) {
+            WaldColumns w(M);
+            const WaldArrays wa = w.arrays();
+            fit_null_reml(h.get(), y.data());
+            test_bed(h.get(), y.data(), body.data(), M, maf, miss, lrt.data(), lam.data(), p.data(), af.data(), n_miss.data(), tested.data(), &wa);
+            std::string text;
+            const uint64_t n_tested = append_assoc4(text, bim_fields(base, bim, 0, M, tested.data()), n_miss.data(), af.data(), lam.data(),
+                                                    p.data(), w, tested.data());
+            write_text(out, text, "wb");
+            write_log4(out, base, kinship_path, nf, n, M, n_tested, h.get(), h->st.rotate_ms - before.rotate_ms, h->st.grid_ms - before.grid_ms,
+                       h->st.refine_ms - before.refine_ms, now_ms() - t_start);
+            continue;
+        }
         test_bed(h.get(), y.data(), body.data(), M, maf, miss, lrt.data(), lam.data(), p.data(), af.data(), n_miss.data(), tested.data());
         std::string text = assoc_header();
         const uint64_t n_tested =
@@ -506,6 +576,13 @@ int kgwas_lmm_run_files(const char* kinship_path, uint64_t n_beds, const char* c
     return guarded([&] { run_files(kinship_path, n_beds, bfile_bases, out_paths, pheno_col, maf, miss, lmin, lmax, chunk_variants, device, total); });
 }
 
+int kgwas_lmm_run_files_all(const char* kinship_path, uint64_t n_beds, const char* const* bfile_bases, const char* const* out_paths,
+                            uint32_t pheno_col, double maf, double miss, double lmin, double lmax, uint64_t chunk_variants, int32_t device,
+                            kgwas_lmm_stats* total) {
+    return guarded(
+        [&] { run_files(kinship_path, n_beds, bfile_bases, out_paths, pheno_col, maf, miss, lmin, lmax, chunk_variants, device, total, true); });
+}
+
 int kgwas_lmm_run_file_multi(const char* kinship_path, const char* bfile_base, uint32_t n_cols, const uint32_t* pheno_cols,
                              const char* const* out_paths, double maf, double miss, double lmin, double lmax, uint64_t chunk_variants,
                              int32_t device, kgwas_lmm_stats* total) {
@@ -563,5 +640,18 @@ uint64_t kgwas_lmm_format_assoc(const char* chr, const char* rs, const char* ps,
     });
     return need;
 }
+
+uint64_t kgwas_lmm_format_assoc4(const char* chr, const char* rs, const char* ps, uint32_t n_miss, const char* allele1, const char* allele0,
+                                 double af, double beta, double se, double l_remle, double l_mle, double p_wald, double p_lrt, double p_score,
+                                 char* out, uint64_t cap) {
+    uint64_t need = 0;
+    guarded([&] {
+        if (chr && (!rs || !ps || !allele1 || !allele0)) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_format_assoc4: null argument");
+        need = format_assoc4(chr, rs, ps, n_miss, allele1, allele0, af, beta, se, l_remle, l_mle, p_wald, p_lrt, p_score, out, cap);
+    });
+    return need;
+}
+
+double kgwas_fdist_tail(double F, double df) { return kgwas::fdist_tail(F, df); }
 
 }  // extern "C"

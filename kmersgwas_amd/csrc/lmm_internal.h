@@ -44,6 +44,8 @@ struct kgwas_lmm {
     std::vector<double> y_cur;
     bool have_null = false;
     double l0 = 0, lambda0 = 0;
+    bool have_null_reml = false;  // -lmm 4: the REML null model of y_cur (fit_null_reml); falls with have_null
+    double l0_reml = 0, lambda0_reml = 0, vg = 0, ve = 0;
     kgwas_lmm_stats st{};
     bool on_device = false;
     LmmStageTimer timer;
@@ -68,6 +70,13 @@ struct kgwas_lmm {
     kgwas::DevBuf<kgwas::LmmTableRecord> d_sel_rec;
     kgwas::PinBuf<kgwas::LmmTableRecord> h_sel_rec;
     void ensure_select();
+    // ensure_wald, -lmm 4: per chunk beta, se, l_remle, p_wald, p_score ([5][chunk]); the REML null model's four numbers
+    bool have_wald = false;
+    kgwas::DevBuf<double> d_wald, d_null_reml;
+    void ensure_wald();
+    kgwas::LmmWaldOut wald_out() const {
+        return {d_wald.p, d_wald.p + chunk, d_wald.p + 2 * (uint64_t)chunk, d_wald.p + 3 * (uint64_t)chunk, d_wald.p + 4 * (uint64_t)chunk};
+    }
     kgwas::Stream stream;  // (behind the buffers its work reads and writes: it goes first)
     ~kgwas_lmm() {
         if (on_device) (void)hipSetDevice(device);  // (before any member is released)
@@ -92,14 +101,20 @@ inline double now_ms() { return std::chrono::duration<double, std::milli>(std::c
 // ---- lmm.cpp: the session and the .bed passes (what each does stands at its definition) ----
 kgwas_lmm* create(uint64_t n, const double* K, int device, double lmin, double lmax, uint64_t chunk_variants);
 void fit_null(kgwas_lmm* h, const double* y);
+// -lmm 4's five further outputs of a .bed pass (host arrays over all variants; any may be null). With `wald` the pass runs the
+// -lmm 4 refinement; lrt, lam, p, af, n_miss and tested are the same either way.
+struct WaldArrays {
+    double *beta, *se, *lam_remle, *p_wald, *p_score;
+};
+void fit_null_reml(kgwas_lmm* h, const double* y);
 void test_bed(kgwas_lmm* h, const double* y, const uint8_t* body, uint64_t nv, double maf, double miss, double* lrt, double* lam,
-              double* p, double* af, uint32_t* n_miss, uint8_t* tested);
+              double* p, double* af, uint32_t* n_miss, uint8_t* tested, const WaldArrays* wald = nullptr);
 void multi_prepare(kgwas_lmm* h, uint32_t n_pheno, const double* Y, double* logl0, double* lambda0,
                    const char* who = "kgwas_lmm_test_bed_multi");
 void multi_run(kgwas_lmm* h, uint32_t n_pheno, const uint8_t* body, uint64_t nv, double maf, double miss, double* lrt, double* lam,
                double* p, double* af, uint32_t* n_miss, uint8_t* tested);
 // ---- lmm.cpp: the back-end steps the .bed passes share with the table route ----
-void single_backend(kgwas_lmm* h, const uint8_t* codes, const LmmVariant* vars, uint32_t cc);
+void single_backend(kgwas_lmm* h, const uint8_t* codes, const LmmVariant* vars, uint32_t cc, bool wald = false);
 void multi_front(kgwas_lmm* h, const uint8_t* codes, const LmmVariant* vars, uint32_t cc);
 void multi_block(kgwas_lmm* h, const LmmVariant* vars, uint32_t cc, uint32_t p0, uint32_t pb);
 // ---- lmm_table.cpp ----

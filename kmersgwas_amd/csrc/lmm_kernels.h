@@ -59,6 +59,17 @@ hipError_t launch_lmm_null_multi(LmmDims dm, const double* d, const double* wt, 
 hipError_t launch_lmm_refine(const double* Xt, const double* G, const LmmVariant* vars, uint32_t nv, LmmDims dm, const double* d,
                              const double* wt, const double* yt, const double* lambda, const double* base, double l0, double* lrt,
                              double* lam, double* p, hipStream_t st);
+// -lmm 4. The REML null model of yt: out[0..4) = lR0, lambda0_remle, vg, ve
+hipError_t launch_lmm_null_reml(LmmDims dm, const double* d, const double* wt, const double* yt, const double* lambda, const double* base,
+                                double* out, hipStream_t st);
+// -lmm 4. launch_lmm_refine's lrt, lam and p with their bits, and per tested variant the REML effect estimate, its standard error,
+// l_remle, the Wald p (both at l_remle) and the score p at lam0, the null model's ML lambda (NaN for the others)
+struct LmmWaldOut {
+    double *beta, *se, *lam, *p_wald, *p_score;
+};
+hipError_t launch_lmm_refine_all(const double* Xt, const double* G, const LmmVariant* vars, uint32_t nv, LmmDims dm, const double* d,
+                                 const double* wt, const double* yt, const double* lambda, const double* base, double l0, double lam0,
+                                 double* lrt, double* lam, double* p, LmmWaldOut w, hipStream_t st);
 // the same per (variant, column) of a block of np <= LMM_PBLOCK columns, results at [p][v] (row stride nv); Yt, base and null
 // (pairs l0, lambda0) start at the block's first column
 hipError_t launch_lmm_refine_multi(const double* Xt, const double* Gx, const double* Gxy, const LmmVariant* vars, uint32_t nv, LmmDims dm,

@@ -22,11 +22,16 @@
 //                      every third one a bisection) whose sums run over i with lanes striding and a fixed butterfly; the
 //                      evaluated point with the smallest |dl/dt| is the interval's candidate. Both ends and every such point
 //                      are candidates; the largest l wins, the earliest on a tie.
+//   lmm_null_reml_kernel / lmm_refine_all_kernel   -lmm 4: the same maximisation of the REML likelihood (a compile-time switch of
+//                      ll_from_sums and maximise; the ML instantiations are the code they were), then beta, se, the Wald and the
+//                      score statistic from direct_sums at l_remle and at lambda0, and their F(1, n - 2) tails (fdist_tail.h).
 // Nothing here depends on a variant's neighbours or uses an atomic: a variant's numbers are the same in any batch.
 //
 // f64 MFMA layout (16x16x4): lane l holds A[row l & 15][k l >> 4] and B[k l >> 4][col l & 15]; result register j of lane l is
 // D[row (l >> 4) + 4 j][col l & 15] - not the f32 forms' 4 (l >> 4) + j.
 #include "lmm_kernels.h"
+
+#include "fdist_tail.h"
 
 namespace kgwas {
 
@@ -239,21 +244,34 @@ struct Sums {
     double xx, xw, xy, dxx, dxw, dxy;
 };
 
-// l and dl/dt from the weighted sums
-template <bool HAS_X>
+// l and dl/dt from the weighted sums. REML = false: the ML likelihood above. REML = true: the restricted likelihood of -lmm 4,
+//     lR(lambda) = df/2 (log(df / 2 pi) - 1) + 1/2 sum log h_i - 1/2 log |X^T H X| - df/2 log RSS,  df = n - 1 (H0) or n - 2 (H1),
+// X = [wt] or [wt xt], |X^T H X| = ww or ww xx.w; its derivative adds -1/2 d log |X^T H X| / dt, from the h' sums.
+template <bool HAS_X, bool REML = false>
 __device__ inline void ll_from_sums(const Sums& s, double n, double& l, double& dl) {
     const double bw0 = s.wy / s.ww;
     double rss = s.yy - s.wy * bw0, drss;
+    double det = s.ww, ddet = s.dww;  // |X^T H X| and its derivative (REML)
     if (HAS_X) {
         const double xxw = s.xx - s.xw * s.xw / s.ww, xyw = s.xy - s.xw * bw0;
         const double bx = xyw / xxw, bw = (s.wy - s.xw * bx) / s.ww;
         rss -= xyw * bx;
         drss = s.dyy - 2.0 * (bw * s.dwy + bx * s.dxy) + bw * bw * s.dww + 2.0 * bw * bx * s.dxw + bx * bx * s.dxx;
+        if (REML) {
+            det = s.ww * xxw;
+            ddet = s.dww * s.xx + s.dxx * s.ww - 2.0 * s.dxw * s.xw;
+        }
     } else {
         drss = s.dyy - 2.0 * bw0 * s.dwy + bw0 * bw0 * s.dww;
     }
-    l = 0.5 * n * (log(n / 6.283185307179586476925) - 1.0) + 0.5 * s.slog - 0.5 * n * log(rss);
-    dl = 0.5 * (s.sh - n) - 0.5 * n * drss / rss;
+    if (REML) {
+        const double df = n - (HAS_X ? 2.0 : 1.0);
+        l = 0.5 * df * (log(df / 6.283185307179586476925) - 1.0) + 0.5 * s.slog - 0.5 * log(det) - 0.5 * df * log(rss);
+        dl = 0.5 * (s.sh - n) - 0.5 * ddet / det - 0.5 * df * drss / rss;
+    } else {
+        l = 0.5 * n * (log(n / 6.283185307179586476925) - 1.0) + 0.5 * s.slog - 0.5 * n * log(rss);
+        dl = 0.5 * (s.sh - n) - 0.5 * n * drss / rss;
+    }
 }
 
 // the sums at one lambda, over i with lanes striding; every lane gets them
@@ -294,8 +312,8 @@ __device__ inline Sums direct_sums(double lam, uint32_t n, const double* __restr
 
 // One wave (a block of 64): the maximum of l over the grid's ends and the refined interior points. grid = lambda[101], then
 // t[101] = log lambda. Gx = the variant's xt^2 and xt wt rows of the grid sums, Gxy = its xt yt row (HAS_X). s_l, s_dl: LMM_GRID
-// doubles of LDS each.
-template <bool HAS_X>
+// doubles of LDS each. REML: the objective of ll_from_sums; the sums, the steps and the rules are the same.
+template <bool HAS_X, bool REML = false>
 __device__ void maximise(uint32_t n, const double* __restrict__ d, const double* __restrict__ wt, const double* __restrict__ yt,
                          const double* __restrict__ xt, const double* __restrict__ Gx, const double* __restrict__ Gxy,
                          const double* __restrict__ grid, const double* __restrict__ base, double* s_l, double* s_dl, double& best_l,
@@ -308,7 +326,7 @@ __device__ void maximise(uint32_t n, const double* __restrict__ d, const double*
             s.xx = Gx[g], s.xw = Gx[LMM_HB_COLS + g], s.xy = Gxy[g];
             s.dxx = Gx[LMM_GRID + g], s.dxw = Gx[LMM_HB_COLS + LMM_GRID + g], s.dxy = Gxy[LMM_GRID + g];
         }
-        ll_from_sums<HAS_X>(s, nd, s_l[g], s_dl[g]);
+        ll_from_sums<HAS_X, REML>(s, nd, s_l[g], s_dl[g]);
     }
     __syncthreads();
     best_l = s_l[0];
@@ -330,7 +348,7 @@ __device__ void maximise(uint32_t n, const double* __restrict__ d, const double*
             if (step % 3 == 2 || !(tm > ta && tm < tb)) tm = 0.5 * (ta + tb);
             const Sums s = direct_sums<HAS_X, false>(exp(tm), n, d, wt, yt, xt);
             double l, dl;
-            ll_from_sums<HAS_X>(s, nd, l, dl);
+            ll_from_sums<HAS_X, REML>(s, nd, l, dl);
             if (fabs(dl) < f_best) {
                 f_best = fabs(dl);
                 t_best = tm;
@@ -349,7 +367,7 @@ __device__ void maximise(uint32_t n, const double* __restrict__ d, const double*
         const double lam = exp(t_best);
         const Sums s = direct_sums<HAS_X, true>(lam, n, d, wt, yt, xt);
         double l, dl;
-        ll_from_sums<HAS_X>(s, nd, l, dl);
+        ll_from_sums<HAS_X, REML>(s, nd, l, dl);
         if (l > best_l) {
             best_l = l;
             best_lam = lam;
@@ -418,6 +436,79 @@ __global__ void __launch_bounds__(64) lmm_refine_multi_kernel(const double* __re
         lrt[o] = stat;
         lam_out[o] = lam;
         p_out[o] = erfc(sqrt(0.5 * stat));
+    }
+}
+
+// -lmm 4. The REML null model: out = (lR0, lambda0_remle, vg, ve), ve = yy.w / (n - 1) and vg = lambda ve at the maximiser.
+__global__ void __launch_bounds__(64) lmm_null_reml_kernel(LmmDims dm, const double* __restrict__ d, const double* __restrict__ wt,
+                                                           const double* __restrict__ yt, const double* __restrict__ grid,
+                                                           const double* __restrict__ base, double* __restrict__ out) {
+    __shared__ double s_l[LMM_GRID], s_dl[LMM_GRID];
+    double l, lam;
+    maximise<false, true>(dm.n, d, wt, yt, nullptr, nullptr, nullptr, grid, base, s_l, s_dl, l, lam);
+    const Sums s = direct_sums<false, false>(lam, dm.n, d, wt, yt, nullptr);
+    if (threadIdx.x == 0) {
+        const double ve = (s.yy - s.wy * (s.wy / s.ww)) / ((double)dm.n - 1.0);
+        out[0] = l;
+        out[1] = lam;
+        out[2] = lam * ve;
+        out[3] = ve;
+    }
+}
+
+// The Schur complements after w of the sums at one lambda
+struct AfterW {
+    double xx, xy, yy;
+};
+__device__ inline AfterW after_w(const Sums& s) {
+    const double bw0 = s.wy / s.ww;
+    return {s.xx - s.xw * s.xw / s.ww, s.xy - s.xw * bw0, s.yy - s.wy * bw0};
+}
+
+// -lmm 4, one wave per variant: lmm_refine_kernel's ML maximisation (the same call on the same rows: lrt, lambda and p keep their
+// bits), then the REML maximisation over the same rows of G and base in the same LDS, then the sums at l_remle (Wald) and at the
+// null model's ML lambda0 (score). Lane 0 closes the Wald test and lane 1 the score test, so the two tails run side by side.
+__global__ void __launch_bounds__(64) lmm_refine_all_kernel(const double* __restrict__ Xt, const double* __restrict__ G,
+                                                            const LmmVariant* __restrict__ vars, LmmDims dm, const double* __restrict__ d,
+                                                            const double* __restrict__ wt, const double* __restrict__ yt,
+                                                            const double* __restrict__ grid, const double* __restrict__ base, double l0,
+                                                            double lam0, double* __restrict__ lrt, double* __restrict__ lam_out,
+                                                            double* __restrict__ p_out, LmmWaldOut w) {
+    __shared__ double s_l[LMM_GRID], s_dl[LMM_GRID];
+    const uint32_t v = blockIdx.x;
+    if (!vars[v].tested) {  // (the whole block leaves)
+        if (threadIdx.x == 0)
+            lrt[v] = lam_out[v] = p_out[v] = w.beta[v] = w.se[v] = w.lam[v] = w.p_wald[v] = w.p_score[v] = __builtin_nan("");
+        return;
+    }
+    double l, lam;
+    const double* Gv = G + (uint64_t)v * 3 * LMM_HB_COLS;
+    const double* xt = Xt + (uint64_t)v * dm.ldi;
+    maximise<true>(dm.n, d, wt, yt, xt, Gv, Gv + 2 * LMM_HB_COLS, grid, base, s_l, s_dl, l, lam);
+    if (threadIdx.x == 0) {
+        const double stat = fmax(0.0, 2.0 * (l - l0));
+        lrt[v] = stat;
+        lam_out[v] = lam;
+        p_out[v] = erfc(sqrt(0.5 * stat));
+    }
+    __syncthreads();  // (s_l and s_dl are written again)
+    double lr, lamr;
+    maximise<true, true>(dm.n, d, wt, yt, xt, Gv, Gv + 2 * LMM_HB_COLS, grid, base, s_l, s_dl, lr, lamr);
+    const AfterW a = after_w(direct_sums<true, false>(lamr, dm.n, d, wt, yt, xt));
+    const AfterW a0 = after_w(direct_sums<true, false>(lam0, dm.n, d, wt, yt, xt));
+    if (threadIdx.x >= 2) return;
+    const double nd = (double)dm.n, df = nd - 2.0;
+    const double beta = a.xy / a.xx, rss1 = a.yy - a.xy * beta;
+    // F_wald = (yy.w - RSS1) df / RSS1 with yy.w - RSS1 = xy.w beta taken as the product it is: (beta / se)^2 to a few ulps
+    const double F = threadIdx.x == 0 ? a.xy * beta * df / rss1 : nd * a0.xy * a0.xy / (a0.xx * a0.yy);
+    const double p = fdist_tail(F, df);
+    if (threadIdx.x == 0) {
+        w.beta[v] = beta;
+        w.se[v] = sqrt(rss1 / (df * a.xx));
+        w.lam[v] = lamr;
+        w.p_wald[v] = p;
+    } else {
+        w.p_score[v] = p;
     }
 }
 
@@ -492,6 +583,20 @@ hipError_t launch_lmm_refine(const double* Xt, const double* G, const LmmVariant
                              double* lam, double* p, hipStream_t st) {
     if (!nv) return hipSuccess;
     hipLaunchKernelGGL(lmm_refine_kernel, dim3(nv), dim3(64), 0, st, Xt, G, vars, dm, d, wt, yt, grid, base, l0, lrt, lam, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_lmm_null_reml(LmmDims dm, const double* d, const double* wt, const double* yt, const double* grid, const double* base,
+                                double* out, hipStream_t st) {
+    hipLaunchKernelGGL(lmm_null_reml_kernel, dim3(1), dim3(64), 0, st, dm, d, wt, yt, grid, base, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_lmm_refine_all(const double* Xt, const double* G, const LmmVariant* vars, uint32_t nv, LmmDims dm, const double* d,
+                                 const double* wt, const double* yt, const double* grid, const double* base, double l0, double lam0,
+                                 double* lrt, double* lam, double* p, LmmWaldOut w, hipStream_t st) {
+    if (!nv) return hipSuccess;
+    hipLaunchKernelGGL(lmm_refine_all_kernel, dim3(nv), dim3(64), 0, st, Xt, G, vars, dm, d, wt, yt, grid, base, l0, lam0, lrt, lam, p, w);
     return hipGetLastError();
 }
 

@@ -542,6 +542,29 @@ class LmmLrt:
                                      ptr(n_miss), ptr(tested)))
         return {"lrt": lrt, "lambda": lam, "p": p, "af": af, "n_miss": n_miss, "tested": tested.astype(bool)}
 
+    def null_reml(self, y):
+        """The null model by REML (`-lmm 4`): (log restricted likelihood, lambda, vg, ve), ve = yy.w / (n - 1) and vg = lambda ve
+        at the maximiser - emma.REMLE's vg and ve."""
+        v = [C.c_double() for _ in range(4)]
+        check(lib.kgwas_lmm_null_reml(self._h, ptr(self._y(y)), *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def test_all(self, bed, y, maf: float = 0.0, miss: float = 1.0):
+        """test with the numbers of `-lmm 4` beside the LRT: beta (the REML effect estimate per unit of the decoded dosage), se,
+        lambda_remle, p_wald (both tests at lambda_remle) and p_score (at the null model's ML lambda). lrt, lambda, p, af, n_miss and
+        tested have the bits test gives; all eight statistics are NaN where tested is False."""
+        bps = (self.n + 3) // 4
+        body = np.frombuffer(bed, np.uint8) if isinstance(bed, (bytes, bytearray, memoryview)) else np.ascontiguousarray(bed, np.uint8)
+        if body.size % bps:
+            raise ValueError("the .bed body is not a whole number of variants of %d bytes" % bps)
+        m = body.size // bps
+        lrt, lam, p, beta, se, lam_r, p_wald, p_score, af = (np.zeros(m) for _ in range(9))
+        n_miss, tested = np.zeros(m, np.uint32), np.zeros(m, np.uint8)
+        check(lib.kgwas_lmm_test_bed_all(self._h, ptr(self._y(y)), ptr(body), m, maf, miss, ptr(lrt), ptr(lam), ptr(p), ptr(beta), ptr(se),
+                                         ptr(lam_r), ptr(p_wald), ptr(p_score), ptr(af), ptr(n_miss), ptr(tested)))
+        return {"lrt": lrt, "lambda": lam, "p": p, "beta": beta, "se": se, "lambda_remle": lam_r, "p_wald": p_wald, "p_score": p_score,
+                "af": af, "n_miss": n_miss, "tested": tested.astype(bool)}
+
     def test_bed_multi(self, Y, bed, maf: float = 0.0, miss: float = 1.0):
         """Y: (P, n), P phenotype columns tested against one .bed body (as in test) in one pass over it. Returns a dict of
         numpy arrays: lrt, lambda, p of shape (P, M), logl0, lambda0 of shape (P,), af, n_miss, tested of shape (M,). Every value
