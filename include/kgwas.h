@@ -235,7 +235,8 @@ typedef struct kgwas_scan_stats {
  * Version 14: no struct changed; new entry points kgwas_lmm_test_bed_multi, kgwas_lmm_run_file_multi (lmm_lrt --columns).
  * Version 15: no struct changed; new entry points kgwas_lmm_test_table, kgwas_lmm_run_table (lmm_lrt --kmers_table), and later,
  * without a new version number, kgwas_lmm_test_table_multi, kgwas_lmm_run_table_multi (lmm_lrt --kmers_table --pheno_columns), and
- * kgwas_lmm_null_reml, kgwas_lmm_test_bed_all, kgwas_lmm_run_files_all, kgwas_lmm_format_assoc4, kgwas_fdist_tail (lmm_lrt -lmm 4).
+ * kgwas_lmm_null_reml, kgwas_lmm_test_bed_all, kgwas_lmm_run_files_all, kgwas_lmm_format_assoc4, kgwas_fdist_tail (lmm_lrt -lmm 4),
+ * and kgwas_lmm_set_covariates, kgwas_lmm_read_covariates, kgwas_lmm_run_files_cov, kgwas_lmm_run_table_cov (lmm_lrt -c).
  * Those came after version 15 without a bump: a caller that may meet an older version-15 library probes for them by symbol
  * (dlsym, or hasattr on a ctypes handle). */
 #define KGWAS_ABI_VERSION 15
@@ -667,6 +668,29 @@ void kgwas_snpkin_close(kgwas_snpkin* h);
  *            subnormal or 0, which parses back).
  * fdist_tail: Q(F; 1, df) = I_x(df / 2, 1 / 2), x = df / (df + F): the tail both tests use, the host instance of the function the
  *            kernel calls (no GPU). F <= 0 -> 1; relative error below 1e-9 for df <= 65533 also where p is tiny.
+ *
+ * Covariates (after ABI version 15, no bump: probe by symbol). The model y = W a + x b + u + e with W (n x q, 1 <= q <= 8) in place
+ * of W = 1. The column space of W must hold the constant vector (give W a column of 1s). Every n - 1 above becomes n - q and every
+ * n - 2 becomes n - q - 1: the REML df, ve = RSS0 / (n - q), the F(1, n - q - 1) tails. n >= q + 2.
+ * set_covariates: W[n][q] row-major for every later kgwas_lmm_null, _null_reml, _test_bed, _test_bed_all and _test_table on the
+ *            handle; q = 0 restores W = 1 and the bits of a handle that never had covariates. W is replaced by an orthonormal
+ *            basis of its columns (modified Gram-Schmidt, in column order), so every output but logl0_reml is the same for W and
+ *            W A, A invertible, to rounding; logl0_reml is the restricted likelihood of W as given. Refused (KGWAS_ERR_ARG, nothing
+ *            changed): q > 8, a value that is not finite, n < q + 2, a column whose remainder after the columns before it is
+ *            <= 1e-8 of its norm (rank), a constant vector whose remainder is > 1e-8 sqrt(n) (span). The cached null models are
+ *            forgotten. A variant that lies in the span of W to rounding has no test and is not detected. The multi-phenotype
+ *            passes (kgwas_lmm_test_bed_multi, kgwas_lmm_test_table_multi) refuse a handle with covariates.
+ * read_covariates: GEMMA's -c file (no GPU): one row per individual, whitespace-separated numbers, NA for a missing value, every
+ *            row with the same number of fields. *q_out = q always. values[row][q] (NaN where NA) and keep[row] (0 where the row
+ *            has an NA; one byte per row) are written when rows * q <= cap, cap counting the doubles of `values`; otherwise
+ *            neither is touched. The call does not return the number of rows: pass it as n_expected (a file with another number
+ *            is refused) and size both arrays by it; n_expected == 0 accepts any number and is of use only to learn q. Lines
+ *            that are empty or hold only blanks are skipped and do not count as rows, as in the kinship and .fam parsers, so a
+ *            stray blank line shifts nothing but a lost row does: the row count against n_expected is the check for that.
+ * run_files_cov: run_files (all_tests = 0) or run_files_all (all_tests != 0) with covar_path, rows in .fam order: an individual is
+ *            used iff its phenotype is present and no covariate is NA. The log gains the lines covariates and n_covariates behind
+ *            kinship. covar_path == NULL: exactly run_files / run_files_all.
+ * run_table_cov: run_table with covar_path, one row per accession of the phenotype file in its order; NA is refused.
  * ---------------------------------------------------------------------------------- */
 typedef struct kgwas_lmm kgwas_lmm;
 typedef struct kgwas_lmm_stats {
@@ -717,6 +741,14 @@ uint64_t kgwas_lmm_format_assoc4(const char* chr, const char* rs, const char* ps
                                  double af, double beta, double se, double l_remle, double l_mle, double p_wald, double p_lrt, double p_score,
                                  char* out, uint64_t cap);
 double kgwas_fdist_tail(double F, double df);
+int kgwas_lmm_set_covariates(kgwas_lmm* h, uint32_t q, const double* W);
+int kgwas_lmm_read_covariates(const char* path, uint64_t n_expected, uint64_t cap, double* values, uint8_t* keep, uint32_t* q_out);
+int kgwas_lmm_run_files_cov(const char* kinship_path, const char* covar_path, uint64_t n_beds, const char* const* bfile_bases,
+                            const char* const* out_paths, uint32_t pheno_col, double maf, double miss, double lmin, double lmax,
+                            uint64_t chunk_variants, int32_t device, int32_t all_tests, kgwas_lmm_stats* total);
+int kgwas_lmm_run_table_cov(const char* kinship_path, const char* covar_path, const char* table_base, uint32_t kmer_len,
+                            const char* pheno_path, uint32_t pheno_col, uint64_t mac, double maf, uint64_t best_n, double lmin, double lmax,
+                            uint64_t chunk_variants, int32_t device, const char* out_path, kgwas_lmm_stats* total);
 
 /* ------------------------------------------------------------------------------------
  * Seeded synthetic table rows: kmer = row + 1, per-row frequency q/256 with

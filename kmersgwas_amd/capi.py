@@ -47,6 +47,7 @@ SYMBOLS = [
     "kgwas_lmm_test_table_multi", "kgwas_lmm_run_table_multi",
     "kgwas_lmm_destroy", "kgwas_lmm_read_kinship", "kgwas_lmm_read_fam", "kgwas_lmm_format_assoc",
     "kgwas_lmm_null_reml", "kgwas_lmm_test_bed_all", "kgwas_lmm_run_files_all", "kgwas_lmm_format_assoc4", "kgwas_fdist_tail",
+    "kgwas_lmm_set_covariates", "kgwas_lmm_read_covariates", "kgwas_lmm_run_files_cov", "kgwas_lmm_run_table_cov",
     "kgwas_synth_rows_device", "kgwas_synth_rows_host",
 ]
 
@@ -294,6 +295,13 @@ lib.kgwas_lmm_format_assoc4.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, _u32
 lib.kgwas_lmm_format_assoc4.restype = _u64
 lib.kgwas_fdist_tail.argtypes = [_dbl, _dbl]
 lib.kgwas_fdist_tail.restype = _dbl
+# covariates (-c): added after ABI version 15 without a bump
+lib.kgwas_lmm_set_covariates.argtypes = [_vp, _u32, _vp]
+lib.kgwas_lmm_read_covariates.argtypes = [C.c_char_p, _u64, _u64, _vp, _vp, C.POINTER(_u32)]
+lib.kgwas_lmm_run_files_cov.argtypes = [C.c_char_p, C.c_char_p, _u64, _pstr, _pstr, _u32, _dbl, _dbl, _dbl, _dbl, _u64, _i32, _i32,
+                                        C.POINTER(LmmStats)]
+lib.kgwas_lmm_run_table_cov.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, _u32, C.c_char_p, _u32, _u64, _dbl, _u64, _dbl, _dbl, _u64, _i32,
+                                        C.c_char_p, C.POINTER(LmmStats)]
 lib.kgwas_synth_rows_device.argtypes = [_vp, _u64, _u64, _u64, _u64, _vp]
 lib.kgwas_synth_rows_host.argtypes = [_vp, _u64, _u64, _u64, _u64]
 

@@ -14,6 +14,8 @@
 // to D/name.assoc.txt with a log (kgwas_lmm_run_table_multi): what calc_best_pvals / get_threshold_from_perm read.
 // -lmm 4 (with -bfile or --bfiles only) writes chr rs ps n_miss allele1 allele0 af beta se l_remle l_mle p_wald p_lrt p_score: the
 // REML effect estimate, its standard error, the Wald and the score test beside the LRT (kgwas_lmm_run_files_all).
+// -c FILE (with -bfile, --bfiles or --kmers_table -n; -lmm 2 or 4) gives the model covariates beside the variant, GEMMA's format: one
+// row per individual (.fam lines, or the accessions of PHENO), whitespace-separated numbers, NA missing, a column of 1s among them.
 #include <sys/stat.h>
 
 #include <cstdlib>
@@ -31,7 +33,7 @@ using namespace std;
 
 static void usage(const char* prog) {
     cerr << "usage: " << prog
-         << " -bfile B [--columns LIST] | --bfiles LIST  -lmm 2|4  -k KINSHIP  [-outdir D] [-o NAME] [-n i] [-maf f] [-miss f] [-lmin x] [-lmax x]\n"
+         << " -bfile B [--columns LIST] | --bfiles LIST  -lmm 2|4  -k KINSHIP  [-c COVARIATES] [-outdir D] [-o NAME] [-n i] [-maf f] [-miss f] [-lmin x] [-lmax x]\n"
             "  -bfile B       PLINK base name (B.bed, B.bim, B.fam)\n"
             "  --bfiles LIST  file of 'bfile<TAB>name' lines: every bfile is tested, output D/name.assoc.txt\n"
             "  --columns LIST file of 'col<TAB>name' lines, with -bfile: every listed phenotype column of B.fam (from 1) is tested in\n"
@@ -41,13 +43,17 @@ static void usage(const char* prog) {
             "                 p_score (with -bfile or --bfiles; not with --columns, --kmers_table or --pheno_columns). -lmm 1 and -lmm 3\n"
             "                 are not built as formats of their own: their columns are in the -lmm 4 file\n"
             "  -k FILE        kinship matrix, text, one row per .fam line\n"
+            "  -c FILE        covariates, text: one row per .fam line (with --kmers_table: per accession of PHENO), up to 8 numbers per\n"
+            "                 row, NA for a missing value; the columns must span the constant (give a column of 1s). An individual is used\n"
+            "                 iff its phenotype is present and no covariate is NA (NA is refused with --kmers_table). Not with --columns\n"
+            "                 or --pheno_columns\n"
             "  -outdir D      output directory (default ./output), -o NAME output prefix (default result)\n"
             "  -n i           phenotype column of the .fam, from 1 (default 1)\n"
             "  -maf f         minor allele frequency filter (default 0.01), -miss f missingness filter (default 0.05)\n"
             "  -lmin x, -lmax x  search range of lambda (defaults 1e-5, 1e5)\n"
             "or, every k-mer of a k-mers table (no PLINK files in between):\n"
             "       " << prog
-         << " --kmers_table T --kmers_len K -p PHENO  -lmm 2  -k KINSHIP  [--mac M] [-maf f] [--best N] [-n i | --pheno_columns LIST]\n"
+         << " --kmers_table T --kmers_len K -p PHENO  -lmm 2  -k KINSHIP  [-c COVARIATES] [--mac M] [-maf f] [--best N] [-n i | --pheno_columns LIST]\n"
             "       [-outdir D] [-o NAME]\n"
             "       [-lmin x] [-lmax x] [--chunk_variants c] [--device d]\n"
             "  --kmers_table T  k-mers table base name (T.table, T.names); excludes -bfile, --bfiles and --columns\n"
@@ -151,7 +157,9 @@ static int table_mode(map<string, string>& a, const char* prog) {
     const double maf = a.count("maf") ? num("-maf", a["maf"]) : 0.01;
     if (a.count("miss")) (void)num("-miss", a["miss"]);
     const double lmin = a.count("lmin") ? num("-lmin", a["lmin"]) : 1e-5, lmax = a.count("lmax") ? num("-lmax", a["lmax"]) : 1e5;
-    for (const string& f : {a["kmers_table"] + ".names", a["kmers_table"] + ".table", a["p"], a["k"]}) {
+    vector<string> inputs = {a["kmers_table"] + ".names", a["kmers_table"] + ".table", a["p"], a["k"]};
+    if (a.count("c")) inputs.push_back(a["c"]);
+    for (const string& f : inputs) {
         ifstream probe(f);
         if (!probe.good()) {
             cerr << "Couldn't find file: " << f << endl;
@@ -170,7 +178,9 @@ static int table_mode(map<string, string>& a, const char* prog) {
     vector<const char*> op;
     for (const string& o : outs) op.push_back(o.c_str());
     kgwas_lmm_stats st{};
-    const int rc = columns.empty() ? kgwas_lmm_run_table(a["k"].c_str(), a["kmers_table"].c_str(), (uint32_t)klen, a["p"].c_str(), (uint32_t)col,
+    const int rc = a.count("c")    ? kgwas_lmm_run_table_cov(a["k"].c_str(), a["c"].c_str(), a["kmers_table"].c_str(), (uint32_t)klen, a["p"].c_str(),
+                                                             (uint32_t)col, mac, maf, best, lmin, lmax, chunk, (int32_t)device, op[0], &st)
+                   : columns.empty() ? kgwas_lmm_run_table(a["k"].c_str(), a["kmers_table"].c_str(), (uint32_t)klen, a["p"].c_str(), (uint32_t)col,
                                                          mac, maf, best, lmin, lmax, chunk, (int32_t)device, op[0], &st)
                                    : kgwas_lmm_run_table_multi(a["k"].c_str(), a["kmers_table"].c_str(), (uint32_t)klen, a["p"].c_str(),
                                                                (uint32_t)columns.size(), columns.data(), op.data(), mac, maf, best, lmin,
@@ -189,7 +199,7 @@ static int table_mode(map<string, string>& a, const char* prog) {
 
 int main(int argc, char* argv[]) {
     static const char* const valued[] = {"bfile", "bfiles", "lmm", "k", "outdir", "o", "n", "maf", "miss", "lmin", "lmax", "chunk_variants", "columns",
-                                         "kmers_table", "kmers_len", "p", "mac", "best", "device", "pheno_columns"};
+                                         "kmers_table", "kmers_len", "p", "mac", "best", "device", "pheno_columns", "c"};
     map<string, string> a;
     for (int i = 1; i < argc; i++) {
         string s = argv[i];
@@ -226,6 +236,13 @@ int main(int argc, char* argv[]) {
             cerr << "lmm_lrt: -lmm 4 is not built for " << given << ": it takes -bfile or --bfiles (-lmm 2 runs with them)" << endl;
             return 1;
         }
+    }
+    if (a.count("c")) {  // (before any file is opened)
+        for (const char* o : {"columns", "pheno_columns"})
+            if (a.count(o)) {
+                cerr << "lmm_lrt: -c is not built for --" << o << ": covariates go with one phenotype column (-n)" << endl;
+                return 1;
+            }
     }
     if (a.count("kmers_table")) return table_mode(a, argv[0]);
     for (const char* o : {"kmers_len", "p", "mac", "best", "device", "pheno_columns"})
@@ -281,7 +298,9 @@ int main(int argc, char* argv[]) {
     for (const string& b : bases) bp.push_back(b.c_str());
     for (const string& o : outs) op.push_back(o.c_str());
     kgwas_lmm_stats st{};
-    const int rc = all_tests       ? kgwas_lmm_run_files_all(a["k"].c_str(), bases.size(), bp.data(), op.data(), (uint32_t)col, maf, miss, lmin,
+    const int rc = a.count("c")    ? kgwas_lmm_run_files_cov(a["k"].c_str(), a["c"].c_str(), bases.size(), bp.data(), op.data(), (uint32_t)col, maf,
+                                                             miss, lmin, lmax, (uint64_t)chunk, 0, all_tests ? 1 : 0, &st)
+                   : all_tests     ? kgwas_lmm_run_files_all(a["k"].c_str(), bases.size(), bp.data(), op.data(), (uint32_t)col, maf, miss, lmin,
                                                              lmax, (uint64_t)chunk, 0, &st)
                    : columns.empty() ? kgwas_lmm_run_files(a["k"].c_str(), bases.size(), bp.data(), op.data(), (uint32_t)col, maf, miss, lmin,
                                                            lmax, (uint64_t)chunk, 0, &st)

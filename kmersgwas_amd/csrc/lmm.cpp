@@ -11,6 +11,9 @@
 //            xt yt sums and the refinement run per block of LMM_PBLOCK columns. Every number has the bits of test_bed's.
 // -lmm 4  : null_reml fits the REML null model (vg, ve) on the sums null left; test_bed_all is test_bed with the other refinement
 //            kernel, which adds beta, se, l_remle and the Wald and score p-values and leaves lrt, lambda and p their bits.
+// covariates: set_covariates replaces W = 1 by W (n x q): W is checked and orthonormalised on the host (orthonormal_covariates),
+//            rotated like y and uploaded; null, null_reml, test_bed, test_bed_all and the table pass then launch the *_cov kernels,
+//            the multi-phenotype passes refuse. Without covariates every launch is the one it was.
 // No CPU fallback: the statistics need the GPU.
 #include <algorithm>
 #include <cmath>
@@ -210,8 +213,13 @@ void kgwas::lmm::fit_null(kgwas_lmm* h, const double* y) {
     KGWAS_HIP(hipSetDevice(h->device));
     h->have_null = h->have_null_reml = false;
     KGWAS_HIP(hipMemcpyAsync(h->d_yt.p, yt.data(), yt.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    KGWAS_HIP(launch_lmm_base(h->dm, h->d_d.p, h->d_wt.p, h->d_yt.p, h->d_grid.p, h->d_base.p, h->stream));
-    KGWAS_HIP(launch_lmm_null(h->dm, h->d_d.p, h->d_wt.p, h->d_yt.p, h->d_grid.p, h->d_base.p, h->d_null.p, h->stream));
+    if (h->q) {
+        KGWAS_HIP(launch_lmm_base_cov(h->dm, h->q, h->d_d.p, h->d_Wt.p, h->d_yt.p, h->d_grid.p, h->d_basec.p, h->stream));
+        KGWAS_HIP(launch_lmm_null_cov(h->dm, h->q, h->d_d.p, h->d_Wt.p, h->d_yt.p, h->d_grid.p, h->d_basec.p, h->d_null.p, h->stream));
+    } else {
+        KGWAS_HIP(launch_lmm_base(h->dm, h->d_d.p, h->d_wt.p, h->d_yt.p, h->d_grid.p, h->d_base.p, h->stream));
+        KGWAS_HIP(launch_lmm_null(h->dm, h->d_d.p, h->d_wt.p, h->d_yt.p, h->d_grid.p, h->d_base.p, h->d_null.p, h->stream));
+    }
     double out[2];
     KGWAS_HIP(hipMemcpyAsync(out, h->d_null.p, sizeof(out), hipMemcpyDeviceToHost, h->stream));
     KGWAS_HIP(hipStreamSynchronize(h->stream));  // (yt is read by the copy until here)
@@ -227,15 +235,100 @@ void kgwas::lmm::fit_null_reml(kgwas_lmm* h, const double* y) {
     if (h->have_null_reml) return;
     KGWAS_HIP(hipSetDevice(h->device));
     h->ensure_wald();
-    KGWAS_HIP(launch_lmm_null_reml(h->dm, h->d_d.p, h->d_wt.p, h->d_yt.p, h->d_grid.p, h->d_base.p, h->d_null_reml.p, h->stream));
+    if (h->q)
+        KGWAS_HIP(launch_lmm_null_reml_cov(h->dm, h->q, h->d_d.p, h->d_Wt.p, h->d_yt.p, h->d_grid.p, h->d_basec.p, h->d_null_reml.p, h->stream));
+    else
+        KGWAS_HIP(launch_lmm_null_reml(h->dm, h->d_d.p, h->d_wt.p, h->d_yt.p, h->d_grid.p, h->d_base.p, h->d_null_reml.p, h->stream));
     double out[4];
     KGWAS_HIP(hipMemcpyAsync(out, h->d_null_reml.p, sizeof(out), hipMemcpyDeviceToHost, h->stream));
     KGWAS_HIP(hipStreamSynchronize(h->stream));
-    h->l0_reml = out[0];
+    h->l0_reml = out[0] - h->log_det_R;  // (0 without covariates)
     h->lambda0_reml = out[1];
     h->vg = out[2];
     h->ve = out[3];
     h->have_null_reml = true;
+}
+
+// ---- covariates ----
+
+void kgwas::lmm::orthonormal_covariates(uint64_t n, uint32_t q, const double* W, std::vector<double>& Qw, double& log_det_R,
+                                        const std::string& who) {
+    if (q < 1 || q > LMM_MAXC)
+        throw Error(KGWAS_ERR_ARG, who + ": " + std::to_string(q) + " covariate columns; at most " + std::to_string(LMM_MAXC) + " are built");
+    for (uint64_t k = 0; k < n * q; k++)
+        if (!std::isfinite(W[k])) throw Error(KGWAS_ERR_ARG, who + ": a covariate value is not finite");
+    if (n < (uint64_t)q + 2)
+        throw Error(KGWAS_ERR_ARG, who + ": " + std::to_string(n) + " individuals are too few for " + std::to_string(q) +
+                                       " covariate columns (at least " + std::to_string(q + 2) + " are needed)");
+    std::vector<std::vector<double>> col(q, std::vector<double>(n));
+    const auto dot = [n](const std::vector<double>& a, const std::vector<double>& b) {
+        double s = 0;
+        for (uint64_t k = 0; k < n; k++) s += a[k] * b[k];
+        return s;
+    };
+    const auto project_out = [&](std::vector<double>& v, uint32_t upto) {  // twice: the second pass removes what rounding left
+        for (int pass = 0; pass < 2; pass++)
+            for (uint32_t c = 0; c < upto; c++) {
+                const double t = dot(col[c], v);
+                for (uint64_t k = 0; k < n; k++) v[k] -= t * col[c][k];
+            }
+    };
+    log_det_R = 0;
+    for (uint32_t j = 0; j < q; j++) {
+        std::vector<double>& v = col[j];
+        for (uint64_t k = 0; k < n; k++) v[k] = W[k * q + j];
+        const double norm = std::sqrt(dot(v, v));
+        project_out(v, j);
+        const double rest = std::sqrt(dot(v, v));
+        if (!(rest > 1e-8 * norm))
+            throw Error(KGWAS_ERR_ARG, who + ": the covariates are rank-deficient: column " + std::to_string(j + 1) +
+                                           " is a combination of the columns before it");
+        for (uint64_t k = 0; k < n; k++) v[k] /= rest;
+        log_det_R += std::log(rest);
+    }
+    std::vector<double> one(n, 1.0);
+    project_out(one, q);
+    if (!(std::sqrt(dot(one, one)) <= 1e-8 * std::sqrt((double)n)))
+        throw Error(KGWAS_ERR_ARG, who + ": the covariates do not span the constant vector: give the file a column of 1s (the intercept)");
+    Qw.resize(n * q);
+    for (uint32_t j = 0; j < q; j++)
+        for (uint64_t k = 0; k < n; k++) Qw[k * q + j] = col[j][k];
+}
+
+// W[n][q] in place of W = 1 for every later call with one phenotype; q = 0 restores W = 1. The null models are forgotten.
+void kgwas::lmm::set_covariates(kgwas_lmm* h, uint32_t q, const double* W) {
+    const uint64_t n = h->n, ldi = h->dm.ldi;
+    if (!q) {
+        h->q = 0;
+        h->log_det_R = 0;
+        h->have_null = h->have_null_reml = false;
+        return;
+    }
+    if (!W) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_set_covariates: null argument");
+    std::vector<double> Qw;
+    double log_det_R = 0;
+    orthonormal_covariates(n, q, W, Qw, log_det_R, "kgwas_lmm_set_covariates");
+    std::vector<double> Wt((uint64_t)q * ldi, 0.0);
+    for (uint64_t k = 0; k < n; k++) {  // U^T Q, in row order
+        const double* u = &h->U[k * n];
+        for (uint32_t j = 0; j < q; j++) {
+            const double w = Qw[k * q + j];
+            double* out = &Wt[(uint64_t)j * ldi];
+            for (uint64_t i = 0; i < n; i++) out[i] += u[i] * w;
+        }
+    }
+    KGWAS_HIP(hipSetDevice(h->device));
+    KGWAS_HIP(hipStreamSynchronize(h->stream));
+    h->have_null = h->have_null_reml = false;
+    h->q = 0;  // (until everything below is in place)
+    if (h->g_rows < (uint64_t)q + 2) {
+        h->d_G.alloc((uint64_t)h->chunk * (q + 2) * LMM_HB_COLS);
+        h->g_rows = (uint64_t)q + 2;
+    }
+    if (!h->d_basec.p) h->d_basec.alloc((uint64_t)LMM_GRID * LMM_BASEC);
+    upload(h->d_Wt, Wt);
+    h->q = q;
+    h->log_det_R = log_det_R;
 }
 
 // ---- the back-end steps. They launch on the handle's stream and time their stages; the caller issues the copies, synchronises
@@ -247,6 +340,18 @@ void kgwas::lmm::single_backend(kgwas_lmm* h, const uint8_t* codes, const LmmVar
     hipStream_t st = h->stream;
     KGWAS_HIP(launch_lmm_rotate(codes, vars, cc, h->dm, h->d_U.p, h->d_Xt.p, st));
     h->timer.end(&kgwas_lmm_stats::rotate_ms, st);
+    if (h->q) {  // covariates: the same stages on their own kernels
+        KGWAS_HIP(launch_lmm_grid_cov(h->d_Xt.p, cc, h->dm, h->q, h->d_Wt.p, h->d_yt.p, h->d_HB.p, h->d_G.p, st));
+        h->timer.end(&kgwas_lmm_stats::grid_ms, st);
+        if (wald)
+            KGWAS_HIP(launch_lmm_refine_all_cov(h->d_Xt.p, h->d_G.p, vars, cc, h->dm, h->q, h->d_d.p, h->d_Wt.p, h->d_yt.p, h->d_grid.p,
+                                                h->d_basec.p, h->l0, h->lambda0, h->d_lrt.p, h->d_lam.p, h->d_p.p, h->wald_out(), st));
+        else
+            KGWAS_HIP(launch_lmm_refine_cov(h->d_Xt.p, h->d_G.p, vars, cc, h->dm, h->q, h->d_d.p, h->d_Wt.p, h->d_yt.p, h->d_grid.p,
+                                            h->d_basec.p, h->l0, h->d_lrt.p, h->d_lam.p, h->d_p.p, st));
+        h->timer.end(&kgwas_lmm_stats::refine_ms, st);
+        return;
+    }
     KGWAS_HIP(launch_lmm_grid(h->d_Xt.p, cc, h->dm, h->d_wt.p, h->d_yt.p, h->d_HB.p, h->d_G.p, st));
     h->timer.end(&kgwas_lmm_stats::grid_ms, st);
     if (wald)  // -lmm 4 (the caller has called ensure_wald): d_wald too
@@ -317,6 +422,7 @@ void kgwas::lmm::test_bed(kgwas_lmm* h, const double* y, const uint8_t* body, ui
 // The multi-phenotype pass. Nothing of the single-phenotype null (y_cur, have_null, d_yt, d_base, l0) is touched.
 // multi_prepare: Y[n_pheno][n] -> Yt, the base sums and the null models of all columns on the device; logl0, lambda0 [n_pheno].
 void kgwas::lmm::multi_prepare(kgwas_lmm* h, uint32_t n_pheno, const double* Y, double* logl0, double* lambda0, const char* who) {
+    if (h->q) throw Error(KGWAS_ERR_ARG, std::string(who) + ": covariates are not built for the multi-phenotype passes");
     if (!n_pheno) throw Error(KGWAS_ERR_ARG, std::string(who) + ": n_pheno is 0");
     const uint64_t n = h->n, ldi = h->dm.ldi;
     std::vector<double> Yt((uint64_t)n_pheno * ldi, 0.0);
@@ -428,6 +534,13 @@ int kgwas_lmm_test_bed_multi(kgwas_lmm* h, uint32_t n_pheno, const double* Y, co
         if (!h || (!Y && n_pheno) || (!bed_body && n_variants)) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_test_bed_multi: null argument");
         multi_prepare(h, n_pheno, Y, logl0, lambda0);
         multi_run(h, n_pheno, bed_body, n_variants, maf, miss, lrt, lambda, p, af, n_miss, tested);
+    });
+}
+
+int kgwas_lmm_set_covariates(kgwas_lmm* h, uint32_t q, const double* W) {
+    return guarded([&] {
+        if (!h) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_set_covariates: null argument");
+        set_covariates(h, q, W);
     });
 }
 

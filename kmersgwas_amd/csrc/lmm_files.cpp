@@ -8,6 +8,8 @@
 //            kmers_gwas.py:193-223);
 // run_table, run_table_multi: lmm_lrt --kmers_table, with -n and with --pheno_columns.
 // -lmm 4   : run_files with all_tests writes the 14-column file (format_assoc4) and four more lines in the log.
+// -c       : run_files and run_table with a covariates file (read_covariates): its rows are checked on the host, subset with
+//            everything else and handed to the session (set_covariates); the log gains two lines.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -75,7 +77,65 @@ std::vector<double> kgwas::lmm::read_kinship(const std::string& path, uint64_t n
     return K;
 }
 
+void kgwas::lmm::read_covariates(const std::string& path, std::vector<double>& values, std::vector<uint8_t>& keep, uint32_t& q) {
+    const std::vector<std::string> lines = read_lines(path, "covariates");
+    if (lines.empty()) throw Error(KGWAS_ERR_FORMAT, "covariates file " + path + " has no rows");
+    q = 0;
+    values.clear();
+    keep.assign(lines.size(), 1);
+    for (size_t r = 0; r < lines.size(); r++) {
+        const std::vector<std::string> f = split_ws(lines[r]);
+        if (r == 0) {
+            if (f.size() > LMM_MAXC)
+                throw Error(KGWAS_ERR_FORMAT, "covariates file " + path + " has " + std::to_string(f.size()) + " columns; at most " +
+                                                  std::to_string(LMM_MAXC) + " are built");
+            q = (uint32_t)f.size();
+        } else if (f.size() != q) {
+            throw Error(KGWAS_ERR_FORMAT, "covariates file " + path + ": row " + std::to_string(r + 1) + " has " + std::to_string(f.size()) +
+                                              " fields, row 1 has " + std::to_string(q));
+        }
+        for (const std::string& t : f) {
+            double v = std::nan("");
+            if (t == "NA") {
+                keep[r] = 0;
+            } else {
+                char* end = nullptr;
+                v = strtod(t.c_str(), &end);
+                if (end == t.c_str() || *end || !std::isfinite(v))
+                    throw Error(KGWAS_ERR_FORMAT, "covariates file " + path + ": row " + std::to_string(r + 1) + ": '" + t + "' is no number");
+            }
+            values.push_back(v);
+        }
+    }
+}
+
 namespace {
+
+// the covariates of a run: the file's rows, and the rows of the individuals idx as set_covariates takes them (checked on the host)
+struct Covariates {
+    std::string path;
+    uint32_t q = 0;
+    std::vector<double> values;
+    std::vector<uint8_t> keep;
+    void load(const char* p, uint64_t rows_expected, const char* counted_in) {
+        path = p;
+        read_covariates(path, values, keep, q);
+        if (keep.size() != rows_expected)
+            throw Error(KGWAS_ERR_FORMAT, "covariates file " + path + " has " + std::to_string(keep.size()) + " rows, " + counted_in + " has " +
+                                              std::to_string(rows_expected) + " individuals");
+    }
+    // The rows as given, after orthonormal_covariates has accepted them. Its basis and log |det R| are discarded on purpose:
+    // set_covariates makes them again once the handle exists; this call is only there to refuse before the kinship file is read.
+    std::vector<double> checked_rows_of(const std::vector<uint32_t>& idx) const {
+        std::vector<double> W(idx.size() * q);
+        for (size_t r = 0; r < idx.size(); r++)
+            for (uint32_t j = 0; j < q; j++) W[r * q + j] = values[(uint64_t)idx[r] * q + j];
+        std::vector<double> Qw;
+        double log_det_R;
+        orthonormal_covariates(idx.size(), q, W.data(), Qw, log_det_R, "covariates file " + path);
+        return W;
+    }
+};
 
 // a phenotype field as a .fam gives it: "-9" and "NA" are missing, anything else must be one finite number
 enum class Pheno { missing, number, no_number };
@@ -274,40 +334,48 @@ void write_log_text(const std::string& out, const char* log, size_t cap, int ll)
     write_text(log_path_of(out), std::string(log, std::min((size_t)ll, cap - 1)), "wb");
 }
 
+// the two lines a log gains behind `kinship` with -c (nothing without)
+std::string covariate_lines(const Covariates* cov) {
+    return cov ? "covariates\t" + cov->path + "\nn_covariates\t" + std::to_string(cov->q) + "\n" : std::string();
+}
+
 void write_log(const std::string& out, const std::string& base, const char* kinship_path, uint64_t nf, uint64_t n, uint64_t M,
                uint64_t n_tested, double lambda0, double l0, double eigen_ms, double rotate_ms, double grid_ms, double refine_ms,
-               double total_ms) {
-    char log[1024];
+               double total_ms, const Covariates* cov = nullptr) {
+    char log[2048];
     const int ll = snprintf(log, sizeof(log),
-                            "lmm_lrt: ML likelihood-ratio test (-lmm 2)\nbfile\t%s\nkinship\t%s\nindividuals_in_fam\t%llu\n"
+                            "lmm_lrt: ML likelihood-ratio test (-lmm 2)\nbfile\t%s\nkinship\t%s\n%sindividuals_in_fam\t%llu\n"
                             "individuals_used\t%llu\nvariants_read\t%llu\nvariants_tested\t%llu\nlambda0\t%.6e\nlogl_H0\t%.6f\n"
                             "ms: eigen=%.3f rotate=%.3f grid=%.3f refine=%.3f total=%.3f\n",
-                            base.c_str(), kinship_path, (unsigned long long)nf, (unsigned long long)n, (unsigned long long)M,
+                            base.c_str(), kinship_path, covariate_lines(cov).c_str(), (unsigned long long)nf, (unsigned long long)n, (unsigned long long)M,
                             (unsigned long long)n_tested, lambda0, l0, eigen_ms, rotate_ms, grid_ms, refine_ms, total_ms);
     write_log_text(out, log, sizeof(log), ll);
 }
 
 // the log of -lmm 4: write_log's lines under its own title, with the REML null model's four behind logl_H0
 void write_log4(const std::string& out, const std::string& base, const char* kinship_path, uint64_t nf, uint64_t n, uint64_t M,
-                uint64_t n_tested, const kgwas_lmm* h, double rotate_ms, double grid_ms, double refine_ms, double total_ms) {
-    char log[1280];
+                uint64_t n_tested, const kgwas_lmm* h, double rotate_ms, double grid_ms, double refine_ms, double total_ms,
+                const Covariates* cov = nullptr) {
+    char log[2304];
     const int ll = snprintf(log, sizeof(log),
-                            "lmm_lrt: ML likelihood-ratio test, REML Wald test and score test (-lmm 4)\nbfile\t%s\nkinship\t%s\n"
+                            "lmm_lrt: ML likelihood-ratio test, REML Wald test and score test (-lmm 4)\nbfile\t%s\nkinship\t%s\n%s"
                             "individuals_in_fam\t%llu\nindividuals_used\t%llu\nvariants_read\t%llu\nvariants_tested\t%llu\nlambda0\t%.6e\n"
                             "logl_H0\t%.6f\nlambda0_remle\t%.6e\nlogl_remle_H0\t%.6f\nvg\t%.6e\nve\t%.6e\n"
                             "ms: eigen=%.3f rotate=%.3f grid=%.3f refine=%.3f total=%.3f\n",
-                            base.c_str(), kinship_path, (unsigned long long)nf, (unsigned long long)n, (unsigned long long)M,
-                            (unsigned long long)n_tested, h->lambda0, h->l0, h->lambda0_reml, h->l0_reml, h->vg, h->ve, h->st.eigen_ms, rotate_ms,
+                            base.c_str(), kinship_path, covariate_lines(cov).c_str(), (unsigned long long)nf, (unsigned long long)n,
+                            (unsigned long long)M, (unsigned long long)n_tested, h->lambda0, h->l0, h->lambda0_reml, h->l0_reml, h->vg, h->ve, h->st.eigen_ms, rotate_ms,
                             grid_ms, refine_ms, total_ms);
     write_log_text(out, log, sizeof(log), ll);
 }
 
 void run_files(const char* kinship_path, uint64_t n_beds, const char* const* bases, const char* const* outs, uint32_t pheno_col,
                double maf, double miss, double lmin, double lmax, uint64_t chunk_variants, int device, kgwas_lmm_stats* total,
-               bool all_tests = false) {
+               bool all_tests = false, const char* covar_path = nullptr) {
     if (!kinship_path || (n_beds && (!bases || !outs)))
         throw Error(KGWAS_ERR_ARG, std::string(all_tests ? "kgwas_lmm_run_files_all" : "kgwas_lmm_run_files") + ": null argument");
     kgwas_lmm_stats sum{};
+    Covariates cov_file;  // -c: read at the first .fam, whose lines its rows follow
+    const Covariates* cov = covar_path ? &cov_file : nullptr;
     std::vector<double> Kfull;
     Handle h;
     std::vector<uint8_t> keep_cur;
@@ -318,13 +386,20 @@ void run_files(const char* kinship_path, uint64_t n_beds, const char* const* bas
         std::vector<uint8_t> keep;
         read_fam(base + ".fam", pheno_col, vals, keep);
         const uint64_t nf = vals.size();
-        if (Kfull.empty() || Kfull.size() != nf * nf) Kfull = read_kinship(kinship_path, nf);
+        if (cov) {  // an individual is used iff its phenotype is present and no covariate is NA
+            if (cov_file.keep.size() != nf) cov_file.load(covar_path, nf, "the .fam");
+            for (uint64_t i = 0; i < nf; i++) keep[i] &= cov_file.keep[i];
+        }
         const std::vector<uint32_t> idx = kept_lines(keep);
         const uint64_t n = idx.size();
+        std::vector<double> W;
+        if (cov && (!h || keep != keep_cur)) W = cov_file.checked_rows_of(idx);  // (refused here, before the kinship file and the device)
+        if (Kfull.empty() || Kfull.size() != nf * nf) Kfull = read_kinship(kinship_path, nf);
         if (!h || keep != keep_cur) {
             if (h) add_stats(sum, h->st);
             h.reset();
             h.reset(create_for_kept(Kfull, nf, idx, device, lmin, lmax, chunk_variants));
+            if (cov) set_covariates(h.get(), cov_file.q, W.data());
             keep_cur = keep;
         }
         std::vector<double> y(n);
@@ -347,7 +422,7 @@ void run_files(const char* kinship_path, uint64_t n_beds, const char* const* bas
                                                     p.data(), w, tested.data());
             write_text(out, text, "wb");
             write_log4(out, base, kinship_path, nf, n, M, n_tested, h.get(), h->st.rotate_ms - before.rotate_ms, h->st.grid_ms - before.grid_ms,
-                       h->st.refine_ms - before.refine_ms, now_ms() - t_start);
+                       h->st.refine_ms - before.refine_ms, now_ms() - t_start, cov);
             continue;
         }
         test_bed(h.get(), y.data(), body.data(), M, maf, miss, lrt.data(), lam.data(), p.data(), af.data(), n_miss.data(), tested.data());
@@ -356,7 +431,7 @@ void run_files(const char* kinship_path, uint64_t n_beds, const char* const* bas
             append_assoc(text, bim_fields(base, bim, 0, M, tested.data()), n_miss.data(), af.data(), lam.data(), p.data(), tested.data());
         write_text(out, text, "wb");
         write_log(out, base, kinship_path, nf, n, M, n_tested, h->lambda0, h->l0, h->st.eigen_ms, h->st.rotate_ms - before.rotate_ms,
-                  h->st.grid_ms - before.grid_ms, h->st.refine_ms - before.refine_ms, now_ms() - t_start);
+                  h->st.grid_ms - before.grid_ms, h->st.refine_ms - before.refine_ms, now_ms() - t_start, cov);
     }
     if (h) add_stats(sum, h->st);
     if (total) *total = sum;
@@ -484,7 +559,7 @@ struct TableRun {
 // one column's kept k-mers to `out` in table order, with the bytes run_files writes for them after kmers_table_to_bed, and the log
 void write_table_result(const std::string& out, const std::vector<TableHit>& kept, const TableRun& r, const char* table_base,
                         uint32_t pheno_col, const char* kinship_path, uint64_t rows_read, uint64_t rows_tested, uint64_t best_n,
-                        double lambda0, double l0, const kgwas_lmm_stats& st, double total_ms) {
+                        double lambda0, double l0, const kgwas_lmm_stats& st, double total_ms, const Covariates* cov = nullptr) {
     std::string text = assoc_header();
     for (const TableHit& k : kept) {
         char km[33];
@@ -495,12 +570,13 @@ void write_table_result(const std::string& out, const std::vector<TableHit>& kep
         text.append(line, len);
     }
     write_text(out, text, "wb");
-    char log[2048];
+    char log[3072];
     const int ll = snprintf(log, sizeof(log),
-                            "lmm_lrt: ML likelihood-ratio test (-lmm 2)\nkmers_table\t%s\nphenotypes\t%s\nphenotype_column\t%u\nkinship\t%s\n"
+                            "lmm_lrt: ML likelihood-ratio test (-lmm 2)\nkmers_table\t%s\nphenotypes\t%s\nphenotype_column\t%u\nkinship\t%s\n%s"
                             "individuals_used\t%llu\nmin_count\t%llu\nrows_read\t%llu\nrows_tested\t%llu\nrows_kept\t%llu\nbest_n\t%llu\n"
                             "lambda0\t%.6e\nlogl_H0\t%.6f\nms: eigen=%.3f rotate=%.3f grid=%.3f refine=%.3f total=%.3f\n",
-                            table_base, r.pheno_path.c_str(), pheno_col, kinship_path, (unsigned long long)r.S, (unsigned long long)r.min_count,
+                            table_base, r.pheno_path.c_str(), pheno_col, kinship_path, covariate_lines(cov).c_str(), (unsigned long long)r.S,
+                            (unsigned long long)r.min_count,
                             (unsigned long long)rows_read, (unsigned long long)rows_tested, (unsigned long long)kept.size(),
                             (unsigned long long)best_n, lambda0, l0, st.eigen_ms, st.rotate_ms, st.grid_ms, st.refine_ms, total_ms);
     write_log_text(out, log, sizeof(log), ll);
@@ -511,7 +587,7 @@ void write_table_result(const std::string& out, const std::vector<TableHit>& kep
 // the bytes run_files writes for them after kmers_table_to_bed; a log goes beside it.
 void run_table(const char* kinship_path, const char* table_base, uint32_t kmer_len, const char* pheno_path, uint32_t pheno_col,
                uint64_t mac, double maf, uint64_t best_n, double lmin, double lmax, uint64_t chunk_variants, int device, const char* out,
-               kgwas_lmm_stats* total) {
+               kgwas_lmm_stats* total, const char* covar_path = nullptr) {
     if (!kinship_path || !table_base || !pheno_path || !out) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_run_table: null argument");
     if (pheno_col < 1) throw Error(KGWAS_ERR_ARG, "the phenotype column (-n) starts at 1");
     if (!best_n) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_run_table: best_n is 0");
@@ -522,13 +598,28 @@ void run_table(const char* kinship_path, const char* table_base, uint32_t kmer_l
     r.load_values();
     std::vector<double> y(r.S);
     r.column(pheno_col, y.data());
+    Covariates cov_file;  // -c: one row per accession, none missing; refused before the table, the kinship file and the device
+    const Covariates* cov = covar_path ? &cov_file : nullptr;
+    std::vector<double> W;
+    if (cov) {
+        cov_file.load(covar_path, r.S, "the phenotype file");
+        std::vector<uint32_t> all(r.S);
+        for (uint64_t i = 0; i < r.S; i++) {
+            if (!cov_file.keep[i])
+                throw Error(KGWAS_ERR_FORMAT, "covariates file " + cov_file.path + ": row " + std::to_string(i + 1) +
+                                                  " has an NA; with --kmers_table remove the accession from the phenotype file");
+            all[i] = (uint32_t)i;
+        }
+        W = cov_file.checked_rows_of(all);
+    }
     r.open_table(table_base, kmer_len, kinship_path, maf, mac);
     Handle h(create(r.S, r.K.data(), device, lmin, lmax, chunk_variants));
+    if (cov) set_covariates(h.get(), cov_file.q, W.data());
     std::vector<TableHit> kept;
     uint64_t rows_read = 0, rows_tested = 0;
     test_table(h.get(), y.data(), r.t, r.col.data(), r.S, r.min_count, maf, best_n, kept, rows_read, rows_tested);
     write_table_result(out, kept, r, table_base, pheno_col, kinship_path, rows_read, rows_tested, best_n, h->lambda0, h->l0, h->st,
-                       now_ms() - t_start);
+                       now_ms() - t_start, cov);
     if (total) *total = h->st;
 }
 
@@ -606,6 +697,41 @@ int kgwas_lmm_run_table_multi(const char* kinship_path, const char* table_base, 
     return guarded([&] {
         run_table_multi(kinship_path, table_base, kmer_len, pheno_path, n_cols, pheno_cols, out_paths, mac, maf, best_n, lmin, lmax,
                         chunk_variants, device, total);
+    });
+}
+
+int kgwas_lmm_run_files_cov(const char* kinship_path, const char* covar_path, uint64_t n_beds, const char* const* bfile_bases,
+                            const char* const* out_paths, uint32_t pheno_col, double maf, double miss, double lmin, double lmax,
+                            uint64_t chunk_variants, int32_t device, int32_t all_tests, kgwas_lmm_stats* total) {
+    return guarded([&] {
+        run_files(kinship_path, n_beds, bfile_bases, out_paths, pheno_col, maf, miss, lmin, lmax, chunk_variants, device, total, all_tests != 0,
+                  covar_path);
+    });
+}
+
+int kgwas_lmm_run_table_cov(const char* kinship_path, const char* covar_path, const char* table_base, uint32_t kmer_len,
+                            const char* pheno_path, uint32_t pheno_col, uint64_t mac, double maf, uint64_t best_n, double lmin, double lmax,
+                            uint64_t chunk_variants, int32_t device, const char* out_path, kgwas_lmm_stats* total) {
+    return guarded([&] {
+        run_table(kinship_path, table_base, kmer_len, pheno_path, pheno_col, mac, maf, best_n, lmin, lmax, chunk_variants, device, out_path,
+                  total, covar_path);
+    });
+}
+
+int kgwas_lmm_read_covariates(const char* path, uint64_t n_expected, uint64_t cap, double* values, uint8_t* keep, uint32_t* q_out) {
+    return guarded([&] {
+        if (!path || !q_out) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_read_covariates: null argument");
+        std::vector<double> v;
+        std::vector<uint8_t> k;
+        uint32_t q = 0;
+        read_covariates(path, v, k, q);
+        if (n_expected && k.size() != n_expected)
+            throw Error(KGWAS_ERR_FORMAT, std::string("covariates file ") + path + " has " + std::to_string(k.size()) + " rows, expected " +
+                                              std::to_string(n_expected));
+        *q_out = q;
+        if (v.size() > cap) return;
+        if (values) memcpy(values, v.data(), v.size() * sizeof(double));
+        if (keep) memcpy(keep, k.data(), k.size());
     });
 }
 

@@ -77,6 +77,13 @@ struct kgwas_lmm {
     kgwas::LmmWaldOut wald_out() const {
         return {d_wald.p, d_wald.p + chunk, d_wald.p + 2 * (uint64_t)chunk, d_wald.p + 3 * (uint64_t)chunk, d_wald.p + 4 * (uint64_t)chunk};
     }
+    // kgwas_lmm_set_covariates: q > 0 columns of W in place of W = 1. d_Wt[q][ldi] = the rotated columns of W's orthonormal basis,
+    // d_basec the records of the grid points (in place of d_base), d_G grows to chunk x (q + 2) x LMM_HB_COLS. log_det_R = log |det R|
+    // of W = Q R: the REML likelihood of W is that of Q less this.
+    uint32_t q = 0;
+    double log_det_R = 0;
+    uint64_t g_rows = 3;  // rows per variant d_G has room for
+    kgwas::DevBuf<double> d_Wt, d_basec;
     kgwas::Stream stream;  // (behind the buffers its work reads and writes: it goes first)
     ~kgwas_lmm() {
         if (on_device) (void)hipSetDevice(device);  // (before any member is released)
@@ -107,6 +114,11 @@ struct WaldArrays {
     double *beta, *se, *lam_remle, *p_wald, *p_score;
 };
 void fit_null_reml(kgwas_lmm* h, const double* y);
+// W[n][q] -> Qw[n][q], an orthonormal basis of its columns (modified Gram-Schmidt in column order, every projection done twice), and
+// log |det R| of W = Qw R. Refuses q > LMM_MAXC, values that are not finite, n < q + 2, a rank-deficient W and a W whose span does
+// not hold the constant vector; `who` starts the message. Host only: the file layer calls it before any device work.
+void orthonormal_covariates(uint64_t n, uint32_t q, const double* W, std::vector<double>& Qw, double& log_det_R, const std::string& who);
+void set_covariates(kgwas_lmm* h, uint32_t q, const double* W);
 void test_bed(kgwas_lmm* h, const double* y, const uint8_t* body, uint64_t nv, double maf, double miss, double* lrt, double* lam,
               double* p, double* af, uint32_t* n_miss, uint8_t* tested, const WaldArrays* wald = nullptr);
 void multi_prepare(kgwas_lmm* h, uint32_t n_pheno, const double* Y, double* logl0, double* lambda0,
@@ -125,6 +137,8 @@ void test_table_multi(kgwas_lmm* h, uint32_t n_pheno, const double* Y, kgwas_tab
                       double* lambda0, uint64_t& rows_read, uint64_t& rows_tested, uint64_t& pairs_shipped);
 // ---- lmm_files.cpp ----
 std::vector<double> read_kinship(const std::string& path, uint64_t n_expected, const char* counted_in = "the .fam");
+// GEMMA's -c file: one row per individual, whitespace-separated numbers, NA missing. values[rows][q]; keep[r] = 0 where row r has an NA
+void read_covariates(const std::string& path, std::vector<double>& values, std::vector<uint8_t>& keep, uint32_t& q);
 
 }  // namespace lmm
 }  // namespace kgwas

@@ -9,6 +9,22 @@ namespace kgwas {
 constexpr uint32_t LMM_GRID = 101;      // grid points over log lambda: 100 intervals (emma.R's ngrids)
 constexpr uint32_t LMM_HB_COLS = 208;   // the h table's columns: h at the 101 points, then dh/dlog lambda at them, then 6 of zeros
 constexpr uint32_t LMM_BASE = 8;        // per grid point: sum h, sum log h, Sww, Swy, Syy, then Sww', Swy', Syy' (weights dh)
+constexpr uint32_t LMM_MAXC = 8;        // covariates: the most columns of W (kgwas_lmm_set_covariates)
+// With covariates a grid point has a record of LMM_BASEC doubles in place of its LMM_BASE sums (A = Wt^T H Wt, b = Wt^T H yt, dA and
+// db the same with weights dh; matrices are [j][k] with row stride LMM_MAXC, entries past q are zero):
+constexpr uint32_t LMM_REC_SH = 0;       //   sum h
+constexpr uint32_t LMM_REC_SLOG = 1;     //   sum log h
+constexpr uint32_t LMM_REC_RSS0 = 2;     //   yy - b^T A^-1 b
+constexpr uint32_t LMM_REC_LOGDET = 3;   //   log |A|
+constexpr uint32_t LMM_REC_TR = 4;       //   tr(A^-1 dA)
+constexpr uint32_t LMM_REC_DYY = 5;      //   dyy
+constexpr uint32_t LMM_REC_DRSS0 = 6;    //   RSS0': the dh-weighted quadratic form of (A^-1 b, -1)
+constexpr uint32_t LMM_REC_AINV = 7;     //   A^-1
+constexpr uint32_t LMM_REC_DA = LMM_REC_AINV + LMM_MAXC * LMM_MAXC;  // dA
+constexpr uint32_t LMM_REC_A0 = LMM_REC_DA + LMM_MAXC * LMM_MAXC;    // A^-1 b
+constexpr uint32_t LMM_REC_DB = LMM_REC_A0 + LMM_MAXC;               // db
+constexpr uint32_t LMM_REC_B = LMM_REC_DB + LMM_MAXC;                // b
+constexpr uint32_t LMM_BASEC = LMM_REC_B + LMM_MAXC;                 // 159
 constexpr uint32_t LMM_VTILE = 32;      // variants per wave of the rotation; chunk buffers are padded to it
 constexpr uint32_t LMM_REFINE_STEPS = 12;
 constexpr uint32_t LMM_PTILE = 4;       // phenotype columns a wave of lmm_grid_xy_kernel holds accumulators for
@@ -75,6 +91,25 @@ hipError_t launch_lmm_refine_all(const double* Xt, const double* G, const LmmVar
 hipError_t launch_lmm_refine_multi(const double* Xt, const double* Gx, const double* Gxy, const LmmVariant* vars, uint32_t nv, LmmDims dm,
                                    const double* d, const double* wt, const double* Yt, uint32_t np, const double* lambda,
                                    const double* base, const double* null, double* lrt, double* lam, double* p, hipStream_t st);
+
+// Covariates: W (n x q, 1 <= q <= LMM_MAXC, orthonormal columns whose span holds the constant vector) in place of W = 1.
+// Wt[q][ldi] = its rotated columns (zero past n). The launchers mirror the ones above; q outside 1..LMM_MAXC is refused.
+// base[LMM_GRID][LMM_BASEC]: the records of the grid points
+hipError_t launch_lmm_base_cov(LmmDims dm, uint32_t q, const double* d, const double* Wt, const double* yt, const double* lambda,
+                               double* base, hipStream_t st);
+// G[v][q + 2][LMM_HB_COLS]: sums over i of HB[i][c] * (xt^2, xt wt_0 .. xt wt_{q-1}, xt yt)
+hipError_t launch_lmm_grid_cov(const double* Xt, uint32_t nv, LmmDims dm, uint32_t q, const double* Wt, const double* yt,
+                               const double* HB, double* G, hipStream_t st);
+hipError_t launch_lmm_null_cov(LmmDims dm, uint32_t q, const double* d, const double* Wt, const double* yt, const double* lambda,
+                               const double* base, double* out, hipStream_t st);
+hipError_t launch_lmm_null_reml_cov(LmmDims dm, uint32_t q, const double* d, const double* Wt, const double* yt, const double* lambda,
+                                    const double* base, double* out, hipStream_t st);
+hipError_t launch_lmm_refine_cov(const double* Xt, const double* G, const LmmVariant* vars, uint32_t nv, LmmDims dm, uint32_t q,
+                                 const double* d, const double* Wt, const double* yt, const double* lambda, const double* base, double l0,
+                                 double* lrt, double* lam, double* p, hipStream_t st);
+hipError_t launch_lmm_refine_all_cov(const double* Xt, const double* G, const LmmVariant* vars, uint32_t nv, LmmDims dm, uint32_t q,
+                                     const double* d, const double* Wt, const double* yt, const double* lambda, const double* base,
+                                     double l0, double lam0, double* lrt, double* lam, double* p, LmmWaldOut w, hipStream_t st);
 
 // lmm_table_kernels.hip: the front end of the k-mers table route. rows[n_rows][stride] are table rows (k-mer word, then the
 // presence words), sq[n_rows][2 W_m] their bits squeezed to phenotype order (launch_squeeze, zero past dm.n). A row is tested iff

@@ -25,11 +25,14 @@
 //   lmm_null_reml_kernel / lmm_refine_all_kernel   -lmm 4: the same maximisation of the REML likelihood (a compile-time switch of
 //                      ll_from_sums and maximise; the ML instantiations are the code they were), then beta, se, the Wald and the
 //                      score statistic from direct_sums at l_remle and at lambda0, and their F(1, n - 2) tails (fdist_tail.h).
+//   lmm_*_cov_kernel   the same stages for W of q > 1 columns (or q = 1 given as covariates): further down, with their own notes.
 // Nothing here depends on a variant's neighbours or uses an atomic: a variant's numbers are the same in any batch.
 //
 // f64 MFMA layout (16x16x4): lane l holds A[row l & 15][k l >> 4] and B[k l >> 4][col l & 15]; result register j of lane l is
 // D[row (l >> 4) + 4 j][col l & 15] - not the f32 forms' 4 (l >> 4) + j.
 #include "lmm_kernels.h"
+
+#include <utility>
 
 #include "fdist_tail.h"
 
@@ -512,6 +515,492 @@ __global__ void __launch_bounds__(64) lmm_refine_all_kernel(const double* __rest
     }
 }
 
+// ---- covariates: W is n x Q, 1 <= Q <= LMM_MAXC, with orthonormal columns whose span holds the constant vector (lmm.cpp sees to
+// both). Wt[Q][ldi] = (U^T W)^T replaces wt. The kernels above are not touched; a handle without covariates never comes here. ----
+//
+// Per lambda, with z = (wt_0 .. wt_{Q-1}, yt, xt): every sum_i h_i z_a z_b and sum_i h'_i z_a z_b, a <= b. From those without x
+// the wave makes a *record* of LMM_BASEC doubles (the layout stands beside LMM_BASEC): A = Wt^T H Wt is factored (Cholesky, every
+// lane the same arithmetic in registers), lane c < Q solves for column c of A^-1 and lane Q for A^-1 b. A variant then costs
+// O(Q^2) per lambda (ll_cov): g = A^-1 xw, xx.w = xx - xw^T g, xy.w = xy - xw^T A^-1 b, bx = xy.w / xx.w, RSS = RSS0 - xy.w bx,
+// RSS' = the h'-weighted quadratic form of (a, bx, -1) with a = A^-1 b - g bx; REML adds log|A| + log xx.w and its derivative
+// tr(A^-1 dA) + (dxx - 2 g^T dxw + g^T dA g) / xx.w. The record of a grid point comes from lmm_base_cov_kernel; at the lambdas
+// of the refinement the wave sums over i itself, in passes of LMM_COV_PASS pairs (twice that many running sums per lane, the
+// first pass two more), into LDS, and builds the record there.
+
+constexpr int LMM_COV_MZ = LMM_MAXC + 2;  // row stride of the pair sums in LDS
+constexpr int LMM_COV_PASS = 8;
+
+struct CovLds {
+    double Sh[LMM_COV_MZ * LMM_COV_MZ], Sd[LMM_COV_MZ * LMM_COV_MZ];  // [a][b], a <= b: sums with weights h and h'
+    double sh, slog;
+    double rec[LMM_BASEC];
+};
+
+// pair k of the upper triangle of an M x M matrix, row by row
+constexpr int pair_a(int M, int k) {
+    int a = 0;
+    while (k >= M - a) k -= M - a, a++;
+    return a;
+}
+constexpr int pair_b(int M, int k) {
+    int a = 0;
+    while (k >= M - a) k -= M - a, a++;
+    return a + k;
+}
+
+template <int M, int K>
+__device__ inline void cov_acc_pair(const double (&z)[M], double h, double hd, double& ah, double& ad) {
+    constexpr int a = pair_a(M, K), b = pair_b(M, K);
+    const double zz = z[a] * z[b];
+    ah += h * zz;
+    ad += hd * zz;
+}
+template <int M, int K>
+__device__ inline void cov_store_pair(CovLds& L, double ah, double ad) {
+    constexpr int a = pair_a(M, K), b = pair_b(M, K);
+    L.Sh[a * LMM_COV_MZ + b] = ah;
+    L.Sd[a * LMM_COV_MZ + b] = ad;
+}
+
+// pairs K0 .. K0 + NP of the M rows zp (each of n doubles) at one lambda, lanes striding over i, then a fixed butterfly
+template <int M, int K0, bool WITH_LOG, int... I>
+__device__ inline void cov_sum_pass(std::integer_sequence<int, I...>, double lam, uint32_t n, const double* __restrict__ d,
+                                    const double* const (&zp)[M], CovLds& L) {
+    constexpr int NP = sizeof...(I);
+    double ah[NP], ad[NP], sh = 0, slog = 0;
+    for (int k = 0; k < NP; k++) ah[k] = ad[k] = 0;
+    for (uint32_t i = threadIdx.x; i < n; i += 64) {
+        const double ld = lam * d[i], h = 1.0 / (ld + 1.0), hd = h * h - h;
+        double z[M];
+#pragma unroll
+        for (int a = 0; a < M; a++) z[a] = zp[a][i];  // (the rows no pair of this pass names are not loaded)
+        if (K0 == 0) {
+            sh += h;
+            if (WITH_LOG) slog -= log1p(ld);
+        }
+        (cov_acc_pair<M, K0 + I>(z, h, hd, ah[I], ad[I]), ...);
+    }
+#pragma unroll
+    for (int k = 0; k < NP; k++) ah[k] = wave_sum(ah[k]), ad[k] = wave_sum(ad[k]);
+    if (K0 == 0) {
+        sh = wave_sum(sh);
+        if (WITH_LOG) slog = wave_sum(slog);
+    }
+    if (threadIdx.x == 0) {
+        (cov_store_pair<M, K0 + I>(L, ah[I], ad[I]), ...);
+        if (K0 == 0) L.sh = sh, L.slog = slog;
+    }
+}
+template <int M, int K0, bool WITH_LOG>
+__device__ inline void cov_sum_passes(double lam, uint32_t n, const double* __restrict__ d, const double* const (&zp)[M], CovLds& L) {
+    constexpr int TOTAL = M * (M + 1) / 2;
+    if constexpr (K0 < TOTAL) {
+        constexpr int NP = TOTAL - K0 < LMM_COV_PASS ? TOTAL - K0 : LMM_COV_PASS;
+        cov_sum_pass<M, K0, WITH_LOG>(std::make_integer_sequence<int, NP>{}, lam, n, d, zp, L);
+        cov_sum_passes<M, K0 + LMM_COV_PASS, WITH_LOG>(lam, n, d, zp, L);
+    }
+}
+
+// The record from the sums in L.Sh, L.Sd, L.sh, L.slog (written by lane 0; the caller has NOT yet synchronised): L.rec. The wave
+// is synchronised on return.
+template <int Q>
+__device__ inline void cov_record(CovLds& L) {
+    constexpr int MZ = LMM_COV_MZ;
+    const int lane = threadIdx.x;
+    __syncthreads();
+    double C[Q][Q], rc[Q];  // the lower Cholesky factor of A, below the diagonal; rc = 1 / its diagonal
+    double logdet = 0;
+#pragma unroll
+    for (int j = 0; j < Q; j++) {
+#pragma unroll
+        for (int k = 0; k < j; k++) {
+            double s = L.Sh[k * MZ + j];
+#pragma unroll
+            for (int t = 0; t < k; t++) s -= C[j][t] * C[k][t];
+            C[j][k] = s * rc[k];
+        }
+        double s = L.Sh[j * MZ + j];
+#pragma unroll
+        for (int t = 0; t < j; t++) s -= C[j][t] * C[j][t];
+        logdet += log(s);  // (log |A| = sum log C[j][j]^2)
+        rc[j] = 1.0 / sqrt(s);
+    }
+    // lane c < Q: column c of A^-1; the others: A^-1 b (lane Q stores it)
+    double u[Q];
+#pragma unroll
+    for (int k = 0; k < Q; k++) {
+        double s = lane < Q ? (k == lane ? 1.0 : 0.0) : L.Sh[k * MZ + Q];
+#pragma unroll
+        for (int t = 0; t < k; t++) s -= C[k][t] * u[t];
+        u[k] = s * rc[k];
+    }
+#pragma unroll
+    for (int k = Q - 1; k >= 0; k--) {
+        double s = u[k];
+#pragma unroll
+        for (int t = k + 1; t < Q; t++) s -= C[t][k] * u[t];
+        u[k] = s * rc[k];
+    }
+#pragma unroll
+    for (int k = 0; k < Q; k++) {
+        if (lane < Q) L.rec[LMM_REC_AINV + k * LMM_MAXC + lane] = u[k];
+        if (lane == Q) L.rec[LMM_REC_A0 + k] = u[k];
+    }
+    if (lane < Q * Q) {  // dA, both triangles
+        const int j = lane / Q, k = lane % Q;
+        L.rec[LMM_REC_DA + j * LMM_MAXC + k] = L.Sd[(j < k ? j : k) * MZ + (j < k ? k : j)];
+    }
+    if (lane < Q) {
+        L.rec[LMM_REC_DB + lane] = L.Sd[lane * MZ + Q];
+        L.rec[LMM_REC_B + lane] = L.Sh[lane * MZ + Q];
+    }
+    __syncthreads();
+    if (lane == 0) {
+        double tr = 0, ba = 0, aDa = 0, adb = 0;
+        for (int j = 0; j < Q; j++) {
+            const double aj = L.rec[LMM_REC_A0 + j];
+            double Da = 0;
+            for (int k = 0; k < Q; k++) {
+                tr += L.rec[LMM_REC_AINV + j * LMM_MAXC + k] * L.rec[LMM_REC_DA + j * LMM_MAXC + k];
+                Da += L.rec[LMM_REC_DA + j * LMM_MAXC + k] * L.rec[LMM_REC_A0 + k];
+            }
+            ba += L.rec[LMM_REC_B + j] * aj;
+            aDa += aj * Da;
+            adb += aj * L.rec[LMM_REC_DB + j];
+        }
+        const double yy = L.Sh[Q * MZ + Q], dyy = L.Sd[Q * MZ + Q];
+        L.rec[LMM_REC_SH] = L.sh;
+        L.rec[LMM_REC_SLOG] = L.slog;
+        L.rec[LMM_REC_RSS0] = yy - ba;
+        L.rec[LMM_REC_LOGDET] = logdet;
+        L.rec[LMM_REC_TR] = tr;
+        L.rec[LMM_REC_DYY] = dyy;
+        L.rec[LMM_REC_DRSS0] = aDa - 2.0 * adb + dyy;
+    }
+    __syncthreads();
+}
+
+struct XSums {  // a variant's sums at one lambda
+    double xx, xy, dxx, dxy;
+};
+
+// l and dl/dt from a record (global memory or LDS) and, with HAS_X, the variant's sums. Also the Schur complements after W.
+template <int Q, bool HAS_X, bool REML>
+__device__ inline void ll_cov(const double* rec, const XSums& x, const double (&xw)[Q], const double (&dxw)[Q], double n, double& l,
+                              double& dl, AfterW& s) {
+    double rss = rec[LMM_REC_RSS0], drss = rec[LMM_REC_DRSS0], logdet = rec[LMM_REC_LOGDET], dlogdet = rec[LMM_REC_TR];
+    s = {0.0, 0.0, rss};
+    if (HAS_X) {
+        double g[Q], a[Q];
+        double xg = 0, xa0 = 0;
+#pragma unroll
+        for (int j = 0; j < Q; j++) {
+            double t = 0;
+#pragma unroll
+            for (int k = 0; k < Q; k++) t += rec[LMM_REC_AINV + j * LMM_MAXC + k] * xw[k];
+            g[j] = t;
+            xg += xw[j] * t;
+            xa0 += xw[j] * rec[LMM_REC_A0 + j];
+        }
+        const double xxw = x.xx - xg, xyw = x.xy - xa0, bx = xyw / xxw;
+        s.xx = xxw, s.xy = xyw;
+        rss -= xyw * bx;
+        double aDa = 0, adxw = 0, adb = 0, gDg = 0, gdxw = 0;
+#pragma unroll
+        for (int j = 0; j < Q; j++) a[j] = rec[LMM_REC_A0 + j] - g[j] * bx;
+#pragma unroll
+        for (int j = 0; j < Q; j++) {
+            double Da = 0, Dg = 0;
+#pragma unroll
+            for (int k = 0; k < Q; k++) {
+                const double D = rec[LMM_REC_DA + j * LMM_MAXC + k];
+                Da += D * a[k];
+                if (REML) Dg += D * g[k];
+            }
+            aDa += a[j] * Da;
+            adxw += a[j] * dxw[j];
+            adb += a[j] * rec[LMM_REC_DB + j];
+            if (REML) gDg += g[j] * Dg, gdxw += g[j] * dxw[j];
+        }
+        drss = aDa + 2.0 * bx * adxw + bx * bx * x.dxx - 2.0 * adb - 2.0 * bx * x.dxy + rec[LMM_REC_DYY];
+        if (REML) {
+            logdet += log(xxw);
+            dlogdet += (x.dxx - 2.0 * gdxw + gDg) / xxw;
+        }
+    }
+    const double sh = rec[LMM_REC_SH], slog = rec[LMM_REC_SLOG];
+    if (REML) {
+        const double df = n - (double)Q - (HAS_X ? 1.0 : 0.0);
+        l = 0.5 * df * (log(df / 6.283185307179586476925) - 1.0) + 0.5 * slog - 0.5 * logdet - 0.5 * df * log(rss);
+        dl = 0.5 * (sh - n) - 0.5 * dlogdet - 0.5 * df * drss / rss;
+    } else {
+        l = 0.5 * n * (log(n / 6.283185307179586476925) - 1.0) + 0.5 * slog - 0.5 * n * log(rss);
+        dl = 0.5 * (sh - n) - 0.5 * n * drss / rss;
+    }
+}
+
+// l, dl/dt and the Schur complements at one lambda off the grid: the sums over i, the record, then ll_cov; every lane gets them
+template <int Q, bool HAS_X, bool REML, bool WITH_LOG>
+__device__ __forceinline__ void eval_cov(double lam, uint32_t n, uint32_t ldi, const double* __restrict__ d, const double* __restrict__ Wt,
+                                const double* __restrict__ yt, const double* __restrict__ xt, CovLds& L, double& l, double& dl,
+                                AfterW& s) {
+    constexpr int M = Q + (HAS_X ? 2 : 1), MZ = LMM_COV_MZ;
+    const double* zp[M];
+#pragma unroll
+    for (int j = 0; j < Q; j++) zp[j] = Wt + (uint64_t)j * ldi;
+    zp[Q] = yt;
+    if (HAS_X) zp[M - 1] = xt;
+    __syncthreads();  // (the last call's readers of L are done)
+    cov_sum_passes<M, 0, WITH_LOG>(lam, n, d, zp, L);
+    cov_record<Q>(L);
+    XSums x = {0, 0, 0, 0};
+    double xw[Q], dxw[Q];
+#pragma unroll
+    for (int j = 0; j < Q; j++) xw[j] = dxw[j] = 0;
+    if (HAS_X) {
+        x = {L.Sh[(Q + 1) * MZ + Q + 1], L.Sh[Q * MZ + Q + 1], L.Sd[(Q + 1) * MZ + Q + 1], L.Sd[Q * MZ + Q + 1]};
+#pragma unroll
+        for (int j = 0; j < Q; j++) xw[j] = L.Sh[j * MZ + Q + 1], dxw[j] = L.Sd[j * MZ + Q + 1];
+    }
+    ll_cov<Q, HAS_X, REML>(L.rec, x, xw, dxw, (double)n, l, dl, s);
+}
+
+// maximise with covariates: the same candidates, steps and rules. Gv = the variant's Q + 2 rows of the grid sums (xt^2, xt wt_j,
+// xt yt), base = the records of the grid points.
+template <int Q, bool HAS_X, bool REML>
+__device__ __forceinline__ void maximise_cov(uint32_t n, uint32_t ldi, const double* __restrict__ d, const double* __restrict__ Wt,
+                             const double* __restrict__ yt, const double* __restrict__ xt, const double* __restrict__ Gv,
+                             const double* __restrict__ grid, const double* __restrict__ base, double* s_l, double* s_dl, CovLds& L,
+                             double& best_l, double& best_lam) {
+    const double nd = (double)n;
+    AfterW unused;
+    for (uint32_t g = threadIdx.x; g < LMM_GRID; g += 64) {
+        XSums x = {0, 0, 0, 0};
+        double xw[Q], dxw[Q];
+#pragma unroll
+        for (int j = 0; j < Q; j++) xw[j] = dxw[j] = 0;
+        if (HAS_X) {
+            x = {Gv[g], Gv[(Q + 1) * LMM_HB_COLS + g], Gv[LMM_GRID + g], Gv[(Q + 1) * LMM_HB_COLS + LMM_GRID + g]};
+#pragma unroll
+            for (int j = 0; j < Q; j++) xw[j] = Gv[(1 + j) * LMM_HB_COLS + g], dxw[j] = Gv[(1 + j) * LMM_HB_COLS + LMM_GRID + g];
+        }
+        ll_cov<Q, HAS_X, REML>(base + (uint64_t)g * LMM_BASEC, x, xw, dxw, nd, s_l[g], s_dl[g], unused);
+    }
+    __syncthreads();
+    best_l = s_l[0];
+    best_lam = grid[0];
+    if (s_l[LMM_GRID - 1] > best_l) {
+        best_l = s_l[LMM_GRID - 1];
+        best_lam = grid[LMM_GRID - 1];
+    }
+    for (uint32_t g = 0; g + 1 < LMM_GRID; g++) {
+        double fa = s_dl[g], fb = s_dl[g + 1];
+        if (!(fa > 0.0 && fb <= 0.0)) continue;  // (wave-uniform: LDS values)
+        double ta = grid[LMM_GRID + g], tb = grid[LMM_GRID + g + 1];
+        int side = 0;
+        double t_best = fa < -fb ? ta : tb, f_best = fa < -fb ? fa : -fb;
+        for (uint32_t step = 0; step < LMM_REFINE_STEPS; step++) {
+            double tm = (ta * fb - tb * fa) / (fb - fa);
+            if (step % 3 == 2 || !(tm > ta && tm < tb)) tm = 0.5 * (ta + tb);
+            double l, dl;
+            eval_cov<Q, HAS_X, REML, false>(exp(tm), n, ldi, d, Wt, yt, xt, L, l, dl, unused);
+            if (fabs(dl) < f_best) {
+                f_best = fabs(dl);
+                t_best = tm;
+            }
+            if (dl > 0.0) {
+                ta = tm, fa = dl;
+                if (side == 1) fb *= 0.5;
+                side = 1;
+            } else {
+                tb = tm, fb = dl;
+                if (side == -1) fa *= 0.5;
+                side = -1;
+            }
+        }
+        const double lam = exp(t_best);
+        double l, dl;
+        eval_cov<Q, HAS_X, REML, true>(lam, n, ldi, d, Wt, yt, xt, L, l, dl, unused);
+        if (l > best_l) {
+            best_l = l;
+            best_lam = lam;
+        }
+    }
+}
+
+// One wave per grid point: the record of lambda[g] to base[g][LMM_BASEC]
+template <int Q>
+__global__ void __launch_bounds__(64) lmm_base_cov_kernel(LmmDims dm, const double* __restrict__ d, const double* __restrict__ Wt,
+                                                          const double* __restrict__ yt, const double* __restrict__ grid,
+                                                          double* __restrict__ base) {
+    __shared__ CovLds L;
+    const uint32_t g = blockIdx.x;
+    const double* zp[Q + 1];
+#pragma unroll
+    for (int j = 0; j < Q; j++) zp[j] = Wt + (uint64_t)j * dm.ldi;
+    zp[Q] = yt;
+    for (uint32_t k = threadIdx.x; k < LMM_BASEC; k += 64) L.rec[k] = 0.0;  // (the entries past Q stay zero)
+    cov_sum_passes<Q + 1, 0, true>(grid[g], dm.n, d, zp, L);
+    cov_record<Q>(L);
+    for (uint32_t k = threadIdx.x; k < LMM_BASEC; k += 64) base[(uint64_t)g * LMM_BASEC + k] = L.rec[k];
+}
+
+// The grid sums with covariates: G[v][Q + 2][LMM_HB_COLS], rows xt^2, xt wt_j (j < q), xt yt. lmm_grid_kernel's mapping and order
+// of i; blockIdx.z picks a group of up to three rows, so a wave holds lmm_grid_kernel's accumulators whatever q is.
+__global__ void __launch_bounds__(256) lmm_grid_cov_kernel(const double* __restrict__ Xt, uint32_t nv, LmmDims dm, uint32_t q,
+                                                           const double* __restrict__ Wt, const double* __restrict__ yt,
+                                                           const double* __restrict__ HB, double* __restrict__ G) {
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, qq = lane >> 4;
+    const uint32_t v0 = (blockIdx.x * 4 + wave) * 16;
+    if (v0 >= nv) return;
+    const uint32_t tile0 = blockIdx.y * 4, n_tiles = LMM_HB_COLS / 16;
+    const uint32_t row0 = blockIdx.z * 3, n_rows = q + 2, nr = min(3u, n_rows - row0);  // (the launcher gives row0 < n_rows)
+    const double* xrow = Xt + (uint64_t)(v0 + r) * dm.ldi + 4 * qq;  // (rows up to nv rounded up to 16 exist: LMM_VTILE padding)
+    // the other factor of row c of the group: xt itself, a row of Wt, or yt (rows past nr: yt, never used)
+    const double* other[3];
+    for (uint32_t c = 0; c < 3; c++) {
+        const uint32_t row = row0 + c;
+        other[c] = row == 0 ? xrow - 4 * qq : row <= q ? Wt + (uint64_t)(row - 1) * dm.ldi : yt;
+    }
+    d4 acc[3][4];
+    for (int c = 0; c < 3; c++)
+        for (int t = 0; t < 4; t++) acc[c][t] = d4{0, 0, 0, 0};
+    for (uint32_t i0 = 0; i0 < dm.ldi; i0 += 16) {
+#pragma unroll
+        for (uint32_t s = 0; s < 4; s++) {
+            const uint32_t i = i0 + 4 * qq + s;
+            const double x = xrow[i0 + s];
+            const double a0 = x * other[0][i], a1 = nr > 1 ? x * other[1][i] : 0.0, a2 = nr > 2 ? x * other[2][i] : 0.0;
+            const double* hrow = HB + (uint64_t)i * LMM_HB_COLS + r;
+#pragma unroll
+            for (uint32_t t = 0; t < 4; t++) {
+                if (tile0 + t >= n_tiles) continue;
+                const double b = hrow[16 * (tile0 + t)];
+                acc[0][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b, acc[0][t], 0, 0, 0);
+                if (nr > 1) acc[1][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b, acc[1][t], 0, 0, 0);
+                if (nr > 2) acc[2][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a2, b, acc[2][t], 0, 0, 0);
+            }
+        }
+    }
+    for (int j = 0; j < 4; j++) {
+        const uint32_t v = v0 + qq + 4 * j;
+        if (v >= nv) continue;
+        for (uint32_t c = 0; c < 3; c++) {
+            if (c >= nr) continue;
+            for (uint32_t t = 0; t < 4; t++)
+                if (tile0 + t < n_tiles) G[((uint64_t)v * n_rows + row0 + c) * LMM_HB_COLS + 16 * (tile0 + t) + r] = acc[c][t][j];
+        }
+    }
+}
+
+template <int Q>
+__global__ void __launch_bounds__(64) lmm_null_cov_kernel(LmmDims dm, const double* __restrict__ d, const double* __restrict__ Wt,
+                                                          const double* __restrict__ yt, const double* __restrict__ grid,
+                                                          const double* __restrict__ base, double* __restrict__ out) {
+    __shared__ double s_l[LMM_GRID], s_dl[LMM_GRID];
+    __shared__ CovLds L;
+    double l, lam;
+    maximise_cov<Q, false, false>(dm.n, dm.ldi, d, Wt, yt, nullptr, nullptr, grid, base, s_l, s_dl, L, l, lam);
+    if (threadIdx.x == 0) {
+        out[0] = l;
+        out[1] = lam;
+    }
+}
+
+// -lmm 4: out = (lR0, lambda0_remle, vg, ve), ve = RSS0 / (n - q) and vg = lambda ve at the maximiser
+template <int Q>
+__global__ void __launch_bounds__(64) lmm_null_reml_cov_kernel(LmmDims dm, const double* __restrict__ d, const double* __restrict__ Wt,
+                                                               const double* __restrict__ yt, const double* __restrict__ grid,
+                                                               const double* __restrict__ base, double* __restrict__ out) {
+    __shared__ double s_l[LMM_GRID], s_dl[LMM_GRID];
+    __shared__ CovLds L;
+    double l, lam, l_at, dl_at;
+    AfterW a;
+    maximise_cov<Q, false, true>(dm.n, dm.ldi, d, Wt, yt, nullptr, nullptr, grid, base, s_l, s_dl, L, l, lam);
+    eval_cov<Q, false, true, false>(lam, dm.n, dm.ldi, d, Wt, yt, nullptr, L, l_at, dl_at, a);
+    if (threadIdx.x == 0) {
+        const double ve = a.yy / ((double)dm.n - (double)Q);
+        out[0] = l;
+        out[1] = lam;
+        out[2] = lam * ve;
+        out[3] = ve;
+    }
+}
+
+template <int Q>
+__global__ void __launch_bounds__(64) lmm_refine_cov_kernel(const double* __restrict__ Xt, const double* __restrict__ G,
+                                                            const LmmVariant* __restrict__ vars, LmmDims dm, const double* __restrict__ d,
+                                                            const double* __restrict__ Wt, const double* __restrict__ yt,
+                                                            const double* __restrict__ grid, const double* __restrict__ base, double l0,
+                                                            double* __restrict__ lrt, double* __restrict__ lam_out,
+                                                            double* __restrict__ p_out) {
+    __shared__ double s_l[LMM_GRID], s_dl[LMM_GRID];
+    __shared__ CovLds L;
+    const uint32_t v = blockIdx.x;
+    if (!vars[v].tested) {  // (the whole block leaves)
+        if (threadIdx.x == 0) lrt[v] = lam_out[v] = p_out[v] = __builtin_nan("");
+        return;
+    }
+    double l, lam;
+    maximise_cov<Q, true, false>(dm.n, dm.ldi, d, Wt, yt, Xt + (uint64_t)v * dm.ldi, G + (uint64_t)v * (Q + 2) * LMM_HB_COLS, grid, base,
+                                 s_l, s_dl, L, l, lam);
+    if (threadIdx.x == 0) {
+        const double stat = fmax(0.0, 2.0 * (l - l0));
+        lrt[v] = stat;
+        lam_out[v] = lam;
+        p_out[v] = erfc(sqrt(0.5 * stat));
+    }
+}
+
+// -lmm 4 with covariates: lmm_refine_cov_kernel's maximisation (lrt, lambda and p keep its bits), the REML maximisation, then the
+// Schur complements at l_remle (Wald) and at lambda0 (score); the F tails have n - q - 1 degrees of freedom.
+template <int Q>
+__global__ void __launch_bounds__(64) lmm_refine_all_cov_kernel(const double* __restrict__ Xt, const double* __restrict__ G,
+                                                                const LmmVariant* __restrict__ vars, LmmDims dm,
+                                                                const double* __restrict__ d, const double* __restrict__ Wt,
+                                                                const double* __restrict__ yt, const double* __restrict__ grid,
+                                                                const double* __restrict__ base, double l0, double lam0,
+                                                                double* __restrict__ lrt, double* __restrict__ lam_out,
+                                                                double* __restrict__ p_out, LmmWaldOut w) {
+    __shared__ double s_l[LMM_GRID], s_dl[LMM_GRID];
+    __shared__ CovLds L;
+    const uint32_t v = blockIdx.x;
+    if (!vars[v].tested) {  // (the whole block leaves)
+        if (threadIdx.x == 0)
+            lrt[v] = lam_out[v] = p_out[v] = w.beta[v] = w.se[v] = w.lam[v] = w.p_wald[v] = w.p_score[v] = __builtin_nan("");
+        return;
+    }
+    double l, lam;
+    const double* Gv = G + (uint64_t)v * (Q + 2) * LMM_HB_COLS;
+    const double* xt = Xt + (uint64_t)v * dm.ldi;
+    maximise_cov<Q, true, false>(dm.n, dm.ldi, d, Wt, yt, xt, Gv, grid, base, s_l, s_dl, L, l, lam);
+    if (threadIdx.x == 0) {
+        const double stat = fmax(0.0, 2.0 * (l - l0));
+        lrt[v] = stat;
+        lam_out[v] = lam;
+        p_out[v] = erfc(sqrt(0.5 * stat));
+    }
+    __syncthreads();  // (s_l and s_dl are written again)
+    double lr, lamr, l_at, dl_at;
+    AfterW a, a0;
+    maximise_cov<Q, true, true>(dm.n, dm.ldi, d, Wt, yt, xt, Gv, grid, base, s_l, s_dl, L, lr, lamr);
+    eval_cov<Q, true, true, false>(lamr, dm.n, dm.ldi, d, Wt, yt, xt, L, l_at, dl_at, a);
+    eval_cov<Q, true, true, false>(lam0, dm.n, dm.ldi, d, Wt, yt, xt, L, l_at, dl_at, a0);
+    if (threadIdx.x >= 2) return;
+    const double nd = (double)dm.n, df = nd - (double)Q - 1.0;
+    const double beta = a.xy / a.xx, rss1 = a.yy - a.xy * beta;
+    const double F = threadIdx.x == 0 ? a.xy * beta * df / rss1 : nd * a0.xy * a0.xy / (a0.xx * a0.yy);
+    const double p = fdist_tail(F, df);
+    if (threadIdx.x == 0) {
+        w.beta[v] = beta;
+        w.se[v] = sqrt(rss1 / (df * a.xx));
+        w.lam[v] = lamr;
+        w.p_wald[v] = p;
+    } else {
+        w.p_score[v] = p;
+    }
+}
+
 }  // namespace
 
 hipError_t launch_lmm_prep(const uint8_t* bed, uint32_t nv, LmmDims dm, double maf, double miss, uint8_t* codes, LmmVariant* vars,
@@ -607,6 +1096,67 @@ hipError_t launch_lmm_refine_multi(const double* Xt, const double* Gx, const dou
     if (np > LMM_PBLOCK) return hipErrorInvalidValue;
     hipLaunchKernelGGL(lmm_refine_multi_kernel, dim3(nv, np), dim3(64), 0, st, Xt, Gx, Gxy, vars, nv, dm, d, wt, Yt, grid, base, null, lrt,
                        lam, p);
+    return hipGetLastError();
+}
+
+// ---- covariates ----
+
+#define LMM_COV_DISPATCH(q, CALL)                  \
+    switch (q) {                                   \
+        case 1: { constexpr int Q = 1; CALL; break; } \
+        case 2: { constexpr int Q = 2; CALL; break; } \
+        case 3: { constexpr int Q = 3; CALL; break; } \
+        case 4: { constexpr int Q = 4; CALL; break; } \
+        case 5: { constexpr int Q = 5; CALL; break; } \
+        case 6: { constexpr int Q = 6; CALL; break; } \
+        case 7: { constexpr int Q = 7; CALL; break; } \
+        case 8: { constexpr int Q = 8; CALL; break; } \
+        default: return hipErrorInvalidValue;      \
+    }
+static_assert(LMM_MAXC == 8, "LMM_COV_DISPATCH lists the widths");
+
+hipError_t launch_lmm_base_cov(LmmDims dm, uint32_t q, const double* d, const double* Wt, const double* yt, const double* grid,
+                               double* base, hipStream_t st) {
+    LMM_COV_DISPATCH(q, hipLaunchKernelGGL(lmm_base_cov_kernel<Q>, dim3(LMM_GRID), dim3(64), 0, st, dm, d, Wt, yt, grid, base));
+    return hipGetLastError();
+}
+
+hipError_t launch_lmm_grid_cov(const double* Xt, uint32_t nv, LmmDims dm, uint32_t q, const double* Wt, const double* yt,
+                               const double* HB, double* G, hipStream_t st) {
+    if (!nv) return hipSuccess;
+    if (q < 1 || q > LMM_MAXC) return hipErrorInvalidValue;
+    const dim3 grid((nv + 63) / 64, (LMM_HB_COLS / 16 + 3) / 4, (q + 2 + 2) / 3);
+    hipLaunchKernelGGL(lmm_grid_cov_kernel, grid, dim3(256), 0, st, Xt, nv, dm, q, Wt, yt, HB, G);
+    return hipGetLastError();
+}
+
+hipError_t launch_lmm_null_cov(LmmDims dm, uint32_t q, const double* d, const double* Wt, const double* yt, const double* grid,
+                               const double* base, double* out, hipStream_t st) {
+    LMM_COV_DISPATCH(q, hipLaunchKernelGGL(lmm_null_cov_kernel<Q>, dim3(1), dim3(64), 0, st, dm, d, Wt, yt, grid, base, out));
+    return hipGetLastError();
+}
+
+hipError_t launch_lmm_null_reml_cov(LmmDims dm, uint32_t q, const double* d, const double* Wt, const double* yt, const double* grid,
+                                    const double* base, double* out, hipStream_t st) {
+    LMM_COV_DISPATCH(q, hipLaunchKernelGGL(lmm_null_reml_cov_kernel<Q>, dim3(1), dim3(64), 0, st, dm, d, Wt, yt, grid, base, out));
+    return hipGetLastError();
+}
+
+hipError_t launch_lmm_refine_cov(const double* Xt, const double* G, const LmmVariant* vars, uint32_t nv, LmmDims dm, uint32_t q,
+                                 const double* d, const double* Wt, const double* yt, const double* grid, const double* base, double l0,
+                                 double* lrt, double* lam, double* p, hipStream_t st) {
+    if (!nv) return hipSuccess;
+    LMM_COV_DISPATCH(q, hipLaunchKernelGGL(lmm_refine_cov_kernel<Q>, dim3(nv), dim3(64), 0, st, Xt, G, vars, dm, d, Wt, yt, grid, base, l0,
+                                           lrt, lam, p));
+    return hipGetLastError();
+}
+
+hipError_t launch_lmm_refine_all_cov(const double* Xt, const double* G, const LmmVariant* vars, uint32_t nv, LmmDims dm, uint32_t q,
+                                     const double* d, const double* Wt, const double* yt, const double* grid, const double* base,
+                                     double l0, double lam0, double* lrt, double* lam, double* p, LmmWaldOut w, hipStream_t st) {
+    if (!nv) return hipSuccess;
+    LMM_COV_DISPATCH(q, hipLaunchKernelGGL(lmm_refine_all_cov_kernel<Q>, dim3(nv), dim3(64), 0, st, Xt, G, vars, dm, d, Wt, yt, grid, base,
+                                           l0, lam0, lrt, lam, p, w));
     return hipGetLastError();
 }
 

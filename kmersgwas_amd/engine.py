@@ -508,13 +508,31 @@ class LmmLrt:
 
     K is eigendecomposed once (host threads); every phenotype and .bed given to the object reuses that."""
 
-    def __init__(self, K: np.ndarray, device: int = 0, lmin: float = 1e-5, lmax: float = 1e5, chunk_variants: int = 10240):
+    def __init__(self, K: np.ndarray, device: int = 0, lmin: float = 1e-5, lmax: float = 1e5, chunk_variants: int = 10240,
+                 covariates=None):
         K = np.ascontiguousarray(K, np.float64)
         if K.ndim != 2 or K.shape[0] != K.shape[1]:
             raise ValueError("K must be square")
         self.n = K.shape[0]
         self._h = C.c_void_p()
         check(lib.kgwas_lmm_create(self.n, ptr(K), device, lmin, lmax, chunk_variants, C.byref(self._h)))
+        if covariates is not None:
+            self.set_covariates(covariates)
+
+    def set_covariates(self, W):
+        """W: (n, q) covariates, 1 <= q <= 8, whose columns span the constant vector (give it a column of 1s): the model becomes
+        y = W a + x b + u + e for null, null_reml, test, test_all and test_table. None restores the intercept alone. The
+        multi-phenotype passes refuse an object with covariates."""
+        if W is None:
+            check(lib.kgwas_lmm_set_covariates(self._h, 0, None))
+            return
+        W = np.ascontiguousarray(W, np.float64)
+        if W.ndim == 1:
+            W = W[:, None]
+        if W.ndim != 2 or W.shape[0] != self.n:
+            raise ValueError("covariates must have one row per individual")
+        W = np.ascontiguousarray(W)
+        check(lib.kgwas_lmm_set_covariates(self._h, W.shape[1], ptr(W)))
 
     def _y(self, y):
         y = np.ascontiguousarray(y, np.float64)
