@@ -213,13 +213,8 @@ void kgwas::lmm::fit_null(kgwas_lmm* h, const double* y) {
     KGWAS_HIP(hipSetDevice(h->device));
     h->have_null = h->have_null_reml = false;
     KGWAS_HIP(hipMemcpyAsync(h->d_yt.p, yt.data(), yt.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (h->q) {
-        KGWAS_HIP(launch_lmm_base_cov(h->dm, h->q, h->d_d.p, h->d_Wt.p, h->d_yt.p, h->d_grid.p, h->d_basec.p, h->stream));
-        KGWAS_HIP(launch_lmm_null_cov(h->dm, h->q, h->d_d.p, h->d_Wt.p, h->d_yt.p, h->d_grid.p, h->d_basec.p, h->d_null.p, h->stream));
-    } else {
-        KGWAS_HIP(launch_lmm_base(h->dm, h->d_d.p, h->d_wt.p, h->d_yt.p, h->d_grid.p, h->d_base.p, h->stream));
-        KGWAS_HIP(launch_lmm_null(h->dm, h->d_d.p, h->d_wt.p, h->d_yt.p, h->d_grid.p, h->d_base.p, h->d_null.p, h->stream));
-    }
+    KGWAS_HIP(launch_lmm_base(h->dm, h->q, h->d_d.p, h->fixed_t(), h->d_yt.p, 1, h->d_grid.p, h->base_rows(), h->stream));
+    KGWAS_HIP(launch_lmm_null(h->dm, h->q, h->d_d.p, h->fixed_t(), h->d_yt.p, 1, h->d_grid.p, h->base_rows(), h->d_null.p, h->stream));
     double out[2];
     KGWAS_HIP(hipMemcpyAsync(out, h->d_null.p, sizeof(out), hipMemcpyDeviceToHost, h->stream));
     KGWAS_HIP(hipStreamSynchronize(h->stream));  // (yt is read by the copy until here)
@@ -235,10 +230,7 @@ void kgwas::lmm::fit_null_reml(kgwas_lmm* h, const double* y) {
     if (h->have_null_reml) return;
     KGWAS_HIP(hipSetDevice(h->device));
     h->ensure_wald();
-    if (h->q)
-        KGWAS_HIP(launch_lmm_null_reml_cov(h->dm, h->q, h->d_d.p, h->d_Wt.p, h->d_yt.p, h->d_grid.p, h->d_basec.p, h->d_null_reml.p, h->stream));
-    else
-        KGWAS_HIP(launch_lmm_null_reml(h->dm, h->d_d.p, h->d_wt.p, h->d_yt.p, h->d_grid.p, h->d_base.p, h->d_null_reml.p, h->stream));
+    KGWAS_HIP(launch_lmm_null_reml(h->dm, h->q, h->d_d.p, h->fixed_t(), h->d_yt.p, h->d_grid.p, h->base_rows(), h->d_null_reml.p, h->stream));
     double out[4];
     KGWAS_HIP(hipMemcpyAsync(out, h->d_null_reml.p, sizeof(out), hipMemcpyDeviceToHost, h->stream));
     KGWAS_HIP(hipStreamSynchronize(h->stream));
@@ -340,26 +332,14 @@ void kgwas::lmm::single_backend(kgwas_lmm* h, const uint8_t* codes, const LmmVar
     hipStream_t st = h->stream;
     KGWAS_HIP(launch_lmm_rotate(codes, vars, cc, h->dm, h->d_U.p, h->d_Xt.p, st));
     h->timer.end(&kgwas_lmm_stats::rotate_ms, st);
-    if (h->q) {  // covariates: the same stages on their own kernels
-        KGWAS_HIP(launch_lmm_grid_cov(h->d_Xt.p, cc, h->dm, h->q, h->d_Wt.p, h->d_yt.p, h->d_HB.p, h->d_G.p, st));
-        h->timer.end(&kgwas_lmm_stats::grid_ms, st);
-        if (wald)
-            KGWAS_HIP(launch_lmm_refine_all_cov(h->d_Xt.p, h->d_G.p, vars, cc, h->dm, h->q, h->d_d.p, h->d_Wt.p, h->d_yt.p, h->d_grid.p,
-                                                h->d_basec.p, h->l0, h->lambda0, h->d_lrt.p, h->d_lam.p, h->d_p.p, h->wald_out(), st));
-        else
-            KGWAS_HIP(launch_lmm_refine_cov(h->d_Xt.p, h->d_G.p, vars, cc, h->dm, h->q, h->d_d.p, h->d_Wt.p, h->d_yt.p, h->d_grid.p,
-                                            h->d_basec.p, h->l0, h->d_lrt.p, h->d_lam.p, h->d_p.p, st));
-        h->timer.end(&kgwas_lmm_stats::refine_ms, st);
-        return;
-    }
-    KGWAS_HIP(launch_lmm_grid(h->d_Xt.p, cc, h->dm, h->d_wt.p, h->d_yt.p, h->d_HB.p, h->d_G.p, st));
+    KGWAS_HIP(launch_lmm_grid(h->d_Xt.p, cc, h->dm, h->q, h->fixed_t(), h->d_yt.p, h->d_HB.p, h->d_G.p, st));
     h->timer.end(&kgwas_lmm_stats::grid_ms, st);
     if (wald)  // -lmm 4 (the caller has called ensure_wald): d_wald too
-        KGWAS_HIP(launch_lmm_refine_all(h->d_Xt.p, h->d_G.p, vars, cc, h->dm, h->d_d.p, h->d_wt.p, h->d_yt.p, h->d_grid.p, h->d_base.p, h->l0,
-                                        h->lambda0, h->d_lrt.p, h->d_lam.p, h->d_p.p, h->wald_out(), st));
+        KGWAS_HIP(launch_lmm_refine_all(h->d_Xt.p, h->d_G.p, vars, cc, h->dm, h->q, h->d_d.p, h->fixed_t(), h->d_yt.p, h->d_grid.p,
+                                        h->base_rows(), h->l0, h->lambda0, h->d_lrt.p, h->d_lam.p, h->d_p.p, h->wald_out(), st));
     else
-        KGWAS_HIP(launch_lmm_refine(h->d_Xt.p, h->d_G.p, vars, cc, h->dm, h->d_d.p, h->d_wt.p, h->d_yt.p, h->d_grid.p, h->d_base.p, h->l0,
-                                    h->d_lrt.p, h->d_lam.p, h->d_p.p, st));
+        KGWAS_HIP(launch_lmm_refine(h->d_Xt.p, h->d_G.p, vars, cc, h->dm, h->q, h->d_d.p, h->fixed_t(), h->d_yt.p, h->d_grid.p, h->base_rows(),
+                                    h->l0, h->d_lrt.p, h->d_lam.p, h->d_p.p, st));
     h->timer.end(&kgwas_lmm_stats::refine_ms, st);
 }
 
@@ -432,8 +412,8 @@ void kgwas::lmm::multi_prepare(kgwas_lmm* h, uint32_t n_pheno, const double* Y, 
     h->ensure_multi_cols(n_pheno);
     hipStream_t st = h->stream;
     KGWAS_HIP(hipMemcpyAsync(h->d_Ytm.p, Yt.data(), Yt.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    KGWAS_HIP(launch_lmm_base_multi(h->dm, h->d_d.p, h->d_wt.p, h->d_Ytm.p, n_pheno, h->d_grid.p, h->d_basem.p, st));
-    KGWAS_HIP(launch_lmm_null_multi(h->dm, h->d_d.p, h->d_wt.p, h->d_Ytm.p, n_pheno, h->d_grid.p, h->d_basem.p, h->d_nullm.p, st));
+    KGWAS_HIP(launch_lmm_base(h->dm, 0, h->d_d.p, h->d_wt.p, h->d_Ytm.p, n_pheno, h->d_grid.p, h->d_basem.p, st));
+    KGWAS_HIP(launch_lmm_null(h->dm, 0, h->d_d.p, h->d_wt.p, h->d_Ytm.p, n_pheno, h->d_grid.p, h->d_basem.p, h->d_nullm.p, st));
     std::vector<double> nulls(2 * (uint64_t)n_pheno);
     KGWAS_HIP(hipMemcpyAsync(nulls.data(), h->d_nullm.p, nulls.size() * sizeof(double), hipMemcpyDeviceToHost, st));
     KGWAS_HIP(hipStreamSynchronize(st));  // (Yt is read by the copy until here)

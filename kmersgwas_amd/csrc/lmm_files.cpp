@@ -167,33 +167,41 @@ void read_fam(const std::string& path, uint32_t pheno_col, std::vector<double>& 
     }
 }
 
-uint64_t format_assoc(const char* chr, const char* rs, const char* ps, uint32_t n_miss, const char* a1, const char* a0, double af,
-                      double l_mle, double p, char* out, uint64_t cap) {
-    char buf[1024];
-    int len;
-    if (!chr)
-        len = snprintf(buf, sizeof(buf), "chr\trs\tps\tn_miss\tallele1\tallele0\taf\tl_mle\tp_lrt\n");
-    else
-        len = snprintf(buf, sizeof(buf), "%s\t%s\t%s\t%u\t%s\t%s\t%.3f\t%.6e\t%.6e\n", chr, rs, ps, n_miss, a1, a0, af, l_mle, p);
-    if (len < 0 || (size_t)len >= sizeof(buf)) throw Error(KGWAS_ERR_FORMAT, "a .bim line is too long");
+// One line of an .assoc.txt (chr = null: the header): columns 1-7, then every column of cols, a number as %.6e. `limit` is the
+// length a line is refused at.
+struct AssocColumn {
+    const char* name;
+    double value;
+};
+uint64_t format_line(const char* chr, const char* rs, const char* ps, uint32_t n_miss, const char* a1, const char* a0, double af,
+                     const AssocColumn* cols, size_t n_cols, size_t limit, char* out, uint64_t cap) {
+    char buf[1280];
+    int len = chr ? snprintf(buf, limit, "%s\t%s\t%s\t%u\t%s\t%s\t%.3f", chr, rs, ps, n_miss, a1, a0, af)
+                  : snprintf(buf, limit, "chr\trs\tps\tn_miss\tallele1\tallele0\taf");
+    for (size_t k = 0; k <= n_cols && len >= 0 && (size_t)len < limit; k++) {  // (k = n_cols: the end of the line)
+        const int m = k == n_cols ? snprintf(buf + len, limit - len, "\n")
+                      : chr       ? snprintf(buf + len, limit - len, "\t%.6e", cols[k].value)
+                                  : snprintf(buf + len, limit - len, "\t%s", cols[k].name);
+        len = m < 0 ? m : len + m;
+    }
+    if (len < 0 || (size_t)len >= limit) throw Error(KGWAS_ERR_FORMAT, "a .bim line is too long");
     if (out && cap >= (uint64_t)len) memcpy(out, buf, (size_t)len);
     return (uint64_t)len;
+}
+
+uint64_t format_assoc(const char* chr, const char* rs, const char* ps, uint32_t n_miss, const char* a1, const char* a0, double af,
+                      double l_mle, double p, char* out, uint64_t cap) {
+    const AssocColumn cols[] = {{"l_mle", l_mle}, {"p_lrt", p}};
+    return format_line(chr, rs, ps, n_miss, a1, a0, af, cols, 2, 1024, out, cap);
 }
 
 // the -lmm 4 line: columns 1-7, l_mle and p_lrt with the bytes of format_assoc's
 uint64_t format_assoc4(const char* chr, const char* rs, const char* ps, uint32_t n_miss, const char* a1, const char* a0, double af,
                        double beta, double se, double l_remle, double l_mle, double p_wald, double p_lrt, double p_score, char* out,
                        uint64_t cap) {
-    char buf[1280];
-    int len;
-    if (!chr)
-        len = snprintf(buf, sizeof(buf), "chr\trs\tps\tn_miss\tallele1\tallele0\taf\tbeta\tse\tl_remle\tl_mle\tp_wald\tp_lrt\tp_score\n");
-    else
-        len = snprintf(buf, sizeof(buf), "%s\t%s\t%s\t%u\t%s\t%s\t%.3f\t%.6e\t%.6e\t%.6e\t%.6e\t%.6e\t%.6e\t%.6e\n", chr, rs, ps, n_miss, a1, a0,
-                       af, beta, se, l_remle, l_mle, p_wald, p_lrt, p_score);
-    if (len < 0 || (size_t)len >= sizeof(buf)) throw Error(KGWAS_ERR_FORMAT, "a .bim line is too long");
-    if (out && cap >= (uint64_t)len) memcpy(out, buf, (size_t)len);
-    return (uint64_t)len;
+    const AssocColumn cols[] = {{"beta", beta},     {"se", se},       {"l_remle", l_remle}, {"l_mle", l_mle},
+                                {"p_wald", p_wald}, {"p_lrt", p_lrt}, {"p_score", p_score}};
+    return format_line(chr, rs, ps, n_miss, a1, a0, af, cols, 7, 1280, out, cap);
 }
 
 std::string log_path_of(const std::string& out) {
@@ -265,10 +273,10 @@ void read_bim_bed(const std::string& base, uint64_t nf, const std::vector<uint32
     }
 }
 
-std::string assoc_header() {
-    std::string text(format_assoc(nullptr, "", "", 0, "", "", 0, 0, 0, nullptr, 0), '\0');
-    format_assoc(nullptr, "", "", 0, "", "", 0, 0, 0, &text[0], text.size());
-    return text;
+std::string assoc_header(bool all_tests = false) {
+    char line[1280];
+    return std::string(line, all_tests ? format_assoc4(nullptr, "", "", 0, "", "", 0, 0, 0, 0, 0, 0, 0, 0, line, sizeof(line))
+                                       : format_assoc(nullptr, "", "", 0, "", "", 0, 0, 0, line, sizeof(line)));
 }
 
 // the fields of the .bim lines of the tested ones among variants first .. first + cnt (tested starts at `first`; the others stay empty)
@@ -284,38 +292,26 @@ std::vector<std::vector<std::string>> bim_fields(const std::string& base, const 
     return fields;
 }
 
-// appends the lines of the tested ones among fields.size() variants (all arrays start at the first of them); returns their number
-uint64_t append_assoc(std::string& text, const std::vector<std::vector<std::string>>& fields, const uint32_t* n_miss, const double* af,
-                      const double* lam, const double* p, const uint8_t* tested) {
-    uint64_t n_tested = 0;
-    for (uint64_t v = 0; v < fields.size(); v++) {
-        if (!tested[v]) continue;
-        const std::vector<std::string>& f = fields[v];
-        char line[1024];
-        const uint64_t len = format_assoc(f[0].c_str(), f[1].c_str(), f[3].c_str(), n_miss[v], f[4].c_str(), f[5].c_str(), af[v], lam[v],
-                                          p[v], line, sizeof(line));
-        text.append(line, len);
-        n_tested++;
-    }
-    return n_tested;
-}
-
-// -lmm 4: the header and the lines of the tested ones among fields.size() variants; returns their number
+// -lmm 4's five further columns of a .bed pass
 struct WaldColumns {
     std::vector<double> beta, se, lam, p_wald, p_score;
     explicit WaldColumns(uint64_t m) : beta(m), se(m), lam(m), p_wald(m), p_score(m) {}
     WaldArrays arrays() { return {beta.data(), se.data(), lam.data(), p_wald.data(), p_score.data()}; }
 };
-uint64_t append_assoc4(std::string& text, const std::vector<std::vector<std::string>>& fields, const uint32_t* n_miss, const double* af,
-                       const double* lam, const double* p, const WaldColumns& w, const uint8_t* tested) {
-    char line[1280];
-    text.append(line, format_assoc4(nullptr, "", "", 0, "", "", 0, 0, 0, 0, 0, 0, 0, 0, line, sizeof(line)));
+
+// appends the lines of the tested ones among fields.size() variants (all arrays start at the first of them), the 14-column lines
+// of -lmm 4 with w; returns their number
+uint64_t append_assoc(std::string& text, const std::vector<std::vector<std::string>>& fields, const uint32_t* n_miss, const double* af,
+                      const double* lam, const double* p, const uint8_t* tested, const WaldColumns* w = nullptr) {
     uint64_t n_tested = 0;
     for (uint64_t v = 0; v < fields.size(); v++) {
         if (!tested[v]) continue;
         const std::vector<std::string>& f = fields[v];
-        const uint64_t len = format_assoc4(f[0].c_str(), f[1].c_str(), f[3].c_str(), n_miss[v], f[4].c_str(), f[5].c_str(), af[v], w.beta[v],
-                                           w.se[v], w.lam[v], lam[v], w.p_wald[v], p[v], w.p_score[v], line, sizeof(line));
+        const char *chr = f[0].c_str(), *rs = f[1].c_str(), *ps = f[3].c_str(), *a1 = f[4].c_str(), *a0 = f[5].c_str();
+        char line[1280];
+        const uint64_t len = w ? format_assoc4(chr, rs, ps, n_miss[v], a1, a0, af[v], w->beta[v], w->se[v], w->lam[v], lam[v], w->p_wald[v],
+                                               p[v], w->p_score[v], line, sizeof(line))
+                               : format_assoc(chr, rs, ps, n_miss[v], a1, a0, af[v], lam[v], p[v], line, sizeof(line));
         text.append(line, len);
         n_tested++;
     }
@@ -339,33 +335,24 @@ std::string covariate_lines(const Covariates* cov) {
     return cov ? "covariates\t" + cov->path + "\nn_covariates\t" + std::to_string(cov->q) + "\n" : std::string();
 }
 
+// the log of a .bed pass; with reml (-lmm 4: a handle whose REML null model is fitted) under the other title, with that model's
+// four lines behind logl_H0
 void write_log(const std::string& out, const std::string& base, const char* kinship_path, uint64_t nf, uint64_t n, uint64_t M,
                uint64_t n_tested, double lambda0, double l0, double eigen_ms, double rotate_ms, double grid_ms, double refine_ms,
-               double total_ms, const Covariates* cov = nullptr) {
-    char log[2048];
-    const int ll = snprintf(log, sizeof(log),
-                            "lmm_lrt: ML likelihood-ratio test (-lmm 2)\nbfile\t%s\nkinship\t%s\n%sindividuals_in_fam\t%llu\n"
-                            "individuals_used\t%llu\nvariants_read\t%llu\nvariants_tested\t%llu\nlambda0\t%.6e\nlogl_H0\t%.6f\n"
+               double total_ms, const Covariates* cov = nullptr, const kgwas_lmm* reml = nullptr) {
+    char log[2304], reml_lines[1024] = "";
+    if (reml)
+        snprintf(reml_lines, sizeof(reml_lines), "lambda0_remle\t%.6e\nlogl_remle_H0\t%.6f\nvg\t%.6e\nve\t%.6e\n", reml->lambda0_reml,
+                 reml->l0_reml, reml->vg, reml->ve);
+    const size_t cap = reml ? sizeof(log) : 2048;  // (where each of the two logs is cut)
+    const int ll = snprintf(log, cap,
+                            "lmm_lrt: ML likelihood-ratio test%s\nbfile\t%s\nkinship\t%s\n%sindividuals_in_fam\t%llu\n"
+                            "individuals_used\t%llu\nvariants_read\t%llu\nvariants_tested\t%llu\nlambda0\t%.6e\nlogl_H0\t%.6f\n%s"
                             "ms: eigen=%.3f rotate=%.3f grid=%.3f refine=%.3f total=%.3f\n",
-                            base.c_str(), kinship_path, covariate_lines(cov).c_str(), (unsigned long long)nf, (unsigned long long)n, (unsigned long long)M,
-                            (unsigned long long)n_tested, lambda0, l0, eigen_ms, rotate_ms, grid_ms, refine_ms, total_ms);
-    write_log_text(out, log, sizeof(log), ll);
-}
-
-// the log of -lmm 4: write_log's lines under its own title, with the REML null model's four behind logl_H0
-void write_log4(const std::string& out, const std::string& base, const char* kinship_path, uint64_t nf, uint64_t n, uint64_t M,
-                uint64_t n_tested, const kgwas_lmm* h, double rotate_ms, double grid_ms, double refine_ms, double total_ms,
-                const Covariates* cov = nullptr) {
-    char log[2304];
-    const int ll = snprintf(log, sizeof(log),
-                            "lmm_lrt: ML likelihood-ratio test, REML Wald test and score test (-lmm 4)\nbfile\t%s\nkinship\t%s\n%s"
-                            "individuals_in_fam\t%llu\nindividuals_used\t%llu\nvariants_read\t%llu\nvariants_tested\t%llu\nlambda0\t%.6e\n"
-                            "logl_H0\t%.6f\nlambda0_remle\t%.6e\nlogl_remle_H0\t%.6f\nvg\t%.6e\nve\t%.6e\n"
-                            "ms: eigen=%.3f rotate=%.3f grid=%.3f refine=%.3f total=%.3f\n",
-                            base.c_str(), kinship_path, covariate_lines(cov).c_str(), (unsigned long long)nf, (unsigned long long)n,
-                            (unsigned long long)M, (unsigned long long)n_tested, h->lambda0, h->l0, h->lambda0_reml, h->l0_reml, h->vg, h->ve, h->st.eigen_ms, rotate_ms,
-                            grid_ms, refine_ms, total_ms);
-    write_log_text(out, log, sizeof(log), ll);
+                            reml ? ", REML Wald test and score test (-lmm 4)" : " (-lmm 2)", base.c_str(), kinship_path,
+                            covariate_lines(cov).c_str(), (unsigned long long)nf, (unsigned long long)n, (unsigned long long)M,
+                            (unsigned long long)n_tested, lambda0, l0, reml_lines, eigen_ms, rotate_ms, grid_ms, refine_ms, total_ms);
+    write_log_text(out, log, cap, ll);
 }
 
 void run_files(const char* kinship_path, uint64_t n_beds, const char* const* bases, const char* const* outs, uint32_t pheno_col,
@@ -412,26 +399,21 @@ void run_files(const char* kinship_path, uint64_t n_beds, const char* const* bas
         std::vector<uint32_t> n_miss(M);
         std::vector<uint8_t> tested(M);
         const kgwas_lmm_stats before = h->st;
+        std::unique_ptr<WaldColumns> w;  // -lmm 4
+        WaldArrays wa{};
         if (all_tests) {
-            WaldColumns w(M);
-            const WaldArrays wa = w.arrays();
+            w.reset(new WaldColumns(M));
+            wa = w->arrays();
             fit_null_reml(h.get(), y.data());
-            test_bed(h.get(), y.data(), body.data(), M, maf, miss, lrt.data(), lam.data(), p.data(), af.data(), n_miss.data(), tested.data(), &wa);
-            std::string text;
-            const uint64_t n_tested = append_assoc4(text, bim_fields(base, bim, 0, M, tested.data()), n_miss.data(), af.data(), lam.data(),
-                                                    p.data(), w, tested.data());
-            write_text(out, text, "wb");
-            write_log4(out, base, kinship_path, nf, n, M, n_tested, h.get(), h->st.rotate_ms - before.rotate_ms, h->st.grid_ms - before.grid_ms,
-                       h->st.refine_ms - before.refine_ms, now_ms() - t_start, cov);
-            continue;
         }
-        test_bed(h.get(), y.data(), body.data(), M, maf, miss, lrt.data(), lam.data(), p.data(), af.data(), n_miss.data(), tested.data());
-        std::string text = assoc_header();
-        const uint64_t n_tested =
-            append_assoc(text, bim_fields(base, bim, 0, M, tested.data()), n_miss.data(), af.data(), lam.data(), p.data(), tested.data());
+        test_bed(h.get(), y.data(), body.data(), M, maf, miss, lrt.data(), lam.data(), p.data(), af.data(), n_miss.data(), tested.data(),
+                 w ? &wa : nullptr);
+        std::string text = assoc_header(all_tests);
+        const uint64_t n_tested = append_assoc(text, bim_fields(base, bim, 0, M, tested.data()), n_miss.data(), af.data(), lam.data(),
+                                               p.data(), tested.data(), w.get());
         write_text(out, text, "wb");
         write_log(out, base, kinship_path, nf, n, M, n_tested, h->lambda0, h->l0, h->st.eigen_ms, h->st.rotate_ms - before.rotate_ms,
-                  h->st.grid_ms - before.grid_ms, h->st.refine_ms - before.refine_ms, now_ms() - t_start, cov);
+                  h->st.grid_ms - before.grid_ms, h->st.refine_ms - before.refine_ms, now_ms() - t_start, cov, w ? h.get() : nullptr);
     }
     if (h) add_stats(sum, h->st);
     if (total) *total = sum;

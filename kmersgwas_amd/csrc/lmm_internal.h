@@ -84,6 +84,9 @@ struct kgwas_lmm {
     double log_det_R = 0;
     uint64_t g_rows = 3;  // rows per variant d_G has room for
     kgwas::DevBuf<double> d_Wt, d_basec;
+    // what the launchers take as (q, W, base): the rotated fixed effects and the grid points' base rows in use
+    const double* fixed_t() const { return q ? d_Wt.p : d_wt.p; }
+    double* base_rows() const { return q ? d_basec.p : d_base.p; }
     kgwas::Stream stream;  // (behind the buffers its work reads and writes: it goes first)
     ~kgwas_lmm() {
         if (on_device) (void)hipSetDevice(device);  // (before any member is released)

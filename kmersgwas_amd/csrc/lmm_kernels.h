@@ -50,66 +50,45 @@ hipError_t launch_lmm_prep(const uint8_t* bed, uint32_t nv, LmmDims dm, double m
 // Xt[v][i] = sum_k U[k][i] val_v[code_v[k]], v < nv rounded up to LMM_VTILE (rows past nv are zero)
 hipError_t launch_lmm_rotate(const uint8_t* codes, const LmmVariant* vars, uint32_t nv, LmmDims dm, const double* U, double* Xt,
                              hipStream_t st);
-// base[g][LMM_BASE] from d, wt, yt and the grid's lambda[g]
-hipError_t launch_lmm_base(LmmDims dm, const double* d, const double* wt, const double* yt, const double* lambda, double* base,
-                           hipStream_t st);
-// G[v][3][LMM_HB_COLS]: sums over i of HB[i][c] * (xt^2, xt wt, xt yt)
-hipError_t launch_lmm_grid(const double* Xt, uint32_t nv, LmmDims dm, const double* wt, const double* yt, const double* HB, double* G,
-                           hipStream_t st);
-// the same for np columns: Yt[np][ldi] -> base[np][LMM_GRID][LMM_BASE], each block with the bits of a single call
-hipError_t launch_lmm_base_multi(LmmDims dm, const double* d, const double* wt, const double* Yt, uint32_t np, const double* lambda,
-                                 double* base, hipStream_t st);
-// Gx[v][2][LMM_HB_COLS]: the xt^2 and xt wt rows of launch_lmm_grid's G, the same bits
+// The fixed effects W of the launchers below that take (q, W): q = 0 is W = 1, `W` = wt[ldi] = U^T 1, and a grid point has LMM_BASE
+// sums; 1 <= q <= LMM_MAXC is covariates (n x q, orthonormal columns whose span holds the constant vector), `W` = Wt[q][ldi] = the
+// rotated columns (zero past n), a grid point has a record of LMM_BASEC doubles, and G has q + 2 rows per variant. Any other q is
+// refused (hipErrorInvalidValue), and so is q > 0 with more than one phenotype column.
+// Yt[np][ldi] -> base[np][LMM_GRID][LMM_BASE] (q = 0) or base[LMM_GRID][LMM_BASEC] (q > 0, np = 1) from d, W and the grid's lambda[g]
+hipError_t launch_lmm_base(LmmDims dm, uint32_t q, const double* d, const double* W, const double* Yt, uint32_t np, const double* lambda,
+                           double* base, hipStream_t st);
+// G[v][3][LMM_HB_COLS]: sums over i of HB[i][c] * (xt^2, xt wt, xt yt); q > 0: G[v][q + 2][LMM_HB_COLS], rows xt^2, xt wt_0 .. xt wt_{q-1}, xt yt
+hipError_t launch_lmm_grid(const double* Xt, uint32_t nv, LmmDims dm, uint32_t q, const double* W, const double* yt, const double* HB,
+                           double* G, hipStream_t st);
+// Gx[v][2][LMM_HB_COLS]: the xt^2 and xt wt rows of launch_lmm_grid's G at q = 0, the same bits
 hipError_t launch_lmm_grid_shared(const double* Xt, uint32_t nv, LmmDims dm, const double* wt, const double* HB, double* Gx,
                                   hipStream_t st);
 // Gxy[p][v][LMM_HB_COLS], p < np <= LMM_PBLOCK, v < nv: the xt yt row of launch_lmm_grid's G for yt = Yt[p], the same bits
 hipError_t launch_lmm_grid_xy(const double* Xt, uint32_t nv, LmmDims dm, const double* Yt, uint32_t np, const double* HB, double* Gxy,
                               hipStream_t st);
-// the null model: out[0] = l0, out[1] = lambda0
-hipError_t launch_lmm_null(LmmDims dm, const double* d, const double* wt, const double* yt, const double* lambda, const double* base,
-                           double* out, hipStream_t st);
-// the null models of np columns: out[p] = (l0, lambda0)
-hipError_t launch_lmm_null_multi(LmmDims dm, const double* d, const double* wt, const double* Yt, uint32_t np, const double* lambda,
-                                 const double* base, double* out, hipStream_t st);
+// the null models of np columns: out[p] = (l0, lambda0), each with the bits of a call with np = 1
+hipError_t launch_lmm_null(LmmDims dm, uint32_t q, const double* d, const double* W, const double* Yt, uint32_t np, const double* lambda,
+                           const double* base, double* out, hipStream_t st);
 // per tested variant: lrt, lambda, p (NaN for the others)
-hipError_t launch_lmm_refine(const double* Xt, const double* G, const LmmVariant* vars, uint32_t nv, LmmDims dm, const double* d,
-                             const double* wt, const double* yt, const double* lambda, const double* base, double l0, double* lrt,
-                             double* lam, double* p, hipStream_t st);
+hipError_t launch_lmm_refine(const double* Xt, const double* G, const LmmVariant* vars, uint32_t nv, LmmDims dm, uint32_t q,
+                             const double* d, const double* W, const double* yt, const double* lambda, const double* base, double l0,
+                             double* lrt, double* lam, double* p, hipStream_t st);
 // -lmm 4. The REML null model of yt: out[0..4) = lR0, lambda0_remle, vg, ve
-hipError_t launch_lmm_null_reml(LmmDims dm, const double* d, const double* wt, const double* yt, const double* lambda, const double* base,
-                                double* out, hipStream_t st);
+hipError_t launch_lmm_null_reml(LmmDims dm, uint32_t q, const double* d, const double* W, const double* yt, const double* lambda,
+                                const double* base, double* out, hipStream_t st);
 // -lmm 4. launch_lmm_refine's lrt, lam and p with their bits, and per tested variant the REML effect estimate, its standard error,
 // l_remle, the Wald p (both at l_remle) and the score p at lam0, the null model's ML lambda (NaN for the others)
 struct LmmWaldOut {
     double *beta, *se, *lam, *p_wald, *p_score;
 };
-hipError_t launch_lmm_refine_all(const double* Xt, const double* G, const LmmVariant* vars, uint32_t nv, LmmDims dm, const double* d,
-                                 const double* wt, const double* yt, const double* lambda, const double* base, double l0, double lam0,
-                                 double* lrt, double* lam, double* p, LmmWaldOut w, hipStream_t st);
-// the same per (variant, column) of a block of np <= LMM_PBLOCK columns, results at [p][v] (row stride nv); Yt, base and null
-// (pairs l0, lambda0) start at the block's first column
+hipError_t launch_lmm_refine_all(const double* Xt, const double* G, const LmmVariant* vars, uint32_t nv, LmmDims dm, uint32_t q,
+                                 const double* d, const double* W, const double* yt, const double* lambda, const double* base, double l0,
+                                 double lam0, double* lrt, double* lam, double* p, LmmWaldOut w, hipStream_t st);
+// launch_lmm_refine at q = 0 per (variant, column) of a block of np <= LMM_PBLOCK columns, results at [p][v] (row stride nv); Yt,
+// base and null (pairs l0, lambda0) start at the block's first column
 hipError_t launch_lmm_refine_multi(const double* Xt, const double* Gx, const double* Gxy, const LmmVariant* vars, uint32_t nv, LmmDims dm,
                                    const double* d, const double* wt, const double* Yt, uint32_t np, const double* lambda,
                                    const double* base, const double* null, double* lrt, double* lam, double* p, hipStream_t st);
-
-// Covariates: W (n x q, 1 <= q <= LMM_MAXC, orthonormal columns whose span holds the constant vector) in place of W = 1.
-// Wt[q][ldi] = its rotated columns (zero past n). The launchers mirror the ones above; q outside 1..LMM_MAXC is refused.
-// base[LMM_GRID][LMM_BASEC]: the records of the grid points
-hipError_t launch_lmm_base_cov(LmmDims dm, uint32_t q, const double* d, const double* Wt, const double* yt, const double* lambda,
-                               double* base, hipStream_t st);
-// G[v][q + 2][LMM_HB_COLS]: sums over i of HB[i][c] * (xt^2, xt wt_0 .. xt wt_{q-1}, xt yt)
-hipError_t launch_lmm_grid_cov(const double* Xt, uint32_t nv, LmmDims dm, uint32_t q, const double* Wt, const double* yt,
-                               const double* HB, double* G, hipStream_t st);
-hipError_t launch_lmm_null_cov(LmmDims dm, uint32_t q, const double* d, const double* Wt, const double* yt, const double* lambda,
-                               const double* base, double* out, hipStream_t st);
-hipError_t launch_lmm_null_reml_cov(LmmDims dm, uint32_t q, const double* d, const double* Wt, const double* yt, const double* lambda,
-                                    const double* base, double* out, hipStream_t st);
-hipError_t launch_lmm_refine_cov(const double* Xt, const double* G, const LmmVariant* vars, uint32_t nv, LmmDims dm, uint32_t q,
-                                 const double* d, const double* Wt, const double* yt, const double* lambda, const double* base, double l0,
-                                 double* lrt, double* lam, double* p, hipStream_t st);
-hipError_t launch_lmm_refine_all_cov(const double* Xt, const double* G, const LmmVariant* vars, uint32_t nv, LmmDims dm, uint32_t q,
-                                     const double* d, const double* Wt, const double* yt, const double* lambda, const double* base,
-                                     double l0, double lam0, double* lrt, double* lam, double* p, LmmWaldOut w, hipStream_t st);
 
 // lmm_table_kernels.hip: the front end of the k-mers table route. rows[n_rows][stride] are table rows (k-mer word, then the
 // presence words), sq[n_rows][2 W_m] their bits squeezed to phenotype order (launch_squeeze, zero past dm.n). A row is tested iff

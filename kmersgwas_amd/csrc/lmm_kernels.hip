@@ -17,15 +17,21 @@
 //   lmm_grid_xy_kernel the xt yt sums alone, for a block of phenotype columns that share one .bed: a wave keeps its xt values and
 //                      HB operands for LMM_PTILE columns at once. Every sum is the MFMA chain of lmm_grid_kernel's third row, so
 //                      its bits are those of the single-phenotype pass; lmm_grid_kernel<2> leaves the two shared rows;
-//   lmm_null_kernel / lmm_refine_kernel / lmm_refine_multi_kernel   one wave per model: l and dl/dt at the grid points, then every interval where dl/dt
-//                      goes from + to - is refined by LMM_REFINE_STEPS bracketing steps (secant with the Illinois correction,
-//                      every third one a bisection) whose sums run over i with lanes striding and a fixed butterfly; the
-//                      evaluated point with the smallest |dl/dt| is the interval's candidate. Both ends and every such point
-//                      are candidates; the largest l wins, the earliest on a tie.
-//   lmm_null_reml_kernel / lmm_refine_all_kernel   -lmm 4: the same maximisation of the REML likelihood (a compile-time switch of
-//                      ll_from_sums and maximise; the ML instantiations are the code they were), then beta, se, the Wald and the
-//                      score statistic from direct_sums at l_remle and at lambda0, and their F(1, n - 2) tails (fdist_tail.h).
+//   lmm_null_kernel / lmm_refine_kernel / lmm_refine_multi_kernel   one wave per model: l and dl/dt at the grid points, then every
+//                      interval where dl/dt goes from + to - is refined by LMM_REFINE_STEPS bracketing steps (secant with the
+//                      Illinois correction, every third one a bisection) whose sums run over i with lanes striding and a fixed
+//                      butterfly; the evaluated point with the smallest |dl/dt| is the interval's candidate. Both ends and every
+//                      such point are candidates; the largest l wins, the earliest on a tie.
+//   lmm_null_reml_kernel / lmm_refine_all_kernel   -lmm 4: the same maximisation of the REML likelihood, then beta, se, the Wald
+//                      and the score statistic from the sums at l_remle and at lambda0, and their F(1, n - 2) tails (fdist_tail.h).
 //   lmm_*_cov_kernel   the same stages for W of q > 1 columns (or q = 1 given as covariates): further down, with their own notes.
+// Each step is written once. `maximise` is the search, for both models (PlainModel: W = 1, on ll_from_sums and direct_sums;
+// CovModel: covariates, on ll_cov and eval_cov) and both objectives (a compile-time switch). `null_body` and `refine_body` are the
+// bodies of all nine null and refine kernels: the REML kernels are the ML ones plus their REML half, so the ML numbers of -lmm 4
+// are those of -lmm 2 by construction. `store_lrt`, `store_untested` and `store_wald_score` are the three ways a variant's results
+// are written. The __global__ functions only name their model and their LDS. The shared functions take plain pointers: the
+// kernels' parameters carry __restrict__, and a second __restrict__ scope inside them changes what the compiler hoists and merges
+// (it cost registers and duplicated logarithms when tried).
 // Nothing here depends on a variant's neighbours or uses an atomic: a variant's numbers are the same in any batch.
 //
 // f64 MFMA layout (16x16x4): lane l holds A[row l & 15][k l >> 4] and B[k l >> 4][col l & 15]; result register j of lane l is
@@ -313,24 +319,51 @@ __device__ inline Sums direct_sums(double lam, uint32_t n, const double* __restr
     return s;
 }
 
-// One wave (a block of 64): the maximum of l over the grid's ends and the refined interior points. grid = lambda[101], then
-// t[101] = log lambda. Gx = the variant's xt^2 and xt wt rows of the grid sums, Gxy = its xt yt row (HAS_X). s_l, s_dl: LMM_GRID
-// doubles of LDS each. REML: the objective of ll_from_sums; the sums, the steps and the rules are the same.
-template <bool HAS_X, bool REML = false>
-__device__ void maximise(uint32_t n, const double* __restrict__ d, const double* __restrict__ wt, const double* __restrict__ yt,
-                         const double* __restrict__ xt, const double* __restrict__ Gx, const double* __restrict__ Gxy,
-                         const double* __restrict__ grid, const double* __restrict__ base, double* s_l, double* s_dl, double& best_l,
-                         double& best_lam) {
-    const double nd = (double)n;
-    for (uint32_t g = threadIdx.x; g < LMM_GRID; g += 64) {
+// The Schur complements after w of the sums at one lambda
+struct AfterW {
+    double xx, xy, yy;
+};
+__device__ inline AfterW after_w(const Sums& s) {
+    const double bw0 = s.wy / s.ww;
+    return {s.xx - s.xw * s.xw / s.ww, s.xy - s.xw * bw0, s.yy - s.wy * bw0};
+}
+
+// A *model* is what the search below and the bodies of the null and refine kernels see of the likelihood: l and dl/dt at grid
+// point g (from the sums the grid kernels left), l and dl/dt at a lambda off the grid (the wave sums over i itself, with or without
+// the log-determinant sum), the Schur complements at a lambda, and the degrees of freedom of its RSS. REML picks the objective of
+// ll_from_sums / ll_cov. Every lane gets the same numbers.
+//
+// PlainModel: W = 1. Gx = the variant's xt^2 and xt wt rows of the grid sums, Gxy = its xt yt row (HAS_X; null pointers without).
+template <bool HAS_X>
+struct PlainModel {
+    uint32_t n;
+    const double *d, *wt, *yt, *xt, *Gx, *Gxy, *base;
+
+    template <bool REML>
+    __device__ __forceinline__ void at_grid(uint32_t g, double& l, double& dl) const {
         const double* b = base + g * LMM_BASE;
         Sums s = {b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], 0, 0, 0, 0, 0, 0};
         if (HAS_X) {
             s.xx = Gx[g], s.xw = Gx[LMM_HB_COLS + g], s.xy = Gxy[g];
             s.dxx = Gx[LMM_GRID + g], s.dxw = Gx[LMM_HB_COLS + LMM_GRID + g], s.dxy = Gxy[LMM_GRID + g];
         }
-        ll_from_sums<HAS_X, REML>(s, nd, s_l[g], s_dl[g]);
+        ll_from_sums<HAS_X, REML>(s, (double)n, l, dl);
     }
+    template <bool REML, bool WITH_LOG>
+    __device__ __forceinline__ void at_lambda(double lam, double& l, double& dl) const {
+        ll_from_sums<HAS_X, REML>(direct_sums<HAS_X, WITH_LOG>(lam, n, d, wt, yt, xt), (double)n, l, dl);
+    }
+    __device__ __forceinline__ AfterW after_w_at(double lam) const { return after_w(direct_sums<HAS_X, false>(lam, n, d, wt, yt, xt)); }
+    __device__ __forceinline__ double df() const { return (double)n - (HAS_X ? 2.0 : 1.0); }
+};
+
+// One wave (a block of 64): the maximum of l over the grid's ends and the refined interior points. grid = lambda[101], then
+// t[101] = log lambda. s_l, s_dl: LMM_GRID doubles of LDS each. The one copy of the rule: both models, ML and REML, run these
+// steps, so a change to it (the step count, the tie-break, another candidate) reaches every kernel at once.
+template <bool REML, class Model>
+__device__ __forceinline__ void maximise(const Model& m, const double* grid, double* s_l, double* s_dl, double& best_l,
+                                         double& best_lam) {
+    for (uint32_t g = threadIdx.x; g < LMM_GRID; g += 64) m.template at_grid<REML>(g, s_l[g], s_dl[g]);
     __syncthreads();
     best_l = s_l[0];
     best_lam = grid[0];
@@ -349,9 +382,8 @@ __device__ void maximise(uint32_t n, const double* __restrict__ d, const double*
         for (uint32_t step = 0; step < LMM_REFINE_STEPS; step++) {
             double tm = (ta * fb - tb * fa) / (fb - fa);
             if (step % 3 == 2 || !(tm > ta && tm < tb)) tm = 0.5 * (ta + tb);
-            const Sums s = direct_sums<HAS_X, false>(exp(tm), n, d, wt, yt, xt);
             double l, dl;
-            ll_from_sums<HAS_X, REML>(s, nd, l, dl);
+            m.template at_lambda<REML, false>(exp(tm), l, dl);
             if (fabs(dl) < f_best) {
                 f_best = fabs(dl);
                 t_best = tm;
@@ -368,9 +400,8 @@ __device__ void maximise(uint32_t n, const double* __restrict__ d, const double*
         }
         // the candidate: l there, with the log-determinant term
         const double lam = exp(t_best);
-        const Sums s = direct_sums<HAS_X, true>(lam, n, d, wt, yt, xt);
         double l, dl;
-        ll_from_sums<HAS_X, REML>(s, nd, l, dl);
+        m.template at_lambda<REML, true>(lam, l, dl);
         if (l > best_l) {
             best_l = l;
             best_lam = lam;
@@ -378,18 +409,102 @@ __device__ void maximise(uint32_t n, const double* __restrict__ d, const double*
     }
 }
 
+// The body of the null kernels. out = (l0, lambda0) of the ML likelihood; REML (-lmm 4): (lR0, lambda0_remle, vg, ve) with
+// ve = RSS0 / df and vg = lambda ve at the maximiser.
+template <bool REML, class Model>
+__device__ __forceinline__ void null_body(const Model& m, const double* grid, double* s_l, double* s_dl,
+                                          double* out) {
+    double l, lam;
+    maximise<REML>(m, grid, s_l, s_dl, l, lam);
+    AfterW a = {0, 0, 0};
+    if (REML) a = m.after_w_at(lam);
+    if (threadIdx.x == 0) {
+        out[0] = l;
+        out[1] = lam;
+        if (REML) {
+            const double ve = a.yy / m.df();
+            out[2] = lam * ve;
+            out[3] = ve;
+        }
+    }
+}
+
+// What one lane stores for a variant: the LRT of the maximum (l, lam) against the null model's l0 ...
+__device__ inline void store_lrt(uint64_t o, double l, double lam, double l0, double* lrt, double* lam_out,
+                                 double* p_out) {
+    const double stat = fmax(0.0, 2.0 * (l - l0));
+    lrt[o] = stat;
+    lam_out[o] = lam;
+    p_out[o] = erfc(sqrt(0.5 * stat));
+}
+// ... and NaN everywhere for a variant that is not tested (ALL: the five -lmm 4 outputs too)
+template <bool ALL>
+__device__ inline void store_untested(uint64_t o, double* lrt, double* lam_out, double* p_out,
+                                      const LmmWaldOut& w) {
+    lrt[o] = lam_out[o] = p_out[o] = __builtin_nan("");
+    if (ALL) w.beta[o] = w.se[o] = w.lam[o] = w.p_wald[o] = w.p_score[o] = __builtin_nan("");
+}
+
+// -lmm 4's close, from the Schur complements a at l_remle = lamr (Wald) and a0 at the null model's ML lambda0 (score): lane 0
+// closes the Wald test and lane 1 the score test, so the two F(1, df) tails (fdist_tail.h) run side by side. nd = n.
+__device__ inline void store_wald_score(uint64_t o, const AfterW& a, const AfterW& a0, double nd, double df, double lamr,
+                                        const LmmWaldOut& w) {
+    if (threadIdx.x >= 2) return;
+    const double beta = a.xy / a.xx, rss1 = a.yy - a.xy * beta;
+    // F_wald = (yy.w - RSS1) df / RSS1 with yy.w - RSS1 = xy.w beta taken as the product it is: (beta / se)^2 to a few ulps
+    const double F = threadIdx.x == 0 ? a.xy * beta * df / rss1 : nd * a0.xy * a0.xy / (a0.xx * a0.yy);
+    const double p = fdist_tail(F, df);
+    if (threadIdx.x == 0) {
+        w.beta[o] = beta;
+        w.se[o] = sqrt(rss1 / (df * a.xx));
+        w.lam[o] = lamr;
+        w.p_wald[o] = p;
+    } else {
+        w.p_score[o] = p;
+    }
+}
+
+// The body of the refine kernels, one wave per model m of a variant: the ML maximisation and its LRT at index o. ALL (-lmm 4): then
+// the REML maximisation over the same rows in the same LDS, the Schur complements at l_remle and at lam0, and the close. The ML
+// half is one source for both, so lrt, lambda and p have the same bits with and without ALL. l0 is read by lane 0 alone.
+template <bool ALL, class Model>
+__device__ __forceinline__ void refine_body(const Model& m, uint32_t tested, uint64_t o, const double* grid, double* s_l,
+                                            double* s_dl, const double& l0, double lam0, double* lrt,
+                                            double* lam_out, double* p_out, const LmmWaldOut& w) {
+    if (!tested) {  // (the whole block leaves)
+        if (threadIdx.x == 0) store_untested<ALL>(o, lrt, lam_out, p_out, w);
+        return;
+    }
+    double l, lam;
+    maximise<false>(m, grid, s_l, s_dl, l, lam);
+    if (threadIdx.x == 0) store_lrt(o, l, lam, l0, lrt, lam_out, p_out);
+    if constexpr (ALL) {
+        __syncthreads();  // (s_l and s_dl are written again)
+        double lr, lamr;
+        maximise<true>(m, grid, s_l, s_dl, lr, lamr);
+        const AfterW a = m.after_w_at(lamr);
+        const AfterW a0 = m.after_w_at(lam0);
+        store_wald_score(o, a, a0, (double)m.n, m.df(), lamr, w);
+    }
+}
+
+// blockIdx.x: the phenotype column (rows of Yt, blocks of base, pairs of out)
 __global__ void __launch_bounds__(64) lmm_null_kernel(LmmDims dm, const double* __restrict__ d, const double* __restrict__ wt,
                                                       const double* __restrict__ yt, const double* __restrict__ grid,
                                                       const double* __restrict__ base, double* __restrict__ out) {
     __shared__ double s_l[LMM_GRID], s_dl[LMM_GRID];
-    const uint32_t col = blockIdx.x;  // the phenotype column (rows of Yt, blocks of base, pairs of out)
-    double l, lam;
-    maximise<false>(dm.n, d, wt, yt + (uint64_t)col * dm.ldi, nullptr, nullptr, nullptr, grid, base + (uint64_t)col * LMM_GRID * LMM_BASE,
-                    s_l, s_dl, l, lam);
-    if (threadIdx.x == 0) {
-        out[2 * col] = l;
-        out[2 * col + 1] = lam;
-    }
+    const uint32_t col = blockIdx.x;
+    const PlainModel<false> m = {dm.n, d, wt, yt + (uint64_t)col * dm.ldi, nullptr, nullptr, nullptr, base + (uint64_t)col * LMM_GRID * LMM_BASE};
+    null_body<false>(m, grid, s_l, s_dl, out + 2 * col);
+}
+
+// -lmm 4: the REML null model
+__global__ void __launch_bounds__(64) lmm_null_reml_kernel(LmmDims dm, const double* __restrict__ d, const double* __restrict__ wt,
+                                                           const double* __restrict__ yt, const double* __restrict__ grid,
+                                                           const double* __restrict__ base, double* __restrict__ out) {
+    __shared__ double s_l[LMM_GRID], s_dl[LMM_GRID];
+    const PlainModel<false> m = {dm.n, d, wt, yt, nullptr, nullptr, nullptr, base};
+    null_body<true>(m, grid, s_l, s_dl, out);
 }
 
 __global__ void __launch_bounds__(64) lmm_refine_kernel(const double* __restrict__ Xt, const double* __restrict__ G,
@@ -400,19 +515,9 @@ __global__ void __launch_bounds__(64) lmm_refine_kernel(const double* __restrict
                                                         double* __restrict__ p_out) {
     __shared__ double s_l[LMM_GRID], s_dl[LMM_GRID];
     const uint32_t v = blockIdx.x;
-    if (!vars[v].tested) {  // (the whole block leaves)
-        if (threadIdx.x == 0) lrt[v] = lam_out[v] = p_out[v] = __builtin_nan("");
-        return;
-    }
-    double l, lam;
     const double* Gv = G + (uint64_t)v * 3 * LMM_HB_COLS;
-    maximise<true>(dm.n, d, wt, yt, Xt + (uint64_t)v * dm.ldi, Gv, Gv + 2 * LMM_HB_COLS, grid, base, s_l, s_dl, l, lam);
-    if (threadIdx.x == 0) {
-        const double stat = fmax(0.0, 2.0 * (l - l0));
-        lrt[v] = stat;
-        lam_out[v] = lam;
-        p_out[v] = erfc(sqrt(0.5 * stat));
-    }
+    const PlainModel<true> m = {dm.n, d, wt, yt, Xt + (uint64_t)v * dm.ldi, Gv, Gv + 2 * LMM_HB_COLS, base};
+    refine_body<false>(m, vars[v].tested, v, grid, s_l, s_dl, l0, 0.0, lrt, lam_out, p_out, LmmWaldOut{});
 }
 
 // The same per (variant blockIdx.x, phenotype column blockIdx.y of a block): Gx[v][2][LMM_HB_COLS] is shared by the columns,
@@ -427,50 +532,12 @@ __global__ void __launch_bounds__(64) lmm_refine_multi_kernel(const double* __re
     __shared__ double s_l[LMM_GRID], s_dl[LMM_GRID];
     const uint32_t v = blockIdx.x, col = blockIdx.y;
     const uint64_t o = (uint64_t)col * nv + v;
-    if (!vars[v].tested) {  // (the whole block leaves)
-        if (threadIdx.x == 0) lrt[o] = lam_out[o] = p_out[o] = __builtin_nan("");
-        return;
-    }
-    double l, lam;
-    maximise<true>(dm.n, d, wt, Yt + (uint64_t)col * dm.ldi, Xt + (uint64_t)v * dm.ldi, Gx + (uint64_t)v * 2 * LMM_HB_COLS,
-                   Gxy + o * LMM_HB_COLS, grid, base + (uint64_t)col * LMM_GRID * LMM_BASE, s_l, s_dl, l, lam);
-    if (threadIdx.x == 0) {
-        const double stat = fmax(0.0, 2.0 * (l - null[2 * col]));
-        lrt[o] = stat;
-        lam_out[o] = lam;
-        p_out[o] = erfc(sqrt(0.5 * stat));
-    }
+    const PlainModel<true> m = {dm.n, d, wt, Yt + (uint64_t)col * dm.ldi, Xt + (uint64_t)v * dm.ldi, Gx + (uint64_t)v * 2 * LMM_HB_COLS,
+                                Gxy + o * LMM_HB_COLS, base + (uint64_t)col * LMM_GRID * LMM_BASE};
+    refine_body<false>(m, vars[v].tested, o, grid, s_l, s_dl, null[2 * col], 0.0, lrt, lam_out, p_out, LmmWaldOut{});
 }
 
-// -lmm 4. The REML null model: out = (lR0, lambda0_remle, vg, ve), ve = yy.w / (n - 1) and vg = lambda ve at the maximiser.
-__global__ void __launch_bounds__(64) lmm_null_reml_kernel(LmmDims dm, const double* __restrict__ d, const double* __restrict__ wt,
-                                                           const double* __restrict__ yt, const double* __restrict__ grid,
-                                                           const double* __restrict__ base, double* __restrict__ out) {
-    __shared__ double s_l[LMM_GRID], s_dl[LMM_GRID];
-    double l, lam;
-    maximise<false, true>(dm.n, d, wt, yt, nullptr, nullptr, nullptr, grid, base, s_l, s_dl, l, lam);
-    const Sums s = direct_sums<false, false>(lam, dm.n, d, wt, yt, nullptr);
-    if (threadIdx.x == 0) {
-        const double ve = (s.yy - s.wy * (s.wy / s.ww)) / ((double)dm.n - 1.0);
-        out[0] = l;
-        out[1] = lam;
-        out[2] = lam * ve;
-        out[3] = ve;
-    }
-}
-
-// The Schur complements after w of the sums at one lambda
-struct AfterW {
-    double xx, xy, yy;
-};
-__device__ inline AfterW after_w(const Sums& s) {
-    const double bw0 = s.wy / s.ww;
-    return {s.xx - s.xw * s.xw / s.ww, s.xy - s.xw * bw0, s.yy - s.wy * bw0};
-}
-
-// -lmm 4, one wave per variant: lmm_refine_kernel's ML maximisation (the same call on the same rows: lrt, lambda and p keep their
-// bits), then the REML maximisation over the same rows of G and base in the same LDS, then the sums at l_remle (Wald) and at the
-// null model's ML lambda0 (score). Lane 0 closes the Wald test and lane 1 the score test, so the two tails run side by side.
+// -lmm 4, one wave per variant: lmm_refine_kernel's body with its REML half (beta, se, l_remle, the Wald and the score p to w)
 __global__ void __launch_bounds__(64) lmm_refine_all_kernel(const double* __restrict__ Xt, const double* __restrict__ G,
                                                             const LmmVariant* __restrict__ vars, LmmDims dm, const double* __restrict__ d,
                                                             const double* __restrict__ wt, const double* __restrict__ yt,
@@ -479,44 +546,14 @@ __global__ void __launch_bounds__(64) lmm_refine_all_kernel(const double* __rest
                                                             double* __restrict__ p_out, LmmWaldOut w) {
     __shared__ double s_l[LMM_GRID], s_dl[LMM_GRID];
     const uint32_t v = blockIdx.x;
-    if (!vars[v].tested) {  // (the whole block leaves)
-        if (threadIdx.x == 0)
-            lrt[v] = lam_out[v] = p_out[v] = w.beta[v] = w.se[v] = w.lam[v] = w.p_wald[v] = w.p_score[v] = __builtin_nan("");
-        return;
-    }
-    double l, lam;
     const double* Gv = G + (uint64_t)v * 3 * LMM_HB_COLS;
-    const double* xt = Xt + (uint64_t)v * dm.ldi;
-    maximise<true>(dm.n, d, wt, yt, xt, Gv, Gv + 2 * LMM_HB_COLS, grid, base, s_l, s_dl, l, lam);
-    if (threadIdx.x == 0) {
-        const double stat = fmax(0.0, 2.0 * (l - l0));
-        lrt[v] = stat;
-        lam_out[v] = lam;
-        p_out[v] = erfc(sqrt(0.5 * stat));
-    }
-    __syncthreads();  // (s_l and s_dl are written again)
-    double lr, lamr;
-    maximise<true, true>(dm.n, d, wt, yt, xt, Gv, Gv + 2 * LMM_HB_COLS, grid, base, s_l, s_dl, lr, lamr);
-    const AfterW a = after_w(direct_sums<true, false>(lamr, dm.n, d, wt, yt, xt));
-    const AfterW a0 = after_w(direct_sums<true, false>(lam0, dm.n, d, wt, yt, xt));
-    if (threadIdx.x >= 2) return;
-    const double nd = (double)dm.n, df = nd - 2.0;
-    const double beta = a.xy / a.xx, rss1 = a.yy - a.xy * beta;
-    // F_wald = (yy.w - RSS1) df / RSS1 with yy.w - RSS1 = xy.w beta taken as the product it is: (beta / se)^2 to a few ulps
-    const double F = threadIdx.x == 0 ? a.xy * beta * df / rss1 : nd * a0.xy * a0.xy / (a0.xx * a0.yy);
-    const double p = fdist_tail(F, df);
-    if (threadIdx.x == 0) {
-        w.beta[v] = beta;
-        w.se[v] = sqrt(rss1 / (df * a.xx));
-        w.lam[v] = lamr;
-        w.p_wald[v] = p;
-    } else {
-        w.p_score[v] = p;
-    }
+    const PlainModel<true> m = {dm.n, d, wt, yt, Xt + (uint64_t)v * dm.ldi, Gv, Gv + 2 * LMM_HB_COLS, base};
+    refine_body<true>(m, vars[v].tested, v, grid, s_l, s_dl, l0, lam0, lrt, lam_out, p_out, w);
 }
 
 // ---- covariates: W is n x Q, 1 <= Q <= LMM_MAXC, with orthonormal columns whose span holds the constant vector (lmm.cpp sees to
-// both). Wt[Q][ldi] = (U^T W)^T replaces wt. The kernels above are not touched; a handle without covariates never comes here. ----
+// both). Wt[Q][ldi] = (U^T W)^T replaces wt. The search and the kernel bodies are the ones above, on CovModel; a handle without
+// covariates launches the kernels above and never comes here (their instructions are what they were before CovModel existed). ----
 //
 // Per lambda, with z = (wt_0 .. wt_{Q-1}, yt, xt): every sum_i h_i z_a z_b and sum_i h'_i z_a z_b, a <= b. From those without x
 // the wave makes a *record* of LMM_BASEC doubles (the layout stands beside LMM_BASEC): A = Wt^T H Wt is factored (Cholesky, every
@@ -765,16 +802,17 @@ __device__ __forceinline__ void eval_cov(double lam, uint32_t n, uint32_t ldi, c
     ll_cov<Q, HAS_X, REML>(L.rec, x, xw, dxw, (double)n, l, dl, s);
 }
 
-// maximise with covariates: the same candidates, steps and rules. Gv = the variant's Q + 2 rows of the grid sums (xt^2, xt wt_j,
-// xt yt), base = the records of the grid points.
-template <int Q, bool HAS_X, bool REML>
-__device__ __forceinline__ void maximise_cov(uint32_t n, uint32_t ldi, const double* __restrict__ d, const double* __restrict__ Wt,
-                             const double* __restrict__ yt, const double* __restrict__ xt, const double* __restrict__ Gv,
-                             const double* __restrict__ grid, const double* __restrict__ base, double* s_l, double* s_dl, CovLds& L,
-                             double& best_l, double& best_lam) {
-    const double nd = (double)n;
-    AfterW unused;
-    for (uint32_t g = threadIdx.x; g < LMM_GRID; g += 64) {
+// The model with covariates, as maximise, null_body and refine_body see it. Gv = the variant's Q + 2 rows of the grid sums (xt^2,
+// xt wt_j, xt yt; HAS_X), base = the records of the grid points, L = the wave's LDS for the sums off the grid.
+template <int Q, bool HAS_X>
+struct CovModel {
+    uint32_t n, ldi;
+    const double *d, *Wt, *yt, *xt, *Gv, *base;
+    CovLds& L;
+
+    template <bool REML>
+    __device__ __forceinline__ void at_grid(uint32_t g, double& l, double& dl) const {
+        AfterW unused;
         XSums x = {0, 0, 0, 0};
         double xw[Q], dxw[Q];
 #pragma unroll
@@ -784,49 +822,21 @@ __device__ __forceinline__ void maximise_cov(uint32_t n, uint32_t ldi, const dou
 #pragma unroll
             for (int j = 0; j < Q; j++) xw[j] = Gv[(1 + j) * LMM_HB_COLS + g], dxw[j] = Gv[(1 + j) * LMM_HB_COLS + LMM_GRID + g];
         }
-        ll_cov<Q, HAS_X, REML>(base + (uint64_t)g * LMM_BASEC, x, xw, dxw, nd, s_l[g], s_dl[g], unused);
+        ll_cov<Q, HAS_X, REML>(base + (uint64_t)g * LMM_BASEC, x, xw, dxw, (double)n, l, dl, unused);
     }
-    __syncthreads();
-    best_l = s_l[0];
-    best_lam = grid[0];
-    if (s_l[LMM_GRID - 1] > best_l) {
-        best_l = s_l[LMM_GRID - 1];
-        best_lam = grid[LMM_GRID - 1];
+    template <bool REML, bool WITH_LOG>
+    __device__ __forceinline__ void at_lambda(double lam, double& l, double& dl) const {
+        AfterW unused;
+        eval_cov<Q, HAS_X, REML, WITH_LOG>(lam, n, ldi, d, Wt, yt, xt, L, l, dl, unused);
     }
-    for (uint32_t g = 0; g + 1 < LMM_GRID; g++) {
-        double fa = s_dl[g], fb = s_dl[g + 1];
-        if (!(fa > 0.0 && fb <= 0.0)) continue;  // (wave-uniform: LDS values)
-        double ta = grid[LMM_GRID + g], tb = grid[LMM_GRID + g + 1];
-        int side = 0;
-        double t_best = fa < -fb ? ta : tb, f_best = fa < -fb ? fa : -fb;
-        for (uint32_t step = 0; step < LMM_REFINE_STEPS; step++) {
-            double tm = (ta * fb - tb * fa) / (fb - fa);
-            if (step % 3 == 2 || !(tm > ta && tm < tb)) tm = 0.5 * (ta + tb);
-            double l, dl;
-            eval_cov<Q, HAS_X, REML, false>(exp(tm), n, ldi, d, Wt, yt, xt, L, l, dl, unused);
-            if (fabs(dl) < f_best) {
-                f_best = fabs(dl);
-                t_best = tm;
-            }
-            if (dl > 0.0) {
-                ta = tm, fa = dl;
-                if (side == 1) fb *= 0.5;
-                side = 1;
-            } else {
-                tb = tm, fb = dl;
-                if (side == -1) fa *= 0.5;
-                side = -1;
-            }
-        }
-        const double lam = exp(t_best);
+    __device__ __forceinline__ AfterW after_w_at(double lam) const {
         double l, dl;
-        eval_cov<Q, HAS_X, REML, true>(lam, n, ldi, d, Wt, yt, xt, L, l, dl, unused);
-        if (l > best_l) {
-            best_l = l;
-            best_lam = lam;
-        }
+        AfterW a;
+        eval_cov<Q, HAS_X, true, false>(lam, n, ldi, d, Wt, yt, xt, L, l, dl, a);
+        return a;
     }
-}
+    __device__ __forceinline__ double df() const { return (double)n - (double)Q - (HAS_X ? 1.0 : 0.0); }
+};
 
 // One wave per grid point: the record of lambda[g] to base[g][LMM_BASEC]
 template <int Q>
@@ -893,38 +903,27 @@ __global__ void __launch_bounds__(256) lmm_grid_cov_kernel(const double* __restr
     }
 }
 
+// The null and refine kernels with covariates: the bodies of the kernels without, on a CovModel. (The evaluation off the grid is
+// inlined at each of its uses, six in lmm_refine_all_cov_kernel, which costs occupancy at Q >= 5: DESIGN.md 4.12. Sharing the
+// source has left that as it was.)
 template <int Q>
 __global__ void __launch_bounds__(64) lmm_null_cov_kernel(LmmDims dm, const double* __restrict__ d, const double* __restrict__ Wt,
                                                           const double* __restrict__ yt, const double* __restrict__ grid,
                                                           const double* __restrict__ base, double* __restrict__ out) {
     __shared__ double s_l[LMM_GRID], s_dl[LMM_GRID];
     __shared__ CovLds L;
-    double l, lam;
-    maximise_cov<Q, false, false>(dm.n, dm.ldi, d, Wt, yt, nullptr, nullptr, grid, base, s_l, s_dl, L, l, lam);
-    if (threadIdx.x == 0) {
-        out[0] = l;
-        out[1] = lam;
-    }
+    const CovModel<Q, false> m = {dm.n, dm.ldi, d, Wt, yt, nullptr, nullptr, base, L};
+    null_body<false>(m, grid, s_l, s_dl, out);
 }
 
-// -lmm 4: out = (lR0, lambda0_remle, vg, ve), ve = RSS0 / (n - q) and vg = lambda ve at the maximiser
 template <int Q>
 __global__ void __launch_bounds__(64) lmm_null_reml_cov_kernel(LmmDims dm, const double* __restrict__ d, const double* __restrict__ Wt,
                                                                const double* __restrict__ yt, const double* __restrict__ grid,
                                                                const double* __restrict__ base, double* __restrict__ out) {
     __shared__ double s_l[LMM_GRID], s_dl[LMM_GRID];
     __shared__ CovLds L;
-    double l, lam, l_at, dl_at;
-    AfterW a;
-    maximise_cov<Q, false, true>(dm.n, dm.ldi, d, Wt, yt, nullptr, nullptr, grid, base, s_l, s_dl, L, l, lam);
-    eval_cov<Q, false, true, false>(lam, dm.n, dm.ldi, d, Wt, yt, nullptr, L, l_at, dl_at, a);
-    if (threadIdx.x == 0) {
-        const double ve = a.yy / ((double)dm.n - (double)Q);
-        out[0] = l;
-        out[1] = lam;
-        out[2] = lam * ve;
-        out[3] = ve;
-    }
+    const CovModel<Q, false> m = {dm.n, dm.ldi, d, Wt, yt, nullptr, nullptr, base, L};
+    null_body<true>(m, grid, s_l, s_dl, out);
 }
 
 template <int Q>
@@ -937,23 +936,11 @@ __global__ void __launch_bounds__(64) lmm_refine_cov_kernel(const double* __rest
     __shared__ double s_l[LMM_GRID], s_dl[LMM_GRID];
     __shared__ CovLds L;
     const uint32_t v = blockIdx.x;
-    if (!vars[v].tested) {  // (the whole block leaves)
-        if (threadIdx.x == 0) lrt[v] = lam_out[v] = p_out[v] = __builtin_nan("");
-        return;
-    }
-    double l, lam;
-    maximise_cov<Q, true, false>(dm.n, dm.ldi, d, Wt, yt, Xt + (uint64_t)v * dm.ldi, G + (uint64_t)v * (Q + 2) * LMM_HB_COLS, grid, base,
-                                 s_l, s_dl, L, l, lam);
-    if (threadIdx.x == 0) {
-        const double stat = fmax(0.0, 2.0 * (l - l0));
-        lrt[v] = stat;
-        lam_out[v] = lam;
-        p_out[v] = erfc(sqrt(0.5 * stat));
-    }
+    const CovModel<Q, true> m = {dm.n, dm.ldi, d, Wt, yt, Xt + (uint64_t)v * dm.ldi, G + (uint64_t)v * (Q + 2) * LMM_HB_COLS, base, L};
+    refine_body<false>(m, vars[v].tested, v, grid, s_l, s_dl, l0, 0.0, lrt, lam_out, p_out, LmmWaldOut{});
 }
 
-// -lmm 4 with covariates: lmm_refine_cov_kernel's maximisation (lrt, lambda and p keep its bits), the REML maximisation, then the
-// Schur complements at l_remle (Wald) and at lambda0 (score); the F tails have n - q - 1 degrees of freedom.
+// -lmm 4 with covariates; the F tails have n - q - 1 degrees of freedom
 template <int Q>
 __global__ void __launch_bounds__(64) lmm_refine_all_cov_kernel(const double* __restrict__ Xt, const double* __restrict__ G,
                                                                 const LmmVariant* __restrict__ vars, LmmDims dm,
@@ -965,43 +952,29 @@ __global__ void __launch_bounds__(64) lmm_refine_all_cov_kernel(const double* __
     __shared__ double s_l[LMM_GRID], s_dl[LMM_GRID];
     __shared__ CovLds L;
     const uint32_t v = blockIdx.x;
-    if (!vars[v].tested) {  // (the whole block leaves)
-        if (threadIdx.x == 0)
-            lrt[v] = lam_out[v] = p_out[v] = w.beta[v] = w.se[v] = w.lam[v] = w.p_wald[v] = w.p_score[v] = __builtin_nan("");
-        return;
-    }
-    double l, lam;
-    const double* Gv = G + (uint64_t)v * (Q + 2) * LMM_HB_COLS;
-    const double* xt = Xt + (uint64_t)v * dm.ldi;
-    maximise_cov<Q, true, false>(dm.n, dm.ldi, d, Wt, yt, xt, Gv, grid, base, s_l, s_dl, L, l, lam);
-    if (threadIdx.x == 0) {
-        const double stat = fmax(0.0, 2.0 * (l - l0));
-        lrt[v] = stat;
-        lam_out[v] = lam;
-        p_out[v] = erfc(sqrt(0.5 * stat));
-    }
-    __syncthreads();  // (s_l and s_dl are written again)
-    double lr, lamr, l_at, dl_at;
-    AfterW a, a0;
-    maximise_cov<Q, true, true>(dm.n, dm.ldi, d, Wt, yt, xt, Gv, grid, base, s_l, s_dl, L, lr, lamr);
-    eval_cov<Q, true, true, false>(lamr, dm.n, dm.ldi, d, Wt, yt, xt, L, l_at, dl_at, a);
-    eval_cov<Q, true, true, false>(lam0, dm.n, dm.ldi, d, Wt, yt, xt, L, l_at, dl_at, a0);
-    if (threadIdx.x >= 2) return;
-    const double nd = (double)dm.n, df = nd - (double)Q - 1.0;
-    const double beta = a.xy / a.xx, rss1 = a.yy - a.xy * beta;
-    const double F = threadIdx.x == 0 ? a.xy * beta * df / rss1 : nd * a0.xy * a0.xy / (a0.xx * a0.yy);
-    const double p = fdist_tail(F, df);
-    if (threadIdx.x == 0) {
-        w.beta[v] = beta;
-        w.se[v] = sqrt(rss1 / (df * a.xx));
-        w.lam[v] = lamr;
-        w.p_wald[v] = p;
-    } else {
-        w.p_score[v] = p;
-    }
+    const CovModel<Q, true> m = {dm.n, dm.ldi, d, Wt, yt, Xt + (uint64_t)v * dm.ldi, G + (uint64_t)v * (Q + 2) * LMM_HB_COLS, base, L};
+    refine_body<true>(m, vars[v].tested, v, grid, s_l, s_dl, l0, lam0, lrt, lam_out, p_out, w);
 }
 
 }  // namespace
+
+// ---- the launchers. q = 0: W = 1, `W` is wt[ldi] and base holds LMM_BASE sums per grid point; 1 <= q <= LMM_MAXC: `W` is
+// Wt[q][ldi] and base holds records of LMM_BASEC doubles, on the <q> instantiation; any other q is refused. ----
+
+#define LMM_DISPATCH(q, PLAIN, COV)                  \
+    switch (q) {                                    \
+        case 0: { PLAIN; break; }                   \
+        case 1: { constexpr int Q = 1; COV; break; } \
+        case 2: { constexpr int Q = 2; COV; break; } \
+        case 3: { constexpr int Q = 3; COV; break; } \
+        case 4: { constexpr int Q = 4; COV; break; } \
+        case 5: { constexpr int Q = 5; COV; break; } \
+        case 6: { constexpr int Q = 6; COV; break; } \
+        case 7: { constexpr int Q = 7; COV; break; } \
+        case 8: { constexpr int Q = 8; COV; break; } \
+        default: return hipErrorInvalidValue;       \
+    }
+static_assert(LMM_MAXC == 8, "LMM_DISPATCH lists the widths");
 
 hipError_t launch_lmm_prep(const uint8_t* bed, uint32_t nv, LmmDims dm, double maf, double miss, uint8_t* codes, LmmVariant* vars,
                            hipStream_t st) {
@@ -1018,23 +991,24 @@ hipError_t launch_lmm_rotate(const uint8_t* codes, const LmmVariant* vars, uint3
     return hipGetLastError();
 }
 
-hipError_t launch_lmm_base(LmmDims dm, const double* d, const double* wt, const double* yt, const double* grid, double* base,
-                           hipStream_t st) {
-    return launch_lmm_base_multi(dm, d, wt, yt, 1, grid, base, st);
-}
-
-hipError_t launch_lmm_base_multi(LmmDims dm, const double* d, const double* wt, const double* Yt, uint32_t np, const double* grid,
-                                 double* base, hipStream_t st) {
+hipError_t launch_lmm_base(LmmDims dm, uint32_t q, const double* d, const double* W, const double* Yt, uint32_t np, const double* grid,
+                           double* base, hipStream_t st) {
     if (!np) return hipSuccess;
-    hipLaunchKernelGGL(lmm_base_kernel, dim3(LMM_GRID, np), dim3(64), 0, st, dm, d, wt, Yt, grid, base);
+    if (q && np != 1) return hipErrorInvalidValue;
+    LMM_DISPATCH(q, hipLaunchKernelGGL(lmm_base_kernel, dim3(LMM_GRID, np), dim3(64), 0, st, dm, d, W, Yt, grid, base),
+                 hipLaunchKernelGGL(lmm_base_cov_kernel<Q>, dim3(LMM_GRID), dim3(64), 0, st, dm, d, W, Yt, grid, base));
     return hipGetLastError();
 }
 
-hipError_t launch_lmm_grid(const double* Xt, uint32_t nv, LmmDims dm, const double* wt, const double* yt, const double* HB, double* G,
-                           hipStream_t st) {
+hipError_t launch_lmm_grid(const double* Xt, uint32_t nv, LmmDims dm, uint32_t q, const double* W, const double* yt, const double* HB,
+                           double* G, hipStream_t st) {
     if (!nv) return hipSuccess;
-    const dim3 grid((nv + 63) / 64, (LMM_HB_COLS / 16 + 3) / 4);
-    hipLaunchKernelGGL(lmm_grid_kernel<3>, grid, dim3(256), 0, st, Xt, nv, dm, wt, yt, HB, G);
+    if (q > LMM_MAXC) return hipErrorInvalidValue;
+    const dim3 grid((nv + 63) / 64, (LMM_HB_COLS / 16 + 3) / 4, q ? (q + 2 + 2) / 3 : 1);
+    if (q)
+        hipLaunchKernelGGL(lmm_grid_cov_kernel, grid, dim3(256), 0, st, Xt, nv, dm, q, W, yt, HB, G);
+    else
+        hipLaunchKernelGGL(lmm_grid_kernel<3>, grid, dim3(256), 0, st, Xt, nv, dm, W, yt, HB, G);
     return hipGetLastError();
 }
 
@@ -1055,37 +1029,39 @@ hipError_t launch_lmm_grid_xy(const double* Xt, uint32_t nv, LmmDims dm, const d
     return hipGetLastError();
 }
 
-hipError_t launch_lmm_null(LmmDims dm, const double* d, const double* wt, const double* yt, const double* grid, const double* base,
-                           double* out, hipStream_t st) {
-    return launch_lmm_null_multi(dm, d, wt, yt, 1, grid, base, out, st);
-}
-
-hipError_t launch_lmm_null_multi(LmmDims dm, const double* d, const double* wt, const double* Yt, uint32_t np, const double* grid,
-                                 const double* base, double* out, hipStream_t st) {
+hipError_t launch_lmm_null(LmmDims dm, uint32_t q, const double* d, const double* W, const double* Yt, uint32_t np, const double* grid,
+                           const double* base, double* out, hipStream_t st) {
     if (!np) return hipSuccess;
-    hipLaunchKernelGGL(lmm_null_kernel, dim3(np), dim3(64), 0, st, dm, d, wt, Yt, grid, base, out);
+    if (q && np != 1) return hipErrorInvalidValue;
+    LMM_DISPATCH(q, hipLaunchKernelGGL(lmm_null_kernel, dim3(np), dim3(64), 0, st, dm, d, W, Yt, grid, base, out),
+                 hipLaunchKernelGGL(lmm_null_cov_kernel<Q>, dim3(1), dim3(64), 0, st, dm, d, W, Yt, grid, base, out));
     return hipGetLastError();
 }
 
-hipError_t launch_lmm_refine(const double* Xt, const double* G, const LmmVariant* vars, uint32_t nv, LmmDims dm, const double* d,
-                             const double* wt, const double* yt, const double* grid, const double* base, double l0, double* lrt,
-                             double* lam, double* p, hipStream_t st) {
+hipError_t launch_lmm_null_reml(LmmDims dm, uint32_t q, const double* d, const double* W, const double* yt, const double* grid,
+                                const double* base, double* out, hipStream_t st) {
+    LMM_DISPATCH(q, hipLaunchKernelGGL(lmm_null_reml_kernel, dim3(1), dim3(64), 0, st, dm, d, W, yt, grid, base, out),
+                 hipLaunchKernelGGL(lmm_null_reml_cov_kernel<Q>, dim3(1), dim3(64), 0, st, dm, d, W, yt, grid, base, out));
+    return hipGetLastError();
+}
+
+hipError_t launch_lmm_refine(const double* Xt, const double* G, const LmmVariant* vars, uint32_t nv, LmmDims dm, uint32_t q,
+                             const double* d, const double* W, const double* yt, const double* grid, const double* base, double l0,
+                             double* lrt, double* lam, double* p, hipStream_t st) {
     if (!nv) return hipSuccess;
-    hipLaunchKernelGGL(lmm_refine_kernel, dim3(nv), dim3(64), 0, st, Xt, G, vars, dm, d, wt, yt, grid, base, l0, lrt, lam, p);
+    LMM_DISPATCH(q, hipLaunchKernelGGL(lmm_refine_kernel, dim3(nv), dim3(64), 0, st, Xt, G, vars, dm, d, W, yt, grid, base, l0, lrt, lam, p),
+                 hipLaunchKernelGGL(lmm_refine_cov_kernel<Q>, dim3(nv), dim3(64), 0, st, Xt, G, vars, dm, d, W, yt, grid, base, l0, lrt, lam, p));
     return hipGetLastError();
 }
 
-hipError_t launch_lmm_null_reml(LmmDims dm, const double* d, const double* wt, const double* yt, const double* grid, const double* base,
-                                double* out, hipStream_t st) {
-    hipLaunchKernelGGL(lmm_null_reml_kernel, dim3(1), dim3(64), 0, st, dm, d, wt, yt, grid, base, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_lmm_refine_all(const double* Xt, const double* G, const LmmVariant* vars, uint32_t nv, LmmDims dm, const double* d,
-                                 const double* wt, const double* yt, const double* grid, const double* base, double l0, double lam0,
-                                 double* lrt, double* lam, double* p, LmmWaldOut w, hipStream_t st) {
+hipError_t launch_lmm_refine_all(const double* Xt, const double* G, const LmmVariant* vars, uint32_t nv, LmmDims dm, uint32_t q,
+                                 const double* d, const double* W, const double* yt, const double* grid, const double* base, double l0,
+                                 double lam0, double* lrt, double* lam, double* p, LmmWaldOut w, hipStream_t st) {
     if (!nv) return hipSuccess;
-    hipLaunchKernelGGL(lmm_refine_all_kernel, dim3(nv), dim3(64), 0, st, Xt, G, vars, dm, d, wt, yt, grid, base, l0, lam0, lrt, lam, p, w);
+    LMM_DISPATCH(q,
+                 hipLaunchKernelGGL(lmm_refine_all_kernel, dim3(nv), dim3(64), 0, st, Xt, G, vars, dm, d, W, yt, grid, base, l0, lam0, lrt, lam, p, w),
+                 hipLaunchKernelGGL(lmm_refine_all_cov_kernel<Q>, dim3(nv), dim3(64), 0, st, Xt, G, vars, dm, d, W, yt, grid, base, l0, lam0, lrt,
+                                    lam, p, w));
     return hipGetLastError();
 }
 
@@ -1096,67 +1072,6 @@ hipError_t launch_lmm_refine_multi(const double* Xt, const double* Gx, const dou
     if (np > LMM_PBLOCK) return hipErrorInvalidValue;
     hipLaunchKernelGGL(lmm_refine_multi_kernel, dim3(nv, np), dim3(64), 0, st, Xt, Gx, Gxy, vars, nv, dm, d, wt, Yt, grid, base, null, lrt,
                        lam, p);
-    return hipGetLastError();
-}
-
-// ---- covariates ----
-
-#define LMM_COV_DISPATCH(q, CALL)                  \
-    switch (q) {                                   \
-        case 1: { constexpr int Q = 1; CALL; break; } \
-        case 2: { constexpr int Q = 2; CALL; break; } \
-        case 3: { constexpr int Q = 3; CALL; break; } \
-        case 4: { constexpr int Q = 4; CALL; break; } \
-        case 5: { constexpr int Q = 5; CALL; break; } \
-        case 6: { constexpr int Q = 6; CALL; break; } \
-        case 7: { constexpr int Q = 7; CALL; break; } \
-        case 8: { constexpr int Q = 8; CALL; break; } \
-        default: return hipErrorInvalidValue;      \
-    }
-static_assert(LMM_MAXC == 8, "LMM_COV_DISPATCH lists the widths");
-
-hipError_t launch_lmm_base_cov(LmmDims dm, uint32_t q, const double* d, const double* Wt, const double* yt, const double* grid,
-                               double* base, hipStream_t st) {
-    LMM_COV_DISPATCH(q, hipLaunchKernelGGL(lmm_base_cov_kernel<Q>, dim3(LMM_GRID), dim3(64), 0, st, dm, d, Wt, yt, grid, base));
-    return hipGetLastError();
-}
-
-hipError_t launch_lmm_grid_cov(const double* Xt, uint32_t nv, LmmDims dm, uint32_t q, const double* Wt, const double* yt,
-                               const double* HB, double* G, hipStream_t st) {
-    if (!nv) return hipSuccess;
-    if (q < 1 || q > LMM_MAXC) return hipErrorInvalidValue;
-    const dim3 grid((nv + 63) / 64, (LMM_HB_COLS / 16 + 3) / 4, (q + 2 + 2) / 3);
-    hipLaunchKernelGGL(lmm_grid_cov_kernel, grid, dim3(256), 0, st, Xt, nv, dm, q, Wt, yt, HB, G);
-    return hipGetLastError();
-}
-
-hipError_t launch_lmm_null_cov(LmmDims dm, uint32_t q, const double* d, const double* Wt, const double* yt, const double* grid,
-                               const double* base, double* out, hipStream_t st) {
-    LMM_COV_DISPATCH(q, hipLaunchKernelGGL(lmm_null_cov_kernel<Q>, dim3(1), dim3(64), 0, st, dm, d, Wt, yt, grid, base, out));
-    return hipGetLastError();
-}
-
-hipError_t launch_lmm_null_reml_cov(LmmDims dm, uint32_t q, const double* d, const double* Wt, const double* yt, const double* grid,
-                                    const double* base, double* out, hipStream_t st) {
-    LMM_COV_DISPATCH(q, hipLaunchKernelGGL(lmm_null_reml_cov_kernel<Q>, dim3(1), dim3(64), 0, st, dm, d, Wt, yt, grid, base, out));
-    return hipGetLastError();
-}
-
-hipError_t launch_lmm_refine_cov(const double* Xt, const double* G, const LmmVariant* vars, uint32_t nv, LmmDims dm, uint32_t q,
-                                 const double* d, const double* Wt, const double* yt, const double* grid, const double* base, double l0,
-                                 double* lrt, double* lam, double* p, hipStream_t st) {
-    if (!nv) return hipSuccess;
-    LMM_COV_DISPATCH(q, hipLaunchKernelGGL(lmm_refine_cov_kernel<Q>, dim3(nv), dim3(64), 0, st, Xt, G, vars, dm, d, Wt, yt, grid, base, l0,
-                                           lrt, lam, p));
-    return hipGetLastError();
-}
-
-hipError_t launch_lmm_refine_all_cov(const double* Xt, const double* G, const LmmVariant* vars, uint32_t nv, LmmDims dm, uint32_t q,
-                                     const double* d, const double* Wt, const double* yt, const double* grid, const double* base,
-                                     double l0, double lam0, double* lrt, double* lam, double* p, LmmWaldOut w, hipStream_t st) {
-    if (!nv) return hipSuccess;
-    LMM_COV_DISPATCH(q, hipLaunchKernelGGL(lmm_refine_all_cov_kernel<Q>, dim3(nv), dim3(64), 0, st, Xt, G, vars, dm, d, Wt, yt, grid, base,
-                                           l0, lam0, lrt, lam, p, w));
     return hipGetLastError();
 }
 
