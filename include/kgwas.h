@@ -236,7 +236,8 @@ typedef struct kgwas_scan_stats {
  * Version 15: no struct changed; new entry points kgwas_lmm_test_table, kgwas_lmm_run_table (lmm_lrt --kmers_table), and later,
  * without a new version number, kgwas_lmm_test_table_multi, kgwas_lmm_run_table_multi (lmm_lrt --kmers_table --pheno_columns), and
  * kgwas_lmm_null_reml, kgwas_lmm_test_bed_all, kgwas_lmm_run_files_all, kgwas_lmm_format_assoc4, kgwas_fdist_tail (lmm_lrt -lmm 4),
- * and kgwas_lmm_set_covariates, kgwas_lmm_read_covariates, kgwas_lmm_run_files_cov, kgwas_lmm_run_table_cov (lmm_lrt -c).
+ * and kgwas_lmm_set_covariates, kgwas_lmm_read_covariates, kgwas_lmm_run_files_cov, kgwas_lmm_run_table_cov (lmm_lrt -c),
+ * and struct kgwas_lmm_unique_stats, kgwas_lmm_test_table_unique, kgwas_lmm_run_table_unique (lmm_lrt --pattern_cache).
  * Those came after version 15 without a bump: a caller that may meet an older version-15 library probes for them by symbol
  * (dlsym, or hasattr on a ctypes handle). */
 #define KGWAS_ABI_VERSION 15
@@ -691,6 +692,29 @@ void kgwas_snpkin_close(kgwas_snpkin* h);
  *            used iff its phenotype is present and no covariate is NA. The log gains the lines covariates and n_covariates behind
  *            kinship. covar_path == NULL: exactly run_files / run_files_all.
  * run_table_cov: run_table with covar_path, one row per accession of the phenotype file in its order; NA is refused.
+ *
+ * The pattern cache (after ABI version 15, no bump: probe by symbol). Rows of a k-mers table repeat presence/absence patterns, and
+ * two rows with the same pattern over the handle's individuals have the same lrt, lambda, p and af, bit for bit.
+ * test_table_unique: test_table (with or without covariates on the handle) in which each distinct tested pattern goes through
+ *            rotate, grid and refine once and every other row with it takes the stored result. A cache and nothing more: row, kmer,
+ *            lrt, lambda, p, af, *n_kept, *rows_read and *rows_tested are kgwas_lmm_test_table's, byte for byte, for any
+ *            max_patterns, piece size and chunk_variants, also when tags collide or the cache is full. The cache is a hash table
+ *            on the device with max_patterns slots, rounded down to a power of two (at most 2^30), of 40 bytes + the code row
+ *            (n rounded up to 16, / 4 bytes) each; it is allocated for the call and empty at its start (results depend on y and
+ *            the covariates). A tested row hashes its code row to a 64-bit tag and looks at up to 16 slots in a row. *u (may be
+ *            NULL): slots; patterns_cached, the rows that took a new slot; rows_from_cache, the rows whose code row equalled
+ *            their slot's (not rotated); rows_collided, the rows whose slot held another code row with their tag; rows_rejected,
+ *            the rows that found no slot; rows_rotated. rows_tested = patterns_cached + rows_from_cache + rows_collided +
+ *            rows_rejected, rows_rotated = rows_tested - rows_from_cache. With nothing rejected the counters are the same in
+ *            every run and patterns_cached + rows_collided is at least the number of distinct tested patterns (equal to it, and
+ *            rows_collided 0, unless two patterns share a 64-bit tag). max_patterns < 64 -> KGWAS_ERR_ARG before any device
+ *            work, *u and the handle's stats untouched, the handle still usable; the other errors are test_table's. Stats as
+ *            test_table (variants_tested counts tested rows); rotate_ms takes the cache's kernels too.
+ *            KGWAS_LMM_PATTERN_TAG_BITS=k (test hook) cuts the tags to k bits, so that they collide; the results are the same.
+ * run_table_unique: run_table_cov (covar_path may be NULL: run_table) through test_table_unique with a cache of cache_mib MiB: as
+ *            many slots as fit, rounded down to a power of two. out_path gets the bytes of the run without the cache; the log gains,
+ *            behind its present lines, pattern_cache_slots, patterns_cached, rows_from_cache, rows_collided, rows_rejected and
+ *            rows_rotated. cache_mib == 0, or fewer than 64 slots -> KGWAS_ERR_ARG.
  * ---------------------------------------------------------------------------------- */
 typedef struct kgwas_lmm kgwas_lmm;
 typedef struct kgwas_lmm_stats {
@@ -749,6 +773,17 @@ int kgwas_lmm_run_files_cov(const char* kinship_path, const char* covar_path, ui
 int kgwas_lmm_run_table_cov(const char* kinship_path, const char* covar_path, const char* table_base, uint32_t kmer_len,
                             const char* pheno_path, uint32_t pheno_col, uint64_t mac, double maf, uint64_t best_n, double lmin, double lmax,
                             uint64_t chunk_variants, int32_t device, const char* out_path, kgwas_lmm_stats* total);
+typedef struct kgwas_lmm_unique_stats {
+    uint64_t slots, patterns_cached, rows_from_cache, rows_collided, rows_rejected, rows_rotated;
+} kgwas_lmm_unique_stats;
+int kgwas_lmm_test_table_unique(kgwas_lmm* h, const double* y, kgwas_table* t, const uint64_t* col, uint64_t n_acc, uint64_t min_count,
+                                double maf, uint64_t best_n, uint64_t* row, uint64_t* kmer, double* lrt, double* lambda, double* p, double* af,
+                                uint64_t* n_kept, uint64_t* rows_read, uint64_t* rows_tested, uint64_t max_patterns,
+                                kgwas_lmm_unique_stats* u);
+int kgwas_lmm_run_table_unique(const char* kinship_path, const char* covar_path, const char* table_base, uint32_t kmer_len,
+                               const char* pheno_path, uint32_t pheno_col, uint64_t mac, double maf, uint64_t best_n, double lmin,
+                               double lmax, uint64_t chunk_variants, int32_t device, const char* out_path, kgwas_lmm_stats* total,
+                               uint64_t cache_mib, kgwas_lmm_unique_stats* u);
 
 /* ------------------------------------------------------------------------------------
  * Seeded synthetic table rows: kmer = row + 1, per-row frequency q/256 with

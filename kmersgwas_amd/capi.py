@@ -48,6 +48,7 @@ SYMBOLS = [
     "kgwas_lmm_destroy", "kgwas_lmm_read_kinship", "kgwas_lmm_read_fam", "kgwas_lmm_format_assoc",
     "kgwas_lmm_null_reml", "kgwas_lmm_test_bed_all", "kgwas_lmm_run_files_all", "kgwas_lmm_format_assoc4", "kgwas_fdist_tail",
     "kgwas_lmm_set_covariates", "kgwas_lmm_read_covariates", "kgwas_lmm_run_files_cov", "kgwas_lmm_run_table_cov",
+    "kgwas_lmm_test_table_unique", "kgwas_lmm_run_table_unique",
     "kgwas_synth_rows_device", "kgwas_synth_rows_host",
 ]
 
@@ -106,6 +107,13 @@ class LmmStats(C.Structure):
         ("variants_read", C.c_uint64), ("variants_tested", C.c_uint64), ("chunks", C.c_uint64),
         ("eigendecompositions", C.c_uint64), ("n_individuals", C.c_uint64),
     ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class LmmUniqueStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("slots", "patterns_cached", "rows_from_cache", "rows_collided", "rows_rejected", "rows_rotated")]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -302,6 +310,9 @@ lib.kgwas_lmm_run_files_cov.argtypes = [C.c_char_p, C.c_char_p, _u64, _pstr, _ps
                                         C.POINTER(LmmStats)]
 lib.kgwas_lmm_run_table_cov.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, _u32, C.c_char_p, _u32, _u64, _dbl, _u64, _dbl, _dbl, _u64, _i32,
                                         C.c_char_p, C.POINTER(LmmStats)]
+# the pattern cache (--pattern_cache): added after ABI version 15 without a bump
+lib.kgwas_lmm_test_table_unique.argtypes = lib.kgwas_lmm_test_table.argtypes + [_u64, C.POINTER(LmmUniqueStats)]
+lib.kgwas_lmm_run_table_unique.argtypes = lib.kgwas_lmm_run_table_cov.argtypes + [_u64, C.POINTER(LmmUniqueStats)]
 lib.kgwas_synth_rows_device.argtypes = [_vp, _u64, _u64, _u64, _u64, _vp]
 lib.kgwas_synth_rows_host.argtypes = [_vp, _u64, _u64, _u64, _u64]
 

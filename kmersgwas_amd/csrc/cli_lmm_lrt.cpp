@@ -16,6 +16,8 @@
 // REML effect estimate, its standard error, the Wald and the score test beside the LRT (kgwas_lmm_run_files_all).
 // -c FILE (with -bfile, --bfiles or --kmers_table -n; -lmm 2 or 4) gives the model covariates beside the variant, GEMMA's format: one
 // row per individual (.fam lines, or the accessions of PHENO), whitespace-separated numbers, NA missing, a column of 1s among them.
+// --pattern_cache MIB (with --kmers_table -n, with or without -c) tests each distinct presence/absence pattern once: rows that repeat
+// a pattern take its result from a cache of MIB MiB on the device (kgwas_lmm_run_table_unique). The output's bytes are the same.
 #include <sys/stat.h>
 
 #include <cstdlib>
@@ -54,7 +56,7 @@ static void usage(const char* prog) {
             "or, every k-mer of a k-mers table (no PLINK files in between):\n"
             "       " << prog
          << " --kmers_table T --kmers_len K -p PHENO  -lmm 2  -k KINSHIP  [-c COVARIATES] [--mac M] [-maf f] [--best N] [-n i | --pheno_columns LIST]\n"
-            "       [-outdir D] [-o NAME]\n"
+            "       [--pattern_cache MIB] [-outdir D] [-o NAME]\n"
             "       [-lmin x] [-lmax x] [--chunk_variants c] [--device d]\n"
             "  --kmers_table T  k-mers table base name (T.table, T.names); excludes -bfile, --bfiles and --columns\n"
             "  --kmers_len K    length of the k-mers (10-31)\n"
@@ -66,6 +68,10 @@ static void usage(const char* prog) {
             "  --best N         the N k-mers with the largest likelihood ratio are written, in table order (default 10001)\n"
             "  --pheno_columns LIST  file of 'col<TAB>name' lines: every listed phenotype column of PHENO (from 1) is tested in one pass\n"
             "                   over the table, the best N of each to D/name.assoc.txt (no -n, no -o)\n"
+            "  --pattern_cache MIB  each distinct presence/absence pattern over the accessions of PHENO is tested once; the rows that\n"
+            "                   repeat it take its result from a cache of MIB MiB of device memory (a whole number >= 1; a slot takes\n"
+            "                   40 bytes + a byte per 4 accessions). The output is the same, byte for byte; the log gains the cache's\n"
+            "                   counters. Not with --pheno_columns\n"
             "  --device d       GPU ordinal (default 0)\n";
 }
 
@@ -149,6 +155,7 @@ static int table_mode(map<string, string>& a, const char* prog) {
     const uint64_t col = a.count("n") ? whole("-n", a["n"], 1, 1000000) : 1;
     const uint64_t chunk = a.count("chunk_variants") ? whole("--chunk_variants", a["chunk_variants"], 0, 1000000000) : 0;
     const uint64_t device = a.count("device") ? whole("--device", a["device"], 0, 1023) : 0;
+    const uint64_t cache_mib = a.count("pattern_cache") ? whole("--pattern_cache", a["pattern_cache"], 1, 1ull << 20) : 0;
     if (a.count("best") && a["best"].find_first_not_of("0") == string::npos) {
         cerr << "lmm_lrt: --best 0: at least one k-mer must be kept" << endl;
         return 1;
@@ -178,7 +185,11 @@ static int table_mode(map<string, string>& a, const char* prog) {
     vector<const char*> op;
     for (const string& o : outs) op.push_back(o.c_str());
     kgwas_lmm_stats st{};
-    const int rc = a.count("c")    ? kgwas_lmm_run_table_cov(a["k"].c_str(), a["c"].c_str(), a["kmers_table"].c_str(), (uint32_t)klen, a["p"].c_str(),
+    kgwas_lmm_unique_stats us{};
+    const int rc = cache_mib       ? kgwas_lmm_run_table_unique(a["k"].c_str(), a.count("c") ? a["c"].c_str() : nullptr, a["kmers_table"].c_str(),
+                                                                (uint32_t)klen, a["p"].c_str(), (uint32_t)col, mac, maf, best, lmin, lmax, chunk,
+                                                                (int32_t)device, op[0], &st, cache_mib, &us)
+                   : a.count("c")  ? kgwas_lmm_run_table_cov(a["k"].c_str(), a["c"].c_str(), a["kmers_table"].c_str(), (uint32_t)klen, a["p"].c_str(),
                                                              (uint32_t)col, mac, maf, best, lmin, lmax, chunk, (int32_t)device, op[0], &st)
                    : columns.empty() ? kgwas_lmm_run_table(a["k"].c_str(), a["kmers_table"].c_str(), (uint32_t)klen, a["p"].c_str(), (uint32_t)col,
                                                          mac, maf, best, lmin, lmax, chunk, (int32_t)device, op[0], &st)
@@ -191,7 +202,8 @@ static int table_mode(map<string, string>& a, const char* prog) {
     }
     cerr << "[kgwas] lmm_lrt: kmers_table=" << a["kmers_table"] << " columns=" << (columns.empty() ? 1 : columns.size())
          << " individuals=" << st.n_individuals << " rows_read=" << st.variants_read
-         << " rows_tested=" << st.variants_tested << " best=" << best << " eigendecompositions=" << st.eigendecompositions
+         << " rows_tested=" << st.variants_tested << (cache_mib ? " rows_rotated=" + to_string(us.rows_rotated) : string())
+         << " best=" << best << " eigendecompositions=" << st.eigendecompositions
          << " ms: eigen=" << st.eigen_ms << " rotate=" << st.rotate_ms << " grid=" << st.grid_ms << " refine=" << st.refine_ms << endl;
     cli_finish();
     return 0;
@@ -199,7 +211,8 @@ static int table_mode(map<string, string>& a, const char* prog) {
 
 int main(int argc, char* argv[]) {
     static const char* const valued[] = {"bfile", "bfiles", "lmm", "k", "outdir", "o", "n", "maf", "miss", "lmin", "lmax", "chunk_variants", "columns",
-                                         "kmers_table", "kmers_len", "p", "mac", "best", "device", "pheno_columns", "c"};
+                                         "kmers_table", "kmers_len", "p", "mac", "best", "device", "pheno_columns", "c",
+                                         "pattern_cache"};
     map<string, string> a;
     for (int i = 1; i < argc; i++) {
         string s = argv[i];
@@ -244,8 +257,12 @@ int main(int argc, char* argv[]) {
                 return 1;
             }
     }
+    if (a.count("pattern_cache") && a.count("pheno_columns")) {  // (before any file is opened)
+        cerr << "lmm_lrt: --pattern_cache is not built for --pheno_columns: the cache goes with one phenotype column (-n)" << endl;
+        return 1;
+    }
     if (a.count("kmers_table")) return table_mode(a, argv[0]);
-    for (const char* o : {"kmers_len", "p", "mac", "best", "device", "pheno_columns"})
+    for (const char* o : {"kmers_len", "p", "mac", "best", "device", "pheno_columns", "pattern_cache"})
         if (a.count(o)) {
             cerr << "lmm_lrt: option '" << o << "' needs --kmers_table" << endl;
             return 1;

@@ -34,6 +34,8 @@
 //   KGWAS_LMM_PIECE_ROWS=n     (test hook) table rows per piece of kgwas_lmm_test_table (default: up to 2^18, about 64 MiB of rows)
 //   KGWAS_LMM_TABLE_SELECT=0   (test hook) kgwas_lmm_test_table_multi: the select kernel lets every (column, row) pair through to the host
 //                              heaps (default 1: only pairs that can still enter a heap); the results are the same
+//   KGWAS_LMM_PATTERN_TAG_BITS=k   (test hook) kgwas_lmm_test_table_unique: the pattern cache's tags keep only k of their 64 bits, so that
+//                              they collide; the results are the same
 //   KGWAS_BUILD_PIECE_ROWS=n   (test hook) all-k-mers rows per piece of kgwas_build_table (default: about 256 MiB of rows; a piece is whole key windows)
 //   KGWAS_BUILD_BLOCK_WORDS=n  (test hook) words per read block of an accession's slice in kgwas_build_table (default 65 536)
 //   KGWAS_LIST_PIECE_WORDS=n   (test hook) words per piece of kgwas_list_kmers (default 2^25, 256 MiB; a piece is whole key windows)

@@ -10,6 +10,7 @@
 // -lmm 4   : run_files with all_tests writes the 14-column file (format_assoc4) and four more lines in the log.
 // -c       : run_files and run_table with a covariates file (read_covariates): its rows are checked on the host, subset with
 //            everything else and handed to the session (set_covariates); the log gains two lines.
+// --pattern_cache: run_table with cache_mib > 0 goes through test_table_unique; the same .assoc.txt, six more lines in the log.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -541,7 +542,8 @@ struct TableRun {
 // one column's kept k-mers to `out` in table order, with the bytes run_files writes for them after kmers_table_to_bed, and the log
 void write_table_result(const std::string& out, const std::vector<TableHit>& kept, const TableRun& r, const char* table_base,
                         uint32_t pheno_col, const char* kinship_path, uint64_t rows_read, uint64_t rows_tested, uint64_t best_n,
-                        double lambda0, double l0, const kgwas_lmm_stats& st, double total_ms, const Covariates* cov = nullptr) {
+                        double lambda0, double l0, const kgwas_lmm_stats& st, double total_ms, const Covariates* cov = nullptr,
+                        const kgwas_lmm_unique_stats* u = nullptr) {
     std::string text = assoc_header();
     for (const TableHit& k : kept) {
         char km[33];
@@ -552,24 +554,32 @@ void write_table_result(const std::string& out, const std::vector<TableHit>& kep
         text.append(line, len);
     }
     write_text(out, text, "wb");
-    char log[3072];
+    char log[3584], cache_lines[512] = "";
+    if (u)  // --pattern_cache: six lines behind the others
+        snprintf(cache_lines, sizeof(cache_lines),
+                 "pattern_cache_slots\t%llu\npatterns_cached\t%llu\nrows_from_cache\t%llu\nrows_collided\t%llu\nrows_rejected\t%llu\n"
+                 "rows_rotated\t%llu\n",
+                 (unsigned long long)u->slots, (unsigned long long)u->patterns_cached, (unsigned long long)u->rows_from_cache,
+                 (unsigned long long)u->rows_collided, (unsigned long long)u->rows_rejected, (unsigned long long)u->rows_rotated);
     const int ll = snprintf(log, sizeof(log),
                             "lmm_lrt: ML likelihood-ratio test (-lmm 2)\nkmers_table\t%s\nphenotypes\t%s\nphenotype_column\t%u\nkinship\t%s\n%s"
                             "individuals_used\t%llu\nmin_count\t%llu\nrows_read\t%llu\nrows_tested\t%llu\nrows_kept\t%llu\nbest_n\t%llu\n"
-                            "lambda0\t%.6e\nlogl_H0\t%.6f\nms: eigen=%.3f rotate=%.3f grid=%.3f refine=%.3f total=%.3f\n",
+                            "lambda0\t%.6e\nlogl_H0\t%.6f\nms: eigen=%.3f rotate=%.3f grid=%.3f refine=%.3f total=%.3f\n%s",
                             table_base, r.pheno_path.c_str(), pheno_col, kinship_path, covariate_lines(cov).c_str(), (unsigned long long)r.S,
                             (unsigned long long)r.min_count,
                             (unsigned long long)rows_read, (unsigned long long)rows_tested, (unsigned long long)kept.size(),
-                            (unsigned long long)best_n, lambda0, l0, st.eigen_ms, st.rotate_ms, st.grid_ms, st.refine_ms, total_ms);
+                            (unsigned long long)best_n, lambda0, l0, st.eigen_ms, st.rotate_ms, st.grid_ms, st.refine_ms, total_ms,
+                            cache_lines);
     write_log_text(out, log, sizeof(log), ll);
 }
 
 // The file layer of lmm_lrt --kmers_table: the accessions and their order are the phenotype file's, y its column pheno_col (from
 // 1), the k-mers come straight from <table_base>.table. The best best_n k-mers by the exact test go to `out` in table order, with
-// the bytes run_files writes for them after kmers_table_to_bed; a log goes beside it.
+// the bytes run_files writes for them after kmers_table_to_bed; a log goes beside it. With cache_mib > 0 the pass is
+// test_table_unique's with a pattern cache of that many MiB: the same bytes in `out`, six more lines in the log, *u the counters.
 void run_table(const char* kinship_path, const char* table_base, uint32_t kmer_len, const char* pheno_path, uint32_t pheno_col,
                uint64_t mac, double maf, uint64_t best_n, double lmin, double lmax, uint64_t chunk_variants, int device, const char* out,
-               kgwas_lmm_stats* total, const char* covar_path = nullptr) {
+               kgwas_lmm_stats* total, const char* covar_path = nullptr, uint64_t cache_mib = 0, kgwas_lmm_unique_stats* u = nullptr) {
     if (!kinship_path || !table_base || !pheno_path || !out) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_run_table: null argument");
     if (pheno_col < 1) throw Error(KGWAS_ERR_ARG, "the phenotype column (-n) starts at 1");
     if (!best_n) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_run_table: best_n is 0");
@@ -599,10 +609,16 @@ void run_table(const char* kinship_path, const char* table_base, uint32_t kmer_l
     if (cov) set_covariates(h.get(), cov_file.q, W.data());
     std::vector<TableHit> kept;
     uint64_t rows_read = 0, rows_tested = 0;
-    test_table(h.get(), y.data(), r.t, r.col.data(), r.S, r.min_count, maf, best_n, kept, rows_read, rows_tested);
+    kgwas_lmm_unique_stats us{};
+    if (cache_mib)  // as many slots as the bytes hold (test_table_unique takes a power of two, and refuses fewer than 64)
+        test_table_unique(h.get(), y.data(), r.t, r.col.data(), r.S, r.min_count, maf, best_n,
+                          std::min<uint64_t>(cache_mib, 1ull << 40) * (1ull << 20) / lmm_cache_slot_bytes(h->dm), kept, rows_read, rows_tested, us);
+    else
+        test_table(h.get(), y.data(), r.t, r.col.data(), r.S, r.min_count, maf, best_n, kept, rows_read, rows_tested);
     write_table_result(out, kept, r, table_base, pheno_col, kinship_path, rows_read, rows_tested, best_n, h->lambda0, h->l0, h->st,
-                       now_ms() - t_start, cov);
+                       now_ms() - t_start, cov, cache_mib ? &us : nullptr);
     if (total) *total = h->st;
+    if (u && cache_mib) *u = us;
 }
 
 // The same for n_cols columns of the phenotype file (pheno_cols, from 1) in ONE pass over the table: the files are read once, K is
@@ -697,6 +713,17 @@ int kgwas_lmm_run_table_cov(const char* kinship_path, const char* covar_path, co
     return guarded([&] {
         run_table(kinship_path, table_base, kmer_len, pheno_path, pheno_col, mac, maf, best_n, lmin, lmax, chunk_variants, device, out_path,
                   total, covar_path);
+    });
+}
+
+int kgwas_lmm_run_table_unique(const char* kinship_path, const char* covar_path, const char* table_base, uint32_t kmer_len,
+                               const char* pheno_path, uint32_t pheno_col, uint64_t mac, double maf, uint64_t best_n, double lmin,
+                               double lmax, uint64_t chunk_variants, int32_t device, const char* out_path, kgwas_lmm_stats* total,
+                               uint64_t cache_mib, kgwas_lmm_unique_stats* u) {
+    return guarded([&] {
+        if (!cache_mib) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_run_table_unique: cache_mib is 0");
+        run_table(kinship_path, table_base, kmer_len, pheno_path, pheno_col, mac, maf, best_n, lmin, lmax, chunk_variants, device, out_path,
+                  total, covar_path, cache_mib, u);
     });
 }
 

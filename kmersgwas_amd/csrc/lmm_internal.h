@@ -135,6 +135,9 @@ void multi_block(kgwas_lmm* h, const LmmVariant* vars, uint32_t cc, uint32_t p0,
 // ---- lmm_table.cpp ----
 void test_table(kgwas_lmm* h, const double* y, kgwas_table* t, const uint64_t* col, uint64_t n_acc, uint64_t min_count, double maf,
                 uint64_t best_n, std::vector<TableHit>& kept, uint64_t& rows_read, uint64_t& rows_tested);
+void test_table_unique(kgwas_lmm* h, const double* y, kgwas_table* t, const uint64_t* col, uint64_t n_acc, uint64_t min_count, double maf,
+                       uint64_t best_n, uint64_t max_patterns, std::vector<TableHit>& kept, uint64_t& rows_read, uint64_t& rows_tested,
+                       kgwas_lmm_unique_stats& u);
 void test_table_multi(kgwas_lmm* h, uint32_t n_pheno, const double* Y, kgwas_table* t, const uint64_t* col, uint64_t n_acc,
                       uint64_t min_count, double maf, uint64_t best_n, std::vector<std::vector<TableHit>>& kept, double* logl0,
                       double* lambda0, uint64_t& rows_read, uint64_t& rows_tested, uint64_t& pairs_shipped);

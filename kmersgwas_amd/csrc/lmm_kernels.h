@@ -121,4 +121,41 @@ hipError_t launch_lmm_table_select(const double* lrt, const double* lam, const d
                                    const uint64_t* row, const uint64_t* kmer, const LmmSelectCol* cols, uint32_t* block_cnt,
                                    uint32_t* block_off, uint32_t* count, LmmTableRecord* rec, uint32_t cap, hipStream_t st);
 
+// lmm_table_kernels.hip: the pattern cache of kgwas_lmm_test_table_unique ("The pattern cache"). Its key is a
+// compacted code row, codes[t][bpsp] of launch_lmm_table_front. A slot holds a 64-bit tag (0: empty), an owner word, the code row
+// and lrt, lam, p of its pattern. `slots` is a power of two >= 64. Before the first piece of a call every tag is 0 and every
+// owner LMM_CACHE_NO_OWNER; between pieces every owner of a slot in use is 0.
+constexpr uint32_t LMM_CACHE_PROBES = 16;               // slots a row looks at before it gives up
+constexpr uint32_t LMM_CACHE_NONE = 0xFFFFFFFFu;        // slot_of of a row that reached no slot
+constexpr uint32_t LMM_CACHE_NO_OWNER = 0xFFFFFFFFu;
+enum : uint32_t {            // what a tested row of a piece is to the cache
+    LMM_ROW_OWNER = 0,       //   the first row of its tag in a new slot: rotated, and its result goes into the slot
+    LMM_ROW_CACHED = 1,      //   its code row equals its slot's: not rotated, it takes the slot's result
+    LMM_ROW_COLLIDED = 2,    //   its slot holds another code row with its tag: rotated
+    LMM_ROW_REJECTED = 3     //   no slot within LMM_CACHE_PROBES: rotated
+};
+struct LmmCache {
+    unsigned long long* tag;  // [slots]
+    uint32_t* owner;          // [slots] compact index + 1 of the smallest row that reached the slot in this piece
+    uint32_t* key;            // [slots][bpsp / 4]
+    double* res;              // [slots][3]: lrt, lam, p
+    uint32_t slots;
+};
+inline uint64_t lmm_cache_slot_bytes(LmmDims dm) { return 8 + 8 + dm.bpsp + 3 * sizeof(double); }  // (the owner word padded to 8)
+// The look-up of a piece's `total` compacted rows: row_tag[t] = the row's tag (a mix of its code row, cut to tag_mask, never 0),
+// slot_of[t] and cls[t] as above, and the rows to rotate (every class but LMM_ROW_CACHED) compacted in row order: codes2, vars2,
+// back[t2] = t, total2[0] = their number. Scratch: block_cnt and block_off [total / LMM_TABLE_BLOCK rounded up]. Every per-row
+// array has room for `total` rows. 0 < total < 2^31.
+hipError_t launch_lmm_cache_lookup(const uint8_t* codes, const LmmVariant* vars, uint32_t total, LmmDims dm, uint64_t tag_mask, LmmCache c,
+                                   unsigned long long* row_tag, uint32_t* slot_of, uint32_t* cls, uint32_t* block_cnt, uint32_t* block_off,
+                                   uint32_t* total2, uint8_t* codes2, LmmVariant* vars2, uint32_t* back, hipStream_t st);
+// After the back end over the sub-chunk back[0 .. cc) of the rows to rotate: their lrt, lam, p go to the piece's arrays at the
+// rows' places, and an owner's into its slot too.
+hipError_t launch_lmm_cache_scatter(const double* lrt, const double* lam, const double* p, uint32_t cc, const uint32_t* back,
+                                    const uint32_t* slot_of, const uint32_t* cls, uint32_t total, LmmCache c, double* r_lrt, double* r_lam,
+                                    double* r_p, hipStream_t st);
+// After the piece's last sub-chunk: the rows from cache take their slot's result, and the piece's new slots get owner 0.
+hipError_t launch_lmm_cache_fanout(const uint32_t* slot_of, const uint32_t* cls, uint32_t total, LmmCache c, double* r_lrt, double* r_lam,
+                                   double* r_p, hipStream_t st);
+
 }  // namespace kgwas

@@ -5,6 +5,7 @@
 //            AND prep would test, and compacts those into code rows and LmmVariants with prep's bits (lmm_table_kernels.hip);
 //            rotate, grid and refine then run over them unchanged (lmm.cpp's single_backend). The host keeps the best N by
 //            (lrt, table row);
+// test_table_unique: test_table with a pattern cache on the device (--pattern_cache): a code row met before is not rotated again;
 // test_table_multi: several phenotype columns against ONE table in one pass (the phenotype and its permutations). The front end and
 //            the rotation run once per row, the xt yt sums and the refinement per block of LMM_PBLOCK columns (lmm.cpp's
 //            multi_front and multi_block), and a select kernel hands the host only the (column, row) pairs that can still enter a
@@ -117,7 +118,15 @@ class PieceReader {
     std::thread thread_;
 };
 
-// What test_table and test_table_multi share: the checks, the pieces and the front end. Per piece the rows are squeezed, flagged
+// rows per piece of table_pass for a table of n_rows rows of 1 + W_f words: about 64 MiB of rows, at most 2^18
+uint64_t piece_rows(uint64_t n_rows, uint64_t W_f) {
+    uint64_t piece = std::max<uint64_t>(1024, std::min<uint64_t>(1u << 18, (64ull << 20) / (8 * (1 + W_f))));
+    const long long forced = opt_int("KGWAS_LMM_PIECE_ROWS", 0);
+    if (forced > 0) piece = (uint64_t)std::min<long long>(forced, 1 << 20);
+    return std::min(piece, std::max<uint64_t>(n_rows, 1));
+}
+
+// What test_table, test_table_unique and test_table_multi share: the checks, the pieces and the front end. Per piece the rows are squeezed, flagged
 // and compacted (lmm_table_kernels.hip). prepare() runs after the checks and before any device work (the null models);
 // per_piece(total, codes, vars, row, kmer) gets a piece's compacted tested rows on the device, total > 0 of them, and is done
 // with them when it returns. `who` starts the messages; a tested row counts `weight` times in the stats' variants_tested.
@@ -137,10 +146,7 @@ void table_pass(kgwas_lmm* h, kgwas_table* t, const uint64_t* col, uint64_t n_ac
     KGWAS_HIP(hipSetDevice(h->device));
     const uint32_t W_m = (uint32_t)(2 * ((S + 127) / 128));
     const uint64_t stride = 1 + W_f;
-    uint64_t piece = std::max<uint64_t>(1024, std::min<uint64_t>(1u << 18, (64ull << 20) / (8 * stride)));
-    const long long forced = opt_int("KGWAS_LMM_PIECE_ROWS", 0);
-    if (forced > 0) piece = (uint64_t)std::min<long long>(forced, 1 << 20);
-    piece = std::min(piece, std::max<uint64_t>(n_rows, 1));
+    const uint64_t piece = piece_rows(n_rows, W_f);
     const uint64_t n_blocks = (piece + LMM_TABLE_BLOCK - 1) / LMM_TABLE_BLOCK;
 
     std::vector<uint32_t> colmap(64ull * W_m, 0xFFFFFFFFu);
@@ -241,6 +247,107 @@ void kgwas::lmm::test_table(kgwas_lmm* h, const double* y, kgwas_table* t, const
     kept.swap(heap);
 }
 
+// test_table with a pattern cache of at most max_patterns slots (a power of two is taken, at least 64): each distinct code row
+// among the tested rows goes through rotate, grid and refine once, every other row with that code row takes the stored lrt, lam
+// and p (lmm_table_kernels.hip, "the pattern cache"). Equal code rows give equal LmmVariants and so equal results, whatever their
+// chunk and place, and the host is offered every tested row in row order as in test_table: kept has test_table's
+// bytes for any cache size, piece and chunk, with colliding tags and with a full cache too. The cache lives for this call: the
+// results depend on y and W. u is written only when the call succeeds.
+void kgwas::lmm::test_table_unique(kgwas_lmm* h, const double* y, kgwas_table* t, const uint64_t* col, uint64_t n_acc, uint64_t min_count,
+                                   double maf, uint64_t best_n, uint64_t max_patterns, std::vector<TableHit>& kept, uint64_t& rows_read,
+                                   uint64_t& rows_tested, kgwas_lmm_unique_stats& u) {
+    const std::string who = "kgwas_lmm_test_table_unique";
+    if (max_patterns < 64) throw Error(KGWAS_ERR_ARG, who + ": max_patterns is below 64");  // (before any device work)
+    uint32_t slots = 64;
+    while (slots < (1u << 30) && 2ull * slots <= max_patterns) slots *= 2;
+    const long long tag_bits = opt_int("KGWAS_LMM_PATTERN_TAG_BITS", 64);
+    const uint64_t tag_mask = tag_bits >= 1 && tag_bits < 64 ? (1ull << tag_bits) - 1 : ~0ull;
+    const uint64_t chunk = h->chunk, bpsp = h->dm.bpsp;
+    std::vector<TableHit> heap;
+    kgwas_lmm_unique_stats us{};
+    us.slots = slots;
+    // the cache, and per piece: the rows' tags, slots and classes, the rows to rotate, every tested row's result
+    DevBuf<unsigned long long> c_tag, d_tag;
+    DevBuf<uint32_t> c_owner, c_key, d_slot, d_cls, d_back, d_bcnt, d_boff, d_total2;
+    DevBuf<double> c_res, d_rlrt, d_rlam, d_rp;
+    DevBuf<uint8_t> d_codes2;
+    DevBuf<LmmVariant> d_vars2;
+    LmmCache cache{};
+    std::vector<double> o_lrt, o_lam, o_p;
+    std::vector<LmmVariant> o_vars;
+    std::vector<uint64_t> o_row, o_kmer;
+    std::vector<uint32_t> o_cls;
+    auto prepare = [&] {
+        fit_null(h, y);
+        heap.reserve((size_t)std::min<uint64_t>(best_n, 1u << 20));
+        uint64_t S_f = 0, n_rows = 0, W_f = 0;
+        uint32_t klen = 0;
+        if (kgwas_table_info(t, &S_f, &n_rows, &W_f, &klen) != KGWAS_OK) throw Error(KGWAS_ERR_ARG, kgwas_last_error());
+        const uint64_t piece = piece_rows(n_rows, W_f);  // the host and device buffers hold a piece, not a chunk
+        o_lrt.resize(piece), o_lam.resize(piece), o_p.resize(piece), o_vars.resize(piece), o_row.resize(piece), o_kmer.resize(piece);
+        o_cls.resize(piece);
+        KGWAS_HIP(hipSetDevice(h->device));
+        c_tag.alloc(slots), c_owner.alloc(slots), c_key.alloc((uint64_t)slots * (bpsp / 4)), c_res.alloc(3ull * slots);
+        d_tag.alloc(piece), d_slot.alloc(piece), d_cls.alloc(piece), d_back.alloc(piece);
+        d_bcnt.alloc((piece + LMM_TABLE_BLOCK - 1) / LMM_TABLE_BLOCK), d_boff.alloc(d_bcnt.n), d_total2.alloc(1);
+        d_rlrt.alloc(piece), d_rlam.alloc(piece), d_rp.alloc(piece);
+        d_codes2.alloc(piece * bpsp), d_vars2.alloc(piece);
+        cache = LmmCache{c_tag.p, c_owner.p, c_key.p, c_res.p, slots};
+        KGWAS_HIP(hipMemsetAsync(c_tag.p, 0, slots * sizeof(unsigned long long), h->stream));
+        KGWAS_HIP(hipMemsetAsync(c_owner.p, 0xFF, slots * sizeof(uint32_t), h->stream));  // LMM_CACHE_NO_OWNER
+    };
+    auto per_piece = [&](uint32_t total, const uint8_t* d_codes, const LmmVariant* d_vars, const uint64_t* d_row, const uint64_t* d_kmer) {
+        hipStream_t st = h->stream;
+        if (total > d_cls.n) throw Error(KGWAS_ERR_STATE, who + ": a piece has more tested rows than the piece has rows");
+        uint32_t total2 = 0;
+        h->timer.begin(st);  // (the cache's kernels are timed with the front end and the rotation)
+        KGWAS_HIP(launch_lmm_cache_lookup(d_codes, d_vars, total, h->dm, tag_mask, cache, d_tag.p, d_slot.p, d_cls.p, d_bcnt.p, d_boff.p,
+                                          d_total2.p, d_codes2.p, d_vars2.p, d_back.p, st));
+        h->timer.end(&kgwas_lmm_stats::rotate_ms, st);
+        KGWAS_HIP(hipMemcpyAsync(&total2, d_total2.p, sizeof(total2), hipMemcpyDeviceToHost, st));
+        KGWAS_HIP(hipStreamSynchronize(st));
+        h->timer.collect(h->st);
+        if (total2 > total) throw Error(KGWAS_ERR_STATE, who + ": the cache counted more rows to rotate than tested rows");
+        h->timer.begin(st);
+        for (uint64_t sub = 0; sub < total2; sub += chunk) {
+            const uint32_t cc = (uint32_t)std::min<uint64_t>(chunk, total2 - sub);
+            single_backend(h, d_codes2.p + sub * bpsp, d_vars2.p + sub, cc);
+            KGWAS_HIP(launch_lmm_cache_scatter(h->d_lrt.p, h->d_lam.p, h->d_p.p, cc, d_back.p + sub, d_slot.p, d_cls.p, total, cache, d_rlrt.p,
+                                               d_rlam.p, d_rp.p, st));
+            h->timer.end(&kgwas_lmm_stats::rotate_ms, st);
+            h->st.chunks++;
+        }
+        // after the last sub-chunk: an owner may stand in a later sub-chunk than its copies
+        KGWAS_HIP(launch_lmm_cache_fanout(d_slot.p, d_cls.p, total, cache, d_rlrt.p, d_rlam.p, d_rp.p, st));
+        h->timer.end(&kgwas_lmm_stats::rotate_ms, st);
+        KGWAS_HIP(hipMemcpyAsync(o_lrt.data(), d_rlrt.p, total * sizeof(double), hipMemcpyDeviceToHost, st));
+        KGWAS_HIP(hipMemcpyAsync(o_lam.data(), d_rlam.p, total * sizeof(double), hipMemcpyDeviceToHost, st));
+        KGWAS_HIP(hipMemcpyAsync(o_p.data(), d_rp.p, total * sizeof(double), hipMemcpyDeviceToHost, st));
+        KGWAS_HIP(hipMemcpyAsync(o_vars.data(), d_vars, total * sizeof(LmmVariant), hipMemcpyDeviceToHost, st));
+        KGWAS_HIP(hipMemcpyAsync(o_row.data(), d_row, total * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        KGWAS_HIP(hipMemcpyAsync(o_kmer.data(), d_kmer, total * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        KGWAS_HIP(hipMemcpyAsync(o_cls.data(), d_cls.p, total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        KGWAS_HIP(hipStreamSynchronize(st));
+        h->timer.collect(h->st);
+        uint64_t kinds[4] = {0, 0, 0, 0};
+        for (uint32_t v = 0; v < total; v++) {
+            if (o_cls[v] > LMM_ROW_REJECTED) throw Error(KGWAS_ERR_STATE, who + ": a row of no class");
+            kinds[o_cls[v]]++;
+            heap_offer(heap, best_n, TableHit{o_lrt[v], o_lam[v], o_p[v], o_vars[v].af, o_row[v], o_kmer[v]});
+        }
+        if (total - kinds[LMM_ROW_CACHED] != total2) throw Error(KGWAS_ERR_STATE, who + ": the rows' classes and the rows to rotate differ");
+        us.patterns_cached += kinds[LMM_ROW_OWNER];
+        us.rows_from_cache += kinds[LMM_ROW_CACHED];
+        us.rows_collided += kinds[LMM_ROW_COLLIDED];
+        us.rows_rejected += kinds[LMM_ROW_REJECTED];
+        us.rows_rotated += total2;
+    };
+    table_pass(h, t, col, n_acc, min_count, maf, best_n, who, 1, prepare, per_piece, rows_read, rows_tested);
+    sort_by_row(heap);
+    kept.swap(heap);
+    u = us;
+}
+
 // The same for n_pheno columns Y[n_pheno][n] in one pass over the table: the best best_n per column, each with the rows and the
 // bits test_table gives for that column alone. Per sub-chunk the rotation and the grid sums without y run once; per block of
 // LMM_PBLOCK columns the xt yt sums, the refinement and the select kernel, which hands the host only the (column, row) pairs that
@@ -320,6 +427,24 @@ int kgwas_lmm_test_table(kgwas_lmm* h, const double* y, kgwas_table* t, const ui
         if (n_kept) *n_kept = kept.size();
         if (rows_read) *rows_read = n_read;
         if (rows_tested) *rows_tested = n_tested;
+    });
+}
+
+int kgwas_lmm_test_table_unique(kgwas_lmm* h, const double* y, kgwas_table* t, const uint64_t* col, uint64_t n_acc, uint64_t min_count,
+                                double maf, uint64_t best_n, uint64_t* row, uint64_t* kmer, double* lrt, double* lambda, double* p, double* af,
+                                uint64_t* n_kept, uint64_t* rows_read, uint64_t* rows_tested, uint64_t max_patterns,
+                                kgwas_lmm_unique_stats* u) {
+    return guarded([&] {
+        if (!h || !y || !t || !col) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_test_table_unique: null argument");
+        std::vector<TableHit> kept;
+        uint64_t n_read = 0, n_tested = 0;
+        kgwas_lmm_unique_stats us{};
+        test_table_unique(h, y, t, col, n_acc, min_count, maf, best_n, max_patterns, kept, n_read, n_tested, us);
+        copy_hits(kept, 0, row, kmer, lrt, lambda, p, af);
+        if (n_kept) *n_kept = kept.size();
+        if (rows_read) *rows_read = n_read;
+        if (rows_tested) *rows_tested = n_tested;
+        if (u) *u = us;
     });
 }
 

@@ -20,7 +20,17 @@
 //   lmm_table_scan_kernel          as above: the offsets and the number of survivors;
 //   lmm_table_select_kernel        a surviving pair's lane writes its record at offset + rank, so records follow the (column, row)
 //                                  order and are the same in every run.
-// No atomic, no scalar memory write: every value goes out through a vector store from plain C++.
+// And the pattern cache of kgwas_lmm_test_table_unique, which sends each distinct code row through the back end once:
+//   lmm_cache_hash_kernel      one wave per tested row: its 64-bit tag;
+//   lmm_cache_claim_kernel     one lane per row: the slot of its tag (atomicCAS along a linear probe sequence of 16 slots) and, by
+//                              atomicMin, the slot's owner - the smallest row of the piece that reached it;
+//   lmm_cache_publish_kernel   an owner's code row goes into its new slot;
+//   lmm_cache_classify_kernel  one wave per row: owner, from cache (the whole code row equals the slot's), collided or rejected;
+//   lmm_cache_count_kernel, lmm_table_scan_kernel, lmm_cache_emit_kernel   the rows to rotate, compacted in row order;
+//   lmm_cache_scatter_kernel   a sub-chunk's results go back to the rows' places and into the owners' slots;
+//   lmm_cache_fanout_kernel    the rows from cache take their slot's result; the piece's new slots get owner 0.
+// No scalar memory write: every value goes out through a vector store from plain C++. The two atomics of lmm_cache_claim_kernel
+// are the only ones.
 #include "lmm_kernels.h"
 
 namespace kgwas {
@@ -195,7 +205,195 @@ __global__ void __launch_bounds__(TB) lmm_table_select_kernel(const double* __re
     rec[slot] = o;
 }
 
+// ---- the pattern cache of kgwas_lmm_test_table_unique ("The pattern cache") ----
+// Atomics stand in lmm_cache_claim_kernel alone, and there a word an atomic touches is never loaded plainly; everything else one
+// kernel leaves for another crosses a kernel boundary on the one stream. Every loop has a bound no other thread can move.
+
+__device__ inline uint64_t mix64(uint64_t x) {  // the finaliser of splitmix64
+    x ^= x >> 30;
+    x *= 0xBF58476D1CE4E5B9ull;
+    x ^= x >> 27;
+    x *= 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+
+// One wave per row: the tag is a mix of the sum, over the row's dwords, of a mix of (place, dword); a sum of integers, so the same
+// in any order. Never 0, which marks an empty slot.
+__global__ void __launch_bounds__(TB) lmm_cache_hash_kernel(const uint32_t* __restrict__ codes, uint32_t total, uint32_t ndc,
+                                                            uint64_t tag_mask, unsigned long long* __restrict__ row_tag) {
+    const uint32_t t = blockIdx.x * (TB / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (t >= total) return;  // (wave-uniform)
+    unsigned long long acc = 0;
+    for (uint32_t j = lane; j < ndc; j += 64) acc += mix64(((uint64_t)(j + 1) << 32) | codes[(uint64_t)t * ndc + j]);
+#pragma unroll
+    for (uint32_t d = 32; d; d >>= 1) acc += __shfl_xor(acc, d, 64);
+    const unsigned long long tag = mix64(acc) & tag_mask;
+    if (lane == 0) row_tag[t] = tag ? tag : 1ull;
+}
+
+// One lane per row. The probe sequence is a function of the tag alone, and a slot's tag never changes once set, so a tag ends in
+// the same slot all through a call. The owner of a slot new in this piece is the smallest row that reached it; a slot of an
+// earlier piece has owner 0, which the min leaves.
+__global__ void __launch_bounds__(TB) lmm_cache_claim_kernel(const unsigned long long* __restrict__ row_tag, uint32_t total, LmmCache c,
+                                                             uint32_t* __restrict__ slot_of) {
+    const uint32_t t = blockIdx.x * TB + threadIdx.x;
+    if (t >= total) return;
+    const unsigned long long mine = row_tag[t];
+    const uint32_t mask = c.slots - 1u, first = (uint32_t)(mix64(mine) >> 32) & mask;
+    uint32_t found = LMM_CACHE_NONE;
+    for (uint32_t i = 0; i < LMM_CACHE_PROBES && found == LMM_CACHE_NONE; i++) {
+        const uint32_t s = (first + i) & mask;
+        const unsigned long long old = atomicCAS(&c.tag[s], 0ull, mine);
+        if (old == 0ull || old == mine) found = s;
+    }
+    if (found != LMM_CACHE_NONE) (void)atomicMin(&c.owner[found], t + 1u);
+    slot_of[t] = found;
+}
+
+// One lane per (row, dword): an owner's code row goes into its slot.
+__global__ void __launch_bounds__(TB) lmm_cache_publish_kernel(const uint32_t* __restrict__ codes, uint32_t total, uint32_t ndc,
+                                                               const uint32_t* __restrict__ slot_of, LmmCache c) {
+    const uint64_t e = (uint64_t)blockIdx.x * TB + threadIdx.x;
+    const uint64_t t = e / ndc;
+    if (t >= total) return;
+    const uint32_t s = slot_of[t];
+    if (s >= c.slots || c.owner[s] != (uint32_t)t + 1u) return;
+    c.key[(uint64_t)s * ndc + (e - t * ndc)] = codes[e];
+}
+
+// One wave per row: every row that reached a slot and is not its owner compares its whole code row with the slot's.
+__global__ void __launch_bounds__(TB) lmm_cache_classify_kernel(const uint32_t* __restrict__ codes, uint32_t total, uint32_t ndc,
+                                                                const uint32_t* __restrict__ slot_of, LmmCache c,
+                                                                uint32_t* __restrict__ cls) {
+    const uint32_t t = blockIdx.x * (TB / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (t >= total) return;  // (wave-uniform, as every branch below)
+    const uint32_t s = slot_of[t];
+    uint32_t kind;
+    if (s >= c.slots) {
+        kind = LMM_ROW_REJECTED;
+    } else if (c.owner[s] == t + 1u) {
+        kind = LMM_ROW_OWNER;
+    } else {
+        uint32_t diff = 0;
+        for (uint32_t j = lane; j < ndc; j += 64) diff |= codes[(uint64_t)t * ndc + j] ^ c.key[(uint64_t)s * ndc + j];
+        kind = __ballot(diff != 0u) ? LMM_ROW_COLLIDED : LMM_ROW_CACHED;
+    }
+    if (lane == 0) cls[t] = kind;
+}
+
+// The rows to rotate, compacted by the scheme of the front end: the count per block of 256 rows, lmm_table_scan_kernel, the emit.
+__global__ void __launch_bounds__(TB) lmm_cache_count_kernel(const uint32_t* __restrict__ cls, uint32_t total,
+                                                             uint32_t* __restrict__ block_cnt) {
+    __shared__ uint32_t s_wave[TB / 64];
+    const uint32_t t = blockIdx.x * TB + threadIdx.x;
+    const bool rotate = t < total && cls[t] != LMM_ROW_CACHED;
+    uint32_t n;
+    (void)block_rank(rotate, s_wave, n);
+    if (threadIdx.x == 0) block_cnt[blockIdx.x] = n;
+}
+
+__global__ void __launch_bounds__(TB) lmm_cache_emit_kernel(const uint32_t* __restrict__ codes, const LmmVariant* __restrict__ vars,
+                                                            const uint32_t* __restrict__ cls, uint32_t total, uint32_t ndc,
+                                                            const uint32_t* __restrict__ block_off, uint32_t* __restrict__ codes2,
+                                                            LmmVariant* __restrict__ vars2, uint32_t* __restrict__ back) {
+    __shared__ uint32_t s_wave[TB / 64];
+    __shared__ uint32_t s_slot[TB];
+    const uint32_t row0 = blockIdx.x * TB, t = row0 + threadIdx.x;
+    const bool rotate = t < total && cls[t] != LMM_ROW_CACHED;
+    uint32_t n;
+    const uint32_t slot = block_off[blockIdx.x] + block_rank(rotate, s_wave, n);  // (<= t: at most t rows stand before row t)
+    s_slot[threadIdx.x] = rotate && slot < total ? slot : LMM_CACHE_NONE;
+    if (rotate && slot < total) {
+        vars2[slot] = vars[t];
+        back[slot] = t;
+    }
+    __syncthreads();
+    if (n == 0) return;  // (block-uniform)
+    for (uint32_t e = threadIdx.x; e < TB * ndc; e += TB) {
+        const uint32_t rr = e / ndc, j = e - rr * ndc;
+        const uint32_t s = s_slot[rr];
+        if (s == LMM_CACHE_NONE) continue;
+        codes2[(uint64_t)s * ndc + j] = codes[(uint64_t)(row0 + rr) * ndc + j];
+    }
+}
+
+// One lane per row of a sub-chunk that went through the back end.
+__global__ void __launch_bounds__(TB) lmm_cache_scatter_kernel(const double* __restrict__ lrt, const double* __restrict__ lam,
+                                                               const double* __restrict__ p, uint32_t cc, const uint32_t* __restrict__ back,
+                                                               const uint32_t* __restrict__ slot_of, const uint32_t* __restrict__ cls,
+                                                               uint32_t total, LmmCache c, double* __restrict__ r_lrt,
+                                                               double* __restrict__ r_lam, double* __restrict__ r_p) {
+    const uint32_t v = blockIdx.x * TB + threadIdx.x;
+    if (v >= cc) return;
+    const uint32_t t = back[v];
+    if (t >= total) return;
+    const double a = lrt[v], b = lam[v], q = p[v];
+    r_lrt[t] = a;
+    r_lam[t] = b;
+    r_p[t] = q;
+    const uint32_t s = slot_of[t];
+    if (cls[t] != LMM_ROW_OWNER || s >= c.slots) return;
+    c.res[3ull * s] = a;
+    c.res[3ull * s + 1] = b;
+    c.res[3ull * s + 2] = q;
+}
+
+// One lane per row of the piece, after its last sub-chunk (an owner may stand in a later sub-chunk than its copies).
+__global__ void __launch_bounds__(TB) lmm_cache_fanout_kernel(const uint32_t* __restrict__ slot_of, const uint32_t* __restrict__ cls,
+                                                              uint32_t total, LmmCache c, double* __restrict__ r_lrt,
+                                                              double* __restrict__ r_lam, double* __restrict__ r_p) {
+    const uint32_t t = blockIdx.x * TB + threadIdx.x;
+    if (t >= total) return;
+    const uint32_t s = slot_of[t], kind = cls[t];
+    if (s >= c.slots) return;
+    if (kind == LMM_ROW_CACHED) {
+        r_lrt[t] = c.res[3ull * s];
+        r_lam[t] = c.res[3ull * s + 1];
+        r_p[t] = c.res[3ull * s + 2];
+    } else if (kind == LMM_ROW_OWNER) {
+        c.owner[s] = 0u;
+    }
+}
+
 }  // namespace
+
+hipError_t launch_lmm_cache_lookup(const uint8_t* codes, const LmmVariant* vars, uint32_t total, LmmDims dm, uint64_t tag_mask, LmmCache c,
+                                   unsigned long long* row_tag, uint32_t* slot_of, uint32_t* cls, uint32_t* block_cnt, uint32_t* block_off,
+                                   uint32_t* total2, uint8_t* codes2, LmmVariant* vars2, uint32_t* back, hipStream_t st) {
+    // (total2 would stay unwritten; a slot index must fit 31 bits; an empty mask would leave the one tag 1)
+    if (!total || total >= (1u << 31) || dm.bpsp % 4u || !dm.bpsp || c.slots < 64u || c.slots > (1u << 30) || (c.slots & (c.slots - 1u)) ||
+        !tag_mask)
+        return hipErrorInvalidValue;
+    const uint32_t ndc = dm.bpsp / 4, n_blocks = (total + TB - 1) / TB, n_waves = (total + TB / 64 - 1) / (TB / 64);
+    const uint64_t n_words = ((uint64_t)total * ndc + TB - 1) / TB;
+    if (n_words >= (1ull << 31)) return hipErrorInvalidValue;
+    const uint32_t* cw = reinterpret_cast<const uint32_t*>(codes);
+    hipLaunchKernelGGL(lmm_cache_hash_kernel, dim3(n_waves), dim3(TB), 0, st, cw, total, ndc, tag_mask, row_tag);
+    hipLaunchKernelGGL(lmm_cache_claim_kernel, dim3(n_blocks), dim3(TB), 0, st, row_tag, total, c, slot_of);
+    hipLaunchKernelGGL(lmm_cache_publish_kernel, dim3((uint32_t)n_words), dim3(TB), 0, st, cw, total, ndc, slot_of, c);
+    hipLaunchKernelGGL(lmm_cache_classify_kernel, dim3(n_waves), dim3(TB), 0, st, cw, total, ndc, slot_of, c, cls);
+    hipLaunchKernelGGL(lmm_cache_count_kernel, dim3(n_blocks), dim3(TB), 0, st, cls, total, block_cnt);
+    hipLaunchKernelGGL(lmm_table_scan_kernel, dim3(1), dim3(256), 0, st, block_cnt, n_blocks, block_off, total2);
+    hipLaunchKernelGGL(lmm_cache_emit_kernel, dim3(n_blocks), dim3(TB), 0, st, cw, vars, cls, total, ndc, block_off,
+                       reinterpret_cast<uint32_t*>(codes2), vars2, back);
+    return hipGetLastError();
+}
+
+hipError_t launch_lmm_cache_scatter(const double* lrt, const double* lam, const double* p, uint32_t cc, const uint32_t* back,
+                                    const uint32_t* slot_of, const uint32_t* cls, uint32_t total, LmmCache c, double* r_lrt, double* r_lam,
+                                    double* r_p, hipStream_t st) {
+    if (!cc || cc > total) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(lmm_cache_scatter_kernel, dim3((cc + TB - 1) / TB), dim3(TB), 0, st, lrt, lam, p, cc, back, slot_of, cls, total, c,
+                       r_lrt, r_lam, r_p);
+    return hipGetLastError();
+}
+
+hipError_t launch_lmm_cache_fanout(const uint32_t* slot_of, const uint32_t* cls, uint32_t total, LmmCache c, double* r_lrt, double* r_lam,
+                                   double* r_p, hipStream_t st) {
+    if (!total) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(lmm_cache_fanout_kernel, dim3((total + TB - 1) / TB), dim3(TB), 0, st, slot_of, cls, total, c, r_lrt, r_lam, r_p);
+    return hipGetLastError();
+}
 
 hipError_t launch_lmm_table_select(const double* lrt, const double* lam, const double* p, uint32_t cc, uint32_t pb, const LmmVariant* vars,
                                    const uint64_t* row, const uint64_t* kmer, const LmmSelectCol* cols, uint32_t* block_cnt,

@@ -602,20 +602,31 @@ class LmmLrt:
                                            ptr(af), ptr(n_miss), ptr(tested)))
         return {"lrt": lrt, "lambda": lam, "p": p, "logl0": l0, "lambda0": lam0, "af": af, "n_miss": n_miss, "tested": tested.astype(bool)}
 
-    def test_table(self, table: "KmersTable", col, y, min_count: int, maf: float = 0.0, best_n: int = 10001):
+    def test_table(self, table: "KmersTable", col, y, min_count: int, maf: float = 0.0, best_n: int = 10001, max_patterns=None):
         """The exact test of every k-mer of a k-mers table (col: the table column of every individual, in order) and the best
         best_n of them by lrt, ties to the earlier row. A row is tested iff table_to_bed would write it at min_count and test
         would test its .bed row at maf; the numbers have the bits of that route. Returns a dict of numpy arrays in table row
-        order: row, kmer, lrt, lambda, p, af, and the counts rows_read, rows_tested."""
+        order: row, kmer, lrt, lambda, p, af, and the counts rows_read, rows_tested. With max_patterns (>= 64) each distinct
+        presence/absence pattern is tested once and the rows that repeat it take its result from a cache of that many slots
+        (rounded down to a power of two): the same dict, byte for byte, plus `unique`, a dict of the cache's counters (slots,
+        patterns_cached, rows_from_cache, rows_collided, rows_rejected, rows_rotated)."""
         col = np.ascontiguousarray(col, np.uint64)
         row, kmer = np.zeros(best_n, np.uint64), np.zeros(best_n, np.uint64)
         lrt, lam, p, af = (np.zeros(best_n) for _ in range(4))
         kept, n_read, n_tested = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        check(lib.kgwas_lmm_test_table(self._h, ptr(self._y(y)), table._h, ptr(col), len(col), min_count, maf, best_n, ptr(row), ptr(kmer),
-                                       ptr(lrt), ptr(lam), ptr(p), ptr(af), C.byref(kept), C.byref(n_read), C.byref(n_tested)))
+        args = (self._h, ptr(self._y(y)), table._h, ptr(col), len(col), min_count, maf, best_n, ptr(row), ptr(kmer), ptr(lrt), ptr(lam),
+                ptr(p), ptr(af), C.byref(kept), C.byref(n_read), C.byref(n_tested))
+        if max_patterns is None:
+            check(lib.kgwas_lmm_test_table(*args))
+        else:
+            us = capi.LmmUniqueStats()
+            check(lib.kgwas_lmm_test_table_unique(*args, int(max_patterns), C.byref(us)))
         k = kept.value
-        return {"row": row[:k], "kmer": kmer[:k], "lrt": lrt[:k], "lambda": lam[:k], "p": p[:k], "af": af[:k],
-                "rows_read": n_read.value, "rows_tested": n_tested.value}
+        res = {"row": row[:k], "kmer": kmer[:k], "lrt": lrt[:k], "lambda": lam[:k], "p": p[:k], "af": af[:k],
+               "rows_read": n_read.value, "rows_tested": n_tested.value}
+        if max_patterns is not None:
+            res["unique"] = us.as_dict()
+        return res
 
     def test_table_multi(self, table: "KmersTable", col, Y, min_count: int, maf: float = 0.0, best_n: int = 10001):
         """test_table for the P columns Y (P, n) in one pass over the table: the phenotype and its permutations. Returns a dict:

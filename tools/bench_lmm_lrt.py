@@ -21,6 +21,14 @@ and beside them, on the same files, the wall time of the route that needs the PL
 -bfile (files in the page cache, the output of the first removed before every run). Both routes eigendecompose K once per run;
 eigen_ms is printed so that it can be taken off.
 
+--table [ROWS] --distinct F and / or --pattern_cache MIB time the pattern cache of lmm_lrt --kmers_table on that table (the PLINK
+route is left out). With --distinct F the presence words of the rows are drawn from max(1, round(F x ROWS)) distinct synthetic
+patterns: every pattern is there at least once, the other rows take one at random, and all are placed at random (the k-mer words
+stay ascending); F = 1.0 gives a table without a repeated pattern. A warm-up and --reps timed runs of the tool without
+--pattern_cache - the path without the cache - and, with --pattern_cache MIB, as many with it: median, minimum and maximum of the
+wall time and of the kernels' split, the cache's counters from the log, the ratio of the medians, and whether the two outputs have
+the same bytes.
+
 --table [ROWS] --pheno_columns [P] (default 101) times the phenotype and its P - 1 permutations over the same synthetic table,
 --mac 5 -maf 0.05 --best 10001, a warm-up and --reps timed runs of each (median, minimum, maximum of the wall time):
 (a) ONE lmm_lrt --kmers_table --pheno_columns run of the P columns; (b) the way without it, one --kmers_table -n i run per column,
@@ -191,6 +199,85 @@ def bench_table(a):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+def bench_table_cache(a):
+    n, rows = a.individuals, a.table
+    bindir = os.path.join(os.path.dirname(os.path.abspath(kg.__file__)), "bin")
+    rng = np.random.default_rng(20240601)
+    g_rows = 2 * n
+    G = (rng.random((g_rows, n)) < rng.uniform(0.1, 0.9, g_rows)[:, None]).astype(np.float64)
+    K = 1.0 - (G.T @ (1 - G) + (1 - G).T @ G) / g_rows
+    d, U = np.linalg.eigh(K)
+    y = rng.standard_normal(n) + 1.5 * ((U * np.sqrt(np.clip(d, 0, None))) @ rng.standard_normal(n)) + 1.2 * G[7]
+    tmp = tempfile.mkdtemp(prefix="bench_lmm_cache_")
+    try:
+        base = os.path.join(tmp, "t")
+        hdr = np.uint32(0xDDCCBBAA).tobytes() + np.uint64(n).tobytes() + np.uint32(31).tobytes()
+        distinct = rows if a.distinct is None else max(1, min(rows, int(round(a.distinct * rows))))
+        pool = which = None
+        if a.distinct is not None:  # the pool's patterns are the presence words of the first `distinct` synthetic rows
+            pool = np.concatenate([kg.synth_rows_host(r0, min(1_000_000, distinct - r0), n, 20240601)[:, 1:]
+                                   for r0 in range(0, distinct, 1_000_000)])
+            which = rng.permutation(np.concatenate([np.arange(distinct), rng.integers(0, distinct, rows - distinct)]))
+        with open(base + ".table", "wb") as f:
+            f.write(hdr)
+            for r0 in range(0, rows, 1_000_000):
+                part = kg.synth_rows_host(r0, min(1_000_000, rows - r0), n, 20240601)
+                if pool is not None:
+                    part[:, 1:] = pool[which[r0:r0 + len(part)]]
+                part.tofile(f)
+        del pool, which
+        names = ["s%d" % i for i in range(n)]
+        open(base + ".names", "w").write("".join(x + "\n" for x in names))
+        ph = os.path.join(tmp, "ph.tsv")
+        open(ph, "w").write("accession_id\tv\n" + "".join("%s\t%.6f\n" % (x, v) for x, v in zip(names, y)))
+        kin = os.path.join(tmp, "ph.kinship")
+        open(kin, "w").write("\n".join("\t".join("%.17g" % v for v in r) for r in K) + "\n")
+        out = os.path.join(tmp, "out")
+
+        def route(name, extra):
+            t = time.perf_counter()
+            r = subprocess.run([os.path.join(bindir, "lmm_lrt"), "--kmers_table", base, "--kmers_len", "31", "-p", ph, "-lmm", "2", "-k", kin,
+                                "--mac", "5", "-maf", "0.05", "--best", "10001", "-outdir", out, "-o", name,
+                                "--chunk_variants", str(a.chunk_variants)] + extra, capture_output=True, text=True)
+            wall = time.perf_counter() - t
+            if r.returncode != 0:
+                sys.exit("lmm_lrt failed: %s" % r.stderr[-2000:])
+            log = {}
+            for l in open(os.path.join(out, name + ".log.txt")).read().split("\n"):
+                if "\t" in l:
+                    k, v = l.split("\t", 1)
+                    log[k] = v
+                elif l.startswith("ms: "):
+                    log.update((kv.split("=")[0], float(kv.split("=")[1])) for kv in l[4:].split())
+            return dict(wall_s=wall, **log)
+
+        line = {"table_rows": rows, "individuals": n, "distinct_patterns": distinct, "best": 10001, "reps": a.reps}
+        routes = [("table", [])] + ([("cache", ["--pattern_cache", str(a.pattern_cache)])] if a.pattern_cache else [])
+        for name, extra in routes:
+            route(name, extra)  # warm-up
+            runs = [route(name, extra) for _ in range(a.reps)]
+            for k in ("wall_s", "eigen", "rotate", "grid", "refine"):
+                v = sorted(float(r[k]) for r in runs)
+                line["%s_%s" % (name, k if k.endswith("_s") else k + "_ms")] = {"median": round(v[len(v) // 2], 3), "min": round(v[0], 3), "max": round(v[-1], 3)}
+            if name == "table":
+                line["rows_tested"], line["rows_kept"] = int(runs[0]["rows_tested"]), int(runs[0]["rows_kept"])
+            else:
+                line["pattern_cache_mib"] = a.pattern_cache
+                for k in ("pattern_cache_slots", "patterns_cached", "rows_from_cache", "rows_collided", "rows_rejected", "rows_rotated"):
+                    line[k] = int(runs[0][k])
+        same = True
+        if a.pattern_cache:
+            same = open(os.path.join(out, "table.assoc.txt"), "rb").read() == open(os.path.join(out, "cache.assoc.txt"), "rb").read()
+            line["same_bytes"] = bool(same)
+            line["wall_ratio_table_over_cache"] = round(line["table_wall_s"]["median"] / line["cache_wall_s"]["median"], 3)
+            kern = lambda name: sum(line["%s_%s_ms" % (name, k)]["median"] for k in ("rotate", "grid", "refine"))  # noqa: E731
+            line["kernel_ms_ratio_table_over_cache"] = round(kern("table") / max(kern("cache"), 1e-9), 3)
+        print(json.dumps(line))
+        return 0 if same else 1
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
 def bench_table_multi(a):
     n, rows, P = a.individuals, a.table, a.pheno_columns
     bindir = os.path.join(os.path.dirname(os.path.abspath(kg.__file__)), "bin")
@@ -297,8 +384,18 @@ def main():
     ap.add_argument("--pheno_columns", type=int, nargs="?", const=101, default=None,
                     help="with --table: time one --pheno_columns run of P columns (default 101) against P runs of --kmers_table -n i "
                          "(measured on --subset columns and scaled) and against the same run without the device's selection")
+    ap.add_argument("--distinct", type=float, default=None,
+                    help="with --table: the rows' patterns are drawn from F x ROWS distinct ones, placed at random (0 < F <= 1)")
+    ap.add_argument("--pattern_cache", type=int, default=None,
+                    help="with --table: time lmm_lrt --kmers_table with --pattern_cache MIB against the run without it")
     ap.add_argument("--subset", type=int, default=3, help="columns of the --pheno_columns mode's one-run-per-column route that are measured")
     a = ap.parse_args()
+    if a.distinct is not None or a.pattern_cache is not None:
+        if a.table is None or a.pheno_columns is not None:
+            sys.exit("--distinct and --pattern_cache need --table, without --pheno_columns")
+        if a.distinct is not None and not 0 < a.distinct <= 1:
+            sys.exit("--distinct takes a fraction within (0, 1]")
+        sys.exit(bench_table_cache(a))
     if a.pheno_columns is not None:
         if a.table is None:
             sys.exit("--pheno_columns needs --table")
