@@ -56,6 +56,15 @@ class alignas(128) BestHeap {
         }
         return l.score > r.score;
     }
+    static inline int64_t key(const Ent& e) {  // what gt<true> compares
+        int64_t k;
+        memcpy(&k, &e.score, 8);
+        return k;
+    }
+    static inline int64_t pick(bool c, int64_t t, int64_t f) {  // c ? t : f as arithmetic (a select, whatever the compiler thinks of the odds)
+        const int64_t m = -(int64_t)c;
+        return (t & m) | (f & ~m);
+    }
     static inline bool int_comparable(double score) {  // +0 .. +inf
         uint64_t b;
         memcpy(&b, &score, 8);
@@ -182,7 +191,43 @@ class alignas(128) BestHeap {
             // 40 -> 34 ns per push, tools/heap_soa_bench.cpp; in lockstep the extra compare per level costs more).
             bool open = true;
             const bool big = n > BIG_HEAP;
-            while (child < (len - 1) / 2) {
+            // Two levels per load latency. A level of the walk is index -> load -> compare -> select -> next index, and the
+            // array is cache-resident at N = 10001: the walk waits for that chain, thirteen times in a row. The children of
+            // node c are a[2c+1], a[2c+2], its grandchildren a[4c+3 .. 4c+6]: all six addresses depend on c alone, so while
+            // all four grandchildren exist they are loaded together, both sibling pairs of the lower level are compared
+            // beside the upper pair, and the upper compare only selects among the two candidates - one load latency and one
+            // select for two levels. Same child choices (the right one on a tie), the same stop tests at the first and the
+            // second level, the same stores: the array ends up as the one-level walk leaves it; a[4c+6] is inside a[0..len).
+            // EPYC 9575F, a column's record stream at N = 10001: 37.0 -> 28.9 ns per push (tools/heap_one_bench.cpp walk,
+            // both forms alternating; tools/heap_walk_check.cpp: the bounds, under ASan). Heaps that miss the cache keep
+            // the one-level walk: there the prefetches below hide the latency, and the six loads per step only add misses
+            // (N = 10^6: 66 -> 70 ns). In lockstep (replace_top_multi) the K chains already overlap: level at K = 7 (33.6 -> 33.2 ns
+            // per heap, tools/heap_bench.cpp), 34.3 -> 31.5 at K = 4; the groups of a scan are 6-7 wide, so that form is left alone.
+            const int64_t kv = key(value);
+            while (!big && 4 * child + 6 < len) {
+                const Ent* c = a + 2 * child + 1;
+                const Ent* g = a + 4 * child + 3;
+                const int64_t kl = key(c[0]), kr = key(c[1]);
+                const int64_t k0 = key(g[0]), k1 = key(g[1]), k2 = key(g[2]), k3 = key(g[3]);
+                const bool left = kr > kl;
+                const ptrdiff_t dl = 4 * child + 4 - (k1 > k0 ? 1 : 0), dr = 4 * child + 6 - (k3 > k2 ? 1 : 0);
+                const int64_t wl = k1 > k0 ? k0 : k1, wr = k3 > k2 ? k2 : k3;
+                const ptrdiff_t cc = 2 * child + 2 - (left ? 1 : 0);
+                const ptrdiff_t dd = pick(left, dl, dr);
+                if (pick(left, kl, kr) > kv) {
+                    open = false;
+                    break;
+                }
+                a[hole] = a[cc];
+                hole = child = cc;
+                if (pick(left, wl, wr) > kv) {
+                    open = false;
+                    break;
+                }
+                a[hole] = a[dd];
+                hole = child = dd;
+            }
+            while (open && child < (len - 1) / 2) {
                 if (big) prefetch_below(a, child, n);
                 ptrdiff_t cc = 2 * (child + 1);
                 cc -= gt<true>(a[cc], a[cc - 1]) ? 1 : 0;
@@ -494,13 +539,26 @@ class alignas(128) BestHeap {
     }
 
     // std::pop_heap(a, a + n, Greater()) minus the store of the old top into a[n-1] (the caller drops it):
-    // same hole walk and climb as in replace_top.
+    // same hole walk and climb as in replace_top<false>. (The double-compare forms, here and there, keep the one-level
+    // walk: they run on heaps that hold a NaN or a negative score, and nothing measures them.)
     template <bool INT>
     static inline void pop_top(Ent* a, ptrdiff_t n) {
         if (n <= 1) return;
         const Ent value = a[n - 1];
         const ptrdiff_t len = n - 1;
         ptrdiff_t hole = 0, child = 0;
+        if (INT) {  // two levels per load latency, as in replace_top<true> (no stop test here: the hole goes to a leaf)
+            while (4 * child + 6 < len) {  // 26.6 -> 19.6 ns per pop at N = 10001, 72 -> 58 at 10^6 (tools/heap_one_bench.cpp walk)
+                const Ent* c = a + 2 * child + 1;
+                const Ent* g = a + 4 * child + 3;
+                const bool left = key(c[1]) > key(c[0]), left_l = key(g[1]) > key(g[0]), left_r = key(g[3]) > key(g[2]);
+                const ptrdiff_t cc = 2 * child + 2 - (left ? 1 : 0);
+                const ptrdiff_t dd = 2 * cc + 2 - pick(left, left_l, left_r);
+                a[hole] = a[cc];
+                a[cc] = a[dd];
+                hole = child = dd;
+            }
+        }
         while (child < (len - 1) / 2) {
             child = 2 * (child + 1);
             child -= gt<INT>(a[child], a[child - 1]) ? 1 : 0;

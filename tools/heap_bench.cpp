@@ -176,7 +176,10 @@ static inline void replace_pair(Ent* a, Ent* b, ptrdiff_t n, Ent xa, Ent xb) {
 // variants 6,7,8: K = 3, 4, 6 equal-size heaps in lockstep (generic form of replace_pair); 9,10,11,12: K = 5, 7, 8, 2.
 // argv[5]: 1 = prefetch the four grandchildren of the hole before the child is chosen (two levels ahead), 2 = both
 // climbs in lockstep and branch-free per heap. Measured on the EPYC 9575F at K = 6/7: neither beats the plain form
-// (31-35 ns per push either way), identical layouts.
+// (31-35 ns per push either way), identical layouts. 3 = two levels per load latency: while a hole has all four
+// grandchildren, its children and grandchildren are loaded together and the hole moves two levels per round (what heap.h's
+// single-heap walk does; compare the checksums of a run with 0 and a run with 3). EPYC 9575F, 16 threads: K = 4 34.3 ->
+// 31.5 ns per push, K = 7 33.6 -> 33.2 - the K chains overlap already; heap.h's lockstep form is left as it is.
 static int g_pf = 0;
 template <int K>
 static inline void replace_multi(Ent* const* a, ptrdiff_t n, Ent* x) {
@@ -195,7 +198,19 @@ static inline void replace_multi(Ent* const* a, ptrdiff_t n, Ent* x) {
         bool any = false;
 #pragma unroll
         for (int k = 0; k < K; k++) {
-            if (c[k] < lim) {
+            if (g_pf == 3 && 4 * c[k] + 6 < len) {
+                const Ent* ch = a[k] + 2 * c[k] + 1;
+                const Ent* g = a[k] + 4 * c[k] + 3;
+                const bool left = ch[1].score > ch[0].score;
+                const ptrdiff_t dl = 4 * c[k] + 4 - (g[1].score > g[0].score ? 1 : 0), dr = 4 * c[k] + 6 - (g[3].score > g[2].score ? 1 : 0);
+                const ptrdiff_t m = -(ptrdiff_t)left;  // (the select as arithmetic: as ?: it can come out as a branch, a coin flip per round)
+                const ptrdiff_t cc = 2 * c[k] + 2 + m, dd = (dl & m) | (dr & ~m);
+                a[k][h[k]] = a[k][cc];
+                a[k][cc] = a[k][dd];
+                h[k] = dd;
+                c[k] = dd;
+                any = true;
+            } else if (c[k] < lim) {
                 ptrdiff_t cc = 2 * (c[k] + 1);
                 if (g_pf) {
                     const ptrdiff_t g = 4 * c[k] + 3;  // grandchildren 4c+3 .. 4c+6: 64 contiguous bytes
