@@ -237,7 +237,8 @@ typedef struct kgwas_scan_stats {
  * without a new version number, kgwas_lmm_test_table_multi, kgwas_lmm_run_table_multi (lmm_lrt --kmers_table --pheno_columns), and
  * kgwas_lmm_null_reml, kgwas_lmm_test_bed_all, kgwas_lmm_run_files_all, kgwas_lmm_format_assoc4, kgwas_fdist_tail (lmm_lrt -lmm 4),
  * and kgwas_lmm_set_covariates, kgwas_lmm_read_covariates, kgwas_lmm_run_files_cov, kgwas_lmm_run_table_cov (lmm_lrt -c),
- * and struct kgwas_lmm_unique_stats, kgwas_lmm_test_table_unique, kgwas_lmm_run_table_unique (lmm_lrt --pattern_cache).
+ * and struct kgwas_lmm_unique_stats, kgwas_lmm_test_table_unique, kgwas_lmm_run_table_unique (lmm_lrt --pattern_cache),
+ * and struct kgwas_lmm_skip_stats, kgwas_lmm_test_table_multi_skip, kgwas_lmm_run_table_multi_skip (lmm_lrt --pattern_skip).
  * Those came after version 15 without a bump: a caller that may meet an older version-15 library probes for them by symbol
  * (dlsym, or hasattr on a ctypes handle). */
 #define KGWAS_ABI_VERSION 15
@@ -715,6 +716,30 @@ void kgwas_snpkin_close(kgwas_snpkin* h);
  *            many slots as fit, rounded down to a power of two. out_path gets the bytes of the run without the cache; the log gains,
  *            behind its present lines, pattern_cache_slots, patterns_cached, rows_from_cache, rows_collided, rows_rejected and
  *            rows_rotated. cache_mib == 0, or fewer than 64 slots -> KGWAS_ERR_ARG.
+ *
+ * The dead-pattern skip (after ABI version 15, no bump: probe by symbol). In the multi-phenotype table pass a tested row whose
+ * (column, row) pairs were all computed and of which the select kernel shipped none met only full heaps and lay at or below every
+ * column's threshold. A full heap stays full, its worst lrt never falls, and a later row with the same pattern has the same lrt in
+ * every column, bit for bit: it would ship nothing either. Such a pattern is dead.
+ * test_table_multi_skip: test_table_multi that remembers the tested patterns in a hash table on the device (the pattern cache's:
+ *            max_patterns slots rounded down to a power of two, at most 2^30, 16 tries per row, tags of 64 bits) with one state
+ *            word per slot and no results: 16 bytes + the code row (n rounded up to 16, / 4 bytes) each, allocated for the call
+ *            and empty at its start (what ships depends on Y). A row whose pattern was dead when its piece of rows began is left
+ *            out of the rotation, the grid sums, the refinement and the selection; every other tested row is computed, in row
+ *            order, and marks its pattern dead if it shipped no pair. Every output of test_table_multi, *pairs_shipped included,
+ *            is test_table_multi's byte for byte, for any max_patterns, piece size and chunk_variants, also when tags collide or
+ *            the table is full. *u (may be NULL): slots; patterns_cached, the rows that took a new slot; patterns_dead, the slots
+ *            dead at the end; rows_skipped; rows_collided and rows_rejected (computed, and they never mark a pattern); rows_rotated,
+ *            the rows computed. *rows_tested = rows_rotated + rows_skipped counts rows, not rows x columns. With nothing rejected
+ *            the counters are the same in every run. While a column's heap is open (fewer than best_n tested rows so far, or
+ *            KGWAS_LMM_TABLE_SELECT=0) nothing dies and nothing is skipped. max_patterns < 64 -> KGWAS_ERR_ARG before any device
+ *            work, *u and the handle's stats untouched; a handle with covariates is refused as by test_table_multi; the other
+ *            errors are test_table_multi's. Stats as test_table_multi (variants_tested counts a tested row once per column,
+ *            skipped or not); rotate_ms takes the table's kernels. KGWAS_LMM_PATTERN_TAG_BITS as for test_table_unique.
+ * run_table_multi_skip: run_table_multi through test_table_multi_skip with a table of cache_mib MiB: as many slots as fit, rounded
+ *            down to a power of two. The files get the bytes of run_table_multi; every log gains, behind its present lines,
+ *            pattern_skip_slots, patterns_cached, patterns_dead, rows_skipped, rows_collided, rows_rejected and rows_rotated.
+ *            cache_mib == 0, or fewer than 64 slots -> KGWAS_ERR_ARG.
  * ---------------------------------------------------------------------------------- */
 typedef struct kgwas_lmm kgwas_lmm;
 typedef struct kgwas_lmm_stats {
@@ -784,6 +809,18 @@ int kgwas_lmm_run_table_unique(const char* kinship_path, const char* covar_path,
                                const char* pheno_path, uint32_t pheno_col, uint64_t mac, double maf, uint64_t best_n, double lmin,
                                double lmax, uint64_t chunk_variants, int32_t device, const char* out_path, kgwas_lmm_stats* total,
                                uint64_t cache_mib, kgwas_lmm_unique_stats* u);
+typedef struct kgwas_lmm_skip_stats {
+    uint64_t slots, patterns_cached, patterns_dead, rows_skipped, rows_collided, rows_rejected, rows_rotated;
+} kgwas_lmm_skip_stats;
+int kgwas_lmm_test_table_multi_skip(kgwas_lmm* h, uint32_t n_pheno, const double* Y, kgwas_table* t, const uint64_t* col, uint64_t n_acc,
+                                    uint64_t min_count, double maf, uint64_t best_n, uint64_t* row, uint64_t* kmer, double* lrt,
+                                    double* lambda, double* p, double* af, uint64_t* n_kept, double* logl0, double* lambda0,
+                                    uint64_t* rows_read, uint64_t* rows_tested, uint64_t* pairs_shipped, uint64_t max_patterns,
+                                    kgwas_lmm_skip_stats* u);
+int kgwas_lmm_run_table_multi_skip(const char* kinship_path, const char* table_base, uint32_t kmer_len, const char* pheno_path,
+                                   uint32_t n_cols, const uint32_t* pheno_cols, const char* const* out_paths, uint64_t mac, double maf,
+                                   uint64_t best_n, double lmin, double lmax, uint64_t chunk_variants, int32_t device,
+                                   kgwas_lmm_stats* total, uint64_t cache_mib, kgwas_lmm_skip_stats* u);
 
 /* ------------------------------------------------------------------------------------
  * Seeded synthetic table rows: kmer = row + 1, per-row frequency q/256 with

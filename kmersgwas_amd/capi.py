@@ -49,6 +49,7 @@ SYMBOLS = [
     "kgwas_lmm_null_reml", "kgwas_lmm_test_bed_all", "kgwas_lmm_run_files_all", "kgwas_lmm_format_assoc4", "kgwas_fdist_tail",
     "kgwas_lmm_set_covariates", "kgwas_lmm_read_covariates", "kgwas_lmm_run_files_cov", "kgwas_lmm_run_table_cov",
     "kgwas_lmm_test_table_unique", "kgwas_lmm_run_table_unique",
+    "kgwas_lmm_test_table_multi_skip", "kgwas_lmm_run_table_multi_skip",
     "kgwas_synth_rows_device", "kgwas_synth_rows_host",
 ]
 
@@ -114,6 +115,14 @@ class LmmStats(C.Structure):
 
 class LmmUniqueStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("slots", "patterns_cached", "rows_from_cache", "rows_collided", "rows_rejected", "rows_rotated")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class LmmSkipStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("slots", "patterns_cached", "patterns_dead", "rows_skipped", "rows_collided", "rows_rejected",
+                                          "rows_rotated")]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -313,6 +322,9 @@ lib.kgwas_lmm_run_table_cov.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, _u32
 # the pattern cache (--pattern_cache): added after ABI version 15 without a bump
 lib.kgwas_lmm_test_table_unique.argtypes = lib.kgwas_lmm_test_table.argtypes + [_u64, C.POINTER(LmmUniqueStats)]
 lib.kgwas_lmm_run_table_unique.argtypes = lib.kgwas_lmm_run_table_cov.argtypes + [_u64, C.POINTER(LmmUniqueStats)]
+# the dead-pattern skip (--pattern_skip): added after ABI version 15 without a bump
+lib.kgwas_lmm_test_table_multi_skip.argtypes = lib.kgwas_lmm_test_table_multi.argtypes + [_u64, C.POINTER(LmmSkipStats)]
+lib.kgwas_lmm_run_table_multi_skip.argtypes = lib.kgwas_lmm_run_table_multi.argtypes + [_u64, C.POINTER(LmmSkipStats)]
 lib.kgwas_synth_rows_device.argtypes = [_vp, _u64, _u64, _u64, _u64, _vp]
 lib.kgwas_synth_rows_host.argtypes = [_vp, _u64, _u64, _u64, _u64]
 

@@ -18,6 +18,8 @@
 // row per individual (.fam lines, or the accessions of PHENO), whitespace-separated numbers, NA missing, a column of 1s among them.
 // --pattern_cache MIB (with --kmers_table -n, with or without -c) tests each distinct presence/absence pattern once: rows that repeat
 // a pattern take its result from a cache of MIB MiB on the device (kgwas_lmm_run_table_unique). The output's bytes are the same.
+// --pattern_skip MIB (with --kmers_table --pheno_columns) leaves out the rows whose pattern can no longer enter any column's best N:
+// a table of MIB MiB on the device remembers them (kgwas_lmm_run_table_multi_skip). The outputs' bytes are the same.
 #include <sys/stat.h>
 
 #include <cstdlib>
@@ -56,7 +58,7 @@ static void usage(const char* prog) {
             "or, every k-mer of a k-mers table (no PLINK files in between):\n"
             "       " << prog
          << " --kmers_table T --kmers_len K -p PHENO  -lmm 2  -k KINSHIP  [-c COVARIATES] [--mac M] [-maf f] [--best N] [-n i | --pheno_columns LIST]\n"
-            "       [--pattern_cache MIB] [-outdir D] [-o NAME]\n"
+            "       [--pattern_cache MIB | --pattern_skip MIB] [-outdir D] [-o NAME]\n"
             "       [-lmin x] [-lmax x] [--chunk_variants c] [--device d]\n"
             "  --kmers_table T  k-mers table base name (T.table, T.names); excludes -bfile, --bfiles and --columns\n"
             "  --kmers_len K    length of the k-mers (10-31)\n"
@@ -72,6 +74,10 @@ static void usage(const char* prog) {
             "                   repeat it take its result from a cache of MIB MiB of device memory (a whole number >= 1; a slot takes\n"
             "                   40 bytes + a byte per 4 accessions). The output is the same, byte for byte; the log gains the cache's\n"
             "                   counters. Not with --pheno_columns\n"
+            "  --pattern_skip MIB  with --pheno_columns: a presence/absence pattern of which no column kept or could still keep a row is\n"
+            "                   remembered in a table of MIB MiB of device memory (a whole number >= 1; a slot takes 16 bytes + a byte\n"
+            "                   per 4 accessions), and the later rows that repeat it are not computed. The outputs are the same, byte\n"
+            "                   for byte; the logs gain the table's counters. Not with -n (--pattern_cache is the option for one column)\n"
             "  --device d       GPU ordinal (default 0)\n";
 }
 
@@ -156,6 +162,7 @@ static int table_mode(map<string, string>& a, const char* prog) {
     const uint64_t chunk = a.count("chunk_variants") ? whole("--chunk_variants", a["chunk_variants"], 0, 1000000000) : 0;
     const uint64_t device = a.count("device") ? whole("--device", a["device"], 0, 1023) : 0;
     const uint64_t cache_mib = a.count("pattern_cache") ? whole("--pattern_cache", a["pattern_cache"], 1, 1ull << 20) : 0;
+    const uint64_t skip_mib = a.count("pattern_skip") ? whole("--pattern_skip", a["pattern_skip"], 1, 1ull << 20) : 0;
     if (a.count("best") && a["best"].find_first_not_of("0") == string::npos) {
         cerr << "lmm_lrt: --best 0: at least one k-mer must be kept" << endl;
         return 1;
@@ -186,7 +193,11 @@ static int table_mode(map<string, string>& a, const char* prog) {
     for (const string& o : outs) op.push_back(o.c_str());
     kgwas_lmm_stats st{};
     kgwas_lmm_unique_stats us{};
-    const int rc = cache_mib       ? kgwas_lmm_run_table_unique(a["k"].c_str(), a.count("c") ? a["c"].c_str() : nullptr, a["kmers_table"].c_str(),
+    kgwas_lmm_skip_stats ks{};
+    const int rc = skip_mib        ? kgwas_lmm_run_table_multi_skip(a["k"].c_str(), a["kmers_table"].c_str(), (uint32_t)klen, a["p"].c_str(),
+                                                                    (uint32_t)columns.size(), columns.data(), op.data(), mac, maf, best,
+                                                                    lmin, lmax, chunk, (int32_t)device, &st, skip_mib, &ks)
+                   : cache_mib     ? kgwas_lmm_run_table_unique(a["k"].c_str(), a.count("c") ? a["c"].c_str() : nullptr, a["kmers_table"].c_str(),
                                                                 (uint32_t)klen, a["p"].c_str(), (uint32_t)col, mac, maf, best, lmin, lmax, chunk,
                                                                 (int32_t)device, op[0], &st, cache_mib, &us)
                    : a.count("c")  ? kgwas_lmm_run_table_cov(a["k"].c_str(), a["c"].c_str(), a["kmers_table"].c_str(), (uint32_t)klen, a["p"].c_str(),
@@ -203,6 +214,7 @@ static int table_mode(map<string, string>& a, const char* prog) {
     cerr << "[kgwas] lmm_lrt: kmers_table=" << a["kmers_table"] << " columns=" << (columns.empty() ? 1 : columns.size())
          << " individuals=" << st.n_individuals << " rows_read=" << st.variants_read
          << " rows_tested=" << st.variants_tested << (cache_mib ? " rows_rotated=" + to_string(us.rows_rotated) : string())
+         << (skip_mib ? " rows_skipped=" + to_string(ks.rows_skipped) + " rows_rotated=" + to_string(ks.rows_rotated) : string())
          << " best=" << best << " eigendecompositions=" << st.eigendecompositions
          << " ms: eigen=" << st.eigen_ms << " rotate=" << st.rotate_ms << " grid=" << st.grid_ms << " refine=" << st.refine_ms << endl;
     cli_finish();
@@ -212,7 +224,7 @@ static int table_mode(map<string, string>& a, const char* prog) {
 int main(int argc, char* argv[]) {
     static const char* const valued[] = {"bfile", "bfiles", "lmm", "k", "outdir", "o", "n", "maf", "miss", "lmin", "lmax", "chunk_variants", "columns",
                                          "kmers_table", "kmers_len", "p", "mac", "best", "device", "pheno_columns", "c",
-                                         "pattern_cache"};
+                                         "pattern_cache", "pattern_skip"};
     map<string, string> a;
     for (int i = 1; i < argc; i++) {
         string s = argv[i];
@@ -261,8 +273,12 @@ int main(int argc, char* argv[]) {
         cerr << "lmm_lrt: --pattern_cache is not built for --pheno_columns: the cache goes with one phenotype column (-n)" << endl;
         return 1;
     }
+    if (a.count("pattern_skip") && !a.count("pheno_columns")) {  // (before any file is opened)
+        cerr << "lmm_lrt: --pattern_skip goes with --pheno_columns: with one phenotype column (-n) the option is --pattern_cache" << endl;
+        return 1;
+    }
     if (a.count("kmers_table")) return table_mode(a, argv[0]);
-    for (const char* o : {"kmers_len", "p", "mac", "best", "device", "pheno_columns", "pattern_cache"})
+    for (const char* o : {"kmers_len", "p", "mac", "best", "device", "pheno_columns", "pattern_cache", "pattern_skip"})
         if (a.count(o)) {
             cerr << "lmm_lrt: option '" << o << "' needs --kmers_table" << endl;
             return 1;

@@ -11,6 +11,7 @@
 // -c       : run_files and run_table with a covariates file (read_covariates): its rows are checked on the host, subset with
 //            everything else and handed to the session (set_covariates); the log gains two lines.
 // --pattern_cache: run_table with cache_mib > 0 goes through test_table_unique; the same .assoc.txt, six more lines in the log.
+// --pattern_skip: run_table_multi with cache_mib > 0 goes through test_table_multi_skip; the same files, seven more lines in the logs.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -543,7 +544,7 @@ struct TableRun {
 void write_table_result(const std::string& out, const std::vector<TableHit>& kept, const TableRun& r, const char* table_base,
                         uint32_t pheno_col, const char* kinship_path, uint64_t rows_read, uint64_t rows_tested, uint64_t best_n,
                         double lambda0, double l0, const kgwas_lmm_stats& st, double total_ms, const Covariates* cov = nullptr,
-                        const kgwas_lmm_unique_stats* u = nullptr) {
+                        const kgwas_lmm_unique_stats* u = nullptr, const kgwas_lmm_skip_stats* skip = nullptr) {
     std::string text = assoc_header();
     for (const TableHit& k : kept) {
         char km[33];
@@ -561,6 +562,13 @@ void write_table_result(const std::string& out, const std::vector<TableHit>& kep
                  "rows_rotated\t%llu\n",
                  (unsigned long long)u->slots, (unsigned long long)u->patterns_cached, (unsigned long long)u->rows_from_cache,
                  (unsigned long long)u->rows_collided, (unsigned long long)u->rows_rejected, (unsigned long long)u->rows_rotated);
+    if (skip)  // --pattern_skip: seven lines behind the others
+        snprintf(cache_lines, sizeof(cache_lines),
+                 "pattern_skip_slots\t%llu\npatterns_cached\t%llu\npatterns_dead\t%llu\nrows_skipped\t%llu\nrows_collided\t%llu\n"
+                 "rows_rejected\t%llu\nrows_rotated\t%llu\n",
+                 (unsigned long long)skip->slots, (unsigned long long)skip->patterns_cached, (unsigned long long)skip->patterns_dead,
+                 (unsigned long long)skip->rows_skipped, (unsigned long long)skip->rows_collided, (unsigned long long)skip->rows_rejected,
+                 (unsigned long long)skip->rows_rotated);
     const int ll = snprintf(log, sizeof(log),
                             "lmm_lrt: ML likelihood-ratio test (-lmm 2)\nkmers_table\t%s\nphenotypes\t%s\nphenotype_column\t%u\nkinship\t%s\n%s"
                             "individuals_used\t%llu\nmin_count\t%llu\nrows_read\t%llu\nrows_tested\t%llu\nrows_kept\t%llu\nbest_n\t%llu\n"
@@ -623,10 +631,11 @@ void run_table(const char* kinship_path, const char* table_base, uint32_t kmer_l
 
 // The same for n_cols columns of the phenotype file (pheno_cols, from 1) in ONE pass over the table: the files are read once, K is
 // eigendecomposed once, and outs[k] with its log gets what run_table writes for column pheno_cols[k] (the kernels' times are the
-// shared pass's, the same in every column's log).
+// shared pass's, the same in every column's log). With cache_mib > 0 the pass is test_table_multi_skip's with a table of that many
+// MiB: the same bytes in the files, seven more lines in every log, *u the counters.
 void run_table_multi(const char* kinship_path, const char* table_base, uint32_t kmer_len, const char* pheno_path, uint32_t n_cols,
                      const uint32_t* cols, const char* const* outs, uint64_t mac, double maf, uint64_t best_n, double lmin, double lmax,
-                     uint64_t chunk_variants, int device, kgwas_lmm_stats* total) {
+                     uint64_t chunk_variants, int device, kgwas_lmm_stats* total, uint64_t cache_mib = 0, kgwas_lmm_skip_stats* u = nullptr) {
     if (!kinship_path || !table_base || !pheno_path || !cols || !outs) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_run_table_multi: null argument");
     if (!n_cols) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_run_table_multi: no phenotype column given");
     for (uint32_t k = 0; k < n_cols; k++) {
@@ -646,13 +655,20 @@ void run_table_multi(const char* kinship_path, const char* table_base, uint32_t 
     std::vector<std::vector<TableHit>> kept;
     std::vector<double> l0(n_cols), lambda0(n_cols);
     uint64_t rows_read = 0, rows_tested = 0, shipped = 0;
-    test_table_multi(h.get(), n_cols, Y.data(), r.t, r.col.data(), r.S, r.min_count, maf, best_n, kept, l0.data(), lambda0.data(), rows_read,
-                     rows_tested, shipped);
+    kgwas_lmm_skip_stats ks{};
+    if (cache_mib)  // as many slots as the bytes hold (test_table_multi_skip takes a power of two, and refuses fewer than 64)
+        test_table_multi_skip(h.get(), n_cols, Y.data(), r.t, r.col.data(), r.S, r.min_count, maf, best_n,
+                              std::min<uint64_t>(cache_mib, 1ull << 40) * (1ull << 20) / lmm_skip_slot_bytes(h->dm), kept, l0.data(),
+                              lambda0.data(), rows_read, rows_tested, shipped, ks);
+    else
+        test_table_multi(h.get(), n_cols, Y.data(), r.t, r.col.data(), r.S, r.min_count, maf, best_n, kept, l0.data(), lambda0.data(),
+                         rows_read, rows_tested, shipped);
     const double total_ms = now_ms() - t_start;
     for (uint32_t k = 0; k < n_cols; k++)
         write_table_result(outs[k], kept[k], r, table_base, cols[k], kinship_path, rows_read, rows_tested, best_n, lambda0[k], l0[k], h->st,
-                           total_ms);
+                           total_ms, nullptr, nullptr, cache_mib ? &ks : nullptr);
     if (total) *total = h->st;
+    if (u && cache_mib) *u = ks;
 }
 
 }  // namespace
@@ -724,6 +740,17 @@ int kgwas_lmm_run_table_unique(const char* kinship_path, const char* covar_path,
         if (!cache_mib) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_run_table_unique: cache_mib is 0");
         run_table(kinship_path, table_base, kmer_len, pheno_path, pheno_col, mac, maf, best_n, lmin, lmax, chunk_variants, device, out_path,
                   total, covar_path, cache_mib, u);
+    });
+}
+
+int kgwas_lmm_run_table_multi_skip(const char* kinship_path, const char* table_base, uint32_t kmer_len, const char* pheno_path,
+                                   uint32_t n_cols, const uint32_t* pheno_cols, const char* const* out_paths, uint64_t mac, double maf,
+                                   uint64_t best_n, double lmin, double lmax, uint64_t chunk_variants, int32_t device,
+                                   kgwas_lmm_stats* total, uint64_t cache_mib, kgwas_lmm_skip_stats* u) {
+    return guarded([&] {
+        if (!cache_mib) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_run_table_multi_skip: cache_mib is 0");
+        run_table_multi(kinship_path, table_base, kmer_len, pheno_path, n_cols, pheno_cols, out_paths, mac, maf, best_n, lmin, lmax,
+                        chunk_variants, device, total, cache_mib, u);
     });
 }
 

@@ -141,6 +141,10 @@ void test_table_unique(kgwas_lmm* h, const double* y, kgwas_table* t, const uint
 void test_table_multi(kgwas_lmm* h, uint32_t n_pheno, const double* Y, kgwas_table* t, const uint64_t* col, uint64_t n_acc,
                       uint64_t min_count, double maf, uint64_t best_n, std::vector<std::vector<TableHit>>& kept, double* logl0,
                       double* lambda0, uint64_t& rows_read, uint64_t& rows_tested, uint64_t& pairs_shipped);
+void test_table_multi_skip(kgwas_lmm* h, uint32_t n_pheno, const double* Y, kgwas_table* t, const uint64_t* col, uint64_t n_acc,
+                           uint64_t min_count, double maf, uint64_t best_n, uint64_t max_patterns, std::vector<std::vector<TableHit>>& kept,
+                           double* logl0, double* lambda0, uint64_t& rows_read, uint64_t& rows_tested, uint64_t& pairs_shipped,
+                           kgwas_lmm_skip_stats& u);
 // ---- lmm_files.cpp ----
 std::vector<double> read_kinship(const std::string& path, uint64_t n_expected, const char* counted_in = "the .fam");
 // GEMMA's -c file: one row per individual, whitespace-separated numbers, NA missing. values[rows][q]; keep[r] = 0 where row r has an NA

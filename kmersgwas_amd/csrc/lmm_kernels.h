@@ -158,4 +158,33 @@ hipError_t launch_lmm_cache_scatter(const double* lrt, const double* lam, const 
 hipError_t launch_lmm_cache_fanout(const uint32_t* slot_of, const uint32_t* cls, uint32_t total, LmmCache c, double* r_lrt, double* r_lam,
                                    double* r_p, hipStream_t st);
 
+// lmm_table_kernels.hip: the dead-pattern skip of kgwas_lmm_test_table_multi_skip ("The dead-pattern skip"). The
+// table is the pattern cache's without the results (LmmCache with res = nullptr: tag, owner and code row per slot, the same hash,
+// claim and publish kernels) and one state word per slot: 0 live, 1 dead. Before the first piece of a call every tag and state is 0
+// and every owner LMM_CACHE_NO_OWNER; between pieces every owner of a slot in use is 0. A state word only ever goes from 0 to 1.
+enum : uint32_t {                    // what a tested row of a piece is to the skip table, beside LMM_ROW_OWNER, _COLLIDED and _REJECTED
+    LMM_ROW_DEAD = LMM_ROW_CACHED,   //   its code row equals its slot's and the slot was dead when the piece began: not computed
+    LMM_ROW_LIVE = 4                 //   its code row equals its slot's and the slot was live (a new owner's copies too): computed
+};
+inline uint64_t lmm_skip_slot_bytes(LmmDims dm) { return 8 + 4 + 4 + dm.bpsp; }  // tag, owner, state, the code row
+// The look-up of a piece's `total` compacted rows: row_tag, slot_of and cls[t] as above, and every row but the LMM_ROW_DEAD ones
+// compacted in row order with what the back end and the select kernels take: codes2, vars2, row2, kmer2, back[t2] = t, total2[0] =
+// their number. Scratch: block_cnt and block_off [total / LMM_TABLE_BLOCK rounded up]. Every per-row array has room for `total`
+// rows. 0 < total < 2^31.
+hipError_t launch_lmm_skip_lookup(const uint8_t* codes, const LmmVariant* vars, const uint64_t* row, const uint64_t* kmer, uint32_t total,
+                                  LmmDims dm, uint64_t tag_mask, LmmCache c, const uint32_t* state, unsigned long long* row_tag,
+                                  uint32_t* slot_of, uint32_t* cls, uint32_t* block_cnt, uint32_t* block_off, uint32_t* total2,
+                                  uint8_t* codes2, LmmVariant* vars2, uint64_t* row2, uint64_t* kmer2, uint32_t* back, hipStream_t st);
+// After launch_lmm_refine_multi over a sub-chunk of cc rows and a block of pb columns: shipped[v] = 1 where launch_lmm_table_select
+// ships a pair of row v of this block (the same rule on the same cols); the other rows' words are left as they are, so over the
+// blocks of a sub-chunk the words, zero at its start, become "any pair shipped".
+hipError_t launch_lmm_skip_flag(const double* lrt, const LmmSelectCol* cols, uint32_t cc, uint32_t pb, uint32_t* shipped, hipStream_t st);
+// After the last column block of the sub-chunk back[0 .. cc): an owner's or a live row's slot becomes dead where the row shipped no
+// pair, and an owner's slot gets owner 0.
+hipError_t launch_lmm_skip_mark(const uint32_t* shipped, uint32_t cc, const uint32_t* back, const uint32_t* slot_of, const uint32_t* cls,
+                                uint32_t total, LmmCache c, uint32_t* state, hipStream_t st);
+// dead[0] = the number of dead slots. Scratch: block_cnt and block_off [c.slots / LMM_TABLE_BLOCK].
+hipError_t launch_lmm_skip_count_dead(const uint32_t* state, uint32_t slots, uint32_t* block_cnt, uint32_t* block_off, uint32_t* dead,
+                                      hipStream_t st);
+
 }  // namespace kgwas

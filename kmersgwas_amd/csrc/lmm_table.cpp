@@ -6,6 +6,8 @@
 //            rotate, grid and refine then run over them unchanged (lmm.cpp's single_backend). The host keeps the best N by
 //            (lrt, table row);
 // test_table_unique: test_table with a pattern cache on the device (--pattern_cache): a code row met before is not rotated again;
+// test_table_multi_skip: test_table_multi with a table of the patterns that can no longer ship a pair (--pattern_skip): a row with
+//            such a pattern is not computed again;
 // test_table_multi: several phenotype columns against ONE table in one pass (the phenotype and its permutations). The front end and
 //            the rotation run once per row, the xt yt sums and the refinement per block of LMM_PBLOCK columns (lmm.cpp's
 //            multi_front and multi_block), and a select kernel hands the host only the (column, row) pairs that can still enter a
@@ -126,7 +128,7 @@ uint64_t piece_rows(uint64_t n_rows, uint64_t W_f) {
     return std::min(piece, std::max<uint64_t>(n_rows, 1));
 }
 
-// What test_table, test_table_unique and test_table_multi share: the checks, the pieces and the front end. Per piece the rows are squeezed, flagged
+// What test_table, test_table_unique, test_table_multi and test_table_multi_skip share: the checks, the pieces and the front end. Per piece the rows are squeezed, flagged
 // and compacted (lmm_table_kernels.hip). prepare() runs after the checks and before any device work (the null models);
 // per_piece(total, codes, vars, row, kmer) gets a piece's compacted tested rows on the device, total > 0 of them, and is done
 // with them when it returns. `who` starts the messages; a tested row counts `weight` times in the stats' variants_tested.
@@ -348,30 +350,51 @@ void kgwas::lmm::test_table_unique(kgwas_lmm* h, const double* y, kgwas_table* t
     u = us;
 }
 
-// The same for n_pheno columns Y[n_pheno][n] in one pass over the table: the best best_n per column, each with the rows and the
-// bits test_table gives for that column alone. Per sub-chunk the rotation and the grid sums without y run once; per block of
-// LMM_PBLOCK columns the xt yt sums, the refinement and the select kernel, which hands the host only the (column, row) pairs that
-// can still enter the column's heap: all of them while the heap is not full, then those with lrt above the heap's worst as the
-// host knew it before the launch. The heaps still decide; the per-row arrays stay on the device.
-void kgwas::lmm::test_table_multi(kgwas_lmm* h, uint32_t n_pheno, const double* Y, kgwas_table* t, const uint64_t* col, uint64_t n_acc,
-                                  uint64_t min_count, double maf, uint64_t best_n, std::vector<std::vector<TableHit>>& kept,
-                                  double* logl0, double* lambda0, uint64_t& rows_read, uint64_t& rows_tested, uint64_t& pairs_shipped) {
-    const std::string who = "kgwas_lmm_test_table_multi";
-    if (!n_pheno) throw Error(KGWAS_ERR_ARG, who + ": n_pheno is 0");  // (before the table's checks)
-    const uint64_t chunk = h->chunk, cap = (uint64_t)LMM_PBLOCK * chunk;
-    const bool select = opt_int("KGWAS_LMM_TABLE_SELECT", 1) != 0;
-    std::vector<std::vector<TableHit>> heaps(n_pheno);
-    pairs_shipped = 0;
-    auto prepare = [&] {
+namespace {
+
+// What test_table_multi and test_table_multi_skip share: the columns' heaps and the pass of a run of compacted tested rows through
+// the back end and the select stage. Per sub-chunk of at most h->chunk rows the rotation and the grid sums without y run once; per
+// block of LMM_PBLOCK columns the xt yt sums, the refinement and the select kernel, which hands the host only the (column, row)
+// pairs that can still enter the column's heap: all of them while the heap is not full, then those with lrt above the heap's worst
+// as the host knew it before the launch. The heaps still decide; the per-row arrays stay on the device. `hooks` adds launches
+// around that: begin_sub(cc) before a sub-chunk's rotation, after_block(cc, p0, pb) behind a block's select kernels (timed with
+// them; h->d_lrtm and h->d_sel_cols are still the block's) and end_sub(sub, cc) behind the sub-chunk's last block. With `cuts`
+// (ascending, from 0 to total, no step above h->chunk) the sub-chunks are the runs between two cuts, an empty one left out.
+struct MultiPass {
+    kgwas_lmm* h;
+    uint32_t n_pheno;
+    uint64_t best_n;
+    std::string who;
+    bool select = opt_int("KGWAS_LMM_TABLE_SELECT", 1) != 0;
+    std::vector<std::vector<TableHit>> heaps;
+    uint64_t pairs_shipped = 0;
+    struct NoHooks {
+        void begin_sub(uint32_t) {}
+        void after_block(uint32_t, uint32_t, uint32_t) {}
+        void end_sub(uint64_t, uint32_t) {}
+    };
+
+    void prepare(const double* Y, double* logl0, double* lambda0) {
         multi_prepare(h, n_pheno, Y, logl0, lambda0, who.c_str());
         h->ensure_select();
+        heaps.resize(n_pheno);
         for (std::vector<TableHit>& hp : heaps) hp.reserve((size_t)std::min<uint64_t>(best_n, 1u << 14));
-    };
-    auto per_piece = [&](uint32_t total, const uint8_t* d_codes, const LmmVariant* d_vars, const uint64_t* d_row, const uint64_t* d_kmer) {
+    }
+
+    template <class Hooks>
+    void run(uint32_t total, const uint8_t* d_codes, const LmmVariant* d_vars, const uint64_t* d_row, const uint64_t* d_kmer, Hooks& hooks,
+             const std::vector<uint32_t>* cuts = nullptr) {
+        const uint64_t chunk = h->chunk, cap = (uint64_t)LMM_PBLOCK * chunk;
         hipStream_t st = h->stream;
-        for (uint64_t sub = 0; sub < total; sub += chunk) {
-            const uint32_t cc = (uint32_t)std::min<uint64_t>(chunk, total - sub);
+        size_t cut = 0;
+        for (uint64_t sub = 0, end = 0; sub < total; sub = end) {
+            if (cuts && ++cut >= cuts->size()) throw Error(KGWAS_ERR_STATE, who + ": the sub-chunks end before their piece");
+            end = cuts ? (*cuts)[cut] : std::min<uint64_t>(sub + chunk, total);
+            if (end < sub || end - sub > chunk || end > total) throw Error(KGWAS_ERR_STATE, who + ": a sub-chunk outside its piece");
+            if (end == sub) continue;
+            const uint32_t cc = (uint32_t)(end - sub);
             const LmmVariant* vars = d_vars + sub;
+            hooks.begin_sub(cc);
             h->timer.begin(st);
             multi_front(h, d_codes + sub * h->dm.bpsp, vars, cc);
             for (uint32_t p0 = 0; p0 < n_pheno; p0 += LMM_PBLOCK) {
@@ -388,6 +411,7 @@ void kgwas::lmm::test_table_multi(kgwas_lmm* h, uint32_t n_pheno, const double* 
                 multi_block(h, vars, cc, p0, pb);
                 KGWAS_HIP(launch_lmm_table_select(h->d_lrtm.p, h->d_lamm.p, h->d_pm.p, cc, pb, vars, d_row + sub, d_kmer + sub, h->d_sel_cols.p,
                                                   h->d_sel_cnt.p, h->d_sel_off.p, h->d_sel_total.p, h->d_sel_rec.p, (uint32_t)cap, st));
+                hooks.after_block(cc, p0, pb);
                 h->timer.end(&kgwas_lmm_stats::refine_ms, st);  // (the select kernels are timed with the refinement)
                 uint32_t count = 0;
                 KGWAS_HIP(hipMemcpyAsync(&count, h->d_sel_total.p, sizeof(count), hipMemcpyDeviceToHost, st));
@@ -405,12 +429,146 @@ void kgwas::lmm::test_table_multi(kgwas_lmm* h, uint32_t n_pheno, const double* 
                 }
                 pairs_shipped += count;
             }
+            hooks.end_sub(sub, cc);
             h->st.chunks++;
         }
+    }
+
+    void finish(std::vector<std::vector<TableHit>>& kept) {
+        for (std::vector<TableHit>& hp : heaps) sort_by_row(hp);
+        kept.swap(heaps);
+    }
+};
+
+}  // namespace
+
+// The same for n_pheno columns Y[n_pheno][n] in one pass over the table: the best best_n per column, each with the rows and the
+// bits test_table gives for that column alone (MultiPass).
+void kgwas::lmm::test_table_multi(kgwas_lmm* h, uint32_t n_pheno, const double* Y, kgwas_table* t, const uint64_t* col, uint64_t n_acc,
+                                  uint64_t min_count, double maf, uint64_t best_n, std::vector<std::vector<TableHit>>& kept,
+                                  double* logl0, double* lambda0, uint64_t& rows_read, uint64_t& rows_tested, uint64_t& pairs_shipped) {
+    const std::string who = "kgwas_lmm_test_table_multi";
+    if (!n_pheno) throw Error(KGWAS_ERR_ARG, who + ": n_pheno is 0");  // (before the table's checks)
+    MultiPass mp{h, n_pheno, best_n, who};
+    MultiPass::NoHooks none;
+    pairs_shipped = 0;
+    auto prepare = [&] { mp.prepare(Y, logl0, lambda0); };
+    auto per_piece = [&](uint32_t total, const uint8_t* d_codes, const LmmVariant* d_vars, const uint64_t* d_row, const uint64_t* d_kmer) {
+        mp.run(total, d_codes, d_vars, d_row, d_kmer, none);
+        pairs_shipped = mp.pairs_shipped;
     };
     table_pass(h, t, col, n_acc, min_count, maf, best_n, who, n_pheno, prepare, per_piece, rows_read, rows_tested);
-    for (std::vector<TableHit>& hp : heaps) sort_by_row(hp);
-    kept.swap(heaps);
+    mp.finish(kept);
+}
+
+// test_table_multi that skips dead patterns (lmm_table_kernels.hip, "the dead-pattern skip"): a table of at most max_patterns slots
+// (a power of two is taken, at least 64) remembers the code rows met and, per slot, whether an occurrence that went through all
+// n_pheno columns shipped no pair. Such a pattern is dead: the heaps were all full, their worst lrt only rises and equal code rows
+// give equal lrt in every column, so every later occurrence would ship nothing either, and from the next piece on
+// it is left out of the rows that go through MultiPass::run, in test_table_multi's sub-chunks less their dead rows. kept, logl0,
+// lambda0 and pairs_shipped are test_table_multi's, byte for byte. The table lives for this call: what ships depends on Y. u is
+// written only when the call succeeds.
+void kgwas::lmm::test_table_multi_skip(kgwas_lmm* h, uint32_t n_pheno, const double* Y, kgwas_table* t, const uint64_t* col,
+                                       uint64_t n_acc, uint64_t min_count, double maf, uint64_t best_n, uint64_t max_patterns,
+                                       std::vector<std::vector<TableHit>>& kept, double* logl0, double* lambda0, uint64_t& rows_read,
+                                       uint64_t& rows_tested, uint64_t& pairs_shipped, kgwas_lmm_skip_stats& u) {
+    const std::string who = "kgwas_lmm_test_table_multi_skip";
+    if (!n_pheno) throw Error(KGWAS_ERR_ARG, who + ": n_pheno is 0");                        // (before the table's checks)
+    if (max_patterns < 64) throw Error(KGWAS_ERR_ARG, who + ": max_patterns is below 64");  // (before any device work)
+    uint32_t slots = 64;
+    while (slots < (1u << 30) && 2ull * slots <= max_patterns) slots *= 2;
+    const long long tag_bits = opt_int("KGWAS_LMM_PATTERN_TAG_BITS", 64);
+    const uint64_t tag_mask = tag_bits >= 1 && tag_bits < 64 ? (1ull << tag_bits) - 1 : ~0ull;
+    const uint64_t bpsp = h->dm.bpsp;
+    MultiPass mp{h, n_pheno, best_n, who};
+    kgwas_lmm_skip_stats us{};
+    us.slots = slots;
+    pairs_shipped = 0;
+    // the table, and per piece: the rows' tags, slots and classes and the rows to compute; per sub-chunk the rows that shipped a pair
+    DevBuf<unsigned long long> c_tag, d_tag;
+    DevBuf<uint32_t> c_owner, c_key, c_state, d_slot, d_cls, d_back, d_bcnt, d_boff, d_total2, d_shipped;
+    DevBuf<uint8_t> d_codes2;
+    DevBuf<LmmVariant> d_vars2;
+    DevBuf<uint64_t> d_row2, d_kmer2;
+    LmmCache cache{};
+    std::vector<uint32_t> o_cls, cuts;
+    auto prepare = [&] {
+        mp.prepare(Y, logl0, lambda0);
+        uint64_t S_f = 0, n_rows = 0, W_f = 0;
+        uint32_t klen = 0;
+        if (kgwas_table_info(t, &S_f, &n_rows, &W_f, &klen) != KGWAS_OK) throw Error(KGWAS_ERR_ARG, kgwas_last_error());
+        const uint64_t piece = piece_rows(n_rows, W_f);
+        o_cls.resize(piece);
+        c_tag.alloc(slots), c_owner.alloc(slots), c_key.alloc((uint64_t)slots * (bpsp / 4)), c_state.alloc(slots);
+        d_tag.alloc(piece), d_slot.alloc(piece), d_cls.alloc(piece), d_back.alloc(piece);
+        // (the block counts serve the piece's compaction and, at the end, the count of the dead slots)
+        d_bcnt.alloc(std::max<uint64_t>(piece, slots) / LMM_TABLE_BLOCK + 1), d_boff.alloc(d_bcnt.n), d_total2.alloc(1);
+        d_codes2.alloc(piece * bpsp), d_vars2.alloc(piece), d_row2.alloc(piece), d_kmer2.alloc(piece);
+        d_shipped.alloc(h->chunk);
+        cache = LmmCache{c_tag.p, c_owner.p, c_key.p, nullptr, slots};
+        KGWAS_HIP(hipMemsetAsync(c_tag.p, 0, slots * sizeof(unsigned long long), h->stream));
+        KGWAS_HIP(hipMemsetAsync(c_owner.p, 0xFF, slots * sizeof(uint32_t), h->stream));  // LMM_CACHE_NO_OWNER
+        KGWAS_HIP(hipMemsetAsync(c_state.p, 0, slots * sizeof(uint32_t), h->stream));
+    };
+    struct Hooks {
+        kgwas_lmm* h;
+        const LmmCache& cache;
+        uint32_t *shipped, *state, *back, *slot_of, *cls;
+        uint32_t total = 0;  // the piece's tested rows
+        void begin_sub(uint32_t cc) { KGWAS_HIP(hipMemsetAsync(shipped, 0, cc * sizeof(uint32_t), h->stream)); }
+        void after_block(uint32_t cc, uint32_t, uint32_t pb) {
+            KGWAS_HIP(launch_lmm_skip_flag(h->d_lrtm.p, h->d_sel_cols.p, cc, pb, shipped, h->stream));
+        }
+        void end_sub(uint64_t sub, uint32_t cc) {  // (timed with the refinement; collected with the next interval that is)
+            h->timer.begin(h->stream);
+            KGWAS_HIP(launch_lmm_skip_mark(shipped, cc, back + sub, slot_of, cls, total, cache, state, h->stream));
+            h->timer.end(&kgwas_lmm_stats::refine_ms, h->stream);
+        }
+    };
+    auto per_piece = [&](uint32_t total, const uint8_t* d_codes, const LmmVariant* d_vars, const uint64_t* d_row, const uint64_t* d_kmer) {
+        hipStream_t st = h->stream;
+        if (total > d_cls.n) throw Error(KGWAS_ERR_STATE, who + ": a piece has more tested rows than the piece has rows");
+        uint32_t total2 = 0;
+        h->timer.begin(st);  // (the table's kernels are timed with the front end and the rotation)
+        KGWAS_HIP(launch_lmm_skip_lookup(d_codes, d_vars, d_row, d_kmer, total, h->dm, tag_mask, cache, c_state.p, d_tag.p, d_slot.p, d_cls.p,
+                                         d_bcnt.p, d_boff.p, d_total2.p, d_codes2.p, d_vars2.p, d_row2.p, d_kmer2.p, d_back.p, st));
+        h->timer.end(&kgwas_lmm_stats::rotate_ms, st);
+        KGWAS_HIP(hipMemcpyAsync(&total2, d_total2.p, sizeof(total2), hipMemcpyDeviceToHost, st));
+        KGWAS_HIP(hipMemcpyAsync(o_cls.data(), d_cls.p, total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        KGWAS_HIP(hipStreamSynchronize(st));
+        h->timer.collect(h->st);
+        // The sub-chunks are test_table_multi's, cut every h->chunk tested rows, less their dead rows: every computed row meets the
+        // thresholds it meets there, so the pairs shipped are the same ones.
+        uint64_t kinds[5] = {0, 0, 0, 0, 0};
+        cuts.assign(1, 0u);
+        for (uint32_t v = 0; v < total; v++) {
+            if (o_cls[v] > LMM_ROW_LIVE) throw Error(KGWAS_ERR_STATE, who + ": a row of no class");
+            kinds[o_cls[v]]++;
+            if ((v + 1) % h->chunk == 0 || v + 1 == total) cuts.push_back((uint32_t)(v + 1 - kinds[LMM_ROW_DEAD]));
+        }
+        if (total - kinds[LMM_ROW_DEAD] != total2) throw Error(KGWAS_ERR_STATE, who + ": the rows' classes and the rows to compute differ");
+        us.patterns_cached += kinds[LMM_ROW_OWNER];
+        us.rows_skipped += kinds[LMM_ROW_DEAD];
+        us.rows_collided += kinds[LMM_ROW_COLLIDED];
+        us.rows_rejected += kinds[LMM_ROW_REJECTED];
+        us.rows_rotated += total2;
+        Hooks hooks{h, cache, d_shipped.p, c_state.p, d_back.p, d_slot.p, d_cls.p, total};
+        if (total2) mp.run(total2, d_codes2.p, d_vars2.p, d_row2.p, d_kmer2.p, hooks, &cuts);
+        pairs_shipped = mp.pairs_shipped;
+    };
+    table_pass(h, t, col, n_acc, min_count, maf, best_n, who, n_pheno, prepare, per_piece, rows_read, rows_tested);
+    uint32_t dead = 0;
+    hipStream_t st = h->stream;
+    h->timer.begin(st);
+    KGWAS_HIP(launch_lmm_skip_count_dead(c_state.p, slots, d_bcnt.p, d_boff.p, d_total2.p, st));
+    h->timer.end(&kgwas_lmm_stats::rotate_ms, st);
+    KGWAS_HIP(hipMemcpyAsync(&dead, d_total2.p, sizeof(dead), hipMemcpyDeviceToHost, st));
+    KGWAS_HIP(hipStreamSynchronize(st));
+    h->timer.collect(h->st);  // (and the last sub-chunk's mark)
+    if (dead > us.patterns_cached) throw Error(KGWAS_ERR_STATE, who + ": more dead slots than slots in use");
+    us.patterns_dead = dead;
+    mp.finish(kept);
+    u = us;
 }
 
 extern "C" {
@@ -464,6 +622,29 @@ int kgwas_lmm_test_table_multi(kgwas_lmm* h, uint32_t n_pheno, const double* Y, 
         if (rows_read) *rows_read = n_read;
         if (rows_tested) *rows_tested = n_tested;
         if (pairs_shipped) *pairs_shipped = n_shipped;
+    });
+}
+
+int kgwas_lmm_test_table_multi_skip(kgwas_lmm* h, uint32_t n_pheno, const double* Y, kgwas_table* t, const uint64_t* col, uint64_t n_acc,
+                                    uint64_t min_count, double maf, uint64_t best_n, uint64_t* row, uint64_t* kmer, double* lrt,
+                                    double* lambda, double* p, double* af, uint64_t* n_kept, double* logl0, double* lambda0,
+                                    uint64_t* rows_read, uint64_t* rows_tested, uint64_t* pairs_shipped, uint64_t max_patterns,
+                                    kgwas_lmm_skip_stats* u) {
+    return guarded([&] {
+        if (!h || (!Y && n_pheno) || !t || !col) throw Error(KGWAS_ERR_ARG, "kgwas_lmm_test_table_multi_skip: null argument");
+        std::vector<std::vector<TableHit>> kept;
+        uint64_t n_read = 0, n_tested = 0, n_shipped = 0;
+        kgwas_lmm_skip_stats us{};
+        test_table_multi_skip(h, n_pheno, Y, t, col, n_acc, min_count, maf, best_n, max_patterns, kept, logl0, lambda0, n_read, n_tested,
+                              n_shipped, us);
+        for (uint32_t k = 0; k < n_pheno; k++) {
+            copy_hits(kept[k], (uint64_t)k * best_n, row, kmer, lrt, lambda, p, af);
+            if (n_kept) n_kept[k] = kept[k].size();
+        }
+        if (rows_read) *rows_read = n_read;
+        if (rows_tested) *rows_tested = n_tested;
+        if (pairs_shipped) *pairs_shipped = n_shipped;
+        if (u) *u = us;
     });
 }
 

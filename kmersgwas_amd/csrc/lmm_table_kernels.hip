@@ -29,6 +29,15 @@
 //   lmm_cache_count_kernel, lmm_table_scan_kernel, lmm_cache_emit_kernel   the rows to rotate, compacted in row order;
 //   lmm_cache_scatter_kernel   a sub-chunk's results go back to the rows' places and into the owners' slots;
 //   lmm_cache_fanout_kernel    the rows from cache take their slot's result; the piece's new slots get owner 0.
+// And the dead-pattern skip of kgwas_lmm_test_table_multi_skip, on the cache's table without results and a state word per slot:
+//   lmm_cache_hash_kernel, lmm_cache_claim_kernel, lmm_cache_publish_kernel   as above;
+//   lmm_skip_classify_kernel   one wave per row: owner, dead or live (the whole code row equals the slot's; the slot's state as the
+//                              piece found it), collided or rejected;
+//   lmm_cache_count_kernel, lmm_table_scan_kernel, lmm_cache_emit_kernel, lmm_skip_gather_kernel   every row but the dead ones,
+//                              compacted in row order, with its table row index and k-mer word;
+//   lmm_skip_flag_kernel       after a column block's refinement: the rows of which the select kernel ships a pair;
+//   lmm_skip_mark_kernel       after a sub-chunk's last column block: the slot of an owner or live row that shipped nothing is dead;
+//   lmm_skip_count_dead_kernel, lmm_table_scan_kernel   the number of dead slots, once per call.
 // No scalar memory write: every value goes out through a vector store from plain C++. The two atomics of lmm_cache_claim_kernel
 // are the only ones.
 #include "lmm_kernels.h"
@@ -355,7 +364,130 @@ __global__ void __launch_bounds__(TB) lmm_cache_fanout_kernel(const uint32_t* __
     }
 }
 
+// ---- the dead-pattern skip of kgwas_lmm_test_table_multi_skip ("The dead-pattern skip") ----
+// The rules of the pattern cache hold: the table is touched by atomics in lmm_cache_claim_kernel alone, a state word is written by
+// lmm_skip_mark_kernel (only ever the value 1) and read by the classify of the NEXT piece, with kernel boundaries of the one stream
+// between them.
+
+// One wave per row, as lmm_cache_classify_kernel, with the slot's state as it was when the piece began: no kernel between this one
+// and the piece before writes it.
+__global__ void __launch_bounds__(TB) lmm_skip_classify_kernel(const uint32_t* __restrict__ codes, uint32_t total, uint32_t ndc,
+                                                               const uint32_t* __restrict__ slot_of, LmmCache c,
+                                                               const uint32_t* __restrict__ state, uint32_t* __restrict__ cls) {
+    const uint32_t t = blockIdx.x * (TB / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (t >= total) return;  // (wave-uniform, as every branch below)
+    const uint32_t s = slot_of[t];
+    uint32_t kind;
+    if (s >= c.slots) {
+        kind = LMM_ROW_REJECTED;
+    } else if (c.owner[s] == t + 1u) {
+        kind = LMM_ROW_OWNER;
+    } else {
+        uint32_t diff = 0;
+        for (uint32_t j = lane; j < ndc; j += 64) diff |= codes[(uint64_t)t * ndc + j] ^ c.key[(uint64_t)s * ndc + j];
+        kind = __ballot(diff != 0u) ? LMM_ROW_COLLIDED : state[s] != 0u ? LMM_ROW_DEAD : LMM_ROW_LIVE;
+    }
+    if (lane == 0) cls[t] = kind;
+}
+
+// One lane per compacted row: the table row index and the k-mer word follow the row (lmm_cache_emit_kernel left back[v] <= v).
+__global__ void __launch_bounds__(TB) lmm_skip_gather_kernel(const uint32_t* __restrict__ back, const uint32_t* __restrict__ total2,
+                                                             uint32_t total, const uint64_t* __restrict__ row,
+                                                             const uint64_t* __restrict__ kmer, uint64_t* __restrict__ row2,
+                                                             uint64_t* __restrict__ kmer2) {
+    const uint32_t v = blockIdx.x * TB + threadIdx.x;
+    if (v >= total || v >= total2[0]) return;
+    const uint32_t t = back[v];
+    if (t >= total) return;
+    row2[v] = row[t];
+    kmer2[v] = kmer[t];
+}
+
+// One lane per row of the sub-chunk: does lmm_table_select_kernel ship a pair of it in this block of pb columns? The lanes that
+// store all store 1.
+__global__ void __launch_bounds__(TB) lmm_skip_flag_kernel(const double* __restrict__ lrt, const LmmSelectCol* __restrict__ cols,
+                                                           uint32_t cc, uint32_t pb, uint32_t* __restrict__ shipped) {
+    const uint32_t v = blockIdx.x * TB + threadIdx.x;
+    if (v >= cc) return;
+    bool any = false;
+    for (uint32_t k = 0; k < LMM_PBLOCK; k++)
+        if (k < pb) any |= select_survives(lrt, cols, cc, k * cc + v, pb * cc);
+    if (any) shipped[v] = 1u;
+}
+
+// One lane per row of a sub-chunk after its last column block.
+__global__ void __launch_bounds__(TB) lmm_skip_mark_kernel(const uint32_t* __restrict__ shipped, uint32_t cc,
+                                                           const uint32_t* __restrict__ back, const uint32_t* __restrict__ slot_of,
+                                                           const uint32_t* __restrict__ cls, uint32_t total, LmmCache c,
+                                                           uint32_t* __restrict__ state) {
+    const uint32_t v = blockIdx.x * TB + threadIdx.x;
+    if (v >= cc) return;
+    const uint32_t t = back[v];
+    if (t >= total) return;
+    const uint32_t s = slot_of[t], kind = cls[t];
+    if (s >= c.slots || (kind != LMM_ROW_OWNER && kind != LMM_ROW_LIVE)) return;  // (a collided or rejected row has no slot of its own)
+    if (kind == LMM_ROW_OWNER) c.owner[s] = 0u;
+    if (shipped[v] == 0u) state[s] = 1u;
+}
+
+// per block of 256 slots the number of dead ones
+__global__ void __launch_bounds__(TB) lmm_skip_count_dead_kernel(const uint32_t* __restrict__ state, uint32_t slots,
+                                                                 uint32_t* __restrict__ block_cnt) {
+    __shared__ uint32_t s_wave[TB / 64];
+    const uint32_t s = blockIdx.x * TB + threadIdx.x;
+    const bool dead = s < slots && state[s] != 0u;
+    uint32_t n;
+    (void)block_rank(dead, s_wave, n);
+    if (threadIdx.x == 0) block_cnt[blockIdx.x] = n;
+}
+
 }  // namespace
+
+hipError_t launch_lmm_skip_lookup(const uint8_t* codes, const LmmVariant* vars, const uint64_t* row, const uint64_t* kmer, uint32_t total,
+                                  LmmDims dm, uint64_t tag_mask, LmmCache c, const uint32_t* state, unsigned long long* row_tag,
+                                  uint32_t* slot_of, uint32_t* cls, uint32_t* block_cnt, uint32_t* block_off, uint32_t* total2,
+                                  uint8_t* codes2, LmmVariant* vars2, uint64_t* row2, uint64_t* kmer2, uint32_t* back, hipStream_t st) {
+    // (the conditions of launch_lmm_cache_lookup)
+    if (!total || total >= (1u << 31) || dm.bpsp % 4u || !dm.bpsp || c.slots < 64u || c.slots > (1u << 30) || (c.slots & (c.slots - 1u)) ||
+        !tag_mask)
+        return hipErrorInvalidValue;
+    const uint32_t ndc = dm.bpsp / 4, n_blocks = (total + TB - 1) / TB, n_waves = (total + TB / 64 - 1) / (TB / 64);
+    const uint64_t n_words = ((uint64_t)total * ndc + TB - 1) / TB;
+    if (n_words >= (1ull << 31)) return hipErrorInvalidValue;
+    const uint32_t* cw = reinterpret_cast<const uint32_t*>(codes);
+    hipLaunchKernelGGL(lmm_cache_hash_kernel, dim3(n_waves), dim3(TB), 0, st, cw, total, ndc, tag_mask, row_tag);
+    hipLaunchKernelGGL(lmm_cache_claim_kernel, dim3(n_blocks), dim3(TB), 0, st, row_tag, total, c, slot_of);
+    hipLaunchKernelGGL(lmm_cache_publish_kernel, dim3((uint32_t)n_words), dim3(TB), 0, st, cw, total, ndc, slot_of, c);
+    hipLaunchKernelGGL(lmm_skip_classify_kernel, dim3(n_waves), dim3(TB), 0, st, cw, total, ndc, slot_of, c, state, cls);
+    hipLaunchKernelGGL(lmm_cache_count_kernel, dim3(n_blocks), dim3(TB), 0, st, cls, total, block_cnt);  // (every class but LMM_ROW_DEAD)
+    hipLaunchKernelGGL(lmm_table_scan_kernel, dim3(1), dim3(256), 0, st, block_cnt, n_blocks, block_off, total2);
+    hipLaunchKernelGGL(lmm_cache_emit_kernel, dim3(n_blocks), dim3(TB), 0, st, cw, vars, cls, total, ndc, block_off,
+                       reinterpret_cast<uint32_t*>(codes2), vars2, back);
+    hipLaunchKernelGGL(lmm_skip_gather_kernel, dim3(n_blocks), dim3(TB), 0, st, back, total2, total, row, kmer, row2, kmer2);
+    return hipGetLastError();
+}
+
+hipError_t launch_lmm_skip_flag(const double* lrt, const LmmSelectCol* cols, uint32_t cc, uint32_t pb, uint32_t* shipped, hipStream_t st) {
+    if (!cc || !pb || pb > LMM_PBLOCK || (uint64_t)pb * cc >= (1ull << 31)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(lmm_skip_flag_kernel, dim3((cc + TB - 1) / TB), dim3(TB), 0, st, lrt, cols, cc, pb, shipped);
+    return hipGetLastError();
+}
+
+hipError_t launch_lmm_skip_mark(const uint32_t* shipped, uint32_t cc, const uint32_t* back, const uint32_t* slot_of, const uint32_t* cls,
+                                uint32_t total, LmmCache c, uint32_t* state, hipStream_t st) {
+    if (!cc || cc > total) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(lmm_skip_mark_kernel, dim3((cc + TB - 1) / TB), dim3(TB), 0, st, shipped, cc, back, slot_of, cls, total, c, state);
+    return hipGetLastError();
+}
+
+hipError_t launch_lmm_skip_count_dead(const uint32_t* state, uint32_t slots, uint32_t* block_cnt, uint32_t* block_off, uint32_t* dead,
+                                      hipStream_t st) {
+    if (slots < 64u || slots > (1u << 30)) return hipErrorInvalidValue;
+    const uint32_t n_blocks = (slots + TB - 1) / TB;
+    hipLaunchKernelGGL(lmm_skip_count_dead_kernel, dim3(n_blocks), dim3(TB), 0, st, state, slots, block_cnt);
+    hipLaunchKernelGGL(lmm_table_scan_kernel, dim3(1), dim3(256), 0, st, block_cnt, n_blocks, block_off, dead);
+    return hipGetLastError();
+}
 
 hipError_t launch_lmm_cache_lookup(const uint8_t* codes, const LmmVariant* vars, uint32_t total, LmmDims dm, uint64_t tag_mask, LmmCache c,
                                    unsigned long long* row_tag, uint32_t* slot_of, uint32_t* cls, uint32_t* block_cnt, uint32_t* block_off,

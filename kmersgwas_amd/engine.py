@@ -628,11 +628,12 @@ class LmmLrt:
             res["unique"] = us.as_dict()
         return res
 
-    def test_table_multi(self, table: "KmersTable", col, Y, min_count: int, maf: float = 0.0, best_n: int = 10001):
+    def test_table_multi(self, table: "KmersTable", col, Y, min_count: int, maf: float = 0.0, best_n: int = 10001, max_patterns=None):
         """test_table for the P columns Y (P, n) in one pass over the table: the phenotype and its permutations. Returns a dict:
         columns, a list of P dicts shaped like test_table's (each with the rows and the bits test_table(.., Y[k], ..) gives);
         logl0 and lambda0 of shape (P,) with the bits of null(Y[k]); rows_read, rows_tested; and pairs_shipped, the number of
-        (column, row) records the device's selection handed to the host (at most rows_tested * P)."""
+        (column, row) records the device's selection handed to the host (at most rows_tested * P). With max_patterns: see
+        test_table_multi_skip."""
         col = np.ascontiguousarray(col, np.uint64)
         Y = np.ascontiguousarray(Y, np.float64)
         if Y.ndim != 2 or Y.shape[1] != self.n:
@@ -642,16 +643,32 @@ class LmmLrt:
         lrt, lam, p, af = (np.zeros((P, best_n)) for _ in range(4))
         kept, l0, lam0 = np.zeros(P, np.uint64), np.zeros(P), np.zeros(P)
         n_read, n_tested, shipped = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        check(lib.kgwas_lmm_test_table_multi(self._h, P, ptr(Y), table._h, ptr(col), len(col), min_count, maf, best_n, ptr(row), ptr(kmer),
-                                             ptr(lrt), ptr(lam), ptr(p), ptr(af), ptr(kept), ptr(l0), ptr(lam0), C.byref(n_read),
-                                             C.byref(n_tested), C.byref(shipped)))
+        args = (self._h, P, ptr(Y), table._h, ptr(col), len(col), min_count, maf, best_n, ptr(row), ptr(kmer), ptr(lrt), ptr(lam), ptr(p),
+                ptr(af), ptr(kept), ptr(l0), ptr(lam0), C.byref(n_read), C.byref(n_tested), C.byref(shipped))
+        if max_patterns is None:
+            check(lib.kgwas_lmm_test_table_multi(*args))
+        else:
+            ks = capi.LmmSkipStats()
+            check(lib.kgwas_lmm_test_table_multi_skip(*args, int(max_patterns), C.byref(ks)))
         cols = []
         for j in range(P):
             k = int(kept[j])
             cols.append({"row": row[j, :k].copy(), "kmer": kmer[j, :k].copy(), "lrt": lrt[j, :k].copy(), "lambda": lam[j, :k].copy(),
                          "p": p[j, :k].copy(), "af": af[j, :k].copy(), "rows_read": n_read.value, "rows_tested": n_tested.value})
-        return {"columns": cols, "logl0": l0, "lambda0": lam0, "rows_read": n_read.value, "rows_tested": n_tested.value,
-                "pairs_shipped": shipped.value}
+        res = {"columns": cols, "logl0": l0, "lambda0": lam0, "rows_read": n_read.value, "rows_tested": n_tested.value,
+               "pairs_shipped": shipped.value}
+        if max_patterns is not None:
+            res["skip"] = ks.as_dict()
+        return res
+
+    def test_table_multi_skip(self, table: "KmersTable", col, Y, min_count: int, maf: float = 0.0, best_n: int = 10001,
+                              max_patterns: int = 1 << 20):
+        """test_table_multi that leaves out the rows whose presence/absence pattern is dead: an earlier row with it met full heaps
+        in every column and entered none, so no later row with it can. A table of max_patterns slots (>= 64, rounded down to a
+        power of two) on the device remembers the patterns. The same dict, byte for byte, plus `skip`, a dict of the table's
+        counters (slots, patterns_cached, patterns_dead, rows_skipped, rows_collided, rows_rejected, rows_rotated; rows_tested =
+        rows_rotated + rows_skipped)."""
+        return self.test_table_multi(table, col, Y, min_count, maf, best_n, max_patterns=max_patterns)
 
     def stats(self):
         st = capi.LmmStats()

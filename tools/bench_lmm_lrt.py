@@ -36,6 +36,12 @@ measured on --subset columns (default 3: the first, the middle and the last one)
 with KGWAS_LMM_TABLE_SELECT=0, the device's selection switched off. It prints the ratios (b)/(a) and (c)/(a), the kernels' split
 of (a) and (c), and the share of (column, row) pairs the selection handed to the host (from the library, on the same files). The
 outputs of (a) and of the measured columns of (b) are compared byte for byte.
+
+--table [ROWS] --pheno_columns [P] --pattern_skip MIB [--distinct F] [--best N] times the dead-pattern skip of the multi-phenotype
+pass on the table of --distinct (above): a warm-up and --reps timed runs of lmm_lrt --kmers_table --pheno_columns with
+--pattern_skip MIB, and as many without it on the same build - the path without the option. It compares every column's output
+byte for byte (cmp) and prints median, minimum and maximum of the wall time and of the kernels' split, the ratios of the medians
+(kernel time and wall, without over with) and the skip's counters from the log.
 """
 import argparse
 import json
@@ -370,6 +376,87 @@ def bench_table_multi(a):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+def bench_table_multi_skip(a):
+    n, rows, P, best = a.individuals, a.table, a.pheno_columns, a.best
+    bindir = os.path.join(os.path.dirname(os.path.abspath(kg.__file__)), "bin")
+    rng = np.random.default_rng(20240601)
+    g_rows = 2 * n
+    G = (rng.random((g_rows, n)) < rng.uniform(0.1, 0.9, g_rows)[:, None]).astype(np.float64)
+    K = 1.0 - (G.T @ (1 - G) + (1 - G).T @ G) / g_rows
+    d, U = np.linalg.eigh(K)
+    y = rng.standard_normal(n) + 1.5 * ((U * np.sqrt(np.clip(d, 0, None))) @ rng.standard_normal(n)) + 1.2 * G[7]
+    Y = np.stack([y] + [rng.permutation(y) for _ in range(P - 1)])
+    tmp = tempfile.mkdtemp(prefix="bench_lmm_skip_")
+    try:
+        base = os.path.join(tmp, "t")
+        hdr = np.uint32(0xDDCCBBAA).tobytes() + np.uint64(n).tobytes() + np.uint32(31).tobytes()
+        distinct = rows if a.distinct is None else max(1, min(rows, int(round(a.distinct * rows))))
+        pool = which = None
+        if a.distinct is not None:  # as bench_table_cache: the pool's patterns are the presence words of the first `distinct` synthetic rows
+            pool = np.concatenate([kg.synth_rows_host(r0, min(1_000_000, distinct - r0), n, 20240601)[:, 1:]
+                                   for r0 in range(0, distinct, 1_000_000)])
+            which = rng.permutation(np.concatenate([np.arange(distinct), rng.integers(0, distinct, rows - distinct)]))
+        with open(base + ".table", "wb") as f:
+            f.write(hdr)
+            for r0 in range(0, rows, 1_000_000):
+                part = kg.synth_rows_host(r0, min(1_000_000, rows - r0), n, 20240601)
+                if pool is not None:
+                    part[:, 1:] = pool[which[r0:r0 + len(part)]]
+                part.tofile(f)
+        del pool, which
+        names = ["s%d" % i for i in range(n)]
+        open(base + ".names", "w").write("".join(x + "\n" for x in names))
+        ph = os.path.join(tmp, "ph.tsv")
+        open(ph, "w").write("accession_id\t" + "\t".join("P%d" % k for k in range(P)) + "\n"
+                            + "".join(names[i] + "".join("\t%.6f" % Y[k, i] for k in range(P)) + "\n" for i in range(n)))
+        kin = os.path.join(tmp, "ph.kinship")
+        open(kin, "w").write("\n".join("\t".join("%.17g" % v for v in r) for r in K) + "\n")
+        lst = os.path.join(tmp, "cols.txt")
+        open(lst, "w").write("".join("%d\tP%d\n" % (k + 1, k) for k in range(P)))
+        common = [os.path.join(bindir, "lmm_lrt"), "--kmers_table", base, "--kmers_len", "31", "-p", ph, "-lmm", "2", "-k", kin, "--mac", "5",
+                  "-maf", "0.05", "--best", str(best), "--chunk_variants", str(a.chunk_variants), "--pheno_columns", lst]
+
+        def route(name, extra):
+            outdir = os.path.join(tmp, name)
+            t = time.perf_counter()
+            r = subprocess.run(common + ["-outdir", outdir] + extra, capture_output=True, text=True)
+            wall = time.perf_counter() - t
+            if r.returncode != 0:
+                sys.exit("lmm_lrt failed: %s" % r.stderr[-2000:])
+            print("%s: %.1f s" % (name, wall), file=sys.stderr, flush=True)
+            log = {}
+            for l in open(os.path.join(outdir, "P0.log.txt")).read().split("\n"):
+                if "\t" in l:
+                    k, v = l.split("\t", 1)
+                    log[k] = v
+                elif l.startswith("ms: "):
+                    log.update((kv.split("=")[0], float(kv.split("=")[1])) for kv in l[4:].split())
+            return dict(wall_s=wall, **log)
+
+        line = {"table_rows": rows, "individuals": n, "columns": P, "distinct_patterns": distinct, "best": best, "reps": a.reps,
+                "pattern_skip_mib": a.pattern_skip}
+        for name, extra in (("skip", ["--pattern_skip", str(a.pattern_skip)]), ("plain", [])):
+            route(name, extra)  # warm-up
+            runs = [route(name, extra) for _ in range(a.reps)]
+            for k in ("wall_s", "eigen", "rotate", "grid", "refine"):
+                v = sorted(float(r[k]) for r in runs)
+                line["%s_%s" % (name, k if k.endswith("_s") else k + "_ms")] = {"median": round(v[len(v) // 2], 3), "min": round(v[0], 3), "max": round(v[-1], 3)}
+            if name == "skip":
+                line["rows_tested"] = int(runs[0]["rows_tested"])
+                for k in ("pattern_skip_slots", "patterns_cached", "patterns_dead", "rows_skipped", "rows_collided", "rows_rejected", "rows_rotated"):
+                    line[k] = int(runs[0][k])
+        same = all(subprocess.run(["cmp", "-s", os.path.join(tmp, "skip", "P%d.assoc.txt" % k), os.path.join(tmp, "plain", "P%d.assoc.txt" % k)]).returncode == 0
+                   for k in range(P))
+        line["same_bytes"] = bool(same)
+        kern = lambda name: sum(line["%s_%s_ms" % (name, k)]["median"] for k in ("rotate", "grid", "refine"))  # noqa: E731
+        line["kernel_ms_ratio_plain_over_skip"] = round(kern("plain") / max(kern("skip"), 1e-9), 3)
+        line["wall_ratio_plain_over_skip"] = round(line["plain_wall_s"]["median"] / line["skip_wall_s"]["median"], 3)
+        print(json.dumps(line))
+        return 0 if same else 1
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--beds", type=int, default=101)
@@ -388,8 +475,17 @@ def main():
                     help="with --table: the rows' patterns are drawn from F x ROWS distinct ones, placed at random (0 < F <= 1)")
     ap.add_argument("--pattern_cache", type=int, default=None,
                     help="with --table: time lmm_lrt --kmers_table with --pattern_cache MIB against the run without it")
+    ap.add_argument("--pattern_skip", type=int, default=None,
+                    help="with --table --pheno_columns: time the run with --pattern_skip MIB against the run without it (--distinct and --best apply)")
+    ap.add_argument("--best", type=int, default=10001, help="--best of the --pattern_skip mode's runs (default 10001)")
     ap.add_argument("--subset", type=int, default=3, help="columns of the --pheno_columns mode's one-run-per-column route that are measured")
     a = ap.parse_args()
+    if a.pattern_skip is not None:
+        if a.table is None or a.pheno_columns is None or a.pattern_cache is not None:
+            sys.exit("--pattern_skip needs --table and --pheno_columns, without --pattern_cache")
+        if a.distinct is not None and not 0 < a.distinct <= 1:
+            sys.exit("--distinct takes a fraction within (0, 1]")
+        sys.exit(bench_table_multi_skip(a))
     if a.distinct is not None or a.pattern_cache is not None:
         if a.table is None or a.pheno_columns is not None:
             sys.exit("--distinct and --pattern_cache need --table, without --pheno_columns")
