@@ -823,6 +823,45 @@ int kgwas_lmm_run_table_multi_skip(const char* kinship_path, const char* table_b
                                    kgwas_lmm_stats* total, uint64_t cache_mib, kgwas_lmm_skip_stats* u);
 
 /* ------------------------------------------------------------------------------------
+ * clump_kmers: the k-mers of an association file grouped by linkage disequilibrium, the r^2 between two presence/absence
+ * patterns - how many independent signals a list of hits holds. A tool of this project's own (the reference stops at the
+ * list). For k-mers a, b over the n accessions in use, with presence counts ca, cb and n11 accessions that have both,
+ *     num = (n n11 - ca cb)^2,  den = ca (n - ca) cb (n - cb),  r^2 = num / den;
+ * the pair is LINKED iff den > 0 and num * 1000000 >= r2_millionths * den, decided in 128-bit integers on the device: no
+ * rounding anywhere. A constant row (den = 0) is linked to nothing.
+ *
+ * kgwas_r2_millionths: the threshold's decimal text ("0.8", "1", ".25") -> integer millionths, read digit by digit, never
+ * through a double; KGWAS_ERR_ARG unless it has at most 6 digits after the point and 0 < t <= 1.
+ * kgwas_kmers_ld: bits[n_kmers][words_per_row], bit i of a row = accession i (bits at or past n_acc are ignored) ->
+ * adj[n_kmers][ceil(n_kmers / 32)], the upper triangle of the link matrix: adj[a][b / 32] bit b % 32 is 1 iff b > a and the
+ * pair is linked; the diagonal and the lower triangle are zero. n1[n_kmers] (may be NULL) gets the presence counts. The counts
+ * n11 come from the matrix cores (block-scaled FP4 MFMA, float32 accumulation: exact) and never leave the registers. The
+ * matrix is produced in blocks of tile_rows consecutive rows a (rounded up to a multiple of 64; 0: the library picks as many as
+ * make a block of at most 256 MiB), a block's copy back overlapping the next block's kernel. Checked before any device call
+ * (KGWAS_ERR_ARG): null bits or adj, n_acc of 0 or above 8192 (the predicate's integers are sized for that), words_per_row
+ * below ceil(n_acc / 64), r2_millionths of 0 or above 1000000, n_kmers above 2^20.
+ * kgwas_clump_kmers_run: the tool. assoc_path is an lmm_lrt or GEMMA .assoc.txt: the columns `rs` (the k-mer's letters) and
+ * `p_lrt` are found by their names in the header. Refused by name (KGWAS_ERR_FORMAT): an rs of another length than kmer_len or
+ * with an illegal letter, a k-mer given twice, a line with too few fields, a p that is not a number - all before the table is
+ * opened. The hits with p <= p_max (+inf: all) are taken in p order, ties in file order; their rows come from the table
+ * <table_base>.table by kgwas_filter_kmers' search (a hit the table lacks is an error that names it), squeezed to the
+ * accessions of pheno_path in its order (NULL: every accession of the table). Clumping: rows are walked in p order, a row no
+ * lead has taken becomes a lead and takes every later row linked to it and not yet taken. out_path gets a header and one line
+ * per used hit in the file's order: rs, p_lrt (the field's own text), clump (from 1, in lead order), lead (its rs), r2 against
+ * the lead (%.6f; 1.000000 for a lead, nan for a constant row, which is a lead alone), n1, n11 (accessions shared with the
+ * lead); out_path + ".log.txt" the inputs and the counters. *st (may be NULL) is written when the call succeeds.
+ * ---------------------------------------------------------------------------------- */
+typedef struct kgwas_clump_stats {
+    uint64_t hits_read, hits_used, clumps, largest_clump, linked_pairs, accessions;
+    double search_ms, ld_ms, clump_ms; /* the table search, the LD kernels (events around them), the host's clump pass */
+} kgwas_clump_stats;
+int kgwas_r2_millionths(const char* text, uint32_t* r2_millionths);
+int kgwas_kmers_ld(const uint64_t* bits, uint64_t n_kmers, uint64_t words_per_row, uint64_t n_acc, uint32_t r2_millionths, int32_t device,
+                   uint64_t tile_rows, uint32_t* adj, uint32_t* n1);
+int kgwas_clump_kmers_run(const char* table_base, uint32_t kmer_len, const char* pheno_path, const char* assoc_path, uint32_t r2_millionths,
+                          double p_max, int32_t device, uint64_t tile_rows, const char* out_path, kgwas_clump_stats* st);
+
+/* ------------------------------------------------------------------------------------
  * Seeded synthetic table rows: kmer = row + 1, per-row frequency q/256 with
  * q in [5, 250], bits from a counter-based generator, so any shard can be produced on its GPU.
  * The host variant is the bit-identical twin used to write small .table files for the CLIs.

@@ -50,6 +50,7 @@ SYMBOLS = [
     "kgwas_lmm_set_covariates", "kgwas_lmm_read_covariates", "kgwas_lmm_run_files_cov", "kgwas_lmm_run_table_cov",
     "kgwas_lmm_test_table_unique", "kgwas_lmm_run_table_unique",
     "kgwas_lmm_test_table_multi_skip", "kgwas_lmm_run_table_multi_skip",
+    "kgwas_r2_millionths", "kgwas_kmers_ld", "kgwas_clump_kmers_run",
     "kgwas_synth_rows_device", "kgwas_synth_rows_host",
 ]
 
@@ -59,6 +60,13 @@ class KgwasError(RuntimeError):
         super().__init__("libkgwas error %d: %s" % (code, msg))
         self.code = code
         self.msg = msg
+
+
+class ClumpStats(C.Structure):
+    """kgwas_clump_stats"""
+    _fields_ = [("hits_read", C.c_uint64), ("hits_used", C.c_uint64), ("clumps", C.c_uint64), ("largest_clump", C.c_uint64),
+                ("linked_pairs", C.c_uint64), ("accessions", C.c_uint64), ("search_ms", C.c_double), ("ld_ms", C.c_double),
+                ("clump_ms", C.c_double)]
 
 
 class ScanParams(C.Structure):
@@ -279,6 +287,9 @@ lib.kgwas_table_to_bed.argtypes = [_vp, _vp, _u64, _pstr, _vp, _u64, _u64, C.c_i
 lib.kgwas_kmer_encode.argtypes = [C.c_char_p, _u64, _pu64]
 lib.kgwas_filter_kmers.argtypes = [_vp, _vp, _u64, _i32, _vp, _vp, _pu64]
 lib.kgwas_filter_kmers_write.argtypes = [_vp, _vp, _u64, _i32, C.c_char_p, _pu64]
+lib.kgwas_r2_millionths.argtypes = [C.c_char_p, C.POINTER(C.c_uint32)]
+lib.kgwas_kmers_ld.argtypes = [_vp, _u64, _u64, _u64, _u32, _i32, _u64, _vp, _vp]
+lib.kgwas_clump_kmers_run.argtypes = [C.c_char_p, _u32, C.c_char_p, C.c_char_p, _u32, C.c_double, _i32, _u64, C.c_char_p, C.POINTER(ClumpStats)]
 lib.kgwas_build_table.argtypes = [C.c_char_p, _pstr, _pstr, _u64, _u32, _i32, C.c_char_p, _pu64]
 lib.kgwas_list_kmers.argtypes = [_pstr, _u64, _u32, _u64, C.c_double, _i32, C.c_char_p, _pu64]
 lib.kgwas_count_kmers_files.argtypes = [_pstr, _u64, _u32, _u64, _u64, _i32, C.c_char_p, _pu64]

@@ -393,4 +393,17 @@ size_t kin_gram_scratch_bytes(uint32_t S_pad);
 hipError_t launch_kin_gram(const uint32_t* T, uint64_t n_rw, uint32_t S_pad, unsigned long long* H, void* scratch, size_t scratch_bytes,
                            hipStream_t st);
 
+// clump_kmers (ld_kernels.hip): which pairs of presence/absence rows have r^2 >= tm / 10^6, decided in integers.
+//  prep: rows[N][stride_w] (words 0..W-1 of a row are its bits, bit i = accession i) -> P[n_chunks][N_pad] 16-byte chunks of 128
+//        accessions (bits at or past n and rows at or past N zero), n1[N_pad] the counts, pq[N_pad] = n1 (n - n1), tq[N_pad] = tm pq.
+//        N_pad is a multiple of 128 >= N, n_chunks a multiple of 4 >= ceil(n / 128), n <= 8192, tm <= 10^6.
+//  link: rows a of [row0, row0 + n_rows), row0 a multiple of 64, against every row b: out[(a - row0) * pitch_dw + b / 32] bit b % 32
+//        = (b > a and the pair is linked). out holds ceil(n_rows / 64) * 64 rows of pitch_dw dwords, pitch_dw a multiple of 4 with
+//        32 pitch_dw >= N_pad; every dword of it is written. popcount = true: n11 from the vector ALU instead of the matrix cores
+//        (the ablation; the same bits).
+hipError_t launch_ld_prep(const uint64_t* rows, uint64_t stride_w, uint64_t W, uint64_t N, uint32_t n, uint32_t n_chunks, uint64_t N_pad,
+                          uint32_t tm, void* P, uint32_t* n1, uint32_t* pq, uint64_t* tq, hipStream_t st);
+hipError_t launch_ld_link(const void* P, const uint32_t* n1, const uint32_t* pq, const uint64_t* tq, uint64_t N, uint64_t N_pad, uint32_t n,
+                          uint32_t n_chunks, uint64_t row0, uint64_t n_rows, uint32_t* out, uint64_t pitch_dw, bool popcount, hipStream_t st);
+
 }  // namespace kgwas

@@ -24,47 +24,12 @@
 
 #include <algorithm>
 
+#include "fp4_bits.h"  // kin_expand_step: the FP4 operand of an MFMA step from plane dwords (shared with ld_kernels.hip)
 #include "kernels.h"
-
-#ifndef KGWAS_KIN_ABLATE
-#define KGWAS_KIN_ABLATE 0
-#endif
 
 namespace kgwas {
 
-typedef int kin_i32x4 __attribute__((ext_vector_type(4)));
-typedef int kin_i32x8 __attribute__((ext_vector_type(8)));
-typedef float kin_f32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
-
-// FP4 operand of MFMA step j = 0..3 from four plane dwords (128 rows of one sample): nibble e of operand dword q is
-// bit 4e + j of plane dword q, i.e. k-element 8q + e <-> row 32q + 4e + j of the lane's 128 (A and B operands use the
-// same map, so the k index pairs a row with itself). Steps 0..2 are one AND per dword (values 0.5, 1, 2: the block
-// scale 2^(1-j) makes them 1), step 3 moves the FP4 sign bit down first (value 2, scale 2^-1).
-__device__ __forceinline__ kin_i32x8 kin_expand_step(const uint4& w, int j) {
-    kin_i32x8 r = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (KGWAS_KIN_ABLATE & 32) {  // experiments: no expansion work
-        r[0] = (int)w.x;
-        r[1] = (int)w.y;
-        r[2] = (int)w.z;
-        r[3] = (int)w.w;
-        return r;
-    }
-    if (j < 3) {
-        const uint32_t mk = 0x11111111u << j;
-        r[0] = (int)(w.x & mk);
-        r[1] = (int)(w.y & mk);
-        r[2] = (int)(w.z & mk);
-        r[3] = (int)(w.w & mk);
-    } else {
-        r[0] = (int)((w.x >> 1) & 0x44444444u);
-        r[1] = (int)((w.y >> 1) & 0x44444444u);
-        r[2] = (int)((w.z >> 1) & 0x44444444u);
-        r[3] = (int)((w.w >> 1) & 0x44444444u);
-    }
-    return r;
-}
 
 // x of lane (lane ^ J) for J = 1, 2, 4, 8 as DPP moves (vector-ALU operand modifiers: no trip through the LDS
 // crossbar that __shfl_xor's ds_bpermute takes): quad permutes for 1 and 2; for 4 and 8 a row shift left into the

@@ -10,6 +10,7 @@ Names follow the reference's classes (src/kmers_multiple_databases.h, src/best_a
   SnpKinship            <- emma_kinship (the kinship of a PLINK SNP matrix)          (f-5)
   filter_kmers          <- filter_kmers (rows of listed k-mers)                       (f-6)
   build_kmers_table     <- build_kmers_table (the table from sorted k-mer files)      (f-7)
+  kmers_ld              -- this project's own: exact r^2 links between k-mers (clump_kmers)
 
 Everything numeric happens inside libkgwas (HIP kernels on the GPU + the std::priority_queue
 replay); this module only moves buffers.
@@ -777,6 +778,30 @@ def filter_kmers(table: KmersTable, codes, device: int = 0):
     m = C.c_uint64(0)
     check(lib.kgwas_filter_kmers(table._h, ptr(codes), len(codes), device, ptr(file_rows), ptr(rows), C.byref(m)))
     return file_rows[:m.value].copy(), rows[:m.value].copy()
+
+
+def r2_millionths(r2) -> int:
+    """The r2 threshold as integer millionths. Text ("0.8") is read digit by digit by the library; a number goes through its
+    shortest decimal text (repr), so 0.8 is 800000 and never 799999."""
+    text = r2 if isinstance(r2, str) else np.format_float_positional(float(r2), trim="-")
+    out = C.c_uint32(0)
+    check(lib.kgwas_r2_millionths(text.encode(), C.byref(out)))
+    return out.value
+
+
+def kmers_ld(bits, n_acc: int, r2, tile_rows: int = 0, device: int = 0):
+    """Which pairs of presence/absence rows have r^2 >= r2, exactly (kgwas_kmers_ld: the counts of common accessions on the
+    matrix cores, the decision in 128-bit integers). bits: uint64[n_kmers, words], bit i of a row = accession i; bits at or
+    past n_acc are ignored. Returns (adj uint32[n_kmers, ceil(n_kmers / 32)], n1 uint32[n_kmers]): adj[a, b // 32] bit b % 32
+    is set iff b > a and the pair is linked - the upper triangle; the rest is zero."""
+    bits = np.ascontiguousarray(bits, np.uint64)
+    if bits.ndim != 2:
+        raise ValueError("bits must be a 2-d array of uint64 words")
+    n_kmers, words = bits.shape
+    adj = np.zeros((n_kmers, (n_kmers + 31) // 32), np.uint32)
+    n1 = np.zeros(n_kmers, np.uint32)
+    check(lib.kgwas_kmers_ld(ptr(bits), n_kmers, words, n_acc, r2_millionths(r2), device, tile_rows, ptr(adj), ptr(n1)))
+    return adj, n1
 
 
 def filter_kmers_write(path: str, table: KmersTable, codes, device: int = 0) -> int:
