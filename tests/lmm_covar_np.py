@@ -215,3 +215,80 @@ def phenotype(y, W, seed=1):
     Q, _ = orthonormal(W)
     out = y + (Q[:, 1:] * np.sqrt(W.shape[0])) @ rng.uniform(0.5, 1.5, W.shape[1] - 1) if W.shape[1] > 1 else y.copy()
     return out
+
+
+# ---- the fixtures of test_gpu_lmm_lrt_covar_widths.py (test_lmm_covar_model.py qualifies each without a GPU) ----
+
+@functools.lru_cache(maxsize=None)
+def eigen_q(n, rows, q):
+    """[1, the q - 1 leading eigenvectors of fixture(n, rows, .)'s K]: population structure as covariates. Wt is near unit vectors,
+    and the diagonal of A = Wt^T H Wt runs from 1 down to 1 / (lambda d_max + 1). q = 3 is the form "eigen"."""
+    _, K, _ = M.fixture(n, rows, 3.0)
+    d, U = M.eig_of(K)
+    W = np.ascontiguousarray(np.column_stack([np.ones(n)] + [U[:, -1 - j] for j in range(q - 1)]))
+    W.setflags(write=False)
+    return W
+
+
+def _recombine_q8():
+    """A fixed, badly scaled 8 x 8 matrix: standard normals (seeded) with columns scaled from 1e-2 to 1e2. Its condition number is
+    asserted by test_lmm_covar_model.py to lie in [1e4, 1e6], far from the tool's rank refusal at 1e-8."""
+    A = np.random.default_rng([8, 31, 7]).standard_normal((8, 8)) * 10.0 ** np.linspace(-2.0, 2.0, 8)[None, :]
+    A.setflags(write=False)
+    return A
+
+
+RECOMBINE_Q8 = _recombine_q8()
+
+
+@functools.lru_cache(maxsize=None)
+def recombined_q8(n, rows):
+    """width(n, rows, 8) times RECOMBINE_Q8: the same column space in a basis that is neither orthogonal nor scaled"""
+    W = np.ascontiguousarray(width(n, rows, 8) @ RECOMBINE_Q8)
+    W.setflags(write=False)
+    return W
+
+
+# (n, seed, q): two_peak_fixture(n, seed) with q - 1 normal covariates beside the intercept. (16, 148) at q = 3 and (16, 69) are
+# left out: models R and E differ by 2.2e-10 and 3.5e-9 there.
+TWO_PEAK_W_CASES = ((67, 54, 2), (67, 54, 3), (67, 56, 2), (67, 56, 3), (8, 18, 2), (8, 18, 3), (16, 148, 2))
+
+
+@functools.lru_cache(maxsize=None)
+def two_peak_case(n, seed, q):
+    """(K, y, W, V): lmm_lrt_np.two_peak_fixture's K and y (y as it is: phenotype() would flatten the structure), W = [1, q - 1
+    standard normals], V = the fixture's first 16 presence rows (the dosages are 2 V)."""
+    K, y, X = M.two_peak_fixture(n, seed, M.two_peak_rows(n))
+    V = X[:16]
+    assert len(V) == 16
+    W = np.column_stack([np.ones(n), np.random.default_rng([n, seed, q]).standard_normal((n, q - 1))])
+    W.setflags(write=False)
+    return K, y, W, V
+
+
+def interior_maxima(K, y, C, reml=False):
+    """The interior local maxima of model R's l (reml: model R''s lR) of the design C on the 2001-point grid: [(log lambda, l)]"""
+    d, U = M.eig_of(K)
+    t = np.linspace(np.log(M.LMIN), np.log(M.LMAX), M.GRID + 1)
+    v = (WN._reml_R_fast if reml else M._loglik_R_fast)(d, U.T @ y, U.T @ C, np.exp(t))
+    return [(float(t[i]), float(v[i])) for i in range(1, M.GRID) if v[i] > v[i - 1] and v[i] >= v[i + 1]]
+
+
+SPAN_ROWS = 40                 # with chunk_variants 32: a chunk boundary
+SPAN_DEGENERATE = (5, 11, 35)  # b, 1 - b, and b again behind the chunk boundary
+
+
+@functools.lru_cache(maxsize=None)
+def span_panel(n, rows):
+    """(K, y0, V, b): 40 presence rows over fixture(n, rows, 3.0), 37 ordinary ones and, at SPAN_DEGENERATE, the batch covariate b
+    of covariates(n, rows, "batch"), 1 - b and b again: with W = [1, b] their x lies in span(W)."""
+    G, K, y0 = M.fixture(n, rows, 3.0)
+    b = covariates(n, rows, "batch")[:, 1].astype(np.uint8)
+    assert 0 < b.sum() < n
+    ordinary = [r for r in M.varying(G) if not (np.array_equal(r, b) or np.array_equal(r, 1 - b))][:SPAN_ROWS - len(SPAN_DEGENERATE)]
+    V = np.zeros((SPAN_ROWS, n), np.uint8)
+    keep = np.setdiff1d(np.arange(SPAN_ROWS), SPAN_DEGENERATE)
+    V[keep] = ordinary
+    V[SPAN_DEGENERATE[0]], V[SPAN_DEGENERATE[1]], V[SPAN_DEGENERATE[2]] = b, 1 - b, b
+    V.setflags(write=False)
+    return K, y0, V, b
