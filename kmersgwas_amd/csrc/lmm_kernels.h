@@ -121,70 +121,67 @@ hipError_t launch_lmm_table_select(const double* lrt, const double* lam, const d
                                    const uint64_t* row, const uint64_t* kmer, const LmmSelectCol* cols, uint32_t* block_cnt,
                                    uint32_t* block_off, uint32_t* count, LmmTableRecord* rec, uint32_t cap, hipStream_t st);
 
-// lmm_table_kernels.hip: the pattern cache of kgwas_lmm_test_table_unique ("The pattern cache"). Its key is a
-// compacted code row, codes[t][bpsp] of launch_lmm_table_front. A slot holds a 64-bit tag (0: empty), an owner word, the code row
-// and lrt, lam, p of its pattern. `slots` is a power of two >= 64. Before the first piece of a call every tag is 0 and every
-// owner LMM_CACHE_NO_OWNER; between pieces every owner of a slot in use is 0.
+// lmm_table_kernels.hip: the pattern table ("The pattern table"), which kgwas_lmm_test_table_unique (the pattern
+// cache) and kgwas_lmm_test_table_multi_skip (the dead-pattern skip) both keep on the device for one call. Its key is a compacted
+// code row, codes[t][bpsp] of launch_lmm_table_front. A slot holds a 64-bit tag (0: empty), an owner word and the code row; the
+// cache adds lrt, lam, p of the pattern (res), the skip one state word (0 live, 1 dead; it only ever goes from 0 to 1). `slots` is a
+// power of two >= 64. Before the first piece of a call every tag (and state) is 0 and every owner LMM_CACHE_NO_OWNER; between
+// pieces every owner of a slot in use is 0.
 constexpr uint32_t LMM_CACHE_PROBES = 16;               // slots a row looks at before it gives up
 constexpr uint32_t LMM_CACHE_NONE = 0xFFFFFFFFu;        // slot_of of a row that reached no slot
 constexpr uint32_t LMM_CACHE_NO_OWNER = 0xFFFFFFFFu;
-enum : uint32_t {            // what a tested row of a piece is to the cache
-    LMM_ROW_OWNER = 0,       //   the first row of its tag in a new slot: rotated, and its result goes into the slot
-    LMM_ROW_CACHED = 1,      //   its code row equals its slot's: not rotated, it takes the slot's result
-    LMM_ROW_COLLIDED = 2,    //   its slot holds another code row with its tag: rotated
-    LMM_ROW_REJECTED = 3     //   no slot within LMM_CACHE_PROBES: rotated
+enum : uint32_t {                    // what a tested row of a piece is to the table
+    LMM_ROW_OWNER = 0,               //   the first row of its tag in a new slot: computed (the cache keeps its result in the slot)
+    LMM_ROW_CACHED = 1,              //   no state: its code row equals its slot's: not computed, it takes the slot's result
+    LMM_ROW_DEAD = LMM_ROW_CACHED,   //   state: its code row equals its slot's and the slot was dead when the piece began: not computed
+    LMM_ROW_COLLIDED = 2,            //   its slot holds another code row with its tag: computed
+    LMM_ROW_REJECTED = 3,            //   no slot within LMM_CACHE_PROBES: computed
+    LMM_ROW_LIVE = 4                 //   state: its code row equals its slot's and the slot was live (a new owner's copies too): computed
 };
 struct LmmCache {
     unsigned long long* tag;  // [slots]
     uint32_t* owner;          // [slots] compact index + 1 of the smallest row that reached the slot in this piece
     uint32_t* key;            // [slots][bpsp / 4]
-    double* res;              // [slots][3]: lrt, lam, p
+    double* res;              // [slots][3]: lrt, lam, p (the cache; nullptr for the skip)
+    uint32_t* state;          // [slots] (the skip; nullptr for the cache)
     uint32_t slots;
 };
 inline uint64_t lmm_cache_slot_bytes(LmmDims dm) { return 8 + 8 + dm.bpsp + 3 * sizeof(double); }  // (the owner word padded to 8)
-// The look-up of a piece's `total` compacted rows: row_tag[t] = the row's tag (a mix of its code row, cut to tag_mask, never 0),
-// slot_of[t] and cls[t] as above, and the rows to rotate (every class but LMM_ROW_CACHED) compacted in row order: codes2, vars2,
-// back[t2] = t, total2[0] = their number. Scratch: block_cnt and block_off [total / LMM_TABLE_BLOCK rounded up]. Every per-row
-// array has room for `total` rows. 0 < total < 2^31.
-hipError_t launch_lmm_cache_lookup(const uint8_t* codes, const LmmVariant* vars, uint32_t total, LmmDims dm, uint64_t tag_mask, LmmCache c,
-                                   unsigned long long* row_tag, uint32_t* slot_of, uint32_t* cls, uint32_t* block_cnt, uint32_t* block_off,
-                                   uint32_t* total2, uint8_t* codes2, LmmVariant* vars2, uint32_t* back, hipStream_t st);
-// After the back end over the sub-chunk back[0 .. cc) of the rows to rotate: their lrt, lam, p go to the piece's arrays at the
-// rows' places, and an owner's into its slot too.
-hipError_t launch_lmm_cache_scatter(const double* lrt, const double* lam, const double* p, uint32_t cc, const uint32_t* back,
-                                    const uint32_t* slot_of, const uint32_t* cls, uint32_t total, LmmCache c, double* r_lrt, double* r_lam,
-                                    double* r_p, hipStream_t st);
-// After the piece's last sub-chunk: the rows from cache take their slot's result, and the piece's new slots get owner 0.
-hipError_t launch_lmm_cache_fanout(const uint32_t* slot_of, const uint32_t* cls, uint32_t total, LmmCache c, double* r_lrt, double* r_lam,
-                                   double* r_p, hipStream_t st);
-
-// lmm_table_kernels.hip: the dead-pattern skip of kgwas_lmm_test_table_multi_skip ("The dead-pattern skip"). The
-// table is the pattern cache's without the results (LmmCache with res = nullptr: tag, owner and code row per slot, the same hash,
-// claim and publish kernels) and one state word per slot: 0 live, 1 dead. Before the first piece of a call every tag and state is 0
-// and every owner LMM_CACHE_NO_OWNER; between pieces every owner of a slot in use is 0. A state word only ever goes from 0 to 1.
-enum : uint32_t {                    // what a tested row of a piece is to the skip table, beside LMM_ROW_OWNER, _COLLIDED and _REJECTED
-    LMM_ROW_DEAD = LMM_ROW_CACHED,   //   its code row equals its slot's and the slot was dead when the piece began: not computed
-    LMM_ROW_LIVE = 4                 //   its code row equals its slot's and the slot was live (a new owner's copies too): computed
+inline uint64_t lmm_skip_slot_bytes(LmmDims dm) { return 8 + 4 + 4 + dm.bpsp; }                    // tag, owner, state, the code row
+// What the look-up leaves of a piece, and its scratch. Every per-row array has room for the piece's tested rows, block_cnt and
+// block_off for their number / LMM_TABLE_BLOCK rounded up.
+struct LmmPiece {
+    unsigned long long* row_tag;     // [t] the row's tag: a mix of its code row, cut to tag_mask, never 0
+    uint32_t *slot_of, *cls;         // [t] its slot (LMM_CACHE_NONE: none) and its class
+    uint32_t *block_cnt, *block_off;
+    uint32_t* total2;                // [1] the number of rows to compute: every class but LMM_ROW_CACHED / LMM_ROW_DEAD
+    uint8_t* codes2;                 // [t2][bpsp] those rows, compacted in row order
+    LmmVariant* vars2;               // [t2]
+    uint32_t* back;                  // [t2] = t
+    uint64_t *row2, *kmer2;          // [t2] row[t], kmer[t] (optional: both or neither)
 };
-inline uint64_t lmm_skip_slot_bytes(LmmDims dm) { return 8 + 4 + 4 + dm.bpsp; }  // tag, owner, state, the code row
-// The look-up of a piece's `total` compacted rows: row_tag, slot_of and cls[t] as above, and every row but the LMM_ROW_DEAD ones
-// compacted in row order with what the back end and the select kernels take: codes2, vars2, row2, kmer2, back[t2] = t, total2[0] =
-// their number. Scratch: block_cnt and block_off [total / LMM_TABLE_BLOCK rounded up]. Every per-row array has room for `total`
-// rows. 0 < total < 2^31.
-hipError_t launch_lmm_skip_lookup(const uint8_t* codes, const LmmVariant* vars, const uint64_t* row, const uint64_t* kmer, uint32_t total,
-                                  LmmDims dm, uint64_t tag_mask, LmmCache c, const uint32_t* state, unsigned long long* row_tag,
-                                  uint32_t* slot_of, uint32_t* cls, uint32_t* block_cnt, uint32_t* block_off, uint32_t* total2,
-                                  uint8_t* codes2, LmmVariant* vars2, uint64_t* row2, uint64_t* kmer2, uint32_t* back, hipStream_t st);
-// After launch_lmm_refine_multi over a sub-chunk of cc rows and a block of pb columns: shipped[v] = 1 where launch_lmm_table_select
-// ships a pair of row v of this block (the same rule on the same cols); the other rows' words are left as they are, so over the
-// blocks of a sub-chunk the words, zero at its start, become "any pair shipped".
+// The look-up of a piece's `total` compacted rows fills pc; row and kmer are read only where pc.row2 and pc.kmer2 are given. With
+// c.state an equal code row is LMM_ROW_DEAD or LMM_ROW_LIVE by its slot's state as the piece found it, without it LMM_ROW_CACHED.
+// 0 < total < 2^31.
+hipError_t launch_lmm_pattern_lookup(const uint8_t* codes, const LmmVariant* vars, const uint64_t* row, const uint64_t* kmer, uint32_t total,
+                                     LmmDims dm, uint64_t tag_mask, LmmCache c, LmmPiece pc, hipStream_t st);
+
+// The pattern cache. After the back end over the sub-chunk pc.back[first .. first + cc) of the rows to compute: their lrt, lam, p go
+// to the piece's arrays r_* at the rows' places, and an owner's into its slot too.
+hipError_t launch_lmm_cache_scatter(const double* lrt, const double* lam, const double* p, uint32_t first, uint32_t cc, uint32_t total,
+                                    LmmCache c, LmmPiece pc, double* r_lrt, double* r_lam, double* r_p, hipStream_t st);
+// After the piece's last sub-chunk: the rows from cache take their slot's result, and the piece's new slots get owner 0.
+hipError_t launch_lmm_cache_fanout(uint32_t total, LmmCache c, LmmPiece pc, double* r_lrt, double* r_lam, double* r_p, hipStream_t st);
+
+// The dead-pattern skip. After launch_lmm_refine_multi over a sub-chunk of cc rows and a block of pb columns: shipped[v] = 1 where
+// launch_lmm_table_select ships a pair of row v of this block (the same rule on the same cols); the other rows' words are left as
+// they are, so over the blocks of a sub-chunk the words, zero at its start, become "any pair shipped".
 hipError_t launch_lmm_skip_flag(const double* lrt, const LmmSelectCol* cols, uint32_t cc, uint32_t pb, uint32_t* shipped, hipStream_t st);
-// After the last column block of the sub-chunk back[0 .. cc): an owner's or a live row's slot becomes dead where the row shipped no
-// pair, and an owner's slot gets owner 0.
-hipError_t launch_lmm_skip_mark(const uint32_t* shipped, uint32_t cc, const uint32_t* back, const uint32_t* slot_of, const uint32_t* cls,
-                                uint32_t total, LmmCache c, uint32_t* state, hipStream_t st);
+// After the last column block of the sub-chunk pc.back[first .. first + cc): an owner's or a live row's slot becomes dead where the
+// row shipped no pair, and an owner's slot gets owner 0.
+hipError_t launch_lmm_skip_mark(const uint32_t* shipped, uint32_t first, uint32_t cc, uint32_t total, LmmCache c, LmmPiece pc,
+                                hipStream_t st);
 // dead[0] = the number of dead slots. Scratch: block_cnt and block_off [c.slots / LMM_TABLE_BLOCK].
-hipError_t launch_lmm_skip_count_dead(const uint32_t* state, uint32_t slots, uint32_t* block_cnt, uint32_t* block_off, uint32_t* dead,
-                                      hipStream_t st);
+hipError_t launch_lmm_skip_count_dead(LmmCache c, uint32_t* block_cnt, uint32_t* block_off, uint32_t* dead, hipStream_t st);
 
 }  // namespace kgwas

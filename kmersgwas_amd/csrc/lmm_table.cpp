@@ -128,8 +128,9 @@ uint64_t piece_rows(uint64_t n_rows, uint64_t W_f) {
     return std::min(piece, std::max<uint64_t>(n_rows, 1));
 }
 
-// What test_table, test_table_unique, test_table_multi and test_table_multi_skip share: the checks, the pieces and the front end. Per piece the rows are squeezed, flagged
-// and compacted (lmm_table_kernels.hip). prepare() runs after the checks and before any device work (the null models);
+// What test_table, test_table_unique, test_table_multi and test_table_multi_skip share: the checks, the pieces and the front end.
+// Per piece the rows are squeezed, flagged and compacted (lmm_table_kernels.hip). prepare(piece) runs after the checks and before
+// any device work (the null models; `piece` is the most rows a piece has, and so the most tested rows per_piece gets);
 // per_piece(total, codes, vars, row, kmer) gets a piece's compacted tested rows on the device, total > 0 of them, and is done
 // with them when it returns. `who` starts the messages; a tested row counts `weight` times in the stats' variants_tested.
 template <class Prepare, class PerPiece>
@@ -144,11 +145,11 @@ void table_pass(kgwas_lmm* h, kgwas_table* t, const uint64_t* col, uint64_t n_ac
     for (uint64_t i = 0; i < S; i++)
         if (col[i] >= S_f) throw Error(KGWAS_ERR_ARG, who + ": column index out of range");
     check_squeeze_fits(who.c_str(), S_f, S);  // (before any allocation)
-    prepare();
+    const uint64_t piece = piece_rows(n_rows, W_f);
+    prepare(piece);
     KGWAS_HIP(hipSetDevice(h->device));
     const uint32_t W_m = (uint32_t)(2 * ((S + 127) / 128));
     const uint64_t stride = 1 + W_f;
-    const uint64_t piece = piece_rows(n_rows, W_f);
     const uint64_t n_blocks = (piece + LMM_TABLE_BLOCK - 1) / LMM_TABLE_BLOCK;
 
     std::vector<uint32_t> colmap(64ull * W_m, 0xFFFFFFFFu);
@@ -196,18 +197,147 @@ void table_pass(kgwas_lmm* h, kgwas_table* t, const uint64_t* col, uint64_t n_ac
     }
 }
 
-// copies kept into the optional output arrays of the C ABI, from their element `at` on
-void copy_hits(const std::vector<TableHit>& kept, uint64_t at, uint64_t* row, uint64_t* kmer, double* lrt, double* lambda, double* p,
-               double* af) {
-    for (uint64_t i = 0; i < kept.size(); i++) {
-        if (row) row[at + i] = kept[i].row;
-        if (kmer) kmer[at + i] = kept[i].kmer;
-        if (lrt) lrt[at + i] = kept[i].lrt;
-        if (lambda) lambda[at + i] = kept[i].lam;
-        if (p) p[at + i] = kept[i].p;
-        if (af) af[at + i] = kept[i].af;
+// The results of up to `rows` compacted tested rows on their way from the device to a heap of the single-phenotype routes.
+struct RowStage {
+    std::vector<double> lrt, lam, p;
+    std::vector<LmmVariant> vars;
+    std::vector<uint64_t> row, kmer;
+    void resize(uint64_t rows) { lrt.resize(rows), lam.resize(rows), p.resize(rows), vars.resize(rows), row.resize(rows), kmer.resize(rows); }
+    // copies n rows' six arrays to the host, waits for the stream, collects the open timer interval and offers the rows in row order
+    void offer(kgwas_lmm* h, uint32_t n, const double* d_lrt, const double* d_lam, const double* d_p, const LmmVariant* d_vars,
+               const uint64_t* d_row, const uint64_t* d_kmer, std::vector<TableHit>& heap, uint64_t best_n) {
+        hipStream_t st = h->stream;
+        KGWAS_HIP(hipMemcpyAsync(lrt.data(), d_lrt, n * sizeof(double), hipMemcpyDeviceToHost, st));
+        KGWAS_HIP(hipMemcpyAsync(lam.data(), d_lam, n * sizeof(double), hipMemcpyDeviceToHost, st));
+        KGWAS_HIP(hipMemcpyAsync(p.data(), d_p, n * sizeof(double), hipMemcpyDeviceToHost, st));
+        KGWAS_HIP(hipMemcpyAsync(vars.data(), d_vars, n * sizeof(LmmVariant), hipMemcpyDeviceToHost, st));
+        KGWAS_HIP(hipMemcpyAsync(row.data(), d_row, n * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        KGWAS_HIP(hipMemcpyAsync(kmer.data(), d_kmer, n * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        KGWAS_HIP(hipStreamSynchronize(st));
+        h->timer.collect(h->st);
+        for (uint32_t v = 0; v < n; v++) heap_offer(heap, best_n, TableHit{lrt[v], lam[v], p[v], vars[v].af, row[v], kmer[v]});
     }
-}
+};
+
+// The pattern table of test_table_unique and test_table_multi_skip (lmm_table_kernels.hip, "the pattern table"): the slots on the
+// device, which live for one call, and what a look-up leaves of a piece. The constructor checks max_patterns and takes the power
+// of two of slots below it, at least 64, before any device work; alloc() allocates for pieces of `piece` rows and empties the table
+// on the handle's stream.
+class PatternTable {
+  public:
+    enum Extra { RESULTS, STATE };  // what a slot holds beside its tag, owner and code row: lrt, lam, p, or a state word
+    struct Found {
+        uint64_t kinds[LMM_ROW_LIVE + 1];  // the piece's rows per class
+        uint32_t total2;                   // the rows to compute
+    };
+    LmmCache cache{};
+    LmmPiece pc{};
+    std::vector<uint32_t> cls;  // the host's copy of the classes of the piece looked up last
+
+    PatternTable(kgwas_lmm* h, const std::string& who, uint64_t max_patterns, Extra extra) : h_(h), who_(who), extra_(extra) {
+        if (max_patterns < 64) throw Error(KGWAS_ERR_ARG, who + ": max_patterns is below 64");
+        uint32_t slots = 64;
+        while (slots < (1u << 30) && 2ull * slots <= max_patterns) slots *= 2;
+        cache.slots = slots;
+        const long long tag_bits = opt_int("KGWAS_LMM_PATTERN_TAG_BITS", 64);
+        tag_mask_ = tag_bits >= 1 && tag_bits < 64 ? (1ull << tag_bits) - 1 : ~0ull;
+    }
+
+    // with_rows: the look-up also compacts the rows' table index and k-mer word (row2, kmer2)
+    void alloc(uint64_t piece, bool with_rows) {
+        const uint64_t slots = cache.slots, bpsp = h_->dm.bpsp;
+        hipStream_t st = h_->stream;
+        KGWAS_HIP(hipSetDevice(h_->device));
+        cls.resize(piece);
+        tag_.alloc(slots), owner_.alloc(slots), key_.alloc(slots * (bpsp / 4));
+        res_.alloc(extra_ == RESULTS ? 3 * slots : 0), state_.alloc(extra_ == STATE ? slots : 0);
+        row_tag_.alloc(piece), slot_of_.alloc(piece), cls_.alloc(piece), back_.alloc(piece);
+        // (the block counts serve the piece's compaction and the count of the dead slots)
+        bcnt_.alloc(std::max<uint64_t>(piece, slots) / LMM_TABLE_BLOCK + 1), boff_.alloc(bcnt_.n), total2_.alloc(1);
+        codes2_.alloc(piece * bpsp), vars2_.alloc(piece);
+        if (with_rows) row2_.alloc(piece), kmer2_.alloc(piece);
+        cache = LmmCache{tag_.p, owner_.p, key_.p, res_.p, state_.p, cache.slots};
+        pc = LmmPiece{row_tag_.p, slot_of_.p, cls_.p, bcnt_.p, boff_.p, total2_.p, codes2_.p, vars2_.p, back_.p, row2_.p, kmer2_.p};
+        KGWAS_HIP(hipMemsetAsync(tag_.p, 0, slots * sizeof(unsigned long long), st));
+        KGWAS_HIP(hipMemsetAsync(owner_.p, 0xFF, slots * sizeof(uint32_t), st));  // LMM_CACHE_NO_OWNER
+        if (state_.p) KGWAS_HIP(hipMemsetAsync(state_.p, 0, slots * sizeof(uint32_t), st));
+    }
+
+    // The look-up of a piece's compacted tested rows (timed into rotate_ms, with the front end and the rotation): every row's class,
+    // on the device and in cls, and the rows to compute - `what`, for the message - in pc. The stream is idle when it returns.
+    Found lookup(uint32_t total, const uint8_t* d_codes, const LmmVariant* d_vars, const uint64_t* d_row, const uint64_t* d_kmer,
+                 const char* what) {
+        hipStream_t st = h_->stream;
+        if (total > cls.size()) throw Error(KGWAS_ERR_STATE, who_ + ": a piece has more tested rows than the piece has rows");
+        Found f{};
+        h_->timer.begin(st);
+        KGWAS_HIP(launch_lmm_pattern_lookup(d_codes, d_vars, d_row, d_kmer, total, h_->dm, tag_mask_, cache, pc, st));
+        h_->timer.end(&kgwas_lmm_stats::rotate_ms, st);
+        KGWAS_HIP(hipMemcpyAsync(&f.total2, pc.total2, sizeof(f.total2), hipMemcpyDeviceToHost, st));
+        KGWAS_HIP(hipMemcpyAsync(cls.data(), pc.cls, total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        KGWAS_HIP(hipStreamSynchronize(st));
+        h_->timer.collect(h_->st);
+        const uint32_t last = extra_ == STATE ? LMM_ROW_LIVE : LMM_ROW_REJECTED;
+        for (uint32_t v = 0; v < total; v++) {
+            if (cls[v] > last) throw Error(KGWAS_ERR_STATE, who_ + ": a row of no class");
+            f.kinds[cls[v]]++;
+        }
+        if (total - f.kinds[LMM_ROW_CACHED] != f.total2)
+            throw Error(KGWAS_ERR_STATE, who_ + ": the rows' classes and the rows to " + what + " differ");
+        return f;
+    }
+
+    // the number of dead slots (STATE), timed into rotate_ms; collects the intervals still open
+    uint32_t count_dead() {
+        hipStream_t st = h_->stream;
+        uint32_t dead = 0;
+        h_->timer.begin(st);
+        KGWAS_HIP(launch_lmm_skip_count_dead(cache, pc.block_cnt, pc.block_off, pc.total2, st));
+        h_->timer.end(&kgwas_lmm_stats::rotate_ms, st);
+        KGWAS_HIP(hipMemcpyAsync(&dead, pc.total2, sizeof(dead), hipMemcpyDeviceToHost, st));
+        KGWAS_HIP(hipStreamSynchronize(st));
+        h_->timer.collect(h_->st);
+        return dead;
+    }
+
+  private:
+    kgwas_lmm* const h_;
+    const std::string who_;
+    const Extra extra_;
+    uint64_t tag_mask_ = ~0ull;
+    DevBuf<unsigned long long> tag_, row_tag_;
+    DevBuf<uint32_t> owner_, key_, state_, slot_of_, cls_, back_, bcnt_, boff_, total2_;
+    DevBuf<double> res_;
+    DevBuf<uint8_t> codes2_;
+    DevBuf<LmmVariant> vars2_;
+    DevBuf<uint64_t> row2_, kmer2_;
+};
+
+// What the four kgwas_lmm_test_table* calls write beside their own arguments: every output is optional. kept[k] goes to the
+// arrays from element k best_n on, its size to n_kept[k].
+struct TableOut {
+    uint64_t *row, *kmer;
+    double *lrt, *lambda, *p, *af;
+    uint64_t *n_kept, *rows_read, *rows_tested, *pairs_shipped;
+    void write(const std::vector<TableHit>* kept, uint32_t n_cols, uint64_t best_n, uint64_t n_read, uint64_t n_tested,
+               uint64_t n_shipped = 0) const {
+        for (uint32_t k = 0; k < n_cols; k++) {
+            const uint64_t at = (uint64_t)k * best_n;
+            for (uint64_t i = 0; i < kept[k].size(); i++) {
+                if (row) row[at + i] = kept[k][i].row;
+                if (kmer) kmer[at + i] = kept[k][i].kmer;
+                if (lrt) lrt[at + i] = kept[k][i].lrt;
+                if (lambda) lambda[at + i] = kept[k][i].lam;
+                if (p) p[at + i] = kept[k][i].p;
+                if (af) af[at + i] = kept[k][i].af;
+            }
+            if (n_kept) n_kept[k] = kept[k].size();
+        }
+        if (rows_read) *rows_read = n_read;
+        if (rows_tested) *rows_tested = n_tested;
+        if (pairs_shipped) *pairs_shipped = n_shipped;
+    }
+};
 
 }  // namespace
 
@@ -217,31 +347,19 @@ void kgwas::lmm::test_table(kgwas_lmm* h, const double* y, kgwas_table* t, const
                             double maf, uint64_t best_n, std::vector<TableHit>& kept, uint64_t& rows_read, uint64_t& rows_tested) {
     const uint64_t chunk = h->chunk;
     std::vector<TableHit> heap;
-    std::vector<double> o_lrt, o_lam, o_p;
-    std::vector<LmmVariant> o_vars;
-    std::vector<uint64_t> o_row, o_kmer;
-    auto prepare = [&] {
+    RowStage out;
+    auto prepare = [&](uint64_t) {
         fit_null(h, y);
         heap.reserve((size_t)std::min<uint64_t>(best_n, 1u << 20));
-        o_lrt.resize(chunk), o_lam.resize(chunk), o_p.resize(chunk), o_vars.resize(chunk), o_row.resize(chunk), o_kmer.resize(chunk);
+        out.resize(chunk);
     };
     auto per_piece = [&](uint32_t total, const uint8_t* d_codes, const LmmVariant* d_vars, const uint64_t* d_row, const uint64_t* d_kmer) {
-        hipStream_t st = h->stream;
         for (uint64_t sub = 0; sub < total; sub += chunk) {
             const uint32_t cc = (uint32_t)std::min<uint64_t>(chunk, total - sub);
-            const LmmVariant* vars = d_vars + sub;
-            h->timer.begin(st);
-            single_backend(h, d_codes + sub * h->dm.bpsp, vars, cc);
-            KGWAS_HIP(hipMemcpyAsync(o_lrt.data(), h->d_lrt.p, cc * sizeof(double), hipMemcpyDeviceToHost, st));
-            KGWAS_HIP(hipMemcpyAsync(o_lam.data(), h->d_lam.p, cc * sizeof(double), hipMemcpyDeviceToHost, st));
-            KGWAS_HIP(hipMemcpyAsync(o_p.data(), h->d_p.p, cc * sizeof(double), hipMemcpyDeviceToHost, st));
-            KGWAS_HIP(hipMemcpyAsync(o_vars.data(), vars, cc * sizeof(LmmVariant), hipMemcpyDeviceToHost, st));
-            KGWAS_HIP(hipMemcpyAsync(o_row.data(), d_row + sub, cc * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-            KGWAS_HIP(hipMemcpyAsync(o_kmer.data(), d_kmer + sub, cc * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-            KGWAS_HIP(hipStreamSynchronize(st));
-            h->timer.collect(h->st);
+            h->timer.begin(h->stream);
+            single_backend(h, d_codes + sub * h->dm.bpsp, d_vars + sub, cc);
+            out.offer(h, cc, h->d_lrt.p, h->d_lam.p, h->d_p.p, d_vars + sub, d_row + sub, d_kmer + sub, heap, best_n);
             h->st.chunks++;
-            for (uint32_t v = 0; v < cc; v++) heap_offer(heap, best_n, TableHit{o_lrt[v], o_lam[v], o_p[v], o_vars[v].af, o_row[v], o_kmer[v]});
         }
     };
     table_pass(h, t, col, n_acc, min_count, maf, best_n, "kgwas_lmm_test_table", 1, prepare, per_piece, rows_read, rows_tested);
@@ -249,7 +367,7 @@ void kgwas::lmm::test_table(kgwas_lmm* h, const double* y, kgwas_table* t, const
     kept.swap(heap);
 }
 
-// test_table with a pattern cache of at most max_patterns slots (a power of two is taken, at least 64): each distinct code row
+// test_table with a pattern cache of at most max_patterns slots (PatternTable with a result per slot): each distinct code row
 // among the tested rows goes through rotate, grid and refine once, every other row with that code row takes the stored lrt, lam
 // and p (lmm_table_kernels.hip, "the pattern cache"). Equal code rows give equal LmmVariants and so equal results, whatever their
 // chunk and place, and the host is offered every tested row in row order as in test_table: kept has test_table's
@@ -259,90 +377,42 @@ void kgwas::lmm::test_table_unique(kgwas_lmm* h, const double* y, kgwas_table* t
                                    double maf, uint64_t best_n, uint64_t max_patterns, std::vector<TableHit>& kept, uint64_t& rows_read,
                                    uint64_t& rows_tested, kgwas_lmm_unique_stats& u) {
     const std::string who = "kgwas_lmm_test_table_unique";
-    if (max_patterns < 64) throw Error(KGWAS_ERR_ARG, who + ": max_patterns is below 64");  // (before any device work)
-    uint32_t slots = 64;
-    while (slots < (1u << 30) && 2ull * slots <= max_patterns) slots *= 2;
-    const long long tag_bits = opt_int("KGWAS_LMM_PATTERN_TAG_BITS", 64);
-    const uint64_t tag_mask = tag_bits >= 1 && tag_bits < 64 ? (1ull << tag_bits) - 1 : ~0ull;
+    PatternTable table(h, who, max_patterns, PatternTable::RESULTS);
     const uint64_t chunk = h->chunk, bpsp = h->dm.bpsp;
     std::vector<TableHit> heap;
     kgwas_lmm_unique_stats us{};
-    us.slots = slots;
-    // the cache, and per piece: the rows' tags, slots and classes, the rows to rotate, every tested row's result
-    DevBuf<unsigned long long> c_tag, d_tag;
-    DevBuf<uint32_t> c_owner, c_key, d_slot, d_cls, d_back, d_bcnt, d_boff, d_total2;
-    DevBuf<double> c_res, d_rlrt, d_rlam, d_rp;
-    DevBuf<uint8_t> d_codes2;
-    DevBuf<LmmVariant> d_vars2;
-    LmmCache cache{};
-    std::vector<double> o_lrt, o_lam, o_p;
-    std::vector<LmmVariant> o_vars;
-    std::vector<uint64_t> o_row, o_kmer;
-    std::vector<uint32_t> o_cls;
-    auto prepare = [&] {
+    us.slots = table.cache.slots;
+    RowStage out;
+    DevBuf<double> d_rlrt, d_rlam, d_rp;  // every tested row's result, at its place in the piece
+    auto prepare = [&](uint64_t piece) {
         fit_null(h, y);
         heap.reserve((size_t)std::min<uint64_t>(best_n, 1u << 20));
-        uint64_t S_f = 0, n_rows = 0, W_f = 0;
-        uint32_t klen = 0;
-        if (kgwas_table_info(t, &S_f, &n_rows, &W_f, &klen) != KGWAS_OK) throw Error(KGWAS_ERR_ARG, kgwas_last_error());
-        const uint64_t piece = piece_rows(n_rows, W_f);  // the host and device buffers hold a piece, not a chunk
-        o_lrt.resize(piece), o_lam.resize(piece), o_p.resize(piece), o_vars.resize(piece), o_row.resize(piece), o_kmer.resize(piece);
-        o_cls.resize(piece);
-        KGWAS_HIP(hipSetDevice(h->device));
-        c_tag.alloc(slots), c_owner.alloc(slots), c_key.alloc((uint64_t)slots * (bpsp / 4)), c_res.alloc(3ull * slots);
-        d_tag.alloc(piece), d_slot.alloc(piece), d_cls.alloc(piece), d_back.alloc(piece);
-        d_bcnt.alloc((piece + LMM_TABLE_BLOCK - 1) / LMM_TABLE_BLOCK), d_boff.alloc(d_bcnt.n), d_total2.alloc(1);
+        out.resize(piece);  // the host and device buffers hold a piece, not a chunk
+        table.alloc(piece, false);
         d_rlrt.alloc(piece), d_rlam.alloc(piece), d_rp.alloc(piece);
-        d_codes2.alloc(piece * bpsp), d_vars2.alloc(piece);
-        cache = LmmCache{c_tag.p, c_owner.p, c_key.p, c_res.p, slots};
-        KGWAS_HIP(hipMemsetAsync(c_tag.p, 0, slots * sizeof(unsigned long long), h->stream));
-        KGWAS_HIP(hipMemsetAsync(c_owner.p, 0xFF, slots * sizeof(uint32_t), h->stream));  // LMM_CACHE_NO_OWNER
     };
     auto per_piece = [&](uint32_t total, const uint8_t* d_codes, const LmmVariant* d_vars, const uint64_t* d_row, const uint64_t* d_kmer) {
         hipStream_t st = h->stream;
-        if (total > d_cls.n) throw Error(KGWAS_ERR_STATE, who + ": a piece has more tested rows than the piece has rows");
-        uint32_t total2 = 0;
-        h->timer.begin(st);  // (the cache's kernels are timed with the front end and the rotation)
-        KGWAS_HIP(launch_lmm_cache_lookup(d_codes, d_vars, total, h->dm, tag_mask, cache, d_tag.p, d_slot.p, d_cls.p, d_bcnt.p, d_boff.p,
-                                          d_total2.p, d_codes2.p, d_vars2.p, d_back.p, st));
-        h->timer.end(&kgwas_lmm_stats::rotate_ms, st);
-        KGWAS_HIP(hipMemcpyAsync(&total2, d_total2.p, sizeof(total2), hipMemcpyDeviceToHost, st));
-        KGWAS_HIP(hipStreamSynchronize(st));
-        h->timer.collect(h->st);
-        if (total2 > total) throw Error(KGWAS_ERR_STATE, who + ": the cache counted more rows to rotate than tested rows");
+        const PatternTable::Found f = table.lookup(total, d_codes, d_vars, nullptr, nullptr, "rotate");
+        const LmmPiece& pc = table.pc;
         h->timer.begin(st);
-        for (uint64_t sub = 0; sub < total2; sub += chunk) {
-            const uint32_t cc = (uint32_t)std::min<uint64_t>(chunk, total2 - sub);
-            single_backend(h, d_codes2.p + sub * bpsp, d_vars2.p + sub, cc);
-            KGWAS_HIP(launch_lmm_cache_scatter(h->d_lrt.p, h->d_lam.p, h->d_p.p, cc, d_back.p + sub, d_slot.p, d_cls.p, total, cache, d_rlrt.p,
-                                               d_rlam.p, d_rp.p, st));
+        for (uint64_t sub = 0; sub < f.total2; sub += chunk) {
+            const uint32_t cc = (uint32_t)std::min<uint64_t>(chunk, f.total2 - sub);
+            single_backend(h, pc.codes2 + sub * bpsp, pc.vars2 + sub, cc);
+            KGWAS_HIP(launch_lmm_cache_scatter(h->d_lrt.p, h->d_lam.p, h->d_p.p, (uint32_t)sub, cc, total, table.cache, pc, d_rlrt.p, d_rlam.p,
+                                               d_rp.p, st));
             h->timer.end(&kgwas_lmm_stats::rotate_ms, st);
             h->st.chunks++;
         }
         // after the last sub-chunk: an owner may stand in a later sub-chunk than its copies
-        KGWAS_HIP(launch_lmm_cache_fanout(d_slot.p, d_cls.p, total, cache, d_rlrt.p, d_rlam.p, d_rp.p, st));
+        KGWAS_HIP(launch_lmm_cache_fanout(total, table.cache, pc, d_rlrt.p, d_rlam.p, d_rp.p, st));
         h->timer.end(&kgwas_lmm_stats::rotate_ms, st);
-        KGWAS_HIP(hipMemcpyAsync(o_lrt.data(), d_rlrt.p, total * sizeof(double), hipMemcpyDeviceToHost, st));
-        KGWAS_HIP(hipMemcpyAsync(o_lam.data(), d_rlam.p, total * sizeof(double), hipMemcpyDeviceToHost, st));
-        KGWAS_HIP(hipMemcpyAsync(o_p.data(), d_rp.p, total * sizeof(double), hipMemcpyDeviceToHost, st));
-        KGWAS_HIP(hipMemcpyAsync(o_vars.data(), d_vars, total * sizeof(LmmVariant), hipMemcpyDeviceToHost, st));
-        KGWAS_HIP(hipMemcpyAsync(o_row.data(), d_row, total * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        KGWAS_HIP(hipMemcpyAsync(o_kmer.data(), d_kmer, total * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        KGWAS_HIP(hipMemcpyAsync(o_cls.data(), d_cls.p, total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        KGWAS_HIP(hipStreamSynchronize(st));
-        h->timer.collect(h->st);
-        uint64_t kinds[4] = {0, 0, 0, 0};
-        for (uint32_t v = 0; v < total; v++) {
-            if (o_cls[v] > LMM_ROW_REJECTED) throw Error(KGWAS_ERR_STATE, who + ": a row of no class");
-            kinds[o_cls[v]]++;
-            heap_offer(heap, best_n, TableHit{o_lrt[v], o_lam[v], o_p[v], o_vars[v].af, o_row[v], o_kmer[v]});
-        }
-        if (total - kinds[LMM_ROW_CACHED] != total2) throw Error(KGWAS_ERR_STATE, who + ": the rows' classes and the rows to rotate differ");
-        us.patterns_cached += kinds[LMM_ROW_OWNER];
-        us.rows_from_cache += kinds[LMM_ROW_CACHED];
-        us.rows_collided += kinds[LMM_ROW_COLLIDED];
-        us.rows_rejected += kinds[LMM_ROW_REJECTED];
-        us.rows_rotated += total2;
+        out.offer(h, total, d_rlrt.p, d_rlam.p, d_rp.p, d_vars, d_row, d_kmer, heap, best_n);
+        us.patterns_cached += f.kinds[LMM_ROW_OWNER];
+        us.rows_from_cache += f.kinds[LMM_ROW_CACHED];
+        us.rows_collided += f.kinds[LMM_ROW_COLLIDED];
+        us.rows_rejected += f.kinds[LMM_ROW_REJECTED];
+        us.rows_rotated += f.total2;
     };
     table_pass(h, t, col, n_acc, min_count, maf, best_n, who, 1, prepare, per_piece, rows_read, rows_tested);
     sort_by_row(heap);
@@ -452,7 +522,7 @@ void kgwas::lmm::test_table_multi(kgwas_lmm* h, uint32_t n_pheno, const double* 
     MultiPass mp{h, n_pheno, best_n, who};
     MultiPass::NoHooks none;
     pairs_shipped = 0;
-    auto prepare = [&] { mp.prepare(Y, logl0, lambda0); };
+    auto prepare = [&](uint64_t) { mp.prepare(Y, logl0, lambda0); };
     auto per_piece = [&](uint32_t total, const uint8_t* d_codes, const LmmVariant* d_vars, const uint64_t* d_row, const uint64_t* d_kmer) {
         mp.run(total, d_codes, d_vars, d_row, d_kmer, none);
         pairs_shipped = mp.pairs_shipped;
@@ -461,9 +531,9 @@ void kgwas::lmm::test_table_multi(kgwas_lmm* h, uint32_t n_pheno, const double* 
     mp.finish(kept);
 }
 
-// test_table_multi that skips dead patterns (lmm_table_kernels.hip, "the dead-pattern skip"): a table of at most max_patterns slots
-// (a power of two is taken, at least 64) remembers the code rows met and, per slot, whether an occurrence that went through all
-// n_pheno columns shipped no pair. Such a pattern is dead: the heaps were all full, their worst lrt only rises and equal code rows
+// test_table_multi that skips dead patterns (lmm_table_kernels.hip, "the dead-pattern skip"): a PatternTable of at most max_patterns
+// slots with a state word per slot remembers the code rows met and whether an occurrence that went through all n_pheno columns
+// shipped no pair. Such a pattern is dead: the heaps were all full, their worst lrt only rises and equal code rows
 // give equal lrt in every column, so every later occurrence would ship nothing either, and from the next piece on
 // it is left out of the rows that go through MultiPass::run, in test_table_multi's sub-chunks less their dead rows. kept, logl0,
 // lambda0 and pairs_shipped are test_table_multi's, byte for byte. The table lives for this call: what ships depends on Y. u is
@@ -473,98 +543,55 @@ void kgwas::lmm::test_table_multi_skip(kgwas_lmm* h, uint32_t n_pheno, const dou
                                        std::vector<std::vector<TableHit>>& kept, double* logl0, double* lambda0, uint64_t& rows_read,
                                        uint64_t& rows_tested, uint64_t& pairs_shipped, kgwas_lmm_skip_stats& u) {
     const std::string who = "kgwas_lmm_test_table_multi_skip";
-    if (!n_pheno) throw Error(KGWAS_ERR_ARG, who + ": n_pheno is 0");                        // (before the table's checks)
-    if (max_patterns < 64) throw Error(KGWAS_ERR_ARG, who + ": max_patterns is below 64");  // (before any device work)
-    uint32_t slots = 64;
-    while (slots < (1u << 30) && 2ull * slots <= max_patterns) slots *= 2;
-    const long long tag_bits = opt_int("KGWAS_LMM_PATTERN_TAG_BITS", 64);
-    const uint64_t tag_mask = tag_bits >= 1 && tag_bits < 64 ? (1ull << tag_bits) - 1 : ~0ull;
-    const uint64_t bpsp = h->dm.bpsp;
+    if (!n_pheno) throw Error(KGWAS_ERR_ARG, who + ": n_pheno is 0");  // (before the table's checks)
+    PatternTable table(h, who, max_patterns, PatternTable::STATE);
     MultiPass mp{h, n_pheno, best_n, who};
     kgwas_lmm_skip_stats us{};
-    us.slots = slots;
+    us.slots = table.cache.slots;
     pairs_shipped = 0;
-    // the table, and per piece: the rows' tags, slots and classes and the rows to compute; per sub-chunk the rows that shipped a pair
-    DevBuf<unsigned long long> c_tag, d_tag;
-    DevBuf<uint32_t> c_owner, c_key, c_state, d_slot, d_cls, d_back, d_bcnt, d_boff, d_total2, d_shipped;
-    DevBuf<uint8_t> d_codes2;
-    DevBuf<LmmVariant> d_vars2;
-    DevBuf<uint64_t> d_row2, d_kmer2;
-    LmmCache cache{};
-    std::vector<uint32_t> o_cls, cuts;
-    auto prepare = [&] {
+    DevBuf<uint32_t> d_shipped;  // per sub-chunk: the rows that shipped a pair
+    std::vector<uint32_t> cuts;
+    auto prepare = [&](uint64_t piece) {
         mp.prepare(Y, logl0, lambda0);
-        uint64_t S_f = 0, n_rows = 0, W_f = 0;
-        uint32_t klen = 0;
-        if (kgwas_table_info(t, &S_f, &n_rows, &W_f, &klen) != KGWAS_OK) throw Error(KGWAS_ERR_ARG, kgwas_last_error());
-        const uint64_t piece = piece_rows(n_rows, W_f);
-        o_cls.resize(piece);
-        c_tag.alloc(slots), c_owner.alloc(slots), c_key.alloc((uint64_t)slots * (bpsp / 4)), c_state.alloc(slots);
-        d_tag.alloc(piece), d_slot.alloc(piece), d_cls.alloc(piece), d_back.alloc(piece);
-        // (the block counts serve the piece's compaction and, at the end, the count of the dead slots)
-        d_bcnt.alloc(std::max<uint64_t>(piece, slots) / LMM_TABLE_BLOCK + 1), d_boff.alloc(d_bcnt.n), d_total2.alloc(1);
-        d_codes2.alloc(piece * bpsp), d_vars2.alloc(piece), d_row2.alloc(piece), d_kmer2.alloc(piece);
+        table.alloc(piece, true);
         d_shipped.alloc(h->chunk);
-        cache = LmmCache{c_tag.p, c_owner.p, c_key.p, nullptr, slots};
-        KGWAS_HIP(hipMemsetAsync(c_tag.p, 0, slots * sizeof(unsigned long long), h->stream));
-        KGWAS_HIP(hipMemsetAsync(c_owner.p, 0xFF, slots * sizeof(uint32_t), h->stream));  // LMM_CACHE_NO_OWNER
-        KGWAS_HIP(hipMemsetAsync(c_state.p, 0, slots * sizeof(uint32_t), h->stream));
     };
     struct Hooks {
         kgwas_lmm* h;
-        const LmmCache& cache;
-        uint32_t *shipped, *state, *back, *slot_of, *cls;
-        uint32_t total = 0;  // the piece's tested rows
+        const PatternTable& table;
+        uint32_t* shipped;
+        uint32_t total;  // the piece's tested rows
         void begin_sub(uint32_t cc) { KGWAS_HIP(hipMemsetAsync(shipped, 0, cc * sizeof(uint32_t), h->stream)); }
         void after_block(uint32_t cc, uint32_t, uint32_t pb) {
             KGWAS_HIP(launch_lmm_skip_flag(h->d_lrtm.p, h->d_sel_cols.p, cc, pb, shipped, h->stream));
         }
         void end_sub(uint64_t sub, uint32_t cc) {  // (timed with the refinement; collected with the next interval that is)
             h->timer.begin(h->stream);
-            KGWAS_HIP(launch_lmm_skip_mark(shipped, cc, back + sub, slot_of, cls, total, cache, state, h->stream));
+            KGWAS_HIP(launch_lmm_skip_mark(shipped, (uint32_t)sub, cc, total, table.cache, table.pc, h->stream));
             h->timer.end(&kgwas_lmm_stats::refine_ms, h->stream);
         }
     };
     auto per_piece = [&](uint32_t total, const uint8_t* d_codes, const LmmVariant* d_vars, const uint64_t* d_row, const uint64_t* d_kmer) {
-        hipStream_t st = h->stream;
-        if (total > d_cls.n) throw Error(KGWAS_ERR_STATE, who + ": a piece has more tested rows than the piece has rows");
-        uint32_t total2 = 0;
-        h->timer.begin(st);  // (the table's kernels are timed with the front end and the rotation)
-        KGWAS_HIP(launch_lmm_skip_lookup(d_codes, d_vars, d_row, d_kmer, total, h->dm, tag_mask, cache, c_state.p, d_tag.p, d_slot.p, d_cls.p,
-                                         d_bcnt.p, d_boff.p, d_total2.p, d_codes2.p, d_vars2.p, d_row2.p, d_kmer2.p, d_back.p, st));
-        h->timer.end(&kgwas_lmm_stats::rotate_ms, st);
-        KGWAS_HIP(hipMemcpyAsync(&total2, d_total2.p, sizeof(total2), hipMemcpyDeviceToHost, st));
-        KGWAS_HIP(hipMemcpyAsync(o_cls.data(), d_cls.p, total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        KGWAS_HIP(hipStreamSynchronize(st));
-        h->timer.collect(h->st);
+        const PatternTable::Found f = table.lookup(total, d_codes, d_vars, d_row, d_kmer, "compute");
         // The sub-chunks are test_table_multi's, cut every h->chunk tested rows, less their dead rows: every computed row meets the
         // thresholds it meets there, so the pairs shipped are the same ones.
-        uint64_t kinds[5] = {0, 0, 0, 0, 0};
         cuts.assign(1, 0u);
-        for (uint32_t v = 0; v < total; v++) {
-            if (o_cls[v] > LMM_ROW_LIVE) throw Error(KGWAS_ERR_STATE, who + ": a row of no class");
-            kinds[o_cls[v]]++;
-            if ((v + 1) % h->chunk == 0 || v + 1 == total) cuts.push_back((uint32_t)(v + 1 - kinds[LMM_ROW_DEAD]));
+        for (uint32_t v = 0, dead = 0; v < total; v++) {
+            dead += table.cls[v] == LMM_ROW_DEAD;
+            if ((v + 1) % h->chunk == 0 || v + 1 == total) cuts.push_back(v + 1 - dead);
         }
-        if (total - kinds[LMM_ROW_DEAD] != total2) throw Error(KGWAS_ERR_STATE, who + ": the rows' classes and the rows to compute differ");
-        us.patterns_cached += kinds[LMM_ROW_OWNER];
-        us.rows_skipped += kinds[LMM_ROW_DEAD];
-        us.rows_collided += kinds[LMM_ROW_COLLIDED];
-        us.rows_rejected += kinds[LMM_ROW_REJECTED];
-        us.rows_rotated += total2;
-        Hooks hooks{h, cache, d_shipped.p, c_state.p, d_back.p, d_slot.p, d_cls.p, total};
-        if (total2) mp.run(total2, d_codes2.p, d_vars2.p, d_row2.p, d_kmer2.p, hooks, &cuts);
+        us.patterns_cached += f.kinds[LMM_ROW_OWNER];
+        us.rows_skipped += f.kinds[LMM_ROW_DEAD];
+        us.rows_collided += f.kinds[LMM_ROW_COLLIDED];
+        us.rows_rejected += f.kinds[LMM_ROW_REJECTED];
+        us.rows_rotated += f.total2;
+        Hooks hooks{h, table, d_shipped.p, total};
+        const LmmPiece& pc = table.pc;
+        if (f.total2) mp.run(f.total2, pc.codes2, pc.vars2, pc.row2, pc.kmer2, hooks, &cuts);
         pairs_shipped = mp.pairs_shipped;
     };
     table_pass(h, t, col, n_acc, min_count, maf, best_n, who, n_pheno, prepare, per_piece, rows_read, rows_tested);
-    uint32_t dead = 0;
-    hipStream_t st = h->stream;
-    h->timer.begin(st);
-    KGWAS_HIP(launch_lmm_skip_count_dead(c_state.p, slots, d_bcnt.p, d_boff.p, d_total2.p, st));
-    h->timer.end(&kgwas_lmm_stats::rotate_ms, st);
-    KGWAS_HIP(hipMemcpyAsync(&dead, d_total2.p, sizeof(dead), hipMemcpyDeviceToHost, st));
-    KGWAS_HIP(hipStreamSynchronize(st));
-    h->timer.collect(h->st);  // (and the last sub-chunk's mark)
+    const uint32_t dead = table.count_dead();  // (collects the last sub-chunk's mark too)
     if (dead > us.patterns_cached) throw Error(KGWAS_ERR_STATE, who + ": more dead slots than slots in use");
     us.patterns_dead = dead;
     mp.finish(kept);
@@ -581,10 +608,7 @@ int kgwas_lmm_test_table(kgwas_lmm* h, const double* y, kgwas_table* t, const ui
         std::vector<TableHit> kept;
         uint64_t n_read = 0, n_tested = 0;
         test_table(h, y, t, col, n_acc, min_count, maf, best_n, kept, n_read, n_tested);
-        copy_hits(kept, 0, row, kmer, lrt, lambda, p, af);
-        if (n_kept) *n_kept = kept.size();
-        if (rows_read) *rows_read = n_read;
-        if (rows_tested) *rows_tested = n_tested;
+        TableOut{row, kmer, lrt, lambda, p, af, n_kept, rows_read, rows_tested, nullptr}.write(&kept, 1, best_n, n_read, n_tested);
     });
 }
 
@@ -598,10 +622,7 @@ int kgwas_lmm_test_table_unique(kgwas_lmm* h, const double* y, kgwas_table* t, c
         uint64_t n_read = 0, n_tested = 0;
         kgwas_lmm_unique_stats us{};
         test_table_unique(h, y, t, col, n_acc, min_count, maf, best_n, max_patterns, kept, n_read, n_tested, us);
-        copy_hits(kept, 0, row, kmer, lrt, lambda, p, af);
-        if (n_kept) *n_kept = kept.size();
-        if (rows_read) *rows_read = n_read;
-        if (rows_tested) *rows_tested = n_tested;
+        TableOut{row, kmer, lrt, lambda, p, af, n_kept, rows_read, rows_tested, nullptr}.write(&kept, 1, best_n, n_read, n_tested);
         if (u) *u = us;
     });
 }
@@ -615,13 +636,8 @@ int kgwas_lmm_test_table_multi(kgwas_lmm* h, uint32_t n_pheno, const double* Y, 
         std::vector<std::vector<TableHit>> kept;
         uint64_t n_read = 0, n_tested = 0, n_shipped = 0;
         test_table_multi(h, n_pheno, Y, t, col, n_acc, min_count, maf, best_n, kept, logl0, lambda0, n_read, n_tested, n_shipped);
-        for (uint32_t k = 0; k < n_pheno; k++) {
-            copy_hits(kept[k], (uint64_t)k * best_n, row, kmer, lrt, lambda, p, af);
-            if (n_kept) n_kept[k] = kept[k].size();
-        }
-        if (rows_read) *rows_read = n_read;
-        if (rows_tested) *rows_tested = n_tested;
-        if (pairs_shipped) *pairs_shipped = n_shipped;
+        TableOut{row, kmer, lrt, lambda, p, af, n_kept, rows_read, rows_tested, pairs_shipped}.write(kept.data(), n_pheno, best_n, n_read,
+                                                                                                     n_tested, n_shipped);
     });
 }
 
@@ -637,13 +653,8 @@ int kgwas_lmm_test_table_multi_skip(kgwas_lmm* h, uint32_t n_pheno, const double
         kgwas_lmm_skip_stats us{};
         test_table_multi_skip(h, n_pheno, Y, t, col, n_acc, min_count, maf, best_n, max_patterns, kept, logl0, lambda0, n_read, n_tested,
                               n_shipped, us);
-        for (uint32_t k = 0; k < n_pheno; k++) {
-            copy_hits(kept[k], (uint64_t)k * best_n, row, kmer, lrt, lambda, p, af);
-            if (n_kept) n_kept[k] = kept[k].size();
-        }
-        if (rows_read) *rows_read = n_read;
-        if (rows_tested) *rows_tested = n_tested;
-        if (pairs_shipped) *pairs_shipped = n_shipped;
+        TableOut{row, kmer, lrt, lambda, p, af, n_kept, rows_read, rows_tested, pairs_shipped}.write(kept.data(), n_pheno, best_n, n_read,
+                                                                                                     n_tested, n_shipped);
         if (u) *u = us;
     });
 }

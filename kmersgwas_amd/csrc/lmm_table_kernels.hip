@@ -14,31 +14,31 @@
 //                          and popcount below the lane), so slots follow the row order - the same content in every run. The row's
 //                          lane writes the LmmVariant, the table row index and the k-mer word; then the block writes the padded
 //                          2-bit code rows, one dword (16 accessions, every presence bit doubled) per lane and step.
+// Wherever flags are only counted, lmm_table_count_kernel<P> stands for the flag kernel: per block of 256 elements the number that
+// meet the predicate P, and the scan kernel behind it (count_and_scan).
 // And the first stage of the selection of the multi-phenotype pass (kgwas_lmm_test_table_multi), by the same scheme:
-//   lmm_table_select_count_kernel  one lane per (column, row) pair of a refined block: does it pass its column's threshold; per
-//                                  block of 256 pairs the number that do;
-//   lmm_table_scan_kernel          as above: the offsets and the number of survivors;
-//   lmm_table_select_kernel        a surviving pair's lane writes its record at offset + rank, so records follow the (column, row)
-//                                  order and are the same in every run.
-// And the pattern cache of kgwas_lmm_test_table_unique, which sends each distinct code row through the back end once:
-//   lmm_cache_hash_kernel      one wave per tested row: its 64-bit tag;
-//   lmm_cache_claim_kernel     one lane per row: the slot of its tag (atomicCAS along a linear probe sequence of 16 slots) and, by
-//                              atomicMin, the slot's owner - the smallest row of the piece that reached it;
-//   lmm_cache_publish_kernel   an owner's code row goes into its new slot;
-//   lmm_cache_classify_kernel  one wave per row: owner, from cache (the whole code row equals the slot's), collided or rejected;
-//   lmm_cache_count_kernel, lmm_table_scan_kernel, lmm_cache_emit_kernel   the rows to rotate, compacted in row order;
+//   lmm_table_count_kernel<lmm_table_select_count>, lmm_table_scan_kernel   one lane per (column, row) pair of a refined block:
+//                              does it pass its column's threshold; the offsets and the number of survivors;
+//   lmm_table_select_kernel    a surviving pair's lane writes its record at offset + rank, so records follow the (column, row)
+//                              order and are the same in every run.
+// And the pattern table, the set of the code rows met so far in a call (launch_lmm_pattern_lookup, once per piece):
+//   lmm_pattern_hash_kernel      one wave per tested row: its 64-bit tag;
+//   lmm_pattern_claim_kernel     one lane per row: the slot of its tag (atomicCAS along a linear probe sequence of 16 slots) and, by
+//                                atomicMin, the slot's owner - the smallest row of the piece that reached it;
+//   lmm_pattern_publish_kernel   an owner's code row goes into its new slot;
+//   lmm_pattern_classify_kernel  one wave per row: owner, equal (the whole code row equals the slot's), collided or rejected;
+//   lmm_table_count_kernel<lmm_pattern_count>, lmm_table_scan_kernel, lmm_pattern_emit_kernel   the rows to compute - every row
+//                                but the equal ones (of a dead slot, where slots have a state) - compacted in row order.
+// To which the pattern cache of kgwas_lmm_test_table_unique adds a result per slot, so that each distinct code row goes through the
+// back end once:
 //   lmm_cache_scatter_kernel   a sub-chunk's results go back to the rows' places and into the owners' slots;
 //   lmm_cache_fanout_kernel    the rows from cache take their slot's result; the piece's new slots get owner 0.
-// And the dead-pattern skip of kgwas_lmm_test_table_multi_skip, on the cache's table without results and a state word per slot:
-//   lmm_cache_hash_kernel, lmm_cache_claim_kernel, lmm_cache_publish_kernel   as above;
-//   lmm_skip_classify_kernel   one wave per row: owner, dead or live (the whole code row equals the slot's; the slot's state as the
-//                              piece found it), collided or rejected;
-//   lmm_cache_count_kernel, lmm_table_scan_kernel, lmm_cache_emit_kernel, lmm_skip_gather_kernel   every row but the dead ones,
-//                              compacted in row order, with its table row index and k-mer word;
+// And the dead-pattern skip of kgwas_lmm_test_table_multi_skip a state word per slot, by which an equal row is dead or live:
+//   lmm_skip_gather_kernel     a row to compute takes its table row index and k-mer word along;
 //   lmm_skip_flag_kernel       after a column block's refinement: the rows of which the select kernel ships a pair;
 //   lmm_skip_mark_kernel       after a sub-chunk's last column block: the slot of an owner or live row that shipped nothing is dead;
-//   lmm_skip_count_dead_kernel, lmm_table_scan_kernel   the number of dead slots, once per call.
-// No scalar memory write: every value goes out through a vector store from plain C++. The two atomics of lmm_cache_claim_kernel
+//   lmm_table_count_kernel<lmm_skip_dead_count>, lmm_table_scan_kernel   the number of dead slots, once per call.
+// No scalar memory write: every value goes out through a vector store from plain C++. The two atomics of lmm_pattern_claim_kernel
 // are the only ones.
 #include "lmm_kernels.h"
 
@@ -127,6 +127,25 @@ __global__ void __launch_bounds__(256) lmm_table_scan_kernel(const uint32_t* __r
     if (threadIdx.x == 0) total[0] = carry;
 }
 
+// block_cnt[b] = the number of elements e of block b, e < n, with pred(e)
+template <class Pred>
+__global__ void __launch_bounds__(TB) lmm_table_count_kernel(Pred pred, uint32_t n, uint32_t* __restrict__ block_cnt) {
+    __shared__ uint32_t s_wave[TB / 64];
+    const uint32_t e = blockIdx.x * TB + threadIdx.x;
+    const bool keep = e < n && pred(e);
+    uint32_t total;
+    (void)block_rank(keep, s_wave, total);
+    if (threadIdx.x == 0) block_cnt[blockIdx.x] = total;
+}
+
+// the count and the scan over n > 0 elements: block_off for an emit kernel with the same predicate, total[0] = how many meet it
+template <class Pred>
+void count_and_scan(Pred pred, uint32_t n, uint32_t* block_cnt, uint32_t* block_off, uint32_t* total, hipStream_t st) {
+    const uint32_t n_blocks = (n + TB - 1) / TB;
+    hipLaunchKernelGGL(lmm_table_count_kernel<Pred>, dim3(n_blocks), dim3(TB), 0, st, pred, n, block_cnt);
+    hipLaunchKernelGGL(lmm_table_scan_kernel, dim3(1), dim3(256), 0, st, block_cnt, n_blocks, block_off, total);
+}
+
 __global__ void __launch_bounds__(TB) lmm_table_emit_kernel(const uint64_t* __restrict__ rows, uint64_t stride,
                                                             const uint32_t* __restrict__ sq, uint32_t n_rows, uint32_t ndw, uint32_t S,
                                                             uint64_t first_row, const uint32_t* __restrict__ n1flag,
@@ -179,14 +198,12 @@ __device__ inline bool select_survives(const double* __restrict__ lrt, const Lmm
     return sc.open != 0u || lrt[e] > sc.thr;
 }
 
-__global__ void __launch_bounds__(TB) lmm_table_select_count_kernel(const double* __restrict__ lrt, const LmmSelectCol* __restrict__ cols,
-                                                                    uint32_t cc, uint32_t n, uint32_t* __restrict__ block_cnt) {
-    __shared__ uint32_t s_wave[TB / 64];
-    const bool keep = select_survives(lrt, cols, cc, blockIdx.x * TB + threadIdx.x, n);
-    uint32_t total;
-    (void)block_rank(keep, s_wave, total);
-    if (threadIdx.x == 0) block_cnt[blockIdx.x] = total;
-}
+struct lmm_table_select_count {
+    const double* lrt;
+    const LmmSelectCol* cols;
+    uint32_t cc, n;
+    __device__ bool operator()(uint32_t e) const { return select_survives(lrt, cols, cc, e, n); }
+};
 
 // a survivor's slot is its block's offset plus its rank in the block: slots follow the element order. Its lane writes the record.
 __global__ void __launch_bounds__(TB) lmm_table_select_kernel(const double* __restrict__ lrt, const double* __restrict__ lam,
@@ -214,9 +231,10 @@ __global__ void __launch_bounds__(TB) lmm_table_select_kernel(const double* __re
     rec[slot] = o;
 }
 
-// ---- the pattern cache of kgwas_lmm_test_table_unique ("The pattern cache") ----
-// Atomics stand in lmm_cache_claim_kernel alone, and there a word an atomic touches is never loaded plainly; everything else one
-// kernel leaves for another crosses a kernel boundary on the one stream. Every loop has a bound no other thread can move.
+// ---- the pattern table of the pattern cache and of the dead-pattern skip ("The pattern table") ----
+// Atomics stand in lmm_pattern_claim_kernel alone, and there a word an atomic touches is never loaded plainly; everything else one
+// kernel leaves for another crosses a kernel boundary on the one stream. Every loop has a bound no other thread can move. A state
+// word is written by lmm_skip_mark_kernel (only ever the value 1) and read by the classify of the NEXT piece.
 
 __device__ inline uint64_t mix64(uint64_t x) {  // the finaliser of splitmix64
     x ^= x >> 30;
@@ -228,8 +246,8 @@ __device__ inline uint64_t mix64(uint64_t x) {  // the finaliser of splitmix64
 
 // One wave per row: the tag is a mix of the sum, over the row's dwords, of a mix of (place, dword); a sum of integers, so the same
 // in any order. Never 0, which marks an empty slot.
-__global__ void __launch_bounds__(TB) lmm_cache_hash_kernel(const uint32_t* __restrict__ codes, uint32_t total, uint32_t ndc,
-                                                            uint64_t tag_mask, unsigned long long* __restrict__ row_tag) {
+__global__ void __launch_bounds__(TB) lmm_pattern_hash_kernel(const uint32_t* __restrict__ codes, uint32_t total, uint32_t ndc,
+                                                              uint64_t tag_mask, unsigned long long* __restrict__ row_tag) {
     const uint32_t t = blockIdx.x * (TB / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (t >= total) return;  // (wave-uniform)
     unsigned long long acc = 0;
@@ -243,8 +261,8 @@ __global__ void __launch_bounds__(TB) lmm_cache_hash_kernel(const uint32_t* __re
 // One lane per row. The probe sequence is a function of the tag alone, and a slot's tag never changes once set, so a tag ends in
 // the same slot all through a call. The owner of a slot new in this piece is the smallest row that reached it; a slot of an
 // earlier piece has owner 0, which the min leaves.
-__global__ void __launch_bounds__(TB) lmm_cache_claim_kernel(const unsigned long long* __restrict__ row_tag, uint32_t total, LmmCache c,
-                                                             uint32_t* __restrict__ slot_of) {
+__global__ void __launch_bounds__(TB) lmm_pattern_claim_kernel(const unsigned long long* __restrict__ row_tag, uint32_t total, LmmCache c,
+                                                               uint32_t* __restrict__ slot_of) {
     const uint32_t t = blockIdx.x * TB + threadIdx.x;
     if (t >= total) return;
     const unsigned long long mine = row_tag[t];
@@ -260,8 +278,8 @@ __global__ void __launch_bounds__(TB) lmm_cache_claim_kernel(const unsigned long
 }
 
 // One lane per (row, dword): an owner's code row goes into its slot.
-__global__ void __launch_bounds__(TB) lmm_cache_publish_kernel(const uint32_t* __restrict__ codes, uint32_t total, uint32_t ndc,
-                                                               const uint32_t* __restrict__ slot_of, LmmCache c) {
+__global__ void __launch_bounds__(TB) lmm_pattern_publish_kernel(const uint32_t* __restrict__ codes, uint32_t total, uint32_t ndc,
+                                                                 const uint32_t* __restrict__ slot_of, LmmCache c) {
     const uint64_t e = (uint64_t)blockIdx.x * TB + threadIdx.x;
     const uint64_t t = e / ndc;
     if (t >= total) return;
@@ -270,10 +288,11 @@ __global__ void __launch_bounds__(TB) lmm_cache_publish_kernel(const uint32_t* _
     c.key[(uint64_t)s * ndc + (e - t * ndc)] = codes[e];
 }
 
-// One wave per row: every row that reached a slot and is not its owner compares its whole code row with the slot's.
-__global__ void __launch_bounds__(TB) lmm_cache_classify_kernel(const uint32_t* __restrict__ codes, uint32_t total, uint32_t ndc,
-                                                                const uint32_t* __restrict__ slot_of, LmmCache c,
-                                                                uint32_t* __restrict__ cls) {
+// One wave per row: every row that reached a slot and is not its owner compares its whole code row with the slot's. Where slots
+// have a state it is read as it was when the piece began: no kernel between this one and the piece before writes it.
+__global__ void __launch_bounds__(TB) lmm_pattern_classify_kernel(const uint32_t* __restrict__ codes, uint32_t total, uint32_t ndc,
+                                                                  const uint32_t* __restrict__ slot_of, LmmCache c,
+                                                                  uint32_t* __restrict__ cls) {
     const uint32_t t = blockIdx.x * (TB / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (t >= total) return;  // (wave-uniform, as every branch below)
     const uint32_t s = slot_of[t];
@@ -285,30 +304,30 @@ __global__ void __launch_bounds__(TB) lmm_cache_classify_kernel(const uint32_t* 
     } else {
         uint32_t diff = 0;
         for (uint32_t j = lane; j < ndc; j += 64) diff |= codes[(uint64_t)t * ndc + j] ^ c.key[(uint64_t)s * ndc + j];
-        kind = __ballot(diff != 0u) ? LMM_ROW_COLLIDED : LMM_ROW_CACHED;
+        if (__ballot(diff != 0u))
+            kind = LMM_ROW_COLLIDED;
+        else if (!c.state)  // (a kernel argument)
+            kind = LMM_ROW_CACHED;
+        else
+            kind = c.state[s] != 0u ? LMM_ROW_DEAD : LMM_ROW_LIVE;
     }
     if (lane == 0) cls[t] = kind;
 }
 
-// The rows to rotate, compacted by the scheme of the front end: the count per block of 256 rows, lmm_table_scan_kernel, the emit.
-__global__ void __launch_bounds__(TB) lmm_cache_count_kernel(const uint32_t* __restrict__ cls, uint32_t total,
-                                                             uint32_t* __restrict__ block_cnt) {
-    __shared__ uint32_t s_wave[TB / 64];
-    const uint32_t t = blockIdx.x * TB + threadIdx.x;
-    const bool rotate = t < total && cls[t] != LMM_ROW_CACHED;
-    uint32_t n;
-    (void)block_rank(rotate, s_wave, n);
-    if (threadIdx.x == 0) block_cnt[blockIdx.x] = n;
-}
+// The rows to compute, compacted by the scheme of the front end: the count per block of 256 rows, lmm_table_scan_kernel, the emit.
+struct lmm_pattern_count {
+    const uint32_t* cls;
+    __device__ bool operator()(uint32_t t) const { return cls[t] != LMM_ROW_CACHED; }  // (LMM_ROW_DEAD is the same value)
+};
 
-__global__ void __launch_bounds__(TB) lmm_cache_emit_kernel(const uint32_t* __restrict__ codes, const LmmVariant* __restrict__ vars,
-                                                            const uint32_t* __restrict__ cls, uint32_t total, uint32_t ndc,
-                                                            const uint32_t* __restrict__ block_off, uint32_t* __restrict__ codes2,
-                                                            LmmVariant* __restrict__ vars2, uint32_t* __restrict__ back) {
+__global__ void __launch_bounds__(TB) lmm_pattern_emit_kernel(const uint32_t* __restrict__ codes, const LmmVariant* __restrict__ vars,
+                                                              const uint32_t* __restrict__ cls, uint32_t total, uint32_t ndc,
+                                                              const uint32_t* __restrict__ block_off, uint32_t* __restrict__ codes2,
+                                                              LmmVariant* __restrict__ vars2, uint32_t* __restrict__ back) {
     __shared__ uint32_t s_wave[TB / 64];
     __shared__ uint32_t s_slot[TB];
     const uint32_t row0 = blockIdx.x * TB, t = row0 + threadIdx.x;
-    const bool rotate = t < total && cls[t] != LMM_ROW_CACHED;
+    const bool rotate = t < total && lmm_pattern_count{cls}(t);
     uint32_t n;
     const uint32_t slot = block_off[blockIdx.x] + block_rank(rotate, s_wave, n);  // (<= t: at most t rows stand before row t)
     s_slot[threadIdx.x] = rotate && slot < total ? slot : LMM_CACHE_NONE;
@@ -365,32 +384,9 @@ __global__ void __launch_bounds__(TB) lmm_cache_fanout_kernel(const uint32_t* __
 }
 
 // ---- the dead-pattern skip of kgwas_lmm_test_table_multi_skip ("The dead-pattern skip") ----
-// The rules of the pattern cache hold: the table is touched by atomics in lmm_cache_claim_kernel alone, a state word is written by
-// lmm_skip_mark_kernel (only ever the value 1) and read by the classify of the NEXT piece, with kernel boundaries of the one stream
-// between them.
+// The rules of the pattern table hold; the state words of the table are this section's.
 
-// One wave per row, as lmm_cache_classify_kernel, with the slot's state as it was when the piece began: no kernel between this one
-// and the piece before writes it.
-__global__ void __launch_bounds__(TB) lmm_skip_classify_kernel(const uint32_t* __restrict__ codes, uint32_t total, uint32_t ndc,
-                                                               const uint32_t* __restrict__ slot_of, LmmCache c,
-                                                               const uint32_t* __restrict__ state, uint32_t* __restrict__ cls) {
-    const uint32_t t = blockIdx.x * (TB / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (t >= total) return;  // (wave-uniform, as every branch below)
-    const uint32_t s = slot_of[t];
-    uint32_t kind;
-    if (s >= c.slots) {
-        kind = LMM_ROW_REJECTED;
-    } else if (c.owner[s] == t + 1u) {
-        kind = LMM_ROW_OWNER;
-    } else {
-        uint32_t diff = 0;
-        for (uint32_t j = lane; j < ndc; j += 64) diff |= codes[(uint64_t)t * ndc + j] ^ c.key[(uint64_t)s * ndc + j];
-        kind = __ballot(diff != 0u) ? LMM_ROW_COLLIDED : state[s] != 0u ? LMM_ROW_DEAD : LMM_ROW_LIVE;
-    }
-    if (lane == 0) cls[t] = kind;
-}
-
-// One lane per compacted row: the table row index and the k-mer word follow the row (lmm_cache_emit_kernel left back[v] <= v).
+// One lane per compacted row: the table row index and the k-mer word follow the row (lmm_pattern_emit_kernel left back[v] <= v).
 __global__ void __launch_bounds__(TB) lmm_skip_gather_kernel(const uint32_t* __restrict__ back, const uint32_t* __restrict__ total2,
                                                              uint32_t total, const uint64_t* __restrict__ row,
                                                              const uint64_t* __restrict__ kmer, uint64_t* __restrict__ row2,
@@ -418,8 +414,7 @@ __global__ void __launch_bounds__(TB) lmm_skip_flag_kernel(const double* __restr
 // One lane per row of a sub-chunk after its last column block.
 __global__ void __launch_bounds__(TB) lmm_skip_mark_kernel(const uint32_t* __restrict__ shipped, uint32_t cc,
                                                            const uint32_t* __restrict__ back, const uint32_t* __restrict__ slot_of,
-                                                           const uint32_t* __restrict__ cls, uint32_t total, LmmCache c,
-                                                           uint32_t* __restrict__ state) {
+                                                           const uint32_t* __restrict__ cls, uint32_t total, LmmCache c) {
     const uint32_t v = blockIdx.x * TB + threadIdx.x;
     if (v >= cc) return;
     const uint32_t t = back[v];
@@ -427,43 +422,51 @@ __global__ void __launch_bounds__(TB) lmm_skip_mark_kernel(const uint32_t* __res
     const uint32_t s = slot_of[t], kind = cls[t];
     if (s >= c.slots || (kind != LMM_ROW_OWNER && kind != LMM_ROW_LIVE)) return;  // (a collided or rejected row has no slot of its own)
     if (kind == LMM_ROW_OWNER) c.owner[s] = 0u;
-    if (shipped[v] == 0u) state[s] = 1u;
+    if (shipped[v] == 0u) c.state[s] = 1u;
 }
 
-// per block of 256 slots the number of dead ones
-__global__ void __launch_bounds__(TB) lmm_skip_count_dead_kernel(const uint32_t* __restrict__ state, uint32_t slots,
-                                                                 uint32_t* __restrict__ block_cnt) {
-    __shared__ uint32_t s_wave[TB / 64];
-    const uint32_t s = blockIdx.x * TB + threadIdx.x;
-    const bool dead = s < slots && state[s] != 0u;
-    uint32_t n;
-    (void)block_rank(dead, s_wave, n);
-    if (threadIdx.x == 0) block_cnt[blockIdx.x] = n;
-}
+struct lmm_skip_dead_count {  // is slot s dead
+    const uint32_t* state;
+    __device__ bool operator()(uint32_t s) const { return state[s] != 0u; }
+};
 
 }  // namespace
 
-hipError_t launch_lmm_skip_lookup(const uint8_t* codes, const LmmVariant* vars, const uint64_t* row, const uint64_t* kmer, uint32_t total,
-                                  LmmDims dm, uint64_t tag_mask, LmmCache c, const uint32_t* state, unsigned long long* row_tag,
-                                  uint32_t* slot_of, uint32_t* cls, uint32_t* block_cnt, uint32_t* block_off, uint32_t* total2,
-                                  uint8_t* codes2, LmmVariant* vars2, uint64_t* row2, uint64_t* kmer2, uint32_t* back, hipStream_t st) {
-    // (the conditions of launch_lmm_cache_lookup)
+hipError_t launch_lmm_pattern_lookup(const uint8_t* codes, const LmmVariant* vars, const uint64_t* row, const uint64_t* kmer, uint32_t total,
+                                     LmmDims dm, uint64_t tag_mask, LmmCache c, LmmPiece pc, hipStream_t st) {
+    // (total2 would stay unwritten; a slot index must fit 31 bits; an empty mask would leave the one tag 1)
     if (!total || total >= (1u << 31) || dm.bpsp % 4u || !dm.bpsp || c.slots < 64u || c.slots > (1u << 30) || (c.slots & (c.slots - 1u)) ||
         !tag_mask)
         return hipErrorInvalidValue;
+    const bool gather = pc.row2 || pc.kmer2;
+    if (gather && !(pc.row2 && pc.kmer2 && row && kmer)) return hipErrorInvalidValue;
     const uint32_t ndc = dm.bpsp / 4, n_blocks = (total + TB - 1) / TB, n_waves = (total + TB / 64 - 1) / (TB / 64);
     const uint64_t n_words = ((uint64_t)total * ndc + TB - 1) / TB;
     if (n_words >= (1ull << 31)) return hipErrorInvalidValue;
     const uint32_t* cw = reinterpret_cast<const uint32_t*>(codes);
-    hipLaunchKernelGGL(lmm_cache_hash_kernel, dim3(n_waves), dim3(TB), 0, st, cw, total, ndc, tag_mask, row_tag);
-    hipLaunchKernelGGL(lmm_cache_claim_kernel, dim3(n_blocks), dim3(TB), 0, st, row_tag, total, c, slot_of);
-    hipLaunchKernelGGL(lmm_cache_publish_kernel, dim3((uint32_t)n_words), dim3(TB), 0, st, cw, total, ndc, slot_of, c);
-    hipLaunchKernelGGL(lmm_skip_classify_kernel, dim3(n_waves), dim3(TB), 0, st, cw, total, ndc, slot_of, c, state, cls);
-    hipLaunchKernelGGL(lmm_cache_count_kernel, dim3(n_blocks), dim3(TB), 0, st, cls, total, block_cnt);  // (every class but LMM_ROW_DEAD)
-    hipLaunchKernelGGL(lmm_table_scan_kernel, dim3(1), dim3(256), 0, st, block_cnt, n_blocks, block_off, total2);
-    hipLaunchKernelGGL(lmm_cache_emit_kernel, dim3(n_blocks), dim3(TB), 0, st, cw, vars, cls, total, ndc, block_off,
-                       reinterpret_cast<uint32_t*>(codes2), vars2, back);
-    hipLaunchKernelGGL(lmm_skip_gather_kernel, dim3(n_blocks), dim3(TB), 0, st, back, total2, total, row, kmer, row2, kmer2);
+    hipLaunchKernelGGL(lmm_pattern_hash_kernel, dim3(n_waves), dim3(TB), 0, st, cw, total, ndc, tag_mask, pc.row_tag);
+    hipLaunchKernelGGL(lmm_pattern_claim_kernel, dim3(n_blocks), dim3(TB), 0, st, pc.row_tag, total, c, pc.slot_of);
+    hipLaunchKernelGGL(lmm_pattern_publish_kernel, dim3((uint32_t)n_words), dim3(TB), 0, st, cw, total, ndc, pc.slot_of, c);
+    hipLaunchKernelGGL(lmm_pattern_classify_kernel, dim3(n_waves), dim3(TB), 0, st, cw, total, ndc, pc.slot_of, c, pc.cls);
+    count_and_scan(lmm_pattern_count{pc.cls}, total, pc.block_cnt, pc.block_off, pc.total2, st);
+    hipLaunchKernelGGL(lmm_pattern_emit_kernel, dim3(n_blocks), dim3(TB), 0, st, cw, vars, pc.cls, total, ndc, pc.block_off,
+                       reinterpret_cast<uint32_t*>(pc.codes2), pc.vars2, pc.back);
+    if (gather)
+        hipLaunchKernelGGL(lmm_skip_gather_kernel, dim3(n_blocks), dim3(TB), 0, st, pc.back, pc.total2, total, row, kmer, pc.row2, pc.kmer2);
+    return hipGetLastError();
+}
+
+hipError_t launch_lmm_cache_scatter(const double* lrt, const double* lam, const double* p, uint32_t first, uint32_t cc, uint32_t total,
+                                    LmmCache c, LmmPiece pc, double* r_lrt, double* r_lam, double* r_p, hipStream_t st) {
+    if (!cc || cc > total || first > total - cc || !c.res) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(lmm_cache_scatter_kernel, dim3((cc + TB - 1) / TB), dim3(TB), 0, st, lrt, lam, p, cc, pc.back + first, pc.slot_of,
+                       pc.cls, total, c, r_lrt, r_lam, r_p);
+    return hipGetLastError();
+}
+
+hipError_t launch_lmm_cache_fanout(uint32_t total, LmmCache c, LmmPiece pc, double* r_lrt, double* r_lam, double* r_p, hipStream_t st) {
+    if (!total || !c.res) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(lmm_cache_fanout_kernel, dim3((total + TB - 1) / TB), dim3(TB), 0, st, pc.slot_of, pc.cls, total, c, r_lrt, r_lam, r_p);
     return hipGetLastError();
 }
 
@@ -473,57 +476,17 @@ hipError_t launch_lmm_skip_flag(const double* lrt, const LmmSelectCol* cols, uin
     return hipGetLastError();
 }
 
-hipError_t launch_lmm_skip_mark(const uint32_t* shipped, uint32_t cc, const uint32_t* back, const uint32_t* slot_of, const uint32_t* cls,
-                                uint32_t total, LmmCache c, uint32_t* state, hipStream_t st) {
-    if (!cc || cc > total) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(lmm_skip_mark_kernel, dim3((cc + TB - 1) / TB), dim3(TB), 0, st, shipped, cc, back, slot_of, cls, total, c, state);
+hipError_t launch_lmm_skip_mark(const uint32_t* shipped, uint32_t first, uint32_t cc, uint32_t total, LmmCache c, LmmPiece pc,
+                                hipStream_t st) {
+    if (!cc || cc > total || first > total - cc || !c.state) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(lmm_skip_mark_kernel, dim3((cc + TB - 1) / TB), dim3(TB), 0, st, shipped, cc, pc.back + first, pc.slot_of, pc.cls, total,
+                       c);
     return hipGetLastError();
 }
 
-hipError_t launch_lmm_skip_count_dead(const uint32_t* state, uint32_t slots, uint32_t* block_cnt, uint32_t* block_off, uint32_t* dead,
-                                      hipStream_t st) {
-    if (slots < 64u || slots > (1u << 30)) return hipErrorInvalidValue;
-    const uint32_t n_blocks = (slots + TB - 1) / TB;
-    hipLaunchKernelGGL(lmm_skip_count_dead_kernel, dim3(n_blocks), dim3(TB), 0, st, state, slots, block_cnt);
-    hipLaunchKernelGGL(lmm_table_scan_kernel, dim3(1), dim3(256), 0, st, block_cnt, n_blocks, block_off, dead);
-    return hipGetLastError();
-}
-
-hipError_t launch_lmm_cache_lookup(const uint8_t* codes, const LmmVariant* vars, uint32_t total, LmmDims dm, uint64_t tag_mask, LmmCache c,
-                                   unsigned long long* row_tag, uint32_t* slot_of, uint32_t* cls, uint32_t* block_cnt, uint32_t* block_off,
-                                   uint32_t* total2, uint8_t* codes2, LmmVariant* vars2, uint32_t* back, hipStream_t st) {
-    // (total2 would stay unwritten; a slot index must fit 31 bits; an empty mask would leave the one tag 1)
-    if (!total || total >= (1u << 31) || dm.bpsp % 4u || !dm.bpsp || c.slots < 64u || c.slots > (1u << 30) || (c.slots & (c.slots - 1u)) ||
-        !tag_mask)
-        return hipErrorInvalidValue;
-    const uint32_t ndc = dm.bpsp / 4, n_blocks = (total + TB - 1) / TB, n_waves = (total + TB / 64 - 1) / (TB / 64);
-    const uint64_t n_words = ((uint64_t)total * ndc + TB - 1) / TB;
-    if (n_words >= (1ull << 31)) return hipErrorInvalidValue;
-    const uint32_t* cw = reinterpret_cast<const uint32_t*>(codes);
-    hipLaunchKernelGGL(lmm_cache_hash_kernel, dim3(n_waves), dim3(TB), 0, st, cw, total, ndc, tag_mask, row_tag);
-    hipLaunchKernelGGL(lmm_cache_claim_kernel, dim3(n_blocks), dim3(TB), 0, st, row_tag, total, c, slot_of);
-    hipLaunchKernelGGL(lmm_cache_publish_kernel, dim3((uint32_t)n_words), dim3(TB), 0, st, cw, total, ndc, slot_of, c);
-    hipLaunchKernelGGL(lmm_cache_classify_kernel, dim3(n_waves), dim3(TB), 0, st, cw, total, ndc, slot_of, c, cls);
-    hipLaunchKernelGGL(lmm_cache_count_kernel, dim3(n_blocks), dim3(TB), 0, st, cls, total, block_cnt);
-    hipLaunchKernelGGL(lmm_table_scan_kernel, dim3(1), dim3(256), 0, st, block_cnt, n_blocks, block_off, total2);
-    hipLaunchKernelGGL(lmm_cache_emit_kernel, dim3(n_blocks), dim3(TB), 0, st, cw, vars, cls, total, ndc, block_off,
-                       reinterpret_cast<uint32_t*>(codes2), vars2, back);
-    return hipGetLastError();
-}
-
-hipError_t launch_lmm_cache_scatter(const double* lrt, const double* lam, const double* p, uint32_t cc, const uint32_t* back,
-                                    const uint32_t* slot_of, const uint32_t* cls, uint32_t total, LmmCache c, double* r_lrt, double* r_lam,
-                                    double* r_p, hipStream_t st) {
-    if (!cc || cc > total) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(lmm_cache_scatter_kernel, dim3((cc + TB - 1) / TB), dim3(TB), 0, st, lrt, lam, p, cc, back, slot_of, cls, total, c,
-                       r_lrt, r_lam, r_p);
-    return hipGetLastError();
-}
-
-hipError_t launch_lmm_cache_fanout(const uint32_t* slot_of, const uint32_t* cls, uint32_t total, LmmCache c, double* r_lrt, double* r_lam,
-                                   double* r_p, hipStream_t st) {
-    if (!total) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(lmm_cache_fanout_kernel, dim3((total + TB - 1) / TB), dim3(TB), 0, st, slot_of, cls, total, c, r_lrt, r_lam, r_p);
+hipError_t launch_lmm_skip_count_dead(LmmCache c, uint32_t* block_cnt, uint32_t* block_off, uint32_t* dead, hipStream_t st) {
+    if (c.slots < 64u || c.slots > (1u << 30) || !c.state) return hipErrorInvalidValue;
+    count_and_scan(lmm_skip_dead_count{c.state}, c.slots, block_cnt, block_off, dead, st);
     return hipGetLastError();
 }
 
@@ -532,8 +495,7 @@ hipError_t launch_lmm_table_select(const double* lrt, const double* lam, const d
                                    uint32_t* block_off, uint32_t* count, LmmTableRecord* rec, uint32_t cap, hipStream_t st) {
     if (!cc || !pb || pb > LMM_PBLOCK || (uint64_t)pb * cc >= (1ull << 31)) return hipErrorInvalidValue;  // (count would stay unwritten)
     const uint32_t n = pb * cc, n_blocks = (n + TB - 1) / TB;
-    hipLaunchKernelGGL(lmm_table_select_count_kernel, dim3(n_blocks), dim3(TB), 0, st, lrt, cols, cc, n, block_cnt);
-    hipLaunchKernelGGL(lmm_table_scan_kernel, dim3(1), dim3(256), 0, st, block_cnt, n_blocks, block_off, count);
+    count_and_scan(lmm_table_select_count{lrt, cols, cc, n}, n, block_cnt, block_off, count, st);
     hipLaunchKernelGGL(lmm_table_select_kernel, dim3(n_blocks), dim3(TB), 0, st, lrt, lam, p, cols, cc, n, vars, row, kmer, block_off, rec,
                        cap);
     return hipGetLastError();

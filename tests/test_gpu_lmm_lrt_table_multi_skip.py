@@ -1,4 +1,4 @@
-"""lmm_lrt --pattern_skip (kgwas_lmm_test_table_multi_skip, the lmm_skip_* kernels of lmm_table_kernels.hip): in the multi-phenotype
+"""lmm_lrt --pattern_skip (kgwas_lmm_test_table_multi_skip, the lmm_pattern_* and lmm_skip_* kernels of lmm_table_kernels.hip): in the multi-phenotype
 table pass a pattern of which a fully computed row shipped no pair is dead, and later pieces leave its rows out.
 
 The yardstick everywhere is kgwas_lmm_test_table_multi on the same handle and table, at the same piece and chunk_variants: the

@@ -1,4 +1,4 @@
-"""lmm_lrt --pattern_cache (kgwas_lmm_test_table_unique, the lmm_cache_* kernels of lmm_table_kernels.hip): each distinct tested
+"""lmm_lrt --pattern_cache (kgwas_lmm_test_table_unique, the lmm_pattern_* and lmm_cache_* kernels of lmm_table_kernels.hip): each distinct tested
 pattern of a k-mers table goes through rotate, grid and refine once, every other row with it takes the stored result.
 
 The yardstick everywhere is kgwas_lmm_test_table on the same handle and table: row, kmer, lrt, lambda, p and af are compared by

@@ -60,14 +60,106 @@ import kmersgwas_amd as kg  # noqa: E402
 FP64_MATRIX_PEAK_TFLOPS = 78.6
 
 
-def bench_columns(a):
-    n, m, P = a.individuals, a.variants if a.variants != 10001 else 200000, a.columns
-    rng = np.random.default_rng(20240601)
+BINDIR = os.path.join(os.path.dirname(os.path.abspath(kg.__file__)), "bin")
+SEED = 20240601
+
+
+def synth_model(n, rng):
+    """K, y: the kinship matrix of 2 n synthetic markers and a phenotype with a polygenic part and one strong marker"""
     rows = 2 * n
     G = (rng.random((rows, n)) < rng.uniform(0.1, 0.9, rows)[:, None]).astype(np.float64)
     K = 1.0 - (G.T @ (1 - G) + (1 - G).T @ G) / rows
     d, U = np.linalg.eigh(K)
     y = rng.standard_normal(n) + 1.5 * ((U * np.sqrt(np.clip(d, 0, None))) @ rng.standard_normal(n)) + 1.2 * G[7]
+    return K, y
+
+
+def write_inputs(tmp, n, rows, K, Y, rng, fraction=None):
+    """The files of a --table mode in tmp: the synthetic k-mers table t.table of `rows` rows with t.names, the phenotype file (one
+    column v for a vector Y, columns P0 .. for a matrix, then with the column list cols.txt) and the kinship file. With `fraction`
+    the rows' presence words are drawn from max(1, round(fraction x rows)) distinct patterns, the presence words of the first
+    synthetic rows: every pattern is there at least once, the other rows take one at random, all placed at random. Returns the
+    paths and the number of distinct patterns."""
+    base = os.path.join(tmp, "t")
+    distinct = rows if fraction is None else max(1, min(rows, int(round(fraction * rows))))
+    pool = which = None
+    if fraction is not None:
+        pool = np.concatenate([kg.synth_rows_host(r0, min(1_000_000, distinct - r0), n, SEED)[:, 1:] for r0 in range(0, distinct, 1_000_000)])
+        which = rng.permutation(np.concatenate([np.arange(distinct), rng.integers(0, distinct, rows - distinct)]))
+    with open(base + ".table", "wb") as f:
+        f.write(np.uint32(0xDDCCBBAA).tobytes() + np.uint64(n).tobytes() + np.uint32(31).tobytes())
+        for r0 in range(0, rows, 1_000_000):
+            part = kg.synth_rows_host(r0, min(1_000_000, rows - r0), n, SEED)
+            if pool is not None:
+                part[:, 1:] = pool[which[r0:r0 + len(part)]]
+            part.tofile(f)
+    del pool, which
+    names = ["s%d" % i for i in range(n)]
+    open(base + ".names", "w").write("".join(x + "\n" for x in names))
+    ph, kin, lst = os.path.join(tmp, "ph.tsv"), os.path.join(tmp, "ph.kinship"), None
+    if Y.ndim == 1:
+        open(ph, "w").write("accession_id\tv\n" + "".join("%s\t%.6f\n" % (x, v) for x, v in zip(names, Y)))
+    else:
+        P = len(Y)
+        open(ph, "w").write("accession_id\t" + "\t".join("P%d" % k for k in range(P)) + "\n"
+                            + "".join(names[i] + "".join("\t%.6f" % Y[k, i] for k in range(P)) + "\n" for i in range(n)))
+        lst = os.path.join(tmp, "cols.txt")
+        open(lst, "w").write("".join("%d\tP%d\n" % (k + 1, k) for k in range(P)))
+    open(kin, "w").write("\n".join("\t".join("%.17g" % v for v in r) for r in K) + "\n")
+    return {"base": base, "ph": ph, "kin": kin, "lst": lst, "distinct": distinct}
+
+
+def table_cmd(inp, best, chunk_variants):
+    """lmm_lrt --kmers_table on the files of write_inputs; the mode adds the outputs and its options"""
+    return [os.path.join(BINDIR, "lmm_lrt"), "--kmers_table", inp["base"], "--kmers_len", "31", "-p", inp["ph"], "-lmm", "2", "-k", inp["kin"],
+            "--mac", "5", "-maf", "0.05", "--best", str(best), "--chunk_variants", str(chunk_variants)]
+
+
+def run_tool(cmd, env=None):
+    """the wall time of one run of a tool"""
+    t = time.perf_counter()
+    r = subprocess.run(cmd, capture_output=True, text=True, env=env)
+    if r.returncode != 0:
+        sys.exit("%s failed: %s" % (os.path.basename(cmd[0]), r.stderr[-2000:]))
+    return time.perf_counter() - t
+
+
+def read_log(outdir, name):
+    """a .log.txt as a dict: its key<TAB>value lines, and the kernels' split of its "ms: " line as floats"""
+    log = {}
+    for l in open(os.path.join(outdir, name + ".log.txt")).read().split("\n"):
+        if "\t" in l:
+            k, v = l.split("\t", 1)
+            log[k] = v
+        elif l.startswith("ms: "):
+            log.update((kv.split("=")[0], float(kv.split("=")[1])) for kv in l[4:].split())
+    return log
+
+
+def timed_runs(name, fn, reps, keys):
+    """A warm-up of fn and `reps` timed runs; fn returns a dict. Returns the runs and, per key, the record NAME_KEY (a key that names
+    no unit is a log's milliseconds): median, minimum, maximum."""
+    fn()
+    runs = [fn() for _ in range(reps)]
+    rec = {}
+    for k in keys:
+        v = sorted(float(r[k]) for r in runs)
+        rec["%s_%s" % (name, k if k.endswith(("_s", "_ms")) else k + "_ms")] = {"median": round(v[len(v) // 2], 3), "min": round(v[0], 3),
+                                                                              "max": round(v[-1], 3)}
+    return runs, rec
+
+
+LOG_KEYS = ("wall_s", "eigen", "rotate", "grid", "refine")
+
+
+def kernel_ms(line, name):
+    return sum(line["%s_%s_ms" % (name, k)]["median"] for k in ("rotate", "grid", "refine"))
+
+
+def bench_columns(a):
+    n, m, P = a.individuals, a.variants if a.variants != 10001 else 200000, a.columns
+    rng = np.random.default_rng(SEED)
+    K, y = synth_model(n, rng)
     Y = np.stack([y] + [rng.permutation(y) for _ in range(P - 1)])
     bps = (n + 3) // 4
     bed = np.zeros((m, bps), np.uint8)
@@ -77,43 +169,30 @@ def bench_columns(a):
         c = np.where(bits, 0, 3).astype(np.uint8).reshape(v1 - v0, bps, 4)
         bed[v0:v1] = c[:, :, 0] | (c[:, :, 1] << 2) | (c[:, :, 2] << 4) | (c[:, :, 3] << 6)
     lmm = kg.LmmLrt(K, chunk_variants=a.chunk_variants)
+    out = {}
 
-    def timed(fn):
-        before = lmm.stats()
-        t = time.perf_counter()
-        out = fn()
-        wall = time.perf_counter() - t
-        after = lmm.stats()
-        return out, dict(wall_s=wall, **{k: after[k] - before[k] for k in ("rotate_ms", "grid_ms", "refine_ms")})
+    def timed(name, fn):
+        def run():
+            before = lmm.stats()
+            t = time.perf_counter()
+            out[name] = fn()
+            wall = time.perf_counter() - t
+            after = lmm.stats()
+            return dict(wall_s=wall, **{k: after[k] - before[k] for k in ("rotate_ms", "grid_ms", "refine_ms")})
+        return timed_runs(name, run, a.reps, ("wall_s", "rotate_ms", "grid_ms", "refine_ms"))[1]
 
-    def run_multi():
-        return lmm.test_bed_multi(Y, bed, maf=0.05, miss=0.5)
-
-    def run_single():
-        return [lmm.test(bed, Y[k], maf=0.05, miss=0.5) for k in range(P)]
-
-    res = {}
-    for name, fn in (("multi", run_multi), ("single", run_single)):
-        timed(fn)  # warm-up
-        runs = []
-        for _ in range(a.reps):
-            out, t = timed(fn)
-            runs.append(t)
-        res[name] = (out, runs)
+    recs = [timed("multi", lambda: lmm.test_bed_multi(Y, bed, maf=0.05, miss=0.5)),
+            timed("single", lambda: [lmm.test(bed, Y[k], maf=0.05, miss=0.5) for k in range(P)])]
     lmm.close()
-    mo, so = res["multi"][0], res["single"][0]
+    mo, so = out["multi"], out["single"]
     same = all(mo[k][j].tobytes() == so[j][k].tobytes() for k in ("lrt", "lambda", "p") for j in range(P))
     same = same and all(mo[k].tobytes() == so[0][k].tobytes() for k in ("af", "n_miss", "tested"))
     line = {"columns": P, "variants": m, "individuals": n, "variants_tested": int(mo["tested"].sum()), "reps": a.reps, "same_bits": bool(same)}
-    for name in ("multi", "single"):
-        runs = res[name][1]
-        for k in ("wall_s", "rotate_ms", "grid_ms", "refine_ms"):
-            v = sorted(r[k] for r in runs)
-            line["%s_%s" % (name, k)] = {"median": round(v[len(v) // 2], 3), "min": round(v[0], 3), "max": round(v[-1], 3)}
+    for rec in recs:
+        line.update(rec)
     med = lambda name, k: line["%s_%s" % (name, k)]["median"]  # noqa: E731
-    kern = lambda name: med(name, "rotate_ms") + med(name, "grid_ms") + med(name, "refine_ms")  # noqa: E731
     line["wall_ratio"] = round(med("single", "wall_s") / med("multi", "wall_s"), 3)
-    line["kernel_ms_ratio"] = round(kern("single") / kern("multi"), 3)
+    line["kernel_ms_ratio"] = round(kernel_ms(line, "single") / kernel_ms(line, "multi"), 3)
     tf = 2.0 * n * 202 * m * (P + 2) / (med("multi", "grid_ms") * 1e-3) / 1e12
     line["multi_grid_tflops"] = round(tf, 3)
     line["multi_grid_fraction_of_fp64_matrix_peak"] = round(tf / FP64_MATRIX_PEAK_TFLOPS, 4)
@@ -125,79 +204,38 @@ def bench_columns(a):
 
 def bench_table(a):
     n, rows = a.individuals, a.table
-    bindir = os.path.join(os.path.dirname(os.path.abspath(kg.__file__)), "bin")
-    rng = np.random.default_rng(20240601)
-    g_rows = 2 * n
-    G = (rng.random((g_rows, n)) < rng.uniform(0.1, 0.9, g_rows)[:, None]).astype(np.float64)
-    K = 1.0 - (G.T @ (1 - G) + (1 - G).T @ G) / g_rows
-    d, U = np.linalg.eigh(K)
-    y = rng.standard_normal(n) + 1.5 * ((U * np.sqrt(np.clip(d, 0, None))) @ rng.standard_normal(n)) + 1.2 * G[7]
+    rng = np.random.default_rng(SEED)
+    K, y = synth_model(n, rng)
     tmp = tempfile.mkdtemp(prefix="bench_lmm_table_")
     try:
-        base = os.path.join(tmp, "t")
-        hdr = np.uint32(0xDDCCBBAA).tobytes() + np.uint64(n).tobytes() + np.uint32(31).tobytes()
-        with open(base + ".table", "wb") as f:
-            f.write(hdr)
-            for r0 in range(0, rows, 1_000_000):
-                kg.synth_rows_host(r0, min(1_000_000, rows - r0), n, 20240601).tofile(f)
-        names = ["s%d" % i for i in range(n)]
-        open(base + ".names", "w").write("".join(x + "\n" for x in names))
-        ph = os.path.join(tmp, "ph.tsv")
-        open(ph, "w").write("accession_id\tv\n" + "".join("%s\t%.6f\n" % (x, v) for x, v in zip(names, y)))
-        kin = os.path.join(tmp, "ph.kinship")
-        open(kin, "w").write("\n".join("\t".join("%.17g" % v for v in r) for r in K) + "\n")
+        inp = write_inputs(tmp, n, rows, K, y, rng)
         out = os.path.join(tmp, "out")
 
-        def tool(cmd):
-            t = time.perf_counter()
-            r = subprocess.run(cmd, capture_output=True, text=True)
-            if r.returncode != 0:
-                sys.exit("%s failed: %s" % (cmd[0], r.stderr[-2000:]))
-            return time.perf_counter() - t
-
-        def log_of(name):
-            log = {}
-            for l in open(os.path.join(out, name + ".log.txt")).read().split("\n"):
-                if "\t" in l:
-                    k, v = l.split("\t", 1)
-                    log[k] = v
-                elif l.startswith("ms: "):
-                    log.update((kv.split("=")[0], float(kv.split("=")[1])) for kv in l[4:].split())
-            return log
-
         def table_route():
-            wall = tool([os.path.join(bindir, "lmm_lrt"), "--kmers_table", base, "--kmers_len", "31", "-p", ph, "-lmm", "2", "-k", kin,
-                         "--mac", "5", "-maf", "0.05", "--best", "10001", "-outdir", out, "-o", "table",
-                         "--chunk_variants", str(a.chunk_variants)])
-            return dict(wall_s=wall, **log_of("table"))
+            wall = run_tool(table_cmd(inp, 10001, a.chunk_variants) + ["-outdir", out, "-o", "table"])
+            return dict(wall_s=wall, **read_log(out, "table"))
 
         def bed_route():
             for f in os.listdir(tmp):
                 if f.startswith("plink."):
                     os.remove(os.path.join(tmp, f))
-            t1 = tool([os.path.join(bindir, "kmers_table_to_bed"), "-t", base, "-k", "31", "-p", ph, "--maf", "0.05", "--mac", "5",
-                       "-b", str(rows + 1), "-o", os.path.join(tmp, "plink")])
-            t2 = tool([os.path.join(bindir, "lmm_lrt"), "-bfile", os.path.join(tmp, "plink.0"), "-lmm", "2", "-k", kin, "-maf", "0.05",
-                       "-outdir", out, "-o", "bed", "--chunk_variants", str(a.chunk_variants)])
-            return dict(wall_s=t1 + t2, table_to_bed_s=t1, lmm_lrt_s=t2, **log_of("bed"))
+            t1 = run_tool([os.path.join(BINDIR, "kmers_table_to_bed"), "-t", inp["base"], "-k", "31", "-p", inp["ph"], "--maf", "0.05",
+                           "--mac", "5", "-b", str(rows + 1), "-o", os.path.join(tmp, "plink")])
+            t2 = run_tool([os.path.join(BINDIR, "lmm_lrt"), "-bfile", os.path.join(tmp, "plink.0"), "-lmm", "2", "-k", inp["kin"], "-maf", "0.05",
+                           "-outdir", out, "-o", "bed", "--chunk_variants", str(a.chunk_variants)])
+            return dict(wall_s=t1 + t2, table_to_bed_s=t1, lmm_lrt_s=t2, **read_log(out, "bed"))
 
         line = {"table_rows": rows, "individuals": n, "best": 10001, "reps": a.reps}
-        for name, fn in (("table", table_route), ("bed", bed_route)):
-            fn()  # warm-up
-            runs = [fn() for _ in range(a.reps)]
-            keys = ["wall_s", "eigen", "rotate", "grid", "refine"] + (["table_to_bed_s", "lmm_lrt_s"] if name == "bed" else [])
-            for k in keys:
-                v = sorted(float(r[k]) for r in runs)
-                line["%s_%s" % (name, k if k.endswith("_s") else k + "_ms")] = {"median": round(v[len(v) // 2], 3), "min": round(v[0], 3), "max": round(v[-1], 3)}
-            if name == "table":
-                line["rows_tested"], line["rows_kept"] = int(runs[0]["rows_tested"]), int(runs[0]["rows_kept"])
-            else:
-                line["bed_variants_tested"] = int(runs[0]["variants_tested"])
+        runs, rec = timed_runs("table", table_route, a.reps, LOG_KEYS)
+        line.update(rec)
+        line["rows_tested"], line["rows_kept"] = int(runs[0]["rows_tested"]), int(runs[0]["rows_kept"])
+        runs, rec = timed_runs("bed", bed_route, a.reps, LOG_KEYS + ("table_to_bed_s", "lmm_lrt_s"))
+        line.update(rec)
+        line["bed_variants_tested"] = int(runs[0]["variants_tested"])
         wall = line["table_wall_s"]["median"]
         line["rows_per_s"] = round(rows / wall)
         line["tested_rows_per_s"] = round(line["rows_tested"] / wall)
-        kern = sum(line["table_%s_ms" % k]["median"] for k in ("rotate", "grid", "refine"))
-        line["kernel_ms_per_million_tested"] = round(kern / max(line["rows_tested"], 1) * 1e6, 3)
+        line["kernel_ms_per_million_tested"] = round(kernel_ms(line, "table") / max(line["rows_tested"], 1) * 1e6, 3)
         line["wall_ratio_bed_over_table"] = round(line["bed_wall_s"]["median"] / wall, 3)
         print(json.dumps(line))
         return 0 if line["rows_tested"] == line["bed_variants_tested"] else 1
@@ -207,77 +245,32 @@ def bench_table(a):
 
 def bench_table_cache(a):
     n, rows = a.individuals, a.table
-    bindir = os.path.join(os.path.dirname(os.path.abspath(kg.__file__)), "bin")
-    rng = np.random.default_rng(20240601)
-    g_rows = 2 * n
-    G = (rng.random((g_rows, n)) < rng.uniform(0.1, 0.9, g_rows)[:, None]).astype(np.float64)
-    K = 1.0 - (G.T @ (1 - G) + (1 - G).T @ G) / g_rows
-    d, U = np.linalg.eigh(K)
-    y = rng.standard_normal(n) + 1.5 * ((U * np.sqrt(np.clip(d, 0, None))) @ rng.standard_normal(n)) + 1.2 * G[7]
+    rng = np.random.default_rng(SEED)
+    K, y = synth_model(n, rng)
     tmp = tempfile.mkdtemp(prefix="bench_lmm_cache_")
     try:
-        base = os.path.join(tmp, "t")
-        hdr = np.uint32(0xDDCCBBAA).tobytes() + np.uint64(n).tobytes() + np.uint32(31).tobytes()
-        distinct = rows if a.distinct is None else max(1, min(rows, int(round(a.distinct * rows))))
-        pool = which = None
-        if a.distinct is not None:  # the pool's patterns are the presence words of the first `distinct` synthetic rows
-            pool = np.concatenate([kg.synth_rows_host(r0, min(1_000_000, distinct - r0), n, 20240601)[:, 1:]
-                                   for r0 in range(0, distinct, 1_000_000)])
-            which = rng.permutation(np.concatenate([np.arange(distinct), rng.integers(0, distinct, rows - distinct)]))
-        with open(base + ".table", "wb") as f:
-            f.write(hdr)
-            for r0 in range(0, rows, 1_000_000):
-                part = kg.synth_rows_host(r0, min(1_000_000, rows - r0), n, 20240601)
-                if pool is not None:
-                    part[:, 1:] = pool[which[r0:r0 + len(part)]]
-                part.tofile(f)
-        del pool, which
-        names = ["s%d" % i for i in range(n)]
-        open(base + ".names", "w").write("".join(x + "\n" for x in names))
-        ph = os.path.join(tmp, "ph.tsv")
-        open(ph, "w").write("accession_id\tv\n" + "".join("%s\t%.6f\n" % (x, v) for x, v in zip(names, y)))
-        kin = os.path.join(tmp, "ph.kinship")
-        open(kin, "w").write("\n".join("\t".join("%.17g" % v for v in r) for r in K) + "\n")
+        inp = write_inputs(tmp, n, rows, K, y, rng, a.distinct)
         out = os.path.join(tmp, "out")
 
         def route(name, extra):
-            t = time.perf_counter()
-            r = subprocess.run([os.path.join(bindir, "lmm_lrt"), "--kmers_table", base, "--kmers_len", "31", "-p", ph, "-lmm", "2", "-k", kin,
-                                "--mac", "5", "-maf", "0.05", "--best", "10001", "-outdir", out, "-o", name,
-                                "--chunk_variants", str(a.chunk_variants)] + extra, capture_output=True, text=True)
-            wall = time.perf_counter() - t
-            if r.returncode != 0:
-                sys.exit("lmm_lrt failed: %s" % r.stderr[-2000:])
-            log = {}
-            for l in open(os.path.join(out, name + ".log.txt")).read().split("\n"):
-                if "\t" in l:
-                    k, v = l.split("\t", 1)
-                    log[k] = v
-                elif l.startswith("ms: "):
-                    log.update((kv.split("=")[0], float(kv.split("=")[1])) for kv in l[4:].split())
-            return dict(wall_s=wall, **log)
+            wall = run_tool(table_cmd(inp, 10001, a.chunk_variants) + ["-outdir", out, "-o", name] + extra)
+            return dict(wall_s=wall, **read_log(out, name))
 
-        line = {"table_rows": rows, "individuals": n, "distinct_patterns": distinct, "best": 10001, "reps": a.reps}
-        routes = [("table", [])] + ([("cache", ["--pattern_cache", str(a.pattern_cache)])] if a.pattern_cache else [])
-        for name, extra in routes:
-            route(name, extra)  # warm-up
-            runs = [route(name, extra) for _ in range(a.reps)]
-            for k in ("wall_s", "eigen", "rotate", "grid", "refine"):
-                v = sorted(float(r[k]) for r in runs)
-                line["%s_%s" % (name, k if k.endswith("_s") else k + "_ms")] = {"median": round(v[len(v) // 2], 3), "min": round(v[0], 3), "max": round(v[-1], 3)}
-            if name == "table":
-                line["rows_tested"], line["rows_kept"] = int(runs[0]["rows_tested"]), int(runs[0]["rows_kept"])
-            else:
-                line["pattern_cache_mib"] = a.pattern_cache
-                for k in ("pattern_cache_slots", "patterns_cached", "rows_from_cache", "rows_collided", "rows_rejected", "rows_rotated"):
-                    line[k] = int(runs[0][k])
+        line = {"table_rows": rows, "individuals": n, "distinct_patterns": inp["distinct"], "best": 10001, "reps": a.reps}
+        runs, rec = timed_runs("table", lambda: route("table", []), a.reps, LOG_KEYS)
+        line.update(rec)
+        line["rows_tested"], line["rows_kept"] = int(runs[0]["rows_tested"]), int(runs[0]["rows_kept"])
         same = True
         if a.pattern_cache:
+            runs, rec = timed_runs("cache", lambda: route("cache", ["--pattern_cache", str(a.pattern_cache)]), a.reps, LOG_KEYS)
+            line.update(rec)
+            line["pattern_cache_mib"] = a.pattern_cache
+            for k in ("pattern_cache_slots", "patterns_cached", "rows_from_cache", "rows_collided", "rows_rejected", "rows_rotated"):
+                line[k] = int(runs[0][k])
             same = open(os.path.join(out, "table.assoc.txt"), "rb").read() == open(os.path.join(out, "cache.assoc.txt"), "rb").read()
             line["same_bytes"] = bool(same)
             line["wall_ratio_table_over_cache"] = round(line["table_wall_s"]["median"] / line["cache_wall_s"]["median"], 3)
-            kern = lambda name: sum(line["%s_%s_ms" % (name, k)]["median"] for k in ("rotate", "grid", "refine"))  # noqa: E731
-            line["kernel_ms_ratio_table_over_cache"] = round(kern("table") / max(kern("cache"), 1e-9), 3)
+            line["kernel_ms_ratio_table_over_cache"] = round(kernel_ms(line, "table") / max(kernel_ms(line, "cache"), 1e-9), 3)
         print(json.dumps(line))
         return 0 if same else 1
     finally:
@@ -286,72 +279,31 @@ def bench_table_cache(a):
 
 def bench_table_multi(a):
     n, rows, P = a.individuals, a.table, a.pheno_columns
-    bindir = os.path.join(os.path.dirname(os.path.abspath(kg.__file__)), "bin")
-    rng = np.random.default_rng(20240601)
-    g_rows = 2 * n
-    G = (rng.random((g_rows, n)) < rng.uniform(0.1, 0.9, g_rows)[:, None]).astype(np.float64)
-    K = 1.0 - (G.T @ (1 - G) + (1 - G).T @ G) / g_rows
-    d, U = np.linalg.eigh(K)
-    y = rng.standard_normal(n) + 1.5 * ((U * np.sqrt(np.clip(d, 0, None))) @ rng.standard_normal(n)) + 1.2 * G[7]
+    rng = np.random.default_rng(SEED)
+    K, y = synth_model(n, rng)
     Y = np.stack([y] + [rng.permutation(y) for _ in range(P - 1)])
     tmp = tempfile.mkdtemp(prefix="bench_lmm_table_multi_")
     try:
-        base = os.path.join(tmp, "t")
-        hdr = np.uint32(0xDDCCBBAA).tobytes() + np.uint64(n).tobytes() + np.uint32(31).tobytes()
-        with open(base + ".table", "wb") as f:
-            f.write(hdr)
-            for r0 in range(0, rows, 1_000_000):
-                kg.synth_rows_host(r0, min(1_000_000, rows - r0), n, 20240601).tofile(f)
-        names = ["s%d" % i for i in range(n)]
-        open(base + ".names", "w").write("".join(x + "\n" for x in names))
-        ph = os.path.join(tmp, "ph.tsv")
-        open(ph, "w").write("accession_id\t" + "\t".join("P%d" % k for k in range(P)) + "\n"
-                            + "".join(names[i] + "".join("\t%.6f" % Y[k, i] for k in range(P)) + "\n" for i in range(n)))
-        kin = os.path.join(tmp, "ph.kinship")
-        open(kin, "w").write("\n".join("\t".join("%.17g" % v for v in r) for r in K) + "\n")
-        lst = os.path.join(tmp, "cols.txt")
-        open(lst, "w").write("".join("%d\tP%d\n" % (k + 1, k) for k in range(P)))
-        common = [os.path.join(bindir, "lmm_lrt"), "--kmers_table", base, "--kmers_len", "31", "-p", ph, "-lmm", "2", "-k", kin, "--mac", "5",
-                  "-maf", "0.05", "--best", "10001", "--chunk_variants", str(a.chunk_variants)]
-
-        def tool(args, env=None):
-            t = time.perf_counter()
-            r = subprocess.run(common + args, capture_output=True, text=True, env=env)
-            if r.returncode != 0:
-                sys.exit("lmm_lrt failed: %s" % r.stderr[-2000:])
-            return time.perf_counter() - t
-
-        def log_of(outdir, name):
-            log = {}
-            for l in open(os.path.join(outdir, name + ".log.txt")).read().split("\n"):
-                if "\t" in l:
-                    k, v = l.split("\t", 1)
-                    log[k] = v
-                elif l.startswith("ms: "):
-                    log.update((kv.split("=")[0], float(kv.split("=")[1])) for kv in l[4:].split())
-            return log
-
+        inp = write_inputs(tmp, n, rows, K, Y, rng)
+        common = table_cmd(inp, 10001, a.chunk_variants)
         subset = sorted(set(np.linspace(0, P - 1, max(1, min(a.subset, P))).astype(int).tolist()))
         out_a, out_b, out_c = (os.path.join(tmp, d) for d in ("multi", "single", "noselect"))
         off = dict(os.environ, KGWAS_LMM_TABLE_SELECT="0")
 
         def run_a():
-            return dict(wall_s=tool(["-outdir", out_a, "--pheno_columns", lst]), **log_of(out_a, "P0"))
+            return dict(wall_s=run_tool(common + ["-outdir", out_a, "--pheno_columns", inp["lst"]]), **read_log(out_a, "P0"))
 
         def run_c():
-            return dict(wall_s=tool(["-outdir", out_c, "--pheno_columns", lst], env=off), **log_of(out_c, "P0"))
+            return dict(wall_s=run_tool(common + ["-outdir", out_c, "--pheno_columns", inp["lst"]], env=off), **read_log(out_c, "P0"))
 
         def run_b():
-            walls = [tool(["-outdir", out_b, "-n", str(k + 1), "-o", "P%d" % k]) for k in subset]
-            return dict(wall_s=sum(walls) * P / len(subset), measured_s=sum(walls), **log_of(out_b, "P%d" % subset[0]))
+            walls = [run_tool(common + ["-outdir", out_b, "-n", str(k + 1), "-o", "P%d" % k]) for k in subset]
+            return dict(wall_s=sum(walls) * P / len(subset), measured_s=sum(walls), **read_log(out_b, "P%d" % subset[0]))
 
         line = {"table_rows": rows, "individuals": n, "columns": P, "best": 10001, "reps": a.reps, "single_subset": [k + 1 for k in subset]}
         for name, fn in (("multi", run_a), ("single_scaled", run_b), ("multi_noselect", run_c)):
-            fn()  # warm-up
-            runs = [fn() for _ in range(a.reps)]
-            for k in ("wall_s", "eigen", "rotate", "grid", "refine"):
-                v = sorted(float(r[k]) for r in runs)
-                line["%s_%s" % (name, k if k.endswith("_s") else k + "_ms")] = {"median": round(v[len(v) // 2], 3), "min": round(v[0], 3), "max": round(v[-1], 3)}
+            runs, rec = timed_runs(name, fn, a.reps, LOG_KEYS)
+            line.update(rec)
             if name == "multi":
                 line["rows_tested"] = int(runs[0]["rows_tested"])
         same = all(open(os.path.join(d, "P%d.assoc.txt" % k), "rb").read() == open(os.path.join(out_a, "P%d.assoc.txt" % k), "rb").read()
@@ -361,7 +313,7 @@ def bench_table_multi(a):
         line["wall_ratio_single_over_multi"] = round(med("single_scaled") / med("multi"), 3)
         line["wall_ratio_noselect_over_multi"] = round(med("multi_noselect") / med("multi"), 3)
         # the selection's share, from the library on the same files (one more pass, not timed)
-        tbl = kg.KmersTable(base, 31)
+        tbl = kg.KmersTable(inp["base"], 31)
         lmm = kg.LmmLrt(K, chunk_variants=a.chunk_variants)
         # the values the tool tests: the file's "%.6f" text as the loader's float32, printed with six significant digits, parsed again
         Yt = np.array([[float("%g" % np.float32(float("%.6f" % v))) for v in row] for row in Y])
@@ -378,78 +330,32 @@ def bench_table_multi(a):
 
 def bench_table_multi_skip(a):
     n, rows, P, best = a.individuals, a.table, a.pheno_columns, a.best
-    bindir = os.path.join(os.path.dirname(os.path.abspath(kg.__file__)), "bin")
-    rng = np.random.default_rng(20240601)
-    g_rows = 2 * n
-    G = (rng.random((g_rows, n)) < rng.uniform(0.1, 0.9, g_rows)[:, None]).astype(np.float64)
-    K = 1.0 - (G.T @ (1 - G) + (1 - G).T @ G) / g_rows
-    d, U = np.linalg.eigh(K)
-    y = rng.standard_normal(n) + 1.5 * ((U * np.sqrt(np.clip(d, 0, None))) @ rng.standard_normal(n)) + 1.2 * G[7]
+    rng = np.random.default_rng(SEED)
+    K, y = synth_model(n, rng)
     Y = np.stack([y] + [rng.permutation(y) for _ in range(P - 1)])
     tmp = tempfile.mkdtemp(prefix="bench_lmm_skip_")
     try:
-        base = os.path.join(tmp, "t")
-        hdr = np.uint32(0xDDCCBBAA).tobytes() + np.uint64(n).tobytes() + np.uint32(31).tobytes()
-        distinct = rows if a.distinct is None else max(1, min(rows, int(round(a.distinct * rows))))
-        pool = which = None
-        if a.distinct is not None:  # as bench_table_cache: the pool's patterns are the presence words of the first `distinct` synthetic rows
-            pool = np.concatenate([kg.synth_rows_host(r0, min(1_000_000, distinct - r0), n, 20240601)[:, 1:]
-                                   for r0 in range(0, distinct, 1_000_000)])
-            which = rng.permutation(np.concatenate([np.arange(distinct), rng.integers(0, distinct, rows - distinct)]))
-        with open(base + ".table", "wb") as f:
-            f.write(hdr)
-            for r0 in range(0, rows, 1_000_000):
-                part = kg.synth_rows_host(r0, min(1_000_000, rows - r0), n, 20240601)
-                if pool is not None:
-                    part[:, 1:] = pool[which[r0:r0 + len(part)]]
-                part.tofile(f)
-        del pool, which
-        names = ["s%d" % i for i in range(n)]
-        open(base + ".names", "w").write("".join(x + "\n" for x in names))
-        ph = os.path.join(tmp, "ph.tsv")
-        open(ph, "w").write("accession_id\t" + "\t".join("P%d" % k for k in range(P)) + "\n"
-                            + "".join(names[i] + "".join("\t%.6f" % Y[k, i] for k in range(P)) + "\n" for i in range(n)))
-        kin = os.path.join(tmp, "ph.kinship")
-        open(kin, "w").write("\n".join("\t".join("%.17g" % v for v in r) for r in K) + "\n")
-        lst = os.path.join(tmp, "cols.txt")
-        open(lst, "w").write("".join("%d\tP%d\n" % (k + 1, k) for k in range(P)))
-        common = [os.path.join(bindir, "lmm_lrt"), "--kmers_table", base, "--kmers_len", "31", "-p", ph, "-lmm", "2", "-k", kin, "--mac", "5",
-                  "-maf", "0.05", "--best", str(best), "--chunk_variants", str(a.chunk_variants), "--pheno_columns", lst]
+        inp = write_inputs(tmp, n, rows, K, Y, rng, a.distinct)
+        common = table_cmd(inp, best, a.chunk_variants) + ["--pheno_columns", inp["lst"]]
 
         def route(name, extra):
             outdir = os.path.join(tmp, name)
-            t = time.perf_counter()
-            r = subprocess.run(common + ["-outdir", outdir] + extra, capture_output=True, text=True)
-            wall = time.perf_counter() - t
-            if r.returncode != 0:
-                sys.exit("lmm_lrt failed: %s" % r.stderr[-2000:])
+            wall = run_tool(common + ["-outdir", outdir] + extra)
             print("%s: %.1f s" % (name, wall), file=sys.stderr, flush=True)
-            log = {}
-            for l in open(os.path.join(outdir, "P0.log.txt")).read().split("\n"):
-                if "\t" in l:
-                    k, v = l.split("\t", 1)
-                    log[k] = v
-                elif l.startswith("ms: "):
-                    log.update((kv.split("=")[0], float(kv.split("=")[1])) for kv in l[4:].split())
-            return dict(wall_s=wall, **log)
+            return dict(wall_s=wall, **read_log(outdir, "P0"))
 
-        line = {"table_rows": rows, "individuals": n, "columns": P, "distinct_patterns": distinct, "best": best, "reps": a.reps,
+        line = {"table_rows": rows, "individuals": n, "columns": P, "distinct_patterns": inp["distinct"], "best": best, "reps": a.reps,
                 "pattern_skip_mib": a.pattern_skip}
-        for name, extra in (("skip", ["--pattern_skip", str(a.pattern_skip)]), ("plain", [])):
-            route(name, extra)  # warm-up
-            runs = [route(name, extra) for _ in range(a.reps)]
-            for k in ("wall_s", "eigen", "rotate", "grid", "refine"):
-                v = sorted(float(r[k]) for r in runs)
-                line["%s_%s" % (name, k if k.endswith("_s") else k + "_ms")] = {"median": round(v[len(v) // 2], 3), "min": round(v[0], 3), "max": round(v[-1], 3)}
-            if name == "skip":
-                line["rows_tested"] = int(runs[0]["rows_tested"])
-                for k in ("pattern_skip_slots", "patterns_cached", "patterns_dead", "rows_skipped", "rows_collided", "rows_rejected", "rows_rotated"):
-                    line[k] = int(runs[0][k])
+        runs, rec = timed_runs("skip", lambda: route("skip", ["--pattern_skip", str(a.pattern_skip)]), a.reps, LOG_KEYS)
+        line.update(rec)
+        line["rows_tested"] = int(runs[0]["rows_tested"])
+        for k in ("pattern_skip_slots", "patterns_cached", "patterns_dead", "rows_skipped", "rows_collided", "rows_rejected", "rows_rotated"):
+            line[k] = int(runs[0][k])
+        line.update(timed_runs("plain", lambda: route("plain", []), a.reps, LOG_KEYS)[1])
         same = all(subprocess.run(["cmp", "-s", os.path.join(tmp, "skip", "P%d.assoc.txt" % k), os.path.join(tmp, "plain", "P%d.assoc.txt" % k)]).returncode == 0
                    for k in range(P))
         line["same_bytes"] = bool(same)
-        kern = lambda name: sum(line["%s_%s_ms" % (name, k)]["median"] for k in ("rotate", "grid", "refine"))  # noqa: E731
-        line["kernel_ms_ratio_plain_over_skip"] = round(kern("plain") / max(kern("skip"), 1e-9), 3)
+        line["kernel_ms_ratio_plain_over_skip"] = round(kernel_ms(line, "plain") / max(kernel_ms(line, "skip"), 1e-9), 3)
         line["wall_ratio_plain_over_skip"] = round(line["plain_wall_s"]["median"] / line["skip_wall_s"]["median"], 3)
         print(json.dumps(line))
         return 0 if same else 1
@@ -502,11 +408,7 @@ def main():
         sys.exit(bench_columns(a))
     n, m = a.individuals, a.variants
     rng = np.random.default_rng(20240601)
-    rows = 2 * n
-    G = (rng.random((rows, n)) < rng.uniform(0.1, 0.9, rows)[:, None]).astype(np.float64)
-    K = 1.0 - (G.T @ (1 - G) + (1 - G).T @ G) / rows
-    d, U = np.linalg.eigh(K)
-    y = rng.standard_normal(n) + 1.5 * ((U * np.sqrt(np.clip(d, 0, None))) @ rng.standard_normal(n)) + 1.2 * G[7]
+    K, y = synth_model(n, rng)
     bps = (n + 3) // 4
     t0 = time.perf_counter()
     lmm = kg.LmmLrt(K, chunk_variants=a.chunk_variants)
