@@ -152,8 +152,11 @@ struct MxArgs {
     float eg_max, rall_max, rmax_max;  // as CoarseArgs, in accumulator units
 };
 size_t mx_lds_bytes(uint32_t n_steps, uint32_t CT, uint32_t n_slices, uint32_t s1_fp6);
-uint32_t mx_step_bytes_rt(uint32_t n_slices, uint32_t s1_fp6);
-uint32_t mx_row_tiles(uint32_t CT);  // 16-row tiles per wave pass for this many column tiles
+// Operand bytes of one (MFMA step, column tile), for the kernels and the operand builder alike: the FP6 slice is 64 lanes x
+// 16 B, then 64 lanes x 8 B (1536); the second slice follows in the same layout, an FP4 one with its 16-byte pieces only.
+__host__ __device__ constexpr uint32_t mx_step_bytes(uint32_t n_slices, uint32_t s1_fp6) {
+    return n_slices == 1 ? 1536u : (s1_fp6 ? 2u * 1536u : 1536u + 1024u);
+}
 hipError_t launch_mx(const MxArgs& a, uint32_t CT, uint32_t rows_per_block, hipStream_t st);
 // The same filter with its operands STREAMED through an LDS ring instead of resident (score_mxs.hip): the waves of a block keep
 // the accumulators of ALL column tiles of an operand group (NG column groups of CT tiles: up to 14 tiles, 222 columns), so a row

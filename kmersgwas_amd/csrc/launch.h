@@ -42,6 +42,24 @@ inline void launch_last(void (*kernel)(KA...), dim3 grid, dim3 block, size_t lds
     (void)launch_bound_impl(kernel, grid, block, lds, st, stop, vals, std::index_sequence_for<KA...>{});  // (the launcher reads hipGetLastError)
 }
 
+// The launch shape of a matrix filter (score_coarse.hip, score_mx.hip, score_mxs.hip). The kernels address rows with 32-bit
+// byte offsets, so the chunk must span < 4 GiB; rows_per_block is rounded up to whole block passes of rpp rows; with
+// grid_lg every (row block, LDS / operand group) pair is a block, the row blocks padded to a multiple of 8 (filter_block in
+// filter_common.h undoes the interleave); above 64 KB the kernel's dynamic shared memory has to be asked for.
+struct FilterGrid {
+    uint32_t rows_per_block, n_rowblocks, grid;
+};
+template <class Args>
+inline hipError_t filter_grid(const void* kernel, const Args& a, uint32_t rpp, uint32_t rows_per_block, bool grid_lg, size_t lds, FilterGrid& g) {
+    if ((a.n_rows * a.src.stride_dw + a.src.off_dw + a.src.avail_dw) * 4ull >= (1ull << 32)) return hipErrorInvalidValue;
+    if (lds > 160u * 1024u) return hipErrorInvalidValue;
+    g.rows_per_block = (rows_per_block + rpp - 1) / rpp * rpp;
+    g.n_rowblocks = (uint32_t)((a.n_rows + g.rows_per_block - 1) / g.rows_per_block);
+    g.grid = grid_lg ? (g.n_rowblocks + 7u) / 8u * 8u * a.n_lgroups : g.n_rowblocks;
+    if (lds > 64 * 1024) return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    return hipSuccess;
+}
+
 // run `launcher` (which ends in a launch_last) with `ev` bound to its last kernel; recorded behind it if nothing took it
 template <class F>
 inline hipError_t bind_stop(hipEvent_t ev, hipStream_t st, F&& launcher) {

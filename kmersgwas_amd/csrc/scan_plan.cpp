@@ -644,7 +644,7 @@ PartOperands block_scaled_operands(const ScanShape& sh, const FilterSet& fs, con
     };
     const uint32_t CT = fp.T, slots = CT * 16;
     const uint64_t NGs = fp.ng;  // column groups per block (streaming form; else 1)
-    const uint32_t SB = mx_step_bytes_rt((uint32_t)ns, s1_fp6);
+    const uint32_t SB = mx_step_bytes((uint32_t)ns, s1_fp6);
     const size_t group_bytes = (size_t)n_steps * CT * SB;
     // (the streaming form's last transfer of a slab reads up to 1 KB past it)
     PartOperands op = empty_part(fp, fp.groups * group_bytes + 1024, slots);

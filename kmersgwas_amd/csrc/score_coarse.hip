@@ -32,6 +32,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "filter_common.h"
 #include "score_common.h"
 
 #ifndef KGWAS_COARSE_PHASES
@@ -39,7 +40,7 @@
 #endif
 // Timing experiments only (wrong results; tools/coarse_variants.sh builds the variants). Bits: 1 the tests are replaced by
 // an XOR over all accumulators (every MFMA stays alive), 2 no operand expansion, 4 no LDS operand reads, 8 no row loads,
-// 16 constant row terms, 32 a token side effect instead of the survivor emission.
+// 16 constant row terms, 32 a token side effect instead of the survivor emission (1, 16 and 32 act in filter_common.h).
 #ifndef KGWAS_COARSE_ABLATE
 #define KGWAS_COARSE_ABLATE 0
 #endif
@@ -102,17 +103,9 @@ __global__ void __launch_bounds__(TH) coarse_kernel(CoarseArgs a, uint32_t rows_
     constexpr int SLOTS = PG * 16;
     // Several LDS groups: either this block walks them one after the other over its rows (grid_lg = 0: every pass over
     // the rows re-reads them, 1 MB per block and pass, far more than the L2 keeps across a pass) or every (row block,
-    // group) pair is a block of its own (grid_lg = 1). Blocks go to XCD (id % 8) in id order, so the groups of a row
-    // block get consecutive ids on ONE XCD: they start within a few per cent of a block's run time of each other and
-    // stream through the same rows together - one of them fetches a row from HBM, the others find it in the L2.
-    uint32_t rb = blockIdx.x, lg0 = 0, lg1 = a.n_lgroups;
-    if (grid_lg) {
-        const uint32_t idx = blockIdx.x >> 3;
-        rb = (idx / a.n_lgroups) * 8u + (blockIdx.x & 7u);
-        lg0 = idx % a.n_lgroups;
-        lg1 = lg0 + 1u;
-    }
-    if (rb >= n_rowblocks) return;
+    // group) pair is a block of its own (grid_lg = 1, see filter_block).
+    const FilterBlock fb = filter_block(a.n_lgroups, grid_lg);
+    if (fb.rb >= n_rowblocks) return;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t kg = lane >> 4, m = lane & 15u;
     const uint32_t n_kgroups = a.n_kgroups;
@@ -126,25 +119,17 @@ __global__ void __launch_bounds__(TH) coarse_kernel(CoarseArgs a, uint32_t rows_
     // had to put in (column, row) order: 4.6 ms of a 22 ms pass at 101 columns.
     float* wscr = colc + 3 * SLOTS + wave * 192u;  // wave-private: 64 x N1, 64 x (sqrt(d), E)
     const uint32_t rows_per_pass = (blockDim.x >> 6) * (RT * 16u);
-    const uint64_t blk_row0 = (uint64_t)rb * rows_per_block;
-    const float Nf = (float)a.S;
+    const uint64_t blk_row0 = (uint64_t)fb.rb * rows_per_block;
     const char* rows_base = reinterpret_cast<const char*>(a.src.base);
     const uint32_t avail_b = a.src.avail_dw * 4u;
     uint32_t tested_local = 0;
 
-    for (uint32_t lg = lg0; lg < lg1; lg++) {
-        if (lg != lg0) __syncthreads();
+    for (uint32_t lg = fb.lg0; lg < fb.lg1; lg++) {
+        if (lg != fb.lg0) __syncthreads();
         {
             const i32x4* src = reinterpret_cast<const i32x4*>(a.Bq) + (size_t)lg * group_vec;
             for (uint32_t i = threadIdx.x; i < group_vec; i += blockDim.x) blds[i] = src[i];
-            if (threadIdx.x < SLOTS) {
-                const CoarseCol cc = a.cols[lg * SLOTS + threadIdx.x];
-                float al = __builtin_huge_valf();  // padding / N1 column: nothing survives
-                if (cc.pheno >= 0) al = (float)(sqrt(a.thr[cc.pheno]) * cc.kalpha);  // NaN threshold (frozen column) -> NaN -> nothing survives
-                colc[threadIdx.x] = al;
-                colc[SLOTS + threadIdx.x] = cc.iu;
-                reinterpret_cast<int*>(colc + 2 * SLOTS)[threadIdx.x] = cc.pheno;
-            }
+            filter_col_consts(a, lg * SLOTS, SLOTS, colc);
         }
         __syncthreads();
 
@@ -155,15 +140,7 @@ __global__ void __launch_bounds__(TH) coarse_kernel(CoarseArgs a, uint32_t rows_
         // registers as soon as the current unit has expanded them: 4-5 steps (2000+ cycles) ahead of their use, and
         // across the epilogue.
         uint32_t piece[RT][4];
-        uint32_t ro[RT];  // 32-bit byte offsets (launch_coarse guarantees the chunk spans < 4 GiB) of the rows to fetch next
-        auto set_rows = [&](uint64_t rb0) {
-#pragma unroll
-            for (int rt = 0; rt < RT; rt++) {
-                uint64_t r = rb0 + rt * 16u + m;
-                if (r >= a.n_rows) r = a.n_rows - 1;
-                ro[rt] = ((uint32_t)r * (uint32_t)a.src.stride_dw + a.src.off_dw) * 4u;
-            }
-        };
+        uint32_t ro[RT];  // byte offsets of the rows to fetch next
         auto load_half = [&](uint32_t g, int h) {
             uint32_t b0 = 64u * g + 8u * h + 16u * kg;
             b0 = b0 + 8u <= avail_b ? b0 : avail_b - 8u;  // unconditional load (a branch here splits the scheduling region)
@@ -201,7 +178,7 @@ __global__ void __launch_bounds__(TH) coarse_kernel(CoarseArgs a, uint32_t rows_
             auto run_group = [&](uint32_t g, auto first_tag) {
                 constexpr bool FIRST = decltype(first_tag)::value;  // first sample group: the accumulators start at zero
                 const i32x4* bg = blds + (size_t)g * 8u * T * 64u + lane;
-                if (FIRST) set_rows(rbase);
+                if (FIRST) filter_set_rows(a, ro, rbase, m);
                 load_half(g, 0);
                 load_half(g, 1);
 #pragma unroll
@@ -250,45 +227,13 @@ __global__ void __launch_bounds__(TH) coarse_kernel(CoarseArgs a, uint32_t rows_
             for (uint32_t g = 1; g < n_kgroups; g++) run_group(g, std::false_type{});
 
             TL_STAMP(50);  // main loop done
-            // Per-row terms. Lane (kg, m) holds accumulator registers of the 16 rows kg*4 + jj of the four row tiles
-            // ("row slot" i = rt*4 + jj); the 16 m-lanes of a kg share them. N1 comes from the ones column (slot 15
-            // of the last column group: lane (kg, 15) holds it for all 16 slots); through a wave-private LDS
-            // exchange every lane computes the terms of ONE row (slot i = m) - sqrt(d) rounded down, +inf for a row
-            // that does not exist or fails the MAC filter (nothing survives), and the row's error term E(N1) in
-            // units of Dc, rounded up - and reads back the 16 it needs (the same terms computed 16 times per lane
-            // were a quarter of the kernel's vector work).
+            // Per-row terms (filter_row_terms): N1 from the ones column, sqrt(d) rounded down, E(N1) in units of Dc rounded
+            // up, one row per lane through the wave-private exchange area (the same terms computed 16 times per lane were a
+            // quarter of the kernel's vector work).
             float sqd[RT * 4], er[RT * 4];
             {
-                int* n1s = reinterpret_cast<int*>(wscr);
-                float2* trm = reinterpret_cast<float2*>(wscr + 64);
-                if (m == 15u) {
-#pragma unroll
-                    for (int rt = 0; rt < RT; rt++) *reinterpret_cast<i32x4*>(n1s + kg * 16u + rt * 4) = acc[rt][T - 1];
-                }
-                __builtin_amdgcn_wave_barrier();
-                const uint32_t n1r = (uint32_t)n1s[lane];  // row slot m of this kg
-                const uint64_t left = a.n_rows - rbase;
-                const uint32_t rows_here = left < 64u ? (uint32_t)left : 64u;
-                const bool mac_any = a.S >= 2u * a.min_count;  // else no N1 can satisfy mc <= N1 <= S - mc
-                const uint32_t span = a.S - 2u * a.min_count;
-                const bool ok = mac_any & ((m >> 2) * 16u + kg * 4u + (m & 3u) < rows_here) & ((n1r - a.min_count) <= span);
-                if (lg == 0) tested_local += ok ? 1u : 0u;
-                const float f = (float)n1r;
-                const float sq = __builtin_amdgcn_sqrtf(f * (Nf - f)) * 0.99999905f;  // d < 2^24 is exact; 1 ulp sqrt; (1 - 2^-20)
-                float2 tm;
-                tm.x = ok ? sq : __builtin_huge_valf();
-                tm.y = (a.eg_max + fminf(a.rall_max, f * a.rmax_max)) * 1.000001f;
-                if (KGWAS_COARSE_ABLATE & 16) tm = make_float2(1000.0f + m, 1.0f);
-                trm[lane] = tm;
-                __builtin_amdgcn_wave_barrier();
-#pragma unroll
-                for (int i = 0; i < RT * 4; i += 2) {
-                    const float4 v = *reinterpret_cast<const float4*>(trm + kg * 16u + i);
-                    sqd[i] = v.x;
-                    er[i] = v.y;
-                    sqd[i + 1] = v.z;
-                    er[i + 1] = v.w;
-                }
+                const uint32_t tested = filter_row_terms<int, KGWAS_COARSE_ABLATE>(a, acc, wscr, rbase, lane, sqd, er);
+                if (lg == 0) tested_local += tested;
                 __builtin_amdgcn_wave_barrier();
             }
             TL_STAMP(51);  // row terms exchanged
@@ -316,58 +261,15 @@ __global__ void __launch_bounds__(TH) coarse_kernel(CoarseArgs a, uint32_t rows_
 #pragma unroll
                 for (int i = 0; i < RT * 4; i++) hit[i] = __ballot(mx[i] + er[i] >= 0.0f);
             } else {
-#pragma unroll
-                for (int i = 0; i < RT * 4; i++) hit[i] = 0;
-                int x = 0;  // keeps every accumulator (and its MFMAs) alive at one lane-op each
-#pragma unroll
-                for (int i = 0; i < RT * 4; i++)
-#pragma unroll
-                    for (int t = 0; t < T; t++) x ^= acc[i >> 2][t][i & 3];
-                hit[0] = __ballot(x == 0x7fffffff);
+                filter_xor_hits(acc, hit);
             }
             TL_STAMP(52);  // tests done
-            uint64_t hit_any = 0;
-#pragma unroll
-            for (int i = 0; i < RT * 4; i++) hit_any |= hit[i];
-            if ((KGWAS_COARSE_ABLATE & 32) && hit_any) {  // tests only: a token side effect instead of the emission
-                if (lane == 0) atomicAdd(&a.tested[0], 0ull);
-                hit_any = 0;
-            }
-            // mb[g] bit i = pair (row slot i, column g*16 + m) survives; rebuilt for the row slots that had a hit.
-            uint32_t mb[PG];
-#pragma unroll
-            for (int g = 0; g < PG; g++) mb[g] = 0;
-            if (hit_any) {
-#pragma unroll
-                for (int i = 0; i < RT * 4; i++) {
-                    if (hit[i]) {  // wave-uniform
-#pragma unroll
-                        for (int g = 0; g < PG; g++) {
-                            float al = alc[g];
-                            asm volatile("" : "+v"(al));  // recompute here: keeping all 16 * PG compare masks alive costs more
-                            mb[g] |= (pair_margin(i, g, al) + er[i] >= 0.0f) ? (1u << i) : 0u;
-                        }
-                    }
-                }
-            }
-            if (hit_any) {  // wave-uniform
-                // Column (g, m)'s 64 row bits of this pass sit in four lanes (kg = 0..3; bit i = 4 rt + jj of mb[g] is row
-                // rt * 16 + 4 kg + jj). Each lane stores its 16 bits as quarter kg of the column's word: no cross-lane
-                // traffic, and launch_bitmap_keys(nibble_transposed = true) puts the word's nibbles back in row order.
-                unsigned short* bm16 = reinterpret_cast<unsigned short*>(a.bitmap) + (rbase >> 6) * 4u + kg;
-#pragma unroll
-                for (int g = 0; g < PG; g++)
-                    if (mb[g]) bm16[(uint64_t)colp[g * 16 + m] * a.words_per_col * 4u] = (unsigned short)mb[g];  // column >= 0 wherever a bit is set
-            }
+            // which pairs of the hit row slots passed, and their bits into the bitmap
+            filter_emit<KGWAS_COARSE_ABLATE, PG, RT>(a, hit, alc, er, colp, rbase, lane, pair_margin);
             TL_STAMP(53);  // hits resolved, survivors emitted
         }
     }
-    if (a.tested) {
-        uint32_t v = tested_local;  // every lane counted one row per pass
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d);
-        if (lane == 0u && v) atomicAdd(&a.tested[blockIdx.x % TESTED_SHARDS], (unsigned long long)v);
-    }
+    filter_add_tested(a.tested, tested_local, lane);  // every lane counted one row per pass
 }
 
 // ---- survivors -> exact candidates, compacted in (column, row) order --------------------------------------------
@@ -802,63 +704,52 @@ hipError_t launch_chunk_prep(uint32_t* cand_cnt, uint32_t n_pheno, unsigned long
 size_t coarse_lds_bytes(uint32_t n_kgroups, uint32_t T) { return (size_t)n_kgroups * 8u * T * 1024u + 1536u + 8u * 768u; }
 
 template <int T, int NS, int TH = 512>
-static hipError_t launch_coarse_t(const CoarseArgs& a, uint32_t rows_per_block, uint32_t n_rowblocks, size_t lds,
-                                  hipStream_t st) {
+static hipError_t launch_coarse_t(const CoarseArgs& a, uint32_t rows_per_block, size_t lds, hipStream_t st) {
     lds += (size_t)(TH / 64 - 8) * 768u;  // per-wave scratch of the waves beyond eight
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)coarse_kernel<T, NS, TH>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds);
-        if (e != hipSuccess) return e;
-    }
     static const int grid_env = (int)exp_int("KGWAS_COARSE_GRIDLG", -1);  // experiments
     const uint32_t grid_lg = (grid_env >= 0 ? grid_env != 0 : true) && a.n_lgroups > 1 ? 1u : 0u;
-    const uint32_t grid = grid_lg ? (n_rowblocks + 7u) / 8u * 8u * a.n_lgroups : n_rowblocks;
-    launch_last(coarse_kernel<T, NS, TH>, dim3(grid), dim3(TH), lds, st, a, rows_per_block, n_rowblocks, grid_lg);
+    FilterGrid g;
+    const hipError_t e = filter_grid((const void*)coarse_kernel<T, NS, TH>, a, (TH / 64) * 64u, rows_per_block, grid_lg != 0u, lds, g);
+    if (e != hipSuccess) return e;
+    launch_last(coarse_kernel<T, NS, TH>, dim3(g.grid), dim3(TH), lds, st, a, g.rows_per_block, g.n_rowblocks, grid_lg);
     return hipGetLastError();
 }
 
 hipError_t launch_coarse(const CoarseArgs& a, uint32_t T, uint32_t rows_per_block, hipStream_t st) {
     if (a.n_rows == 0) return hipSuccess;
     const size_t lds = coarse_lds_bytes(a.n_kgroups, T);
-    if (lds > 160u * 1024u) return hipErrorInvalidValue;
-    // Few tiles per LDS group leave registers for a third wave per SIMD (T <= 4: <= 168 VGPRs at 768 threads)
-    static const int th_env = (int)exp_int("KGWAS_COARSE_TH", 768);  // experiments (512: eight waves as for T > 4)
-    const bool wide_block = th_env == 768 && a.n_slices == 1 && T <= 4 && lds + 4u * 768u <= 160u * 1024u;
-    const uint32_t threads = wide_block ? 768 : 512;
-    if ((a.n_rows * a.src.stride_dw + a.src.off_dw + a.src.avail_dw) * 4ull >= (1ull << 32)) return hipErrorInvalidValue;  // 32-bit byte offsets
-    const uint32_t rpp = (threads >> 6) * 64u;
-    rows_per_block = (rows_per_block + rpp - 1) / rpp * rpp;
-    const uint32_t n_rowblocks = (uint32_t)((a.n_rows + rows_per_block - 1) / rows_per_block);
 #ifdef KGWAS_COARSE_BENCH_ONLY  // experiments: only the two shapes of the 1024 x 101 bench (fast compiles)
-    if (a.n_slices == 1 && T == 7) return launch_coarse_t<7, 1>(a, rows_per_block, n_rowblocks, lds, st);
-    if (a.n_slices == 2 && T == 8) return launch_coarse_t<8, 2>(a, rows_per_block, n_rowblocks, lds, st);
+    if (a.n_slices == 1 && T == 7) return launch_coarse_t<7, 1>(a, rows_per_block, lds, st);
+    if (a.n_slices == 2 && T == 8) return launch_coarse_t<8, 2>(a, rows_per_block, lds, st);
     return hipErrorInvalidValue;
 #else
-    if (wide_block) {
+    // Few tiles per LDS group leave registers for a third wave per SIMD (T <= 4: <= 168 VGPRs at 768 threads)
+    static const int th_env = (int)exp_int("KGWAS_COARSE_TH", 768);  // experiments (512: eight waves as for T > 4)
+    if (th_env == 768 && a.n_slices == 1 && T <= 4 && lds + 4u * 768u <= 160u * 1024u) {
         switch (T) {
-            case 1: return launch_coarse_t<1, 1, 768>(a, rows_per_block, n_rowblocks, lds, st);
-            case 2: return launch_coarse_t<2, 1, 768>(a, rows_per_block, n_rowblocks, lds, st);
-            case 3: return launch_coarse_t<3, 1, 768>(a, rows_per_block, n_rowblocks, lds, st);
-            case 4: return launch_coarse_t<4, 1, 768>(a, rows_per_block, n_rowblocks, lds, st);
+            case 1: return launch_coarse_t<1, 1, 768>(a, rows_per_block, lds, st);
+            case 2: return launch_coarse_t<2, 1, 768>(a, rows_per_block, lds, st);
+            case 3: return launch_coarse_t<3, 1, 768>(a, rows_per_block, lds, st);
+            case 4: return launch_coarse_t<4, 1, 768>(a, rows_per_block, lds, st);
         }
     }
     if (a.n_slices == 1) {
         switch (T) {
-            case 1: return launch_coarse_t<1, 1>(a, rows_per_block, n_rowblocks, lds, st);
-            case 2: return launch_coarse_t<2, 1>(a, rows_per_block, n_rowblocks, lds, st);
-            case 3: return launch_coarse_t<3, 1>(a, rows_per_block, n_rowblocks, lds, st);
-            case 4: return launch_coarse_t<4, 1>(a, rows_per_block, n_rowblocks, lds, st);
-            case 5: return launch_coarse_t<5, 1>(a, rows_per_block, n_rowblocks, lds, st);
-            case 6: return launch_coarse_t<6, 1>(a, rows_per_block, n_rowblocks, lds, st);
-            case 7: return launch_coarse_t<7, 1>(a, rows_per_block, n_rowblocks, lds, st);
-            case 8: return launch_coarse_t<8, 1>(a, rows_per_block, n_rowblocks, lds, st);
+            case 1: return launch_coarse_t<1, 1>(a, rows_per_block, lds, st);
+            case 2: return launch_coarse_t<2, 1>(a, rows_per_block, lds, st);
+            case 3: return launch_coarse_t<3, 1>(a, rows_per_block, lds, st);
+            case 4: return launch_coarse_t<4, 1>(a, rows_per_block, lds, st);
+            case 5: return launch_coarse_t<5, 1>(a, rows_per_block, lds, st);
+            case 6: return launch_coarse_t<6, 1>(a, rows_per_block, lds, st);
+            case 7: return launch_coarse_t<7, 1>(a, rows_per_block, lds, st);
+            case 8: return launch_coarse_t<8, 1>(a, rows_per_block, lds, st);
         }
     } else if (a.n_slices == 2) {
         switch (T) {
-            case 2: return launch_coarse_t<2, 2>(a, rows_per_block, n_rowblocks, lds, st);
-            case 4: return launch_coarse_t<4, 2>(a, rows_per_block, n_rowblocks, lds, st);
-            case 6: return launch_coarse_t<6, 2>(a, rows_per_block, n_rowblocks, lds, st);
-            case 8: return launch_coarse_t<8, 2>(a, rows_per_block, n_rowblocks, lds, st);
+            case 2: return launch_coarse_t<2, 2>(a, rows_per_block, lds, st);
+            case 4: return launch_coarse_t<4, 2>(a, rows_per_block, lds, st);
+            case 6: return launch_coarse_t<6, 2>(a, rows_per_block, lds, st);
+            case 8: return launch_coarse_t<8, 2>(a, rows_per_block, lds, st);
         }
     }
     return hipErrorInvalidValue;

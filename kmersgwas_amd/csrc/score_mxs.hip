@@ -43,15 +43,11 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "score_common.h"
+#include "filter_common.h"
 
-#ifndef KGWAS_MXS_DEPHASE  // 1: the upper half of a block's waves runs its passes half a pass behind the lower half (see `dephase`): measured SLOWER, off
-#define KGWAS_MXS_DEPHASE 0
-#endif
-#ifndef KGWAS_MXS_ROWS_NT
-#define KGWAS_MXS_ROWS_NT 0  // (measured: 3.7 x the algorithmic HBM bytes - the second column group's request of a row then always misses - and + 10 % time)
-#endif
-#ifndef KGWAS_MXS_ABLATE  // timing experiments only (wrong results): 1 no tests, 8 no row loads, 16 no operand DMA, 64 no barriers
+// timing experiments only (wrong results): 1 no tests (acts in filter_common.h), 8 no row loads, 16 no operand DMA, 64 no
+// barriers, 128 every row load hits the L2
+#ifndef KGWAS_MXS_ABLATE
 #define KGWAS_MXS_ABLATE 0
 #endif
 
@@ -73,12 +69,8 @@ extern "C" int kgwas_debug_mxs_prof(unsigned long long* out, int reset) {
 }
 #endif
 
-typedef int mxsv8i __attribute__((ext_vector_type(8)));
-typedef float mxsv4f __attribute__((ext_vector_type(4)));
-
 namespace {
-constexpr uint32_t MXS_SB = 2560u;     // FP6 slice (64 lanes x 16 B, then 64 lanes x 8 B) + FP4 slice (64 lanes x 16 B) of one (step, column tile)
-constexpr uint32_t MXS_PART0 = 1536u;
+constexpr uint32_t MXS_SB = mx_step_bytes(2, 0);  // FP6 slice + FP4 slice of one (step, column tile): 2560 B
 }  // namespace
 
 template <int CT, int RT, int NG, int TH, int RING>
@@ -90,16 +82,13 @@ __global__ void __launch_bounds__(TH) mxs_kernel(MxArgs a, uint32_t rows_per_blo
     constexpr int SLOTS = CT * 16;        // operand columns of a column group
     constexpr int SLOTS_ALL = CTA * 16;
     constexpr int WPG = TH / 64 / NG;     // waves per column group
-    constexpr int NSL = RT * 4;           // row slots per lane
     constexpr uint32_t SLAB = CTA * MXS_SB;
     constexpr uint32_t SLOT = (SLAB + 1023u) / 1024u * 1024u;  // ring slot (the last transfer of a slab may run up to 1 KB past it)
+    typedef MxOperands<CT, 2, 4> Ops;  // two slices, FP6 + FP4
     static_assert(RT == 2 || RT == 4, "row tiles per wave");
-    uint32_t rb = blockIdx.x, lg = 0;
-    if (a.n_lgroups > 1) {  // every (row block, operand group) pair is a block; the groups of a row block run next to each other on one XCD
-        const uint32_t idx = blockIdx.x >> 3;
-        rb = (idx / a.n_lgroups) * 8u + (blockIdx.x & 7u);
-        lg = idx % a.n_lgroups;
-    }
+    // every (row block, operand group) pair is a block
+    const FilterBlock fb = filter_block(a.n_lgroups, a.n_lgroups > 1);
+    const uint32_t rb = fb.rb, lg = fb.lg0;
     if (rb >= n_rowblocks) return;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -112,7 +101,6 @@ __global__ void __launch_bounds__(TH) mxs_kernel(MxArgs a, uint32_t rows_per_blo
     float* wscr = colc + 3 * SLOTS_ALL + wave * (RT * 48u);  // wave-private: RT*16 x N1, RT*16 x (sqrt(d), E)
     const uint32_t rows_per_pass = WPG * (RT * 16u);
     const uint64_t blk_row0 = (uint64_t)rb * rows_per_block;
-    const float Nf = (float)a.S;
     const char* rows_base = reinterpret_cast<const char*>(a.src.base);
     const uint32_t avail_b = a.src.avail_dw * 4u;
     const int sc0 = (int)a.scale0;
@@ -163,9 +151,9 @@ __global__ void __launch_bounds__(TH) mxs_kernel(MxArgs a, uint32_t rows_per_blo
     constexpr uint32_t WAIT_N = RT + (MXS_AHEAD - 2u) * (ROUNDS + RT);
     static_assert(MXS_AHEAD >= 2u && WAIT_N < 64u, "vmcnt is a 6-bit immediate");
     const uint32_t lds_fill = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)lds + MXS_RING * SLOT + 3u * SLOTS_ALL * 4u + (TH / 64u) * (RT * 48u * 4u) + wave * 256u;
-    // this wave's row staging area: RT x (64 lanes x 16 B), behind the fillers' scratch (one per wave: waves of different column
-    // groups work on the same rows, but - KGWAS_MXS_DEPHASE - half a pass apart)
-    const uint32_t stage_off = MXS_RING * SLOT + 3u * SLOTS_ALL * 4u + (TH / 64u) * (RT * 48u * 4u) + (TH / 64u) * 256u + (KGWAS_MXS_DEPHASE ? wave : wig) * (RT * 1024u);
+    // this wave's row staging area: RT x (64 lanes x 16 B), behind the fillers' scratch (the waves of different column groups
+    // that work on the same rows share one)
+    const uint32_t stage_off = MXS_RING * SLOT + 3u * SLOTS_ALL * 4u + (TH / 64u) * (RT * 48u * 4u) + (TH / 64u) * 256u + wig * (RT * 1024u);
     const uint32_t lds_stage = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)lds + stage_off;
     const uint32_t voff4 = lane * 4u;
     auto filler_ops = [&]() {
@@ -197,31 +185,16 @@ __global__ void __launch_bounds__(TH) mxs_kernel(MxArgs a, uint32_t rows_per_blo
 #endif
     };
 
-    {
-        if (threadIdx.x < SLOTS_ALL) {
-            const CoarseCol cc = a.cols[lg * SLOTS_ALL + threadIdx.x];
-            float al = __builtin_huge_valf();  // padding / N1 column: nothing survives
-            if (cc.pheno >= 0) al = (float)(sqrt(a.thr[cc.pheno]) * cc.kalpha);  // NaN threshold (frozen column) -> NaN -> nothing survives
-            colc[threadIdx.x] = al;
-            colc[SLOTS_ALL + threadIdx.x] = cc.iu;
-            reinterpret_cast<int*>(colc + 2 * SLOTS_ALL)[threadIdx.x] = cc.pheno;
-        }
+    filter_col_consts(a, lg * SLOTS_ALL, SLOTS_ALL, colc);
 #pragma unroll
-        for (uint32_t i = 0; i < MXS_AHEAD; i++) issue_slab();  // slabs 0 .. MXS_AHEAD - 1
-    }
+    for (uint32_t i = 0; i < MXS_AHEAD; i++) issue_slab();  // slabs 0 .. MXS_AHEAD - 1
     __syncthreads();  // (colc; the compiler's own barrier with its waits)
     asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");  // the first slabs are in the ring
 
-    // (32-bit byte offsets of a lane's rows: launch_mxs guarantees the chunk spans < 4 GiB)
     const uint64_t wave_row0 = blk_row0 + wig * (RT * 16u);
     auto set_rows = [&](uint32_t (&o)[RT], uint64_t rb0) {
-#pragma unroll
-        for (int rt = 0; rt < RT; rt++) {
-            uint64_t r = rb0 + rt * 16u + m;
-            if (KGWAS_MXS_ABLATE & 128) r &= 4095u;  // (experiments: every row load hits the L2)
-            if (r >= a.n_rows) r = a.n_rows - 1;
-            o[rt] = ((uint32_t)r * (uint32_t)a.src.stride_dw + a.src.off_dw) * 4u;
-        }
+        if (KGWAS_MXS_ABLATE & 128) rb0 &= 4095u;  // (experiments: every row load hits the L2; a wave's rows never straddle 4096)
+        filter_set_rows(a, o, rb0, m);
     };
     // This lane's 16 bytes of full group g of each of its RT rows (the four kb-lanes of a row fetch the group's 64 bytes as one
     // contiguous piece; a full group's bytes always exist in the row: n_full = S / 512), requested as LDS-DMA into the wave's
@@ -236,13 +209,7 @@ __global__ void __launch_bounds__(TH) mxs_kernel(MxArgs a, uint32_t rows_per_blo
             uint32_t off = o[rt] + b0;
             if (KGWAS_MXS_ABLATE & 8) off = lane * 16u;
             const uint32_t m0v = lds_stage + rt * 1024u;
-            // (non-temporal: a row is read once - by both column groups' waves at nearly the same time -, and must not push the
-            // operand slabs, which every block re-reads once per pass, out of the L2)
-#if KGWAS_MXS_ROWS_NT
-            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 nt" ::"s"(m0v), "v"(off), "s"(rows_base) : "memory");
-#else
             asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(m0v), "v"(off), "s"(rows_base) : "memory");
-#endif
         }
     };
     auto pickup_group = [&](uint32_t (&pc)[RT][4]) {
@@ -255,110 +222,43 @@ __global__ void __launch_bounds__(TH) mxs_kernel(MxArgs a, uint32_t rows_per_blo
             pc[rt][3] = v.w;
         }
     };
-    // Slice operands of the column tiles, read from the ring one UNIT (two column tiles) ahead of their MFMAs, as in mx_kernel.
-    constexpr int UT = 2;
-    constexpr int NU = (CT + UT - 1) / UT;
+    // Slice operands of the column tiles, read from the ring one unit ahead of their MFMAs (MxOperands).
+    constexpr int NU = Ops::NU;
     static_assert(NU >= 2, "at least three column tiles per wave");
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-    u32x4 Bx[CT], Bz[CT];  // dwords 0-3 of the first slice's operand, the second slice's
-    u32x2 By[CT];          // dwords 4-5 of the first slice's
-#pragma unroll
-    for (int t = 0; t < CT; t++) Bx[t] = Bz[t] = (u32x4){0u, 0u, 0u, 0u}, By[t] = (u32x2){0u, 0u};
-    struct StepAddr {
-        uint32_t o16, o8, o8b;
-    };
+    Ops B;
+    B.clear();
     // operand addresses of the step whose slab lies in ring slot `slot`
-    auto step_addr = [&](uint32_t slot) {
-        StepAddr sa;
-        const uint32_t base = slot * SLOT + grp * (CT * MXS_SB);
-        sa.o16 = base + lane * 16u;
-        sa.o8 = base + lane * 8u + 1024u;
-        sa.o8b = sa.o8 + MXS_SB;
-        asm volatile("" : "+v"(sa.o16), "+v"(sa.o8), "+v"(sa.o8b));
-        return sa;
-    };
-    auto read_unit = [&](int u, const StepAddr& sa) {
-#pragma unroll
-        for (int t = UT * u; t < (UT * u + UT < CT ? UT * u + UT : CT); t++) {
-            const char* p16 = lds + sa.o16 + t * MXS_SB;
-            const char* p8 = (t & 1) ? lds + sa.o8b + (t - 1) * MXS_SB : lds + sa.o8 + t * MXS_SB;
-            Bx[t] = *reinterpret_cast<const u32x4*>(p16);
-            By[t] = *reinterpret_cast<const u32x2*>(p8);
-            Bz[t] = *reinterpret_cast<const u32x4*>(p16 + MXS_PART0);
-        }
-    };
+    auto step_addr = [&](uint32_t slot) { return Ops::step_addr(slot * SLOT + grp * (CT * MXS_SB), lane); };
+    auto read_unit = [&](int u, const MxStepAddr& sa) { B.template read_unit<0>(u, sa, lds, lane); };
     uint32_t slot_cur = 0;  // ring slot of the step about to run
     // Row pieces: `piece` = this lane's 16 bytes of the CURRENT 512-sample group of each of its RT rows. The group after it (the
     // next group of the pass or group 0 of the wave's next rows) is requested in step 1 of the current group and picked up at
     // the top of its own step 0, behind that step's wait.
     uint32_t piece[RT][4];
-    // The waves w and w + 4 of a block share a SIMD and meet at every step's barrier. Had both the same pass boundaries, both
-    // would run their epilogues - 4000 cycles of vector work per 43 000-cycle pass - at the same time, with nobody feeding the
-    // matrix pipe (in the free-running resident kernel the two waves' epilogues hide behind each other's MFMAs). The slab stream
-    // is cyclic and the accumulation order is free, so the upper half of the block's waves (LATE) takes its passes HALF A PASS
-    // behind: a late wave's pass is the groups off .. n_full - 1, the quarter steps, then the groups 0 .. off - 1 of the next
-    // cycle of the stream (off = n_full / 2 whole groups) - the same slabs at the same barriers, its epilogue in the middle of
-    // the early waves' main loop and vice versa. The late waves idle through the block's first 4 off steps (barrier and
-    // transfers only), the early ones through the 4 off steps behind their last pass.
-    // MEASURED (round 5, alternating builds on one box, ms of filter per 100 M rows): 2048 x 201 45.7-46.3 with the offset
-    // against 42.3 without, 1135 x 101 14.3-14.4 against 13.0 - slower by 8-10 %, although the results are identical and the
-    // epilogues provably no longer coincide: partner waves then fetch their rows at different times (the second fetch no
-    // longer hits what the first brought in) and every block runs 4 off steps more. Compiled out (KGWAS_MXS_DEPHASE=0).
-    const bool dephase = KGWAS_MXS_DEPHASE && TH >= 512 && a.n_full >= 2u;
-    const bool late = dephase && wave >= TH / 128;
-    const uint32_t off = late ? a.n_full / 2u : 0u;
-    const uint32_t n_dummy = dephase ? 4u * (a.n_full / 2u) : 0u;
-    uint32_t pf_ps = 0, pf_g = off;  // the group the next request fetches (in the wave's own order: off, off + 1, ..., off - 1)
+    uint32_t pf_ps = 0, pf_g = 0;  // the pass and group the next request fetches
     auto prefetch = [&]() {
         uint32_t o[RT];
         set_rows(o, wave_row0 + (uint64_t)pf_ps * rows_per_pass);
         request_group(o, pf_g);
         pf_g = pf_g + 1u == a.n_full ? 0u : pf_g + 1u;
-        pf_ps = pf_g == off ? pf_ps + 1u : pf_ps;
+        pf_ps = pf_g == 0u ? pf_ps + 1u : pf_ps;
     };
     if (a.n_full) prefetch();  // (the first group: picked up at the top of the first step, as every group's pieces are)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the steps' waits count from an empty queue)
-    StepAddr sadr = step_addr(0);
+    MxStepAddr sadr = step_addr(0);
     read_unit(0, sadr);  // step 0 of the first pass; every step's last unit fetches the next step's first
-    // a step without work for this wave: the barrier and the wave's share of the transfers (the sequence of vector-memory
-    // operations stays uniform), and the next step's first operands
-    auto dummy_step = [&]() __attribute__((always_inline)) {
-        step_sync();
-        issue_slab();
-        filler_ops();
-        const uint32_t slot_next = slot_cur + 1u == MXS_RING ? 0u : slot_cur + 1u;
-        sadr = step_addr(slot_next);
-        read_unit(0, sadr);
-        slot_cur = slot_next;
-    };
-    if (late)
-        for (uint32_t i = 0; i < n_dummy; i++) dummy_step();
     for (uint32_t ps = 0; ps < n_passes; ps++) {
         const uint64_t rbase = wave_row0 + (uint64_t)ps * rows_per_pass;
-        mxsv4f acc[RT][CT];
+        mxv4f acc[RT][CT];
 #pragma unroll
         for (int rt = 0; rt < RT; rt++)
 #pragma unroll
-            for (int t = 0; t < CT; t++) acc[rt][t] = (mxsv4f){0.0f, 0.0f, 0.0f, 0.0f};
+            for (int t = 0; t < CT; t++) acc[rt][t] = (mxv4f){0.0f, 0.0f, 0.0f, 0.0f};
 
-        auto mfma_unit = [&](int u, const mxsv8i (&A)[RT], int sa) {
-#pragma unroll
-            for (int t = UT * u; t < (UT * u + UT < CT ? UT * u + UT : CT); t++) {
-                const mxsv8i B0 = {(int)Bx[t].x, (int)Bx[t].y, (int)Bx[t].z, (int)Bx[t].w, (int)By[t].x, (int)By[t].y, 0, 0};
-#pragma unroll
-                for (int rt = 0; rt < RT; rt++)
-                    acc[rt][t] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(A[rt], B0, acc[rt][t], 4, 2, 0, sa, 0, sc0);
-                const mxsv8i B1 = {(int)Bz[t].x, (int)Bz[t].y, (int)Bz[t].z, (int)Bz[t].w, 0, 0, 0, 0};
-#pragma unroll
-                for (int rt = 0; rt < RT; rt++)
-                    acc[rt][t] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(A[rt], B1, acc[rt][t], 4, 4, 0, sa, 0, 0x7F7F7F7F);
-            }
-        };
         // step = [B_s, slab s + AHEAD, row operations | operands A | reads of unit 1 | MFMAs of unit 0 | reads of unit 2 | MFMAs of unit 1
         //         | ... | reads of the next step's unit 0 | MFMAs of the last unit]
         // kind: 0..3 = step j of a 512-sample group (table bits from `piece`), 4 = a quarter step (operands handed in)
-        auto run_step = [&](auto kind, mxsv8i (&A)[RT], int sa) __attribute__((always_inline)) {
+        auto run_step = [&](auto kind, mxv8i (&A)[RT], int sa) __attribute__((always_inline)) {
             constexpr int J = decltype(kind)::value;
             __builtin_amdgcn_sched_barrier(0);
 #if KGWAS_MXS_PROF
@@ -384,18 +284,10 @@ __global__ void __launch_bounds__(TH) mxs_kernel(MxArgs a, uint32_t rows_per_blo
             vmem_ops();
             __builtin_amdgcn_sched_barrier(0);
             if (J == 0) pickup_group(piece);
-            if (J < 4) {
-#pragma unroll
-                for (int rt = 0; rt < RT; rt++) {
-                    A[rt] = (mxsv8i){0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-                    for (int q = 0; q < 4; q++)
-                        A[rt][q] = J < 3 ? (int)(piece[rt][q] & (0x11111111u << J)) : (int)((piece[rt][q] >> 1) & 0x44444444u);
-                }
-            }
+            if (J < 4) mx_expand_step<0>(A, piece, J);
             __builtin_amdgcn_sched_barrier(0);
             const uint32_t slot_next = slot_cur + 1u == MXS_RING ? 0u : slot_cur + 1u;
-            const StepAddr nadr = step_addr(slot_next);
+            const MxStepAddr nadr = step_addr(slot_next);
 #pragma unroll
             for (int u = 0; u < NU; u++) {
                 if (u + 1 < NU)
@@ -403,7 +295,7 @@ __global__ void __launch_bounds__(TH) mxs_kernel(MxArgs a, uint32_t rows_per_blo
                 else
                     read_unit(0, nadr);
                 __builtin_amdgcn_sched_barrier(0);
-                mfma_unit(u, A, sa);
+                B.mfma_unit(u, A, acc, sa, sc0);
                 __builtin_amdgcn_sched_barrier(0);
             }
             sadr = nadr;
@@ -415,153 +307,36 @@ __global__ void __launch_bounds__(TH) mxs_kernel(MxArgs a, uint32_t rows_per_blo
         };
 
         __builtin_amdgcn_s_setprio(0);
-        auto group_steps = [&]() __attribute__((always_inline)) {
-            mxsv8i A[RT];
-            // nibble bit 0 / 1 / 2 / 2 (bit 3 shifted down): 0.5 / 1.0 / 2.0 / 2.0 x 2^0 / 2^-1 / 2^-2 / 2^-2 = 0.5
-            run_step(std::integral_constant<int, 0>(), A, 0x7F7F7F7F);
-            run_step(std::integral_constant<int, 1>(), A, 0x7E7E7E7E);
-            run_step(std::integral_constant<int, 2>(), A, 0x7D7D7D7D);
-            run_step(std::integral_constant<int, 3>(), A, 0x7D7D7D7D);
-        };
-        for (uint32_t g = off; g < a.n_full; g++) group_steps();
+        for (uint32_t g = 0; g < a.n_full; g++) {
+            mxv8i A[RT];
+            run_step(std::integral_constant<int, 0>(), A, mx_step_scale(0));
+            run_step(std::integral_constant<int, 1>(), A, mx_step_scale(1));
+            run_step(std::integral_constant<int, 2>(), A, mx_step_scale(2));
+            run_step(std::integral_constant<int, 3>(), A, mx_step_scale(3));
+        }
         // quarter groups: 128 samples per step, the lane's own dword shifted by 0..3
         uint32_t ro[RT];  // (made here, not kept across the groups' steps: eight registers the main loop has no room for)
         if (a.n_quarter) set_rows(ro, rbase);
         for (uint32_t x = 0; x < a.n_quarter; x++) {
             uint32_t b0 = 64u * a.n_full + 16u * x + 4u * kb;
             b0 = b0 + 4u <= avail_b ? b0 : avail_b - 4u;
-            mxsv8i A[RT];
+            mxv8i A[RT];
 #pragma unroll
-            for (int rt = 0; rt < RT; rt++) {
-                const uint32_t w = (KGWAS_MXS_ABLATE & 8) ? ro[rt] + b0 : *reinterpret_cast<const uint32_t*>(rows_base + (ro[rt] + b0));
-                A[rt] = (mxsv8i){(int)(w & 0x11111111u), (int)((w >> 1) & 0x11111111u), (int)((w >> 2) & 0x11111111u),
-                                 (int)((w >> 3) & 0x11111111u), 0, 0, 0, 0};
-            }
-            run_step(std::integral_constant<int, 4>(), A, 0x7F7F7F7F);
+            for (int rt = 0; rt < RT; rt++)
+                A[rt] = mx_expand_quarter((KGWAS_MXS_ABLATE & 8) ? ro[rt] + b0 : *reinterpret_cast<const uint32_t*>(rows_base + (ro[rt] + b0)));
+            run_step(std::integral_constant<int, 4>(), A, mx_step_scale(0));
         }
-        for (uint32_t g = 0; g < off; g++) group_steps();  // (late waves: the first groups, from the stream's next cycle)
 
 #if KGWAS_MXS_PROF
         const unsigned long long te0 = __builtin_readcyclecounter();
 #endif
         __builtin_amdgcn_s_setprio(3);  // the epilogue at raised priority (mx_kernel)
-        // Per-row terms, exactly as in mx_kernel: N1 from the ones column (slot 15 of the group's last column tile), sqrt(d)
-        // rounded down (+inf for a row that does not exist or fails the MAC filter), E(N1) rounded up; one row per lane through a
-        // wave-private exchange area.
-        float2* trm = reinterpret_cast<float2*>(wscr + RT * 16);
-        {
-            float* n1s = wscr;
-            if (m == 15u) {
-#pragma unroll
-                for (int rt = 0; rt < RT; rt++) *reinterpret_cast<mxsv4f*>(n1s + kb * NSL + rt * 4) = acc[rt][CT - 1];
-            }
-            __builtin_amdgcn_wave_barrier();
-            const uint64_t left = rbase < a.n_rows ? a.n_rows - rbase : 0;
-            const uint32_t rows_here = left < RT * 16u ? (uint32_t)left : RT * 16u;
-            const bool mac_any = a.S >= 2u * a.min_count;  // else no N1 can satisfy mc <= N1 <= S - mc
-            const uint32_t span = a.S - 2u * a.min_count;
-            if (lane < RT * 16u) {
-                // entry e = lane = (kb' = e / NSL, slot i = e % NSL): row 16 (i / 4) + 4 kb' + i % 4
-                const uint32_t e = lane;
-                const uint32_t kbe = e / NSL, ie = e % NSL;
-                const uint32_t row = 16u * (ie >> 2) + 4u * kbe + (ie & 3u);
-                const float f = n1s[e];
-                const uint32_t n1r = (uint32_t)f;
-                const bool ok = mac_any & (row < rows_here) & ((n1r - a.min_count) <= span);
-                if (lg == 0 && grp == 0) tested_local += ok ? 1u : 0u;
-                const float sq = __builtin_amdgcn_sqrtf(f * (Nf - f)) * 0.99999905f;  // d < 2^24 is exact; 1 ulp sqrt; (1 - 2^-20)
-                float2 tm;
-                tm.x = ok ? sq : __builtin_huge_valf();
-                tm.y = (a.eg_max + fminf(a.rall_max, f * a.rmax_max)) * 1.000001f;
-                trm[e] = tm;
-            }
-            __builtin_amdgcn_wave_barrier();
-        }
-        // The test (mx_kernel): a running maximum of |acc| per row slot, ONE fma + compare per row slot with the smallest
-        // alpha of the lane's columns, the per-pair test only for row slots that hit.
-        float alc[CT];
-        float al_min = __builtin_huge_valf();
-#pragma unroll
-        for (int t = 0; t < CT; t++) {
-            alc[t] = colc[grp * SLOTS + t * 16 + m];
-            al_min = fminf(al_min, alc[t]);  // (a NaN alpha - frozen column - is skipped; +inf = padding / ones column)
-        }
-        const bool ones_lane = m == 15u;  // slot 15 of the last tile is the ones column: its accumulator (N1) is no margin
-        {
-            float sqd[NSL], er[NSL];
-#pragma unroll
-            for (int i = 0; i < NSL; i += 2) {
-                const float4 v = *reinterpret_cast<const float4*>(trm + kb * NSL + i);
-                sqd[i] = v.x;
-                er[i] = v.y;
-                sqd[i + 1] = v.z;
-                er[i + 1] = v.w;
-            }
-            uint64_t hit[NSL];
-            if (!(KGWAS_MXS_ABLATE & 1)) {
-                float mx[NSL];
-#pragma unroll
-                for (int i = 0; i < NSL; i++) {
-                    const float v = acc[i >> 2][CT - 1][i & 3];
-                    mx[i] = ones_lane ? 0.0f : fabsf(v);
-                }
-#pragma unroll
-                for (int t = 0; t + 1 < CT; t++)
-#pragma unroll
-                    for (int i = 0; i < NSL; i++) mx[i] = fmaxf(mx[i], fabsf(acc[i >> 2][t][i & 3]));
-#pragma unroll
-                for (int i = 0; i < NSL; i++) hit[i] = __ballot(fmaf(-al_min, sqd[i], mx[i]) + er[i] >= 0.0f);
-            } else {
-#pragma unroll
-                for (int i = 0; i < NSL; i++) hit[i] = 0;
-                int x = 0;  // keeps every accumulator (and its MFMAs) alive at one lane-op each
-#pragma unroll
-                for (int i = 0; i < NSL; i++)
-#pragma unroll
-                    for (int t = 0; t < CT; t++) x ^= __float_as_int(acc[i >> 2][t][i & 3]);
-                hit[0] = __ballot(x == 0x7fffffff);
-            }
-            uint64_t hit_any = 0;
-#pragma unroll
-            for (int i = 0; i < NSL; i++) hit_any |= hit[i];
-            if (hit_any) {  // wave-uniform
-                uint32_t mb[CT];  // mb[t] bit i = pair (row slot i, column t*16 + m) survives
-#pragma unroll
-                for (int t = 0; t < CT; t++) mb[t] = 0;
-#pragma unroll
-                for (int i = 0; i < NSL; i++) {
-                    if (hit[i]) {  // wave-uniform
-#pragma unroll
-                        for (int t = 0; t < CT; t++) {
-                            float al = alc[t];
-                            asm volatile("" : "+v"(al));
-                            mb[t] |= (fmaf(-al, sqd[i], fabsf(acc[i >> 2][t][i & 3])) + er[i] >= 0.0f) ? (1u << i) : 0u;
-                        }
-                    }
-                }
-                // Column (t, m)'s row bits: bit i = 4 rt + jj is row rt * 16 + 4 kb + jj of the wave's rows. In the bitmap's
-                // nibble-transposed 64-row words (quarter kb, nibble rt' = row / 16) a wave with four row tiles stores its 16
-                // bits as quarter kb, one with two row tiles its 8 bits as byte (rbase / 32) % 2 of that quarter.
-                if (RT == 4) {
-                    unsigned short* bm16 = reinterpret_cast<unsigned short*>(a.bitmap) + (rbase >> 6) * 4u + kb;
-#pragma unroll
-                    for (int t = 0; t < CT; t++)
-                        if (mb[t]) bm16[(uint64_t)colp[t * 16 + m] * a.words_per_col * 4u] = (unsigned short)mb[t];  // column >= 0 wherever a bit is set
-                } else {
-                    unsigned char* bm8 = reinterpret_cast<unsigned char*>(a.bitmap) + (rbase >> 6) * 8u + kb * 2u + ((rbase >> 5) & 1u);
-#pragma unroll
-                    for (int t = 0; t < CT; t++)
-                        if (mb[t]) bm8[(uint64_t)colp[t * 16 + m] * a.words_per_col * 8u] = (unsigned char)mb[t];
-                }
-            }
-        }
-        __builtin_amdgcn_wave_barrier();  // the exchange area is rewritten by the next pass
+        const uint32_t tested = mx_epilogue<KGWAS_MXS_ABLATE & 1>(a, acc, wscr, colc + grp * SLOTS, colp, rbase, lane);
+        if (lg == 0 && grp == 0) tested_local += tested;
 #if KGWAS_MXS_PROF
         pf_epi += __builtin_readcyclecounter() - te0;
 #endif
     }
-    if (!late)
-        for (uint32_t i = 0; i < n_dummy; i++) dummy_step();
 #if KGWAS_MXS_PROF
     if (threadIdx.x == 0) {
         atomicAdd(&mxs_prof[0], pf_sync);
@@ -575,40 +350,26 @@ __global__ void __launch_bounds__(TH) mxs_kernel(MxArgs a, uint32_t rows_per_blo
     }
 #endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the stream's last transfers (never read) must not outlive the block's LDS
-    if (a.tested) {
-        uint32_t v = tested_local;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d);
-        if (lane == 0u && v) atomicAdd(&a.tested[blockIdx.x % TESTED_SHARDS], (unsigned long long)v);
-    }
+    filter_add_tested(a.tested, tested_local, lane);
 }
 
-// ring + the per-column constants + the waves' row-term exchange areas
 // ring + per-column constants + the waves' row-term exchange areas + the fillers' scratch + the row staging areas
 static size_t mxs_lds_bytes_t(uint32_t cta, uint32_t rt, uint32_t ng, uint32_t th, uint32_t ring) {
     const uint32_t waves = th / 64u;
-    return (size_t)ring * ((cta * MXS_SB + 1023u) / 1024u * 1024u) + 3u * cta * 16u * 4u + waves * (rt * 192u) + waves * 256u + (KGWAS_MXS_DEPHASE ? waves : waves / ng) * (rt * 1024u);
+    return (size_t)ring * ((cta * MXS_SB + 1023u) / 1024u * 1024u) + 3u * cta * 16u * 4u + waves * (rt * 192u) + waves * 256u + waves / ng * (rt * 1024u);
 }
 
 template <int CT, int RT, int NG, int TH>
 static hipError_t launch_mxs_t(const MxArgs& a, uint32_t rows_per_block, hipStream_t st) {
     const uint32_t rpp = (TH / 64 / NG) * RT * 16u;
-    rows_per_block = (rows_per_block + rpp - 1) / rpp * rpp;
-    const uint32_t n_rowblocks = (uint32_t)((a.n_rows + rows_per_block - 1) / rows_per_block);
     // four ring slots (slabs and row requests three steps ahead) where they fit the 160 KB, else three
     const bool ring4 = mxs_lds_bytes_t(CT * NG, RT, NG, TH, 4) <= 160u * 1024u;
     const size_t lds = mxs_lds_bytes_t(CT * NG, RT, NG, TH, ring4 ? 4 : 3);
-    if (lds > 160u * 1024u) return hipErrorInvalidValue;
-    const void* fn = ring4 ? (const void*)mxs_kernel<CT, RT, NG, TH, 4> : (const void*)mxs_kernel<CT, RT, NG, TH, 3>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    const uint32_t grid = a.n_lgroups > 1 ? (n_rowblocks + 7u) / 8u * 8u * a.n_lgroups : n_rowblocks;
-    if (ring4)
-        launch_last(mxs_kernel<CT, RT, NG, TH, 4>, dim3(grid), dim3(TH), lds, st, a, rows_per_block, n_rowblocks);
-    else
-        launch_last(mxs_kernel<CT, RT, NG, TH, 3>, dim3(grid), dim3(TH), lds, st, a, rows_per_block, n_rowblocks);
+    const auto kernel = ring4 ? mxs_kernel<CT, RT, NG, TH, 4> : mxs_kernel<CT, RT, NG, TH, 3>;
+    FilterGrid g;
+    const hipError_t e = filter_grid((const void*)kernel, a, rpp, rows_per_block, a.n_lgroups > 1, lds, g);
+    if (e != hipSuccess) return e;
+    launch_last(kernel, dim3(g.grid), dim3(TH), lds, st, a, g.rows_per_block, g.n_rowblocks);
     return hipGetLastError();
 }
 
@@ -629,7 +390,6 @@ size_t mxs_lds_bytes(uint32_t CT, uint32_t NG) {
 hipError_t launch_mxs(const MxArgs& a, uint32_t CT, uint32_t NG, uint32_t form, uint32_t rows_per_block, hipStream_t st) {
     if (a.n_rows == 0) return hipSuccess;
     if (!mxs_supported(CT, NG, a.n_slices, a.s1_fp6)) return hipErrorInvalidValue;
-    if ((a.n_rows * a.src.stride_dw + a.src.off_dw + a.src.avail_dw) * 4ull >= (1ull << 32)) return hipErrorInvalidValue;  // 32-bit byte offsets
 #ifdef KGWAS_MXS_BENCH_ONLY  // experiments: the shapes of the 2048 x 201 and 1135 x 101 benches only (fast compiles)
     if (NG == 2 && CT == 7) return launch_mxs_t<7, 4, 2, 512>(a, rows_per_block, st);
     if (NG == 1 && CT == 13) return form == 2 ? launch_mxs_t<13, 4, 1, 256>(a, rows_per_block, st) : launch_mxs_t<13, 2, 1, 512>(a, rows_per_block, st);

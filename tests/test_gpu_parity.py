@@ -376,6 +376,49 @@ def test_block_scaled_filter_streaming_form(monkeypatch, S_f, S, P, kind, reorde
     scan.close()
 
 
+@pytest.mark.parametrize("form", [0, 1, 2])
+def test_streaming_filter_partial_wave_in_each_half_of_a_bitmap_word(monkeypatch, form):
+    """The survivor store of filter_common.h at the ends of a chunk. With two row tiles per wave (KGWAS_MXS_FORM=1) a wave's 32
+    rows are ONE BYTE of a quarter of the bitmap's nibble-transposed 64-row word, the byte (rbase / 32) % 2; with four row
+    tiles (forms 0 and 2) they are the whole quarter. 241 samples x 113 columns stream as 8 column tiles under forms 1 and 2 and
+    as 2 x 4 tiles under form 0. After one piece of 4096 rows that fills the heaps, four pieces of 2048 + {1, 32, 33, 63} rows
+    (chunks of 2048) make a piece's last chunk end 1, 32, 33 and 63 rows into a word - a partial wave in the lower and in the
+    upper half, a full lower half with nothing above it -, and the last row of each piece is a planted pattern (the samples
+    above column 0's median) that must come out in column 0's top N: its bit is the last one the chunk's last wave stores."""
+    monkeypatch.setenv("KGWAS_COARSE_MX", "1")
+    monkeypatch.setenv("KGWAS_MXS", "3")
+    monkeypatch.setenv("KGWAS_MXS_FORM", str(form))
+    S, P, topn = 241, 113, 211
+    pieces = [4096] + [2048 + k for k in (1, 32, 33, 63)]
+    ends = np.cumsum(pieces)
+    n = int(ends[-1])
+    rows = random_table(n, S, seed=241 * 13 + P, dup_frac=0.25)
+    Y = phenotypes(S, P - 1, seed=P + 17)
+    W = (S + 63) // 64
+    pad = np.zeros(W * 64, dtype=bool)
+    pad[:S] = Y[0] > np.median(Y[0])
+    planted = ends[1:] - 1
+    rows[planted, 1:] = np.packbits(pad.reshape(W, 64), axis=1, bitorder="little").view(np.uint64).reshape(W)
+    col = np.arange(S, dtype=np.uint64)
+    mac = onp.min_count(S, 0.05, 5)
+    exp = ob.associate(rows, S, col, Y, topn, mac, batch_size=9000, threads=4)
+    assert np.isin(planted, exp["per_pheno"][0]["file_row"]).all(), "the planted rows are not in the oracle's top N of column 0"
+    scan = kg.AssociationScan(S, col, Y, topn, mac, kernel=kg.KERNEL_COARSE, chunk_rows=2048)
+    first = 0
+    for e in ends:
+        scan.feed_host(rows[first:int(e)], first)
+        first = int(e)
+    scan.finish()
+    st = scan.stats()
+    ct, stream = (4, 1) if form == 0 else (8, 1 + form)
+    assert st["kernel_used"] == kg.KERNEL_COARSE and st["coarse_mx"] == 1 and st["coarse_launches"] > 0
+    assert st["coarse_mx_stream"] == stream, st
+    assert st["coarse_mode_lgroups"][1] == 1 and st["coarse_mode_tiles"][1] == ct, st
+    _check_topn(scan, exp, P)
+    assert st["rows_tested"] == exp["tested"]
+    scan.close()
+
+
 def test_mixed_filter_sets_int8_steady_state_block_scaled_ramp(monkeypatch):
     """4096 samples x 100 columns with nothing forced: the block-scaled operands (one column tile per LDS group: seven groups)
     would make a row pass through more than one more LDS group than the int8 filter's single slice (four groups of two tiles),
