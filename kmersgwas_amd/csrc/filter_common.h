@@ -9,6 +9,7 @@
 // 1 the tests are replaced by an XOR over all accumulators (every MFMA stays alive), 2 no operand expansion, 4 no LDS
 // operand reads, 16 constant row terms, 32 a token side effect instead of the survivor emission.
 #pragma once
+#include "block_prims.h"  // filter_add_tested: the tested-row count, shared with the narrow filter
 #include "kernels.h"
 
 namespace kgwas {
@@ -131,7 +132,7 @@ __device__ __forceinline__ void filter_xor_hits(const V4 (&acc)[RT][NT], uint64_
 // Column (g, m)'s row bits then sit in four lanes (kb = 0..3; bit i = 4 rt + jj of mb[g] is row 16 rt + 4 kb + jj of the
 // wave's rows). The chunk's bitmap is [column][64-row word], nibble-transposed (quarter kb, nibble rt = row / 16):
 // a wave with four row tiles stores its 16 bits as quarter kb of the column's word, one with two row tiles its 8 bits as
-// byte (rbase / 32) % 2 of that quarter - no cross-lane traffic, and launch_bitmap_keys(nibble_transposed = true) puts
+// byte (rbase / 32) % 2 of that quarter - no cross-lane traffic, and launch_bitmap_keys (survivors.hip) puts
 // the nibbles back in row order. The bitmap is zeroed beforehand; only non-zero pieces are stored.
 template <int ABLATE, int PG, int RT, class Args, class Margin>
 __device__ __forceinline__ void filter_emit(const Args& a, const uint64_t (&hit)[RT * 4], const float (&alc)[PG], const float (&er)[RT * 4],
@@ -171,14 +172,6 @@ __device__ __forceinline__ void filter_emit(const Args& a, const uint64_t (&hit)
         for (int g = 0; g < PG; g++)
             if (mb[g]) bm8[(uint64_t)colp[g * 16 + m] * a.words_per_col * 8u] = (unsigned char)mb[g];
     }
-}
-
-// the block's tested rows (every lane counted its own) into one of the counter's shards
-__device__ __forceinline__ void filter_add_tested(unsigned long long* tested, uint32_t v, uint32_t lane) {
-    if (!tested) return;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d);
-    if (lane == 0u && v) atomicAdd(&tested[blockIdx.x % TESTED_SHARDS], (unsigned long long)v);
 }
 
 // ---- the block-scaled filters (mx_kernel, mxs_kernel) ----------------------------------------------------------------

@@ -99,8 +99,7 @@ hipError_t launch_score_mfma(const ScoreArgs& a, uint32_t rows_per_block, uint32
 size_t mfma_lds_bytes(uint32_t W_m);
 
 // Coarse int8 filter (score_coarse.hip). Survivors are bits of a [column][row] bitmap; launch_bitmap_keys lists them,
-// and launch_rescore scores them exactly, column by column in row order (it takes the sparse-mode ScoreArgs, with
-// Yperm set).
+// and launch_rescore scores them exactly, column by column in row order (survivors.hip, below).
 // Per-slot constants of the coarse filter (score_coarse.hip); a slot is one of the PG*16 operand columns of an LDS
 // group. y_i ~ c + u*(254*q0_i + q1_i) (two slices) or c + u*q0_i (one slice), c = sum/N. A pair survives iff
 // |Dc| >= sqrt(thr)*kalpha*sqrt(d) - iu*E(N1), constants already rounded in the conservative direction by the host.
@@ -166,37 +165,11 @@ hipError_t launch_mx(const MxArgs& a, uint32_t CT, uint32_t rows_per_block, hipS
 bool mxs_supported(uint32_t CT, uint32_t NG, uint32_t n_slices, uint32_t s1_fp6);
 size_t mxs_lds_bytes(uint32_t CT, uint32_t NG);
 hipError_t launch_mxs(const MxArgs& a, uint32_t CT, uint32_t NG, uint32_t form, uint32_t rows_per_block, hipStream_t st);
-// Survivors (sorted keys, per-column ranges) -> exact candidates compacted in (column, row) order into a.so_score /
-// a.so_kmer / a.so_row (HBM); meta[0..P) = candidates per column, meta[P..2P) = their offsets, meta[2P] = total,
-// meta[2P + 1] = survivor keys emitted. tile_pref [P + 1], tile_cnt [key_cap / 256 + P + 1], tmp_score [key_cap].
-hipError_t launch_rescore(const ScoreArgs& a, const uint32_t* keys, const uint32_t* surv_off, const uint32_t* surv_cnt,
-                          uint32_t row_bits, uint32_t* tile_pref, uint32_t* tile_cnt, double* tmp_score,
-                          const uint32_t* key_count, uint32_t* meta, hipStream_t st);
-// Scans of a few columns: every survivor's record goes straight to its place in the key order (a.so_score = exact score or
-// -inf for a survivor that is no candidate - the host's replay skips those), no tile scan, no compaction; meta was written
-// by launch_narrow_keys (records per column = survivors per column).
-hipError_t launch_rescore_direct(const ScoreArgs& a, const uint32_t* keys, const uint32_t* surv_off, const uint32_t* surv_cnt,
-                                 uint32_t row_bits, const uint32_t* tile_pref, hipStream_t st);
-// Counters of the next chunk and its survivors' bitmap (bitmap_words 64-bit words, may be 0) zeroed in one launch;
-// seg_cnt (n_seg_words, may be 0): the narrow filter's per-segment survivor counts. tu.hist != null: the kernel's first
-// blocks also raise the thresholds from the histograms (thr_update_kernel's work without a launch of its own: the chunk
-// that follows is filtered against everything counted before it).
-struct PrepThr {
-    const uint32_t* hist;
-    const uint32_t* hist_base;
-    uint32_t bins;
-    const uint64_t* topn;
-    const double* thr_host;
-    double* thr;
-};
-hipError_t launch_chunk_prep(uint32_t* cand_cnt, uint32_t n_pheno, unsigned long long* tested, uint32_t* key_count,
-                             unsigned long long* bitmap, uint64_t bitmap_words, uint32_t* seg_cnt, uint32_t n_seg_words, const PrepThr& tu,
-                             hipStream_t st);
 
 // Narrow filter (score_narrow.hip): scans with one to four phenotype columns. FP4 table bits x three FP8 slices per
 // column on v_mfma_scale_f32_16x16x128_f8f6f4; operand row 4 p + k = slice k of phenotype column p, row 4 p + 3 = ones
 // (N1), so that lane (table row, p) of the accumulator tile holds everything its pair needs. Survivors go to the same
-// key list as the coarse filter's.
+// bitmap as the wide filters' (in row order: launch_narrow_keys lists them).
 constexpr int NARROW_SLICES = 3;
 constexpr uint32_t NARROW_MAX_COLS = 4;
 struct NarrowCol {
@@ -224,23 +197,51 @@ struct NarrowArgs {
     uint64_t slack_rows;       // rows of the same buffer that follow the launch's rows (readable: the staged kernel may read whole KB past its last row)
     uint32_t pack1;            // one column whose operand rows are replicated in all four column slots: lane (r, kb) tests row 16 kb + r of the pass
 };
+size_t narrow_lds_bytes(uint32_t n_kgroups);
+hipError_t launch_narrow(const NarrowArgs& a, uint32_t rows_per_block, hipStream_t st);
+
+// ---- behind the filters (survivors.hip): bitmap -> keys -> exact records, and the next chunk's prep launch ----------------
 // The bitmap's set bits as row-ordered keys (column << row_bits | row), column after column, with each column's range
 // (surv_off, surv_cnt) and the total (key_count; above key_cap = overflow, the ranges are then emptied). No sort: counts
-// per 65 536-row block, a scan, a scatter. nibble_transposed: the words come from the int8 filters (quarter word kg,
-// nibble rt = rows 16 rt + 4 kg ..+3). tile_pref[n_pheno + 1]: launch_rescore's tile table (first tile of each column). blk_scratch: n_pheno * (ceil(n_rows / 65536) + 1) words;
+// per 65 536-row block, a scan, a scatter. The words are always the wide filters' nibble-transposed ones (quarter word kg,
+// nibble rt = rows 16 rt + 4 kg ..+3: filter_emit in filter_common.h); the scatter puts them back in row order. tile_pref[n_pheno + 1]: launch_rescore's tile table (first tile of each column). blk_scratch: n_pheno * (ceil(n_rows / 65536) + 1) words;
 // blk_mask: 4 x 64 bits per (column, block) - the count kernel marks the threads whose words hold a survivor, the scatter kernel
 // loads only those and CLEARS them: the bitmap is all zero again behind this call (the caller zeroes it once, not per chunk).
 hipError_t launch_bitmap_keys(unsigned long long* bitmap, uint64_t words_per_col, uint64_t n_rows, uint32_t n_pheno, uint32_t* blk_scratch,
                               unsigned long long* blk_mask, uint32_t* keys_sorted, uint32_t key_cap, uint32_t row_bits, uint32_t* surv_off,
-                              uint32_t* surv_cnt, uint32_t* key_count, uint32_t* tile_pref, bool nibble_transposed, hipStream_t st);
+                              uint32_t* surv_cnt, uint32_t* key_count, uint32_t* tile_pref, hipStream_t st);
 // The same for the narrow filter (one to four columns), whose kernels have already counted the survivors per segment
 // (NarrowArgs::seg_cnt): ONE launch instead of four - every (segment, column) block adds up the counts before it and
 // writes its keys; block (0, 0) writes the ranges, the tile table and meta (records = survivors: see launch_rescore_direct).
 hipError_t launch_narrow_keys(const unsigned long long* bitmap, uint64_t words_per_col, uint64_t n_rows, uint32_t n_pheno, const uint32_t* seg_cnt,
                               uint32_t* keys_sorted, uint32_t key_cap, uint32_t row_bits, uint32_t* surv_off, uint32_t* surv_cnt,
                               uint32_t* key_count, uint32_t* tile_pref, uint32_t* meta, const unsigned long long* tested_shards, hipStream_t st);
-size_t narrow_lds_bytes(uint32_t n_kgroups);
-hipError_t launch_narrow(const NarrowArgs& a, uint32_t rows_per_block, hipStream_t st);
+// Survivors (sorted keys, per-column ranges; a sparse-mode ScoreArgs with Yperm set) -> exact candidates compacted in (column, row) order into a.so_score /
+// a.so_kmer / a.so_row (HBM); meta[0..P) = candidates per column, meta[P..2P) = their offsets, meta[2P] = total,
+// meta[2P + 1] = survivor keys emitted. tile_pref [P + 1], tile_cnt [key_cap / 256 + P + 1], tmp_score [key_cap].
+hipError_t launch_rescore(const ScoreArgs& a, const uint32_t* keys, const uint32_t* surv_off, const uint32_t* surv_cnt,
+                          uint32_t row_bits, uint32_t* tile_pref, uint32_t* tile_cnt, double* tmp_score,
+                          const uint32_t* key_count, uint32_t* meta, hipStream_t st);
+// Scans of a few columns: every survivor's record goes straight to its place in the key order (a.so_score = exact score or
+// -inf for a survivor that is no candidate - the host's replay skips those), no tile scan, no compaction; meta was written
+// by launch_narrow_keys (records per column = survivors per column).
+hipError_t launch_rescore_direct(const ScoreArgs& a, const uint32_t* keys, const uint32_t* surv_off, const uint32_t* surv_cnt,
+                                 uint32_t row_bits, const uint32_t* tile_pref, hipStream_t st);
+// Counters of the next chunk and its survivors' bitmap (bitmap_words 64-bit words, may be 0) zeroed in one launch;
+// seg_cnt (n_seg_words, may be 0): the narrow filter's per-segment survivor counts. tu.hist != null: the kernel's first
+// blocks also raise the thresholds from the histograms (thr_update_kernel's work without a launch of its own: the chunk
+// that follows is filtered against everything counted before it).
+struct PrepThr {
+    const uint32_t* hist;
+    const uint32_t* hist_base;
+    uint32_t bins;
+    const uint64_t* topn;
+    const double* thr_host;
+    double* thr;
+};
+hipError_t launch_chunk_prep(uint32_t* cand_cnt, uint32_t n_pheno, unsigned long long* tested, uint32_t* key_count,
+                             unsigned long long* bitmap, uint64_t bitmap_words, uint32_t* seg_cnt, uint32_t n_seg_words, const PrepThr& tu,
+                             hipStream_t st);
 
 // --pattern_counter: append hash_presence_absence_pattern of every MAC-passing row to out[*out_count ...];
 // count_distinct_u64 sorts the collected hashes in place (device) and returns how many are distinct.

@@ -200,7 +200,7 @@ static void alloc_filter_buffers(kgwas_scan* s) {
     s->bitmap_clean = false;
     s->d_surv_cnt.alloc(P);
     s->d_surv_off.alloc(P);
-    s->d_key_count.alloc(2);  // the survivor count; the narrow re-score kernel's block counter
+    s->d_key_count.alloc(1);  // the survivor count
     s->d_tile_pref.alloc(P + 1);
     s->d_tile_cnt.alloc((size_t)s->key_slots / 256 + P + 2);
     s->d_tmp_score.alloc(s->key_slots);

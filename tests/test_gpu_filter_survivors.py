@@ -145,6 +145,77 @@ def test_filter_keeps_its_inner_set_and_nothing_outside_its_outer_set(case, monk
     scan.close()
 
 
+# The chunk sizes a resident table is scanned in - the planner's, not a cap of 2048 to 8192 rows as above. Only there a narrow
+# chunk spans several 65 536-row segments (blocks of 768 rows straddle their boundaries: the per-block two-segment counters, the
+# key kernel's cross-segment offsets) and a wide chunk several 1024-word bitmap blocks (the count scan's carry, the scatter
+# kernel's column base). The model's inner and outer sets stay with the 24 k-row cases above; here every pair above its chunk's
+# threshold must be listed, each key once and in order, and the heaps must be the oracle's.
+_PLANNER_CASES = [
+    # name, columns, table rows, narrow, rows a chunk must exceed (narrow: 262 144 rows = four segments and a 768-row block
+    # across every boundary between them; wide: more than 131 072 rows = three bitmap blocks)
+    ("narrow_241x1_pack1", 1, 600_011, True, 262_144 - 1),
+    ("narrow_241x4", 4, 600_011, True, 262_144 - 1),
+    ("wide_241x5", 5, 300_011, False, 131_072),
+]
+
+
+@pytest.mark.parametrize("name,P,n,narrow,big", _PLANNER_CASES, ids=[c[0] for c in _PLANNER_CASES])
+def test_survivors_at_the_planners_chunk_sizes(name, P, n, narrow, big, monkeypatch):
+    import torch
+    monkeypatch.setenv("KGWAS_DEBUG_SURVIVORS", "1")
+    S, topn, seed = 241, 100, 4711 + P
+    W = 1 + (S + 63) // 64  # 40 bytes per row: the staged narrow kernel reads a wave's 64 rows as three KB
+    rng = np.random.default_rng(31 + P)
+    y0 = rng.standard_normal(S).astype(np.float32)
+    Y = np.stack([y0] + [rng.permutation(y0) for _ in range(P - 1)]).astype(np.float32)
+    col = np.arange(S, dtype=np.uint64)
+    mac = fm.min_count(S)
+    stream = torch.cuda.current_stream().cuda_stream
+    t = torch.empty(n * W, dtype=torch.int64, device="cuda")
+    kg.synth_rows_device(t.data_ptr(), 0, n, S, seed, stream)
+    rows = kg.synth_rows_host(0, n, S, seed)
+    exp = ob.associate(rows, S, col, Y, topn, mac, threads=8)
+    scores, keep = ob.scores_dense(rows, S, col, Y, mac)
+
+    scan = kg.AssociationScan(S, col, Y, topn, mac)  # chunk_rows = 0: the planner's chunks
+    scan.feed_device(t.data_ptr(), n, 0, stream)
+    scan.finish()
+    st = scan.stats()
+    chunks = _logged_chunks(scan, P)
+
+    # not vacuous: the intended path, at the sizes the case exists for
+    assert st["kernel_used"] == (kg.KERNEL_NARROW if narrow else kg.KERNEL_COARSE) and st["direct_mode"] == 1, st
+    assert not any(ch["overflow"] for ch in chunks)
+    sizes = [ch["n"] for ch in chunks]
+    assert max(sizes) > big, sizes
+    assert any(x % 64 for x in sizes), sizes
+    if narrow:
+        assert max((x + 65535) // 65536 for x in sizes) >= 5, sizes  # n_segs
+
+    surv = np.zeros((n, P), bool)
+    must = np.zeros((n, P), bool)
+    end = 0
+    for ci, ch in enumerate(chunks):
+        assert ch["first"] >= end and ch["first"] + ch["n"] <= n and ch["n"] > 0
+        end = ch["first"] + ch["n"]
+        pr = ch["pairs"].astype(np.int64)
+        assert (pr[:, 0] < P).all() and (pr[:, 1] < ch["n"]).all()
+        flat = pr[:, 0] * (1 << 32) + pr[:, 1]
+        assert (np.diff(flat) > 0).all(), "chunk %d: keys out of (column, row) order or repeated" % ci
+        surv[ch["first"] + pr[:, 1], pr[:, 0]] = True
+        assert np.isfinite(ch["thr"]).all() and (ch["thr"] >= 0).all()
+        must[ch["first"]:end] = (scores[:, ch["first"]:end].T > ch["thr"][None, :]) & keep[ch["first"]:end, None]
+    assert not surv[~keep].any(), "a row outside the MAC rule survived"
+    lost = must & ~surv
+    assert not lost.any(), "%d pairs above their chunk's threshold are not among the survivors, first (row, column) %s" % (
+        int(lost.sum()), np.argwhere(lost)[:8].tolist())
+    assert must.any()
+
+    assert st["rows_tested"] == exp["tested"]
+    check_topn(scan, exp, P)
+    scan.close()
+
+
 def test_survivor_log_needs_its_switch(monkeypatch):
     """Without KGWAS_DEBUG_SURVIVORS a session logs nothing and says so."""
     monkeypatch.delenv("KGWAS_DEBUG_SURVIVORS", raising=False)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Build variants of libkgwas.so that differ only in score_narrow.hip's compile-time switches (narrow filter experiments):
-#   tools/rescore_variants.sh name1:"-DFLAG=1 ..." ...  ->  tools/bin/libkgwas_<name>.so   (time them with tools/mx_ab.sh)
+#   tools/narrow_variants.sh name1:"-DFLAG=1 ..." ...  ->  tools/bin/libkgwas_<name>.so   (time them with tools/mx_ab.sh)
 set -e
 cd "$(dirname "$0")/../kmersgwas_amd/csrc"
 make -s -j16 >/dev/null
