@@ -238,7 +238,8 @@ typedef struct kgwas_scan_stats {
  * kgwas_lmm_null_reml, kgwas_lmm_test_bed_all, kgwas_lmm_run_files_all, kgwas_lmm_format_assoc4, kgwas_fdist_tail (lmm_lrt -lmm 4),
  * and kgwas_lmm_set_covariates, kgwas_lmm_read_covariates, kgwas_lmm_run_files_cov, kgwas_lmm_run_table_cov (lmm_lrt -c),
  * and struct kgwas_lmm_unique_stats, kgwas_lmm_test_table_unique, kgwas_lmm_run_table_unique (lmm_lrt --pattern_cache),
- * and struct kgwas_lmm_skip_stats, kgwas_lmm_test_table_multi_skip, kgwas_lmm_run_table_multi_skip (lmm_lrt --pattern_skip).
+ * and struct kgwas_lmm_skip_stats, kgwas_lmm_test_table_multi_skip, kgwas_lmm_run_table_multi_skip (lmm_lrt --pattern_skip),
+ * and structs kgwas_proxy_record, kgwas_proxy_stats, kgwas_kmers_ld_proxies, kgwas_proxy_kmers_run (proxy_kmers).
  * Those came after version 15 without a bump: a caller that may meet an older version-15 library probes for them by symbol
  * (dlsym, or hasattr on a ctypes handle). */
 #define KGWAS_ABI_VERSION 15
@@ -860,6 +861,47 @@ int kgwas_kmers_ld(const uint64_t* bits, uint64_t n_kmers, uint64_t words_per_ro
                    uint64_t tile_rows, uint32_t* adj, uint32_t* n1);
 int kgwas_clump_kmers_run(const char* table_base, uint32_t kmer_len, const char* pheno_path, const char* assoc_path, uint32_t r2_millionths,
                           double p_max, int32_t device, uint64_t tile_rows, const char* out_path, kgwas_clump_stats* st);
+
+/* ------------------------------------------------------------------------------------
+ * proxy_kmers: every k-mer of the table in LD with a lead k-mer - the step after clump_kmers, which ends with one lead per
+ * signal: the k-mers that travel with a lead are the ones to assemble or map. A tool of this project's own. A row of the table
+ * is a PROXY of a lead iff the pair is linked by clump_kmers' predicate (above: num * 1000000 >= r2_millionths * den, den > 0,
+ * in 128-bit integers on the device). Every (lead, row) pair is tested, the lead's own row included: a non-constant lead finds
+ * itself, a constant lead finds nothing, a complement is a proxy (phase -).
+ *
+ * kgwas_kmers_ld_proxies: the array level. lead_bits[n_leads][words_per_row] and bits[n_rows][words_per_row], bit i of a row =
+ * accession i (bits at or past n_acc are ignored). The leads' operands stay on the device; the rows pass in pieces (the next
+ * piece's copy beside this piece's kernels), n11 on the matrix cores, one bit per pair, and the linked pairs are compacted on
+ * the device into records {row, kmer = 0, lead, n1 of the row, n11, pad = 0}: rows ascending (row = the index into bits), leads
+ * ascending within a row, the same bytes in every run. *n_out gets the count of all records; the first min(cap, *n_out) of them
+ * are written to records_out. Checked before any device call (KGWAS_ERR_ARG): a null lead_bits or n_out, null bits with
+ * n_rows > 0, null records_out with cap > 0, n_acc of 0 or above 8192, n_leads of 0 or above 4096, words_per_row below
+ * ceil(n_acc / 64), r2_millionths of 0 or above 1000000. KGWAS_PROXY_PIECE_ROWS (rows per piece, at most 2^18) and
+ * KGWAS_PROXY_RECORDS (records of the device buffer, default 2^20; a piece with more is drained in rounds) are the tests' hooks.
+ * kgwas_proxy_kmers_run: the tool. leads_path is a list of k-mers, one per line, or a clump_kmers output (known by its header:
+ * the distinct values of its column `lead`, in clump order). Refused by name (KGWAS_ERR_FORMAT) before the table is opened: a
+ * k-mer of another length than kmer_len, with an illegal letter, or given twice (in a list). The leads' rows come from
+ * <table_base>.table by kgwas_filter_kmers' search (a lead the table lacks is an error that names it); r2 is taken over the
+ * accessions of pheno_path in its order (NULL: every accession of the table), 1 to 8192 of them; then ONE pass over the table.
+ * out_path gets the header "lead kmer r2 phase n1 n11 row" (tabs) and one line per kept proxy, grouped by lead in the leads'
+ * order and within a lead in table-row order: the lead as its file spells it, the proxy's k-mer, r2 (%.6f of num / den), phase
+ * (+ or -: the sign of n n11 - ca cb), n1 of the proxy, n11 with the lead, the table row. Per lead the first max_per_lead
+ * proxies in table order are kept, the rest only counted. out_path + ".log.txt": the inputs, one line "lead <k-mer> <kept>
+ * <found>" per lead, the counters and the times. *st (may be NULL) is written when the call succeeds.
+ * ---------------------------------------------------------------------------------- */
+typedef struct kgwas_proxy_record {
+    uint64_t row, kmer;
+    uint32_t lead, n1, n11, pad;
+} kgwas_proxy_record;
+typedef struct kgwas_proxy_stats {
+    uint64_t accessions, leads, rows_read, pairs_tested, proxies_found, proxies_kept, drain_rounds;
+    double search_ms, kernel_ms, copy_ms, total_ms; /* the leads' table search, the kernels and the pieces' copies (events), all */
+} kgwas_proxy_stats;
+int kgwas_kmers_ld_proxies(const uint64_t* lead_bits, uint64_t n_leads, const uint64_t* bits, uint64_t n_rows, uint64_t words_per_row,
+                           uint64_t n_acc, uint32_t r2_millionths, int32_t device, kgwas_proxy_record* records_out, uint64_t cap,
+                           uint64_t* n_out);
+int kgwas_proxy_kmers_run(const char* table_base, uint32_t kmer_len, const char* pheno_path, const char* leads_path, uint32_t r2_millionths,
+                          uint64_t max_per_lead, int32_t device, const char* out_path, kgwas_proxy_stats* st);
 
 /* ------------------------------------------------------------------------------------
  * Seeded synthetic table rows: kmer = row + 1, per-row frequency q/256 with

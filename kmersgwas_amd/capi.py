@@ -51,6 +51,7 @@ SYMBOLS = [
     "kgwas_lmm_test_table_unique", "kgwas_lmm_run_table_unique",
     "kgwas_lmm_test_table_multi_skip", "kgwas_lmm_run_table_multi_skip",
     "kgwas_r2_millionths", "kgwas_kmers_ld", "kgwas_clump_kmers_run",
+    "kgwas_kmers_ld_proxies", "kgwas_proxy_kmers_run",
     "kgwas_synth_rows_device", "kgwas_synth_rows_host",
 ]
 
@@ -67,6 +68,18 @@ class ClumpStats(C.Structure):
     _fields_ = [("hits_read", C.c_uint64), ("hits_used", C.c_uint64), ("clumps", C.c_uint64), ("largest_clump", C.c_uint64),
                 ("linked_pairs", C.c_uint64), ("accessions", C.c_uint64), ("search_ms", C.c_double), ("ld_ms", C.c_double),
                 ("clump_ms", C.c_double)]
+
+
+class ProxyRecord(C.Structure):
+    """kgwas_proxy_record"""
+    _fields_ = [("row", C.c_uint64), ("kmer", C.c_uint64), ("lead", C.c_uint32), ("n1", C.c_uint32), ("n11", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class ProxyStats(C.Structure):
+    """kgwas_proxy_stats"""
+    _fields_ = [("accessions", C.c_uint64), ("leads", C.c_uint64), ("rows_read", C.c_uint64), ("pairs_tested", C.c_uint64),
+                ("proxies_found", C.c_uint64), ("proxies_kept", C.c_uint64), ("drain_rounds", C.c_uint64), ("search_ms", C.c_double),
+                ("kernel_ms", C.c_double), ("copy_ms", C.c_double), ("total_ms", C.c_double)]
 
 
 class ScanParams(C.Structure):
@@ -290,6 +303,8 @@ lib.kgwas_filter_kmers_write.argtypes = [_vp, _vp, _u64, _i32, C.c_char_p, _pu64
 lib.kgwas_r2_millionths.argtypes = [C.c_char_p, C.POINTER(C.c_uint32)]
 lib.kgwas_kmers_ld.argtypes = [_vp, _u64, _u64, _u64, _u32, _i32, _u64, _vp, _vp]
 lib.kgwas_clump_kmers_run.argtypes = [C.c_char_p, _u32, C.c_char_p, C.c_char_p, _u32, C.c_double, _i32, _u64, C.c_char_p, C.POINTER(ClumpStats)]
+lib.kgwas_kmers_ld_proxies.argtypes = [_vp, _u64, _vp, _u64, _u64, _u64, _u32, _i32, _vp, _u64, C.POINTER(C.c_uint64)]
+lib.kgwas_proxy_kmers_run.argtypes = [C.c_char_p, _u32, C.c_char_p, C.c_char_p, _u32, _u64, _i32, C.c_char_p, C.POINTER(ProxyStats)]
 lib.kgwas_build_table.argtypes = [C.c_char_p, _pstr, _pstr, _u64, _u32, _i32, C.c_char_p, _pu64]
 lib.kgwas_list_kmers.argtypes = [_pstr, _u64, _u32, _u64, C.c_double, _i32, C.c_char_p, _pu64]
 lib.kgwas_count_kmers_files.argtypes = [_pstr, _u64, _u32, _u64, _u64, _i32, C.c_char_p, _pu64]

@@ -47,9 +47,11 @@
 //   KGWAS_COUNT_PIECE_BYTES=n  (test hook) bytes per pinned upload piece of kgwas_count_kmers_* (default 8 MiB); when set, a file is
 //                              read in blocks of 8 pieces by at most 3 threads and a device segment of the base stream holds 64 pieces
 //   KGWAS_COUNT_PARSE_ONLY=1   kgwas_count_kmers_files stops behind the parse and the upload (the tool's timing mode: no output file)
-//   KGWAS_LD_POPCOUNT=1        kgwas_kmers_ld / clump_kmers: the counts of common accessions come from popcount(AND) on the vector ALU
+//   KGWAS_LD_POPCOUNT=1        kgwas_kmers_ld / clump_kmers / proxy_kmers: the counts of common accessions come from popcount(AND) on the vector ALU
 //                              instead of the matrix cores (the ablation of DESIGN.md 4.13); the results are the same
-//   KGWAS_LD_TIMING=1          kgwas_kmers_ld prints its kernels' time (events around them alone) on stderr
+//   KGWAS_LD_TIMING=1          kgwas_kmers_ld and kgwas_kmers_ld_proxies print their kernels' time (events around them alone) on stderr
+//   KGWAS_PROXY_PIECE_ROWS=n   (test hook) rows per piece of kgwas_kmers_ld_proxies / proxy_kmers (default: up to 2^18, about 64 MiB of rows)
+//   KGWAS_PROXY_RECORDS=n      (test hook) records of their device record buffer (default 2^20); a piece with more is drained in rounds
 //   KGWAS_DEBUG_SLOW_WORKER=w:pct:min_us   (test hook) slows one replay worker down
 //   KGWAS_DEBUG_RESIDUALS=1    (test hook) sessions keep their filters' quantisation residuals (kgwas_scan_debug_residuals)
 //   KGWAS_DEBUG_SURVIVORS=1    (test hook) filter sessions log every filtered chunk's thresholds and survivors, synchronously

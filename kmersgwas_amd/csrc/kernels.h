@@ -410,4 +410,24 @@ hipError_t launch_ld_prep(const uint64_t* rows, uint64_t stride_w, uint64_t W, u
 hipError_t launch_ld_link(const void* P, const uint32_t* n1, const uint32_t* pq, const uint64_t* tq, uint64_t N, uint64_t N_pad, uint32_t n,
                           uint32_t n_chunks, uint64_t row0, uint64_t n_rows, uint32_t* out, uint64_t pitch_dw, bool popcount, hipStream_t st);
 
+// proxy_kmers (ld_kernels.hip): L <= 4096 leads (operands PA[n_chunks][L_pad], n1A, pqA from launch_ld_prep, L_pad a multiple of 64)
+// against a piece of R <= 2^20 rows (PB[n_chunks][R_pad], n1B, tqB, R_pad a multiple of 128); every pair is tested.
+//  rect : out[b * pitch_q + a / 64] bit a % 64 = (lead a and row b are linked); out holds R_pad rows of pitch_q >= L_pad / 64 words,
+//         the first L_pad / 64 of each are written.
+//  count: bcnt[ceil(R / 256)] the records per block of 256 rows, boff[.. + 1] the records before a block and, last, the total.
+//  write: the records numbered [win_lo, win_lo + cap) in (row, lead) order, from the blocks [blk0, blk1), to rec[number - win_lo].
+//         kmers (may be null: 0): row r's k-mer word is kmers[r * kmer_stride]. The record's layout is kgwas_proxy_record's.
+struct ProxyRecord {
+    uint64_t row, kmer;
+    uint32_t lead, n1, n11, pad;
+};
+hipError_t launch_ld_rect(const void* PA, const uint32_t* n1A, const uint32_t* pqA, uint64_t L, uint64_t L_pad, const void* PB, const uint32_t* n1B,
+                          const uint64_t* tqB, uint64_t R, uint64_t R_pad, uint32_t n, uint32_t n_chunks, uint64_t* out, uint64_t pitch_q,
+                          bool popcount, hipStream_t st);
+hipError_t launch_ld_proxy_count(const uint64_t* bits, uint64_t pitch_q, uint64_t R, uint32_t* bcnt, uint32_t* boff, hipStream_t st);
+hipError_t launch_ld_proxy_write(const uint64_t* bits, uint64_t pitch_q, uint64_t R, const uint32_t* boff, uint32_t blk0, uint32_t blk1,
+                                 uint32_t win_lo, uint32_t cap, const void* PA, uint64_t L_pad, const void* PB, uint64_t R_pad, uint32_t n_chunks,
+                                 const uint32_t* n1B, const uint64_t* kmers, uint64_t kmer_stride, uint64_t row_base, ProxyRecord* rec,
+                                 hipStream_t st);
+
 }  // namespace kgwas

@@ -11,6 +11,7 @@ Names follow the reference's classes (src/kmers_multiple_databases.h, src/best_a
   filter_kmers          <- filter_kmers (rows of listed k-mers)                       (f-6)
   build_kmers_table     <- build_kmers_table (the table from sorted k-mer files)      (f-7)
   kmers_ld              -- this project's own: exact r^2 links between k-mers (clump_kmers)
+  kmers_ld_proxies      -- this project's own: the rows in LD with a few lead rows, as records (proxy_kmers)
 
 Everything numeric happens inside libkgwas (HIP kernels on the GPU + the std::priority_queue
 replay); this module only moves buffers.
@@ -802,6 +803,30 @@ def kmers_ld(bits, n_acc: int, r2, tile_rows: int = 0, device: int = 0):
     n1 = np.zeros(n_kmers, np.uint32)
     check(lib.kgwas_kmers_ld(ptr(bits), n_kmers, words, n_acc, r2_millionths(r2), device, tile_rows, ptr(adj), ptr(n1)))
     return adj, n1
+
+
+PROXY_RECORD = np.dtype([("row", np.uint64), ("kmer", np.uint64), ("lead", np.uint32), ("n1", np.uint32), ("n11", np.uint32), ("pad", np.uint32)])
+
+
+def kmers_ld_proxies(lead_bits, bits, n_acc: int, r2, cap: int | None = None, device: int = 0):
+    """Which rows of `bits` have r^2 >= r2 with which rows of `lead_bits`, exactly (kgwas_kmers_ld_proxies: the leads stay on the
+    device, the rows pass in pieces, the linked pairs come back as records). lead_bits: uint64[n_leads, words], bits:
+    uint64[n_rows, words], bit i of a row = accession i; bits at or past n_acc are ignored. Returns (records, n): records is a
+    structured array of dtype PROXY_RECORD (row, kmer = 0, lead, n1 of the row, n11, pad = 0) in (row, lead) order and n the count
+    of all linked pairs. cap=None: every record is returned (a second call where the first guess was too small); otherwise the
+    first min(cap, n)."""
+    lead_bits, bits = np.ascontiguousarray(lead_bits, np.uint64), np.ascontiguousarray(bits, np.uint64)
+    if lead_bits.ndim != 2 or bits.ndim != 2 or lead_bits.shape[1] != bits.shape[1]:
+        raise ValueError("lead_bits and bits must be 2-d arrays of uint64 words with rows of the same width")
+    tm, n = r2_millionths(r2), C.c_uint64(0)
+    room = (4 * len(bits) + 1024) if cap is None else cap
+    while True:
+        rec = np.zeros(room, PROXY_RECORD)
+        check(lib.kgwas_kmers_ld_proxies(ptr(lead_bits), len(lead_bits), ptr(bits), len(bits), bits.shape[1], n_acc, tm, device,
+                                         ptr(rec) if room else None, room, C.byref(n)))
+        if cap is not None or n.value <= room:
+            return rec[:min(n.value, room)], n.value
+        room = n.value
 
 
 def filter_kmers_write(path: str, table: KmersTable, codes, device: int = 0) -> int:
