@@ -1,35 +1,17 @@
 // clump_host.h — the host side of clump_kmers that needs no device (clump.cpp; tools/clump_host_check.cpp runs it under the
-// sanitizers): the threshold's text, the assoc file, the p order, the streaming clump pass and the output's bytes.
+// sanitizers): the assoc file, the p order, the streaming clump pass and the output's bytes, over ld_host.h's text helpers.
 #pragma once
-#include <algorithm>
-#include <cerrno>
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <fstream>
-#include <limits>
-#include <string>
-#include <unordered_map>
-#include <vector>
-
-#include "common.h"
+#include "ld_host.h"
 
 namespace kgwas {
 namespace clump {
 
-// "0.8" -> 800000: decimal text with at most 6 digits after the point, 0 < t <= 1, read digit by digit (never through a double)
-inline uint32_t r2_millionths(const std::string& text) {
-    const Error bad(KGWAS_ERR_ARG, "--r2 '" + text + "' is not a decimal number with at most 6 digits after the point and 0 < r2 <= 1");
-    const size_t dot = text.find('.');
-    const std::string whole = text.substr(0, dot), frac = dot == std::string::npos ? std::string() : text.substr(dot + 1);
-    if ((whole.empty() && frac.empty()) || whole.size() > 6 || frac.size() > 6) throw bad;
-    if (whole.find_first_not_of("0123456789") != std::string::npos || frac.find_first_not_of("0123456789") != std::string::npos) throw bad;
-    uint64_t v = 0;
-    for (char c : whole) v = v * 10 + (uint64_t)(c - '0');
-    for (size_t i = 0; i < 6; i++) v = v * 10 + (i < frac.size() ? (uint64_t)(frac[i] - '0') : 0);
-    if (v < 1 || v > 1000000) throw bad;
-    return (uint32_t)v;
+constexpr uint64_t LD_MAX_KMERS = 1ull << 20;
+
+inline void check_clump_shape(const char* who, uint64_t n_kmers, uint64_t n_acc, uint32_t tm) {
+    check_ld_shape(who, n_acc, tm);
+    if (n_kmers > LD_MAX_KMERS)
+        throw Error(KGWAS_ERR_ARG, std::string(who) + ": " + std::to_string(n_kmers) + " k-mers: at most " + std::to_string(LD_MAX_KMERS) + " are clumped at once");
 }
 
 struct Hit {
@@ -38,22 +20,8 @@ struct Hit {
     uint64_t code = 0, line = 0;  // line: the hit's place among the file's data lines, from 0
 };
 
-inline std::vector<std::string> fields_of(const std::string& line) {
-    std::vector<std::string> f;
-    size_t i = 0;
-    while (i < line.size()) {
-        while (i < line.size() && (line[i] == ' ' || line[i] == '\t' || line[i] == '\r')) i++;
-        size_t j = i;
-        while (j < line.size() && line[j] != ' ' && line[j] != '\t' && line[j] != '\r') j++;
-        if (j > i) f.push_back(line.substr(i, j - i));
-        i = j;
-    }
-    return f;
-}
-
 // An lmm_lrt or GEMMA .assoc.txt: the columns `rs` (the k-mer's letters) and `p_lrt` are found by their names in the header, so
 // the 9-column and the 14-column layouts both read. encode is kgwas_kmer_encode (a status and the code).
-typedef int (*EncodeFn)(const char* word, uint64_t len, uint64_t* code);
 inline std::vector<Hit> read_assoc(const std::string& path, uint32_t kmer_len, EncodeFn encode) {
     std::ifstream f(path);
     if (!f.is_open()) throw Error(KGWAS_ERR_IO, "can't open assoc file: " + path);
@@ -79,9 +47,7 @@ inline std::vector<Hit> read_assoc(const std::string& path, uint32_t kmer_len, E
         h.rs = fl[c_rs];
         h.p_text = fl[c_p];
         h.line = hits.size();
-        if (h.rs.size() != kmer_len)
-            throw Error(KGWAS_ERR_FORMAT, at + "k-mer '" + h.rs + "' has length " + std::to_string(h.rs.size()) + ", not " + std::to_string(kmer_len));
-        if (encode(h.rs.c_str(), h.rs.size(), &h.code) != KGWAS_OK) throw Error(KGWAS_ERR_FORMAT, at + "k-mer '" + h.rs + "' has a letter other than A, C, G, T");
+        h.code = parse_kmer_field(h.rs, kmer_len, encode, at);
         char* end = nullptr;
         errno = 0;
         h.p = strtod(h.p_text.c_str(), &end);
@@ -142,13 +108,6 @@ inline uint32_t count_and(const uint64_t* a, const uint64_t* b, const uint64_t* 
     uint32_t c = 0;
     for (uint64_t w = 0; w < W; w++) c += (uint32_t)__builtin_popcountll(a[w] & b[w] & mask[w]);
     return c;
-}
-
-// r^2 as the quotient of two integers below 2^53; nan for a constant row
-inline double r2_of(uint64_t n, uint64_t ca, uint64_t cb, uint64_t n11) {
-    const int64_t d = (int64_t)(n * n11) - (int64_t)(ca * cb);
-    const uint64_t num = (uint64_t)(d * d), den = ca * (n - ca) * cb * (n - cb);
-    return den ? (double)num / (double)den : std::numeric_limits<double>::quiet_NaN();
 }
 
 // One output line: rs, p_lrt (the field's own text), clump (from 1, in lead order), lead, r2 against the lead, n1, n11.

@@ -1,4 +1,5 @@
-// device.h — the owners of HIP resources on the host side of libkgwas: device memory, streams, events, and the one device check.
+// device.h — the owners of HIP resources on the host side of libkgwas: device memory, streams, events, the squeeze's column map, the
+// r^2 kernels' operands, and the one device check.
 //
 // Teardown order is declaration order, reversed. A Stream's destructor synchronises before it destroys, so an owner declares the
 // pinned and device buffers a stream's work reads BEFORE the stream: the stream goes first, idle, and the buffers after it.
@@ -9,8 +10,10 @@
 #include <atomic>
 #include <cstdint>
 #include <thread>
+#include <vector>
 
 #include "common.h"
+#include "kernels.h"
 
 namespace kgwas {
 
@@ -196,6 +199,43 @@ struct UploadLane {
     }
     // the work queued on st so far reads the block last taken
     void sent() { KGWAS_HIP(hipEventRecord(ev[cur], st)); }
+};
+
+// The squeeze of table rows to a list of the table's columns (launch_squeeze): the padded column map on the device and W_m, the
+// 64-bit words of a squeezed row. Built from col[0..S), the columns in output order, and W_f, the words of a table row's bits.
+struct Squeezer {
+    uint32_t W_m = 0, W_f = 0;
+    DevBuf<uint32_t> d_colmap;
+    void create(const uint64_t* col, uint64_t S, uint64_t table_words) {
+        W_m = (uint32_t)(2 * ((S + 127) / 128));  // the reference's m_hash_words, rounded to the 128-bit unit
+        W_f = (uint32_t)table_words;
+        std::vector<uint32_t> colmap(64ull * W_m, 0xFFFFFFFFu);
+        for (uint64_t i = 0; i < S; i++) colmap[i] = (uint32_t)col[i];
+        d_colmap.alloc(std::max<size_t>(colmap.size(), 1));  // (no column at all: still something to point at)
+        KGWAS_HIP(hipMemcpy(d_colmap.p, colmap.data(), colmap.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    uint64_t words_per_row() const { return 2ull * W_m; }  // 32-bit words of a row of `out`
+    // d_rows[count][stride] (word 0 of a row is its k-mer) -> out[count][words_per_row()]
+    void run(const uint64_t* d_rows, uint64_t stride, uint64_t count, uint32_t* out, hipStream_t st) const {
+        KGWAS_HIP(launch_squeeze(d_rows, stride, count, d_colmap.p, W_m, W_f, out, st));
+    }
+};
+
+// The operands of the exact r^2 kernels for `pad` rows (a multiple of the kernels' tiles) over n accessions (kernels.h,
+// launch_ld_prep): the owner of what an LdView points at. A view is of `count` rows padded to `pad` <= alloc's.
+struct LdOperands {
+    DevBuf<uint4> P;
+    DevBuf<uint32_t> n1, pq;
+    DevBuf<uint64_t> tq;
+    uint32_t n_chunks = 0;
+    void alloc(uint64_t pad, uint64_t n) {
+        n_chunks = (uint32_t)((n + 511) / 512 * 4);
+        P.alloc((size_t)n_chunks * pad), n1.alloc(pad), pq.alloc(pad), tq.alloc(pad);
+    }
+    LdView view(uint64_t count, uint64_t pad) const {
+        if (pad > n1.n) throw Error(KGWAS_ERR_STATE, "LdOperands: a view of more rows than were allocated");
+        return LdView{P.p, n1.p, pq.p, tq.p, count, pad, n_chunks};
+    }
 };
 
 // The devices there are; throws when there is none.

@@ -405,13 +405,21 @@ hipError_t launch_kin_gram(const uint32_t* T, uint64_t n_rw, uint32_t S_pad, uns
 //        = (b > a and the pair is linked). out holds ceil(n_rows / 64) * 64 rows of pitch_dw dwords, pitch_dw a multiple of 4 with
 //        32 pitch_dw >= N_pad; every dword of it is written. popcount = true: n11 from the vector ALU instead of the matrix cores
 //        (the ablation; the same bits).
-hipError_t launch_ld_prep(const uint64_t* rows, uint64_t stride_w, uint64_t W, uint64_t N, uint32_t n, uint32_t n_chunks, uint64_t N_pad,
-                          uint32_t tm, void* P, uint32_t* n1, uint32_t* pq, uint64_t* tq, hipStream_t st);
-hipError_t launch_ld_link(const void* P, const uint32_t* n1, const uint32_t* pq, const uint64_t* tq, uint64_t N, uint64_t N_pad, uint32_t n,
-                          uint32_t n_chunks, uint64_t row0, uint64_t n_rows, uint32_t* out, uint64_t pitch_dw, bool popcount, hipStream_t st);
+// The operands of `count` rows as the launchers take them (device.h's LdOperands owns the memory): P, n1, pq, tq as above with
+// N = count and N_pad = pad.
+struct LdView {
+    void* P;
+    uint32_t *n1, *pq;
+    uint64_t* tq;
+    uint64_t count, pad;
+    uint32_t n_chunks;
+};
+hipError_t launch_ld_prep(const uint64_t* rows, uint64_t stride_w, uint64_t W, uint32_t n, uint32_t tm, const LdView& ops, hipStream_t st);
+hipError_t launch_ld_link(const LdView& ops, uint32_t n, uint64_t row0, uint64_t n_rows, uint32_t* out, uint64_t pitch_dw, bool popcount,
+                          hipStream_t st);
 
-// proxy_kmers (ld_kernels.hip): L <= 4096 leads (operands PA[n_chunks][L_pad], n1A, pqA from launch_ld_prep, L_pad a multiple of 64)
-// against a piece of R <= 2^20 rows (PB[n_chunks][R_pad], n1B, tqB, R_pad a multiple of 128); every pair is tested.
+// proxy_kmers (ld_kernels.hip): L = A.count <= 4096 leads (operands PA[n_chunks][L_pad], n1A, pqA from launch_ld_prep, L_pad a multiple
+// of 64) against a piece of R = B.count <= 2^20 rows (PB[n_chunks][R_pad], n1B, tqB, R_pad a multiple of 128); every pair is tested.
 //  rect : out[b * pitch_q + a / 64] bit a % 64 = (lead a and row b are linked); out holds R_pad rows of pitch_q >= L_pad / 64 words,
 //         the first L_pad / 64 of each are written.
 //  count: bcnt[ceil(R / 256)] the records per block of 256 rows, boff[.. + 1] the records before a block and, last, the total.
@@ -421,13 +429,10 @@ struct ProxyRecord {
     uint64_t row, kmer;
     uint32_t lead, n1, n11, pad;
 };
-hipError_t launch_ld_rect(const void* PA, const uint32_t* n1A, const uint32_t* pqA, uint64_t L, uint64_t L_pad, const void* PB, const uint32_t* n1B,
-                          const uint64_t* tqB, uint64_t R, uint64_t R_pad, uint32_t n, uint32_t n_chunks, uint64_t* out, uint64_t pitch_q,
-                          bool popcount, hipStream_t st);
+hipError_t launch_ld_rect(const LdView& A, const LdView& B, uint32_t n, uint64_t* out, uint64_t pitch_q, bool popcount, hipStream_t st);
 hipError_t launch_ld_proxy_count(const uint64_t* bits, uint64_t pitch_q, uint64_t R, uint32_t* bcnt, uint32_t* boff, hipStream_t st);
-hipError_t launch_ld_proxy_write(const uint64_t* bits, uint64_t pitch_q, uint64_t R, const uint32_t* boff, uint32_t blk0, uint32_t blk1,
-                                 uint32_t win_lo, uint32_t cap, const void* PA, uint64_t L_pad, const void* PB, uint64_t R_pad, uint32_t n_chunks,
-                                 const uint32_t* n1B, const uint64_t* kmers, uint64_t kmer_stride, uint64_t row_base, ProxyRecord* rec,
-                                 hipStream_t st);
+hipError_t launch_ld_proxy_write(const uint64_t* bits, uint64_t pitch_q, const uint32_t* boff, uint32_t blk0, uint32_t blk1, uint32_t win_lo,
+                                 uint32_t cap, const LdView& A, const LdView& B, const uint64_t* kmers, uint64_t kmer_stride, uint64_t row_base,
+                                 ProxyRecord* rec, hipStream_t st);
 
 }  // namespace kgwas

@@ -304,20 +304,20 @@ __global__ void __launch_bounds__(256) ld_proxy_write_kernel(const uint64_t* bit
     }
 }
 
-hipError_t launch_ld_rect(const void* PA, const uint32_t* n1A, const uint32_t* pqA, uint64_t L, uint64_t L_pad, const void* PB, const uint32_t* n1B,
-                          const uint64_t* tqB, uint64_t R, uint64_t R_pad, uint32_t n, uint32_t n_chunks, uint64_t* out, uint64_t pitch_q,
-                          bool popcount, hipStream_t st) {
+hipError_t launch_ld_rect(const LdView& A, const LdView& B, uint32_t n, uint64_t* out, uint64_t pitch_q, bool popcount, hipStream_t st) {
+    const uint64_t L = A.count, L_pad = A.pad, R = B.count, R_pad = B.pad;
     if (!R || !L) return hipSuccess;
     // what the kernels assume and do not check: whole tiles of padded operands and a pitch that holds every lead tile's word
-    if (L_pad % 64u || R_pad % 128u || n_chunks % 4u || L > L_pad || R > R_pad || pitch_q * 64u < L_pad || L_pad > 4096u || R_pad > (1ull << 20))
+    if (L_pad % 64u || R_pad % 128u || A.n_chunks % 4u || B.n_chunks != A.n_chunks || L > L_pad || R > R_pad || pitch_q * 64u < L_pad || L_pad > 4096u ||
+        R_pad > (1ull << 20))
         return hipErrorInvalidValue;
     const dim3 grid((uint32_t)(R_pad / 128u), (uint32_t)(L_pad / 64u));
     if (popcount)
-        hipLaunchKernelGGL(ld_rect_popc_kernel, grid, dim3(64), 0, st, (const uint4*)PA, n1A, pqA, (uint32_t)L, L_pad, (const uint4*)PB, n1B, tqB,
-                           (uint32_t)R, R_pad, n, n_chunks, out, pitch_q);
+        hipLaunchKernelGGL(ld_rect_popc_kernel, grid, dim3(64), 0, st, (const uint4*)A.P, (const uint32_t*)A.n1, (const uint32_t*)A.pq, (uint32_t)L, L_pad,
+                           (const uint4*)B.P, (const uint32_t*)B.n1, (const uint64_t*)B.tq, (uint32_t)R, R_pad, n, A.n_chunks, out, pitch_q);
     else
-        hipLaunchKernelGGL(ld_rect_kernel, grid, dim3(64), 0, st, (const uint4*)PA, n1A, pqA, (uint32_t)L, L_pad, (const uint4*)PB, n1B, tqB,
-                           (uint32_t)R, R_pad, n, n_chunks, out, pitch_q);
+        hipLaunchKernelGGL(ld_rect_kernel, grid, dim3(64), 0, st, (const uint4*)A.P, (const uint32_t*)A.n1, (const uint32_t*)A.pq, (uint32_t)L, L_pad,
+                           (const uint4*)B.P, (const uint32_t*)B.n1, (const uint64_t*)B.tq, (uint32_t)R, R_pad, n, A.n_chunks, out, pitch_q);
     return hipGetLastError();
 }
 
@@ -330,37 +330,38 @@ hipError_t launch_ld_proxy_count(const uint64_t* bits, uint64_t pitch_q, uint64_
     return hipGetLastError();
 }
 
-hipError_t launch_ld_proxy_write(const uint64_t* bits, uint64_t pitch_q, uint64_t R, const uint32_t* boff, uint32_t blk0, uint32_t blk1,
-                                 uint32_t win_lo, uint32_t cap, const void* PA, uint64_t L_pad, const void* PB, uint64_t R_pad, uint32_t n_chunks,
-                                 const uint32_t* n1B, const uint64_t* kmers, uint64_t kmer_stride, uint64_t row_base, ProxyRecord* rec,
-                                 hipStream_t st) {
+hipError_t launch_ld_proxy_write(const uint64_t* bits, uint64_t pitch_q, const uint32_t* boff, uint32_t blk0, uint32_t blk1, uint32_t win_lo,
+                                 uint32_t cap, const LdView& A, const LdView& B, const uint64_t* kmers, uint64_t kmer_stride, uint64_t row_base,
+                                 ProxyRecord* rec, hipStream_t st) {
     if (blk1 <= blk0 || !cap) return hipSuccess;
-    if ((uint64_t)blk1 * 256u > (R + 255u) / 256u * 256u) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(ld_proxy_write_kernel, dim3(blk1 - blk0), dim3(256), 0, st, bits, pitch_q, (uint32_t)R, boff, blk0, win_lo, cap,
-                       (const uint4*)PA, L_pad, (const uint4*)PB, R_pad, n_chunks, n1B, kmers, kmer_stride, row_base, rec);
+    if ((uint64_t)blk1 * 256u > (B.count + 255u) / 256u * 256u || A.n_chunks != B.n_chunks) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ld_proxy_write_kernel, dim3(blk1 - blk0), dim3(256), 0, st, bits, pitch_q, (uint32_t)B.count, boff, blk0, win_lo, cap,
+                       (const uint4*)A.P, A.pad, (const uint4*)B.P, B.pad, B.n_chunks, (const uint32_t*)B.n1, kmers, kmer_stride, row_base, rec);
     return hipGetLastError();
 }
 
-hipError_t launch_ld_prep(const uint64_t* rows, uint64_t stride_w, uint64_t W, uint64_t N, uint32_t n, uint32_t n_chunks, uint64_t N_pad,
-                          uint32_t tm, void* P, uint32_t* n1, uint32_t* pq, uint64_t* tq, hipStream_t st) {
-    const uint64_t total = (uint64_t)n_chunks * N_pad;
+hipError_t launch_ld_prep(const uint64_t* rows, uint64_t stride_w, uint64_t W, uint32_t n, uint32_t tm, const LdView& ops, hipStream_t st) {
+    const uint64_t total = (uint64_t)ops.n_chunks * ops.pad;
     if (!total) return hipSuccess;
-    hipLaunchKernelGGL(ld_prep_kernel, dim3((uint32_t)((total + 255u) / 256u)), dim3(256), 0, st, rows, stride_w, W, N, n, n_chunks, N_pad,
-                       tm, (uint4*)P, n1, pq, tq);
+    hipLaunchKernelGGL(ld_prep_kernel, dim3((uint32_t)((total + 255u) / 256u)), dim3(256), 0, st, rows, stride_w, W, ops.count, n, ops.n_chunks, ops.pad,
+                       tm, (uint4*)ops.P, ops.n1, ops.pq, ops.tq);
     return hipGetLastError();
 }
 
-hipError_t launch_ld_link(const void* P, const uint32_t* n1, const uint32_t* pq, const uint64_t* tq, uint64_t N, uint64_t N_pad, uint32_t n,
-                          uint32_t n_chunks, uint64_t row0, uint64_t n_rows, uint32_t* out, uint64_t pitch_dw, bool popcount, hipStream_t st) {
+hipError_t launch_ld_link(const LdView& ops, uint32_t n, uint64_t row0, uint64_t n_rows, uint32_t* out, uint64_t pitch_dw, bool popcount,
+                          hipStream_t st) {
+    const uint64_t N = ops.count, N_pad = ops.pad;
     if (!n_rows) return hipSuccess;
     // what the kernels assume and do not check: whole tiles of padded operands, and a pitch that holds every tile's 16-byte stores
-    if (N_pad % 128u || n_chunks % 4u || row0 % 64u || row0 + (n_rows + 63u) / 64u * 64u > N_pad || pitch_dw % 4u || pitch_dw * 32u < N_pad)
+    if (N_pad % 128u || ops.n_chunks % 4u || row0 % 64u || row0 + (n_rows + 63u) / 64u * 64u > N_pad || pitch_dw % 4u || pitch_dw * 32u < N_pad)
         return hipErrorInvalidValue;
     const dim3 grid((uint32_t)(N_pad / 128u), (uint32_t)((n_rows + 63u) / 64u));
     if (popcount)
-        hipLaunchKernelGGL(ld_link_popc_kernel, grid, dim3(64), 0, st, (const uint4*)P, n1, pq, tq, N, N_pad, n, n_chunks, row0, out, pitch_dw);
+        hipLaunchKernelGGL(ld_link_popc_kernel, grid, dim3(64), 0, st, (const uint4*)ops.P, (const uint32_t*)ops.n1, (const uint32_t*)ops.pq,
+                           (const uint64_t*)ops.tq, N, N_pad, n, ops.n_chunks, row0, out, pitch_dw);
     else
-        hipLaunchKernelGGL(ld_link_kernel, grid, dim3(64), 0, st, (const uint4*)P, n1, pq, tq, N, N_pad, n, n_chunks, row0, out, pitch_dw);
+        hipLaunchKernelGGL(ld_link_kernel, grid, dim3(64), 0, st, (const uint4*)ops.P, (const uint32_t*)ops.n1, (const uint32_t*)ops.pq,
+                           (const uint64_t*)ops.tq, N, N_pad, n, ops.n_chunks, row0, out, pitch_dw);
     return hipGetLastError();
 }
 

@@ -24,24 +24,12 @@
 #include "fdist_tail.h"
 #include "kernels.h"
 #include "lmm_internal.h"
+#include "table_session.h"
 
 using namespace kgwas;
 using namespace kgwas::lmm;
 
 namespace {
-
-std::vector<std::string> split_ws(const std::string& line) {
-    std::vector<std::string> f;
-    size_t i = 0;
-    while (i < line.size()) {
-        while (i < line.size() && (line[i] == ' ' || line[i] == '\t' || line[i] == '\r')) i++;
-        size_t j = i;
-        while (j < line.size() && line[j] != ' ' && line[j] != '\t' && line[j] != '\r') j++;
-        if (j > i) f.push_back(line.substr(i, j - i));
-        i = j;
-    }
-    return f;
-}
 
 std::vector<std::string> read_lines(const std::string& path, const char* what) {
     std::ifstream f(path);
@@ -86,7 +74,7 @@ void kgwas::lmm::read_covariates(const std::string& path, std::vector<double>& v
     values.clear();
     keep.assign(lines.size(), 1);
     for (size_t r = 0; r < lines.size(); r++) {
-        const std::vector<std::string> f = split_ws(lines[r]);
+        const std::vector<std::string> f = fields_of(lines[r]);
         if (r == 0) {
             if (f.size() > LMM_MAXC)
                 throw Error(KGWAS_ERR_FORMAT, "covariates file " + path + " has " + std::to_string(f.size()) + " columns; at most " +
@@ -155,7 +143,7 @@ void read_fam(const std::string& path, uint32_t pheno_col, std::vector<double>& 
     values.assign(lines.size(), std::nan(""));
     keep.assign(lines.size(), 0);
     for (size_t i = 0; i < lines.size(); i++) {
-        const std::vector<std::string> f = split_ws(lines[i]);
+        const std::vector<std::string> f = fields_of(lines[i]);
         if (f.size() < 5u + pheno_col)
             throw Error(KGWAS_ERR_FORMAT, path + ": line " + std::to_string(i + 1) + " has no phenotype column " + std::to_string(pheno_col));
         const std::string& t = f[4 + pheno_col];
@@ -287,7 +275,7 @@ std::vector<std::vector<std::string>> bim_fields(const std::string& base, const 
     std::vector<std::vector<std::string>> fields(cnt);
     for (uint64_t v = 0; v < cnt; v++) {
         if (!tested[v]) continue;
-        fields[v] = split_ws(bim[first + v]);
+        fields[v] = fields_of(bim[first + v]);
         if (fields[v].size() < 6)
             throw Error(KGWAS_ERR_FORMAT, base + ".bim: line " + std::to_string(first + v + 1) + " has fewer than 6 fields");
     }
@@ -318,12 +306,6 @@ uint64_t append_assoc(std::string& text, const std::vector<std::vector<std::stri
         n_tested++;
     }
     return n_tested;
-}
-
-void write_text(const std::string& path, const std::string& text, const char* mode) {
-    FILE* fo = fopen(path.c_str(), mode);
-    const bool ok = fo && fwrite(text.data(), 1, text.size(), fo) == text.size();
-    if ((fo && fclose(fo) != 0) || !ok) throw Error(KGWAS_ERR_IO, "can't write " + path);
 }
 
 // the log beside `out`: what snprintf left in log[cap], ll being its return value
@@ -484,36 +466,14 @@ void run_file_multi(const char* kinship_path, const char* bfile_base, uint32_t n
 
 // The inputs of lmm_lrt --kmers_table, each read once: the phenotype file (its accessions, in its order, are the individuals), the
 // open table with its column map, the kinship text.
-struct TableRun {
-    kgwas_pheno* ph = nullptr;
-    kgwas_table* t = nullptr;
-    std::string pheno_path;
-    uint64_t n_pheno = 0, S = 0, min_count = 0;
-    uint32_t klen = 0;
-    std::vector<const char*> acc;
+struct TableRun : TableSession {
+    uint64_t min_count = 0;
     const float* Y = nullptr;
-    std::vector<uint64_t> col;
     std::vector<double> K;
-    ~TableRun() {
-        if (t) kgwas_table_close(t);
-        if (ph) kgwas_pheno_free(ph);
-    }
-    static void ck(int rc) {
-        if (rc != KGWAS_OK) throw Error(rc, kgwas_last_error());
-    }
-    void load_pheno(const char* path) {
-        pheno_path = path;
-        ck(kgwas_pheno_load(path, &ph));
-        ck(kgwas_pheno_info(ph, &n_pheno, &S));
-    }
     void need_column(uint32_t pheno_col) const {
         if (pheno_col > n_pheno) throw Error(KGWAS_ERR_FORMAT, pheno_path + " has no phenotype column " + std::to_string(pheno_col));
     }
-    void load_values() {
-        acc.resize(S);
-        for (uint64_t i = 0; i < S; i++) ck(kgwas_pheno_accession(ph, i, &acc[i]));
-        ck(kgwas_pheno_values(ph, &Y));
-    }
+    void load_values() { ck(kgwas_pheno_values(ph, &Y)); }
     // y as it would arrive through kmers_table_to_bed's .fam: the loader's float in ostream's default format, parsed as read_fam does
     void column(uint32_t pheno_col, double* y) const {
         for (uint64_t i = 0; i < S; i++) {
@@ -529,12 +489,8 @@ struct TableRun {
         }
     }
     void open_table(const char* table_base, uint32_t kmer_len, const char* kinship_path, double maf, uint64_t mac) {
-        ck(kgwas_table_open(table_base, kmer_len, &t));
-        col.resize(S);
-        ck(kgwas_table_column_map(t, acc.data(), S, col.data()));
-        uint64_t S_f = 0, n_rows = 0, W_f = 0;
-        ck(kgwas_table_info(t, &S_f, &n_rows, &W_f, &klen));
-        check_squeeze_fits("lmm_lrt --kmers_table", S_f, S);
+        TableSession::open_table(table_base, kmer_len);
+        check_squeeze_fits("lmm_lrt --kmers_table");
         K = read_kinship(kinship_path, S, "the phenotype file");
         min_count = kgwas_min_count(S, maf, mac);
     }
@@ -547,11 +503,8 @@ void write_table_result(const std::string& out, const std::vector<TableHit>& kep
                         const kgwas_lmm_unique_stats* u = nullptr, const kgwas_lmm_skip_stats* skip = nullptr) {
     std::string text = assoc_header();
     for (const TableHit& k : kept) {
-        char km[33];
-        for (uint32_t i = 0; i < r.klen; i++) km[i] = "ACGT"[(k.kmer >> (2 * (r.klen - 1 - i))) & 3];  // bits2kmer31, as kmers_table_to_bed's .bim
-        km[r.klen] = 0;
-        char line[1024];
-        const uint64_t len = format_assoc("0", km, "0", 0, "0", "1", k.af, k.lam, k.p, line, sizeof(line));
+        char line[1024];  // (the k-mer's letters as in kmers_table_to_bed's .bim)
+        const uint64_t len = format_assoc("0", kmer_letters(k.kmer, r.klen).c_str(), "0", 0, "0", "1", k.af, k.lam, k.p, line, sizeof(line));
         text.append(line, len);
     }
     write_text(out, text, "wb");

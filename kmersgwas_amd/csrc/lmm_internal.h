@@ -1,7 +1,6 @@
 // lmm_internal.h — what lmm.cpp (the device session, the .bed passes and the back-end steps), lmm_table.cpp (the k-mers table
 // route) and lmm_files.cpp (the file layer) share: the handle and what they call in each other. Nothing else includes it.
 #pragma once
-#include <chrono>
 #include <memory>
 #include <string>
 #include <vector>
@@ -105,8 +104,6 @@ struct Destroy {
     void operator()(kgwas_lmm* h) const { kgwas_lmm_destroy(h); }
 };
 using Handle = std::unique_ptr<kgwas_lmm, Destroy>;
-
-inline double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // ---- lmm.cpp: the session and the .bed passes (what each does stands at its definition) ----
 kgwas_lmm* create(uint64_t n, const double* K, int device, double lmin, double lmax, uint64_t chunk_variants);

@@ -53,14 +53,6 @@ void sort_by_row(std::vector<TableHit>& heap) {
     std::sort(heap.begin(), heap.end(), [](const TableHit& a, const TableHit& b) { return a.row < b.row; });
 }
 
-// rows per piece of table_pass for a table of n_rows rows of 1 + W_f words: about 64 MiB of rows, at most 2^18
-uint64_t piece_rows(uint64_t n_rows, uint64_t W_f) {
-    uint64_t piece = std::max<uint64_t>(1024, std::min<uint64_t>(1u << 18, (64ull << 20) / (8 * (1 + W_f))));
-    const long long forced = opt_int("KGWAS_LMM_PIECE_ROWS", 0);
-    if (forced > 0) piece = (uint64_t)std::min<long long>(forced, 1 << 20);
-    return std::min(piece, std::max<uint64_t>(n_rows, 1));
-}
-
 // What test_table, test_table_unique, test_table_multi and test_table_multi_skip share: the checks, the pieces and the front end.
 // Per piece the rows are squeezed, flagged and compacted (lmm_table_kernels.hip). prepare(piece) runs after the checks and before
 // any device work (the null models; `piece` is the most rows a piece has, and so the most tested rows per_piece gets);
@@ -78,23 +70,20 @@ void table_pass(kgwas_lmm* h, kgwas_table* t, const uint64_t* col, uint64_t n_ac
     for (uint64_t i = 0; i < S; i++)
         if (col[i] >= S_f) throw Error(KGWAS_ERR_ARG, who + ": column index out of range");
     check_squeeze_fits(who.c_str(), S_f, S);  // (before any allocation)
-    const uint64_t piece = piece_rows(n_rows, W_f);
+    const uint64_t piece = piece_rows(n_rows, 1 + W_f, 64ull << 20, 1u << 18, 1u << 20, "KGWAS_LMM_PIECE_ROWS");  // about 64 MiB, at most 2^18
     prepare(piece);
     KGWAS_HIP(hipSetDevice(h->device));
-    const uint32_t W_m = (uint32_t)(2 * ((S + 127) / 128));
     const uint64_t stride = 1 + W_f;
     const uint64_t n_blocks = (piece + LMM_TABLE_BLOCK - 1) / LMM_TABLE_BLOCK;
 
-    std::vector<uint32_t> colmap(64ull * W_m, 0xFFFFFFFFu);
-    for (uint64_t i = 0; i < S; i++) colmap[i] = (uint32_t)col[i];
-    DevBuf<uint32_t> d_colmap, d_sq, d_n1flag, d_bcnt, d_boff, d_total;
+    Squeezer sq;
+    DevBuf<uint32_t> d_sq, d_n1flag, d_bcnt, d_boff, d_total;
     DevBuf<uint64_t> d_rows, d_row, d_kmer;
     DevBuf<uint8_t> d_codes;
     DevBuf<LmmVariant> d_vars;
-    d_colmap.alloc(colmap.size());
-    KGWAS_HIP(hipMemcpy(d_colmap.p, colmap.data(), colmap.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    sq.create(col, S, W_f);
     d_rows.alloc(piece * stride);
-    d_sq.alloc(piece * 2 * W_m);
+    d_sq.alloc(piece * sq.words_per_row());
     d_n1flag.alloc(piece);
     d_bcnt.alloc(n_blocks);
     d_boff.alloc(n_blocks);
@@ -113,8 +102,8 @@ void table_pass(kgwas_lmm* h, kgwas_table* t, const uint64_t* col, uint64_t n_ac
         uint32_t total = 0;
         KGWAS_HIP(hipMemcpyAsync(d_rows.p, h_rows, c * stride * 8, hipMemcpyHostToDevice, st));
         h->timer.begin(st);
-        KGWAS_HIP(launch_squeeze(d_rows.p, stride, c, d_colmap.p, W_m, (uint32_t)W_f, d_sq.p, st));
-        KGWAS_HIP(launch_lmm_table_front(d_rows.p, stride, d_sq.p, (uint32_t)c, W_m, h->dm, pos, (uint32_t)std::min<uint64_t>(min_count, 0xFFFFFFFFu),
+        sq.run(d_rows.p, stride, c, d_sq.p, st);
+        KGWAS_HIP(launch_lmm_table_front(d_rows.p, stride, d_sq.p, (uint32_t)c, sq.W_m, h->dm, pos, (uint32_t)std::min<uint64_t>(min_count, 0xFFFFFFFFu),
                                          maf, d_n1flag.p, d_bcnt.p, d_boff.p, d_total.p, d_codes.p, d_vars.p, d_row.p, d_kmer.p, st));
         h->timer.end(&kgwas_lmm_stats::rotate_ms, st);
         KGWAS_HIP(hipMemcpyAsync(&total, d_total.p, sizeof(total), hipMemcpyDeviceToHost, st));

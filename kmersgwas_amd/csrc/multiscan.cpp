@@ -95,10 +95,6 @@ void for_each_shard(size_t G, F&& fn) {
         if (rc[g] != KGWAS_OK) throw Error(rc[g], "shard " + std::to_string(g) + ": " + msg[g]);
 }
 
-void ck(int rc) {
-    if (rc != KGWAS_OK) throw Error(rc, kgwas_last_error());
-}
-
 // A later shard's session starts empty at every run call; its counters of the run before are kept in the totals.
 void reset_shard(kgwas_multiscan* m, size_t g) {
     kgwas_scan_stats st;

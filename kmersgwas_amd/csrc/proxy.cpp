@@ -5,9 +5,8 @@
 //          come in pieces through two device buffers that take turns: piece k + 1 is copied on a stream of its own while piece k is
 //          squeezed, prepared, linked (ld_rect_kernel: one bit per pair) and compacted into records, which come back in rounds of at
 //          most the record buffer's size. What leaves the device is the records alone, in (row, lead) order, the same in every run.
-// run      leads file -> their rows from the table (kgwas_filter_kmers' search) -> search over the whole table (PieceReader) ->
-//          the records bucketed per lead (proxy_host.h) -> the output and its log.
-#include <chrono>
+// run      leads file -> the table and their rows from it (table_session.h: kgwas_filter_kmers' search) -> search over the whole
+//          table (PieceReader) -> the records bucketed per lead (proxy_host.h) -> the output and its log.
 #include <cstring>
 #include <functional>
 
@@ -15,6 +14,7 @@
 #include "kernels.h"
 #include "piece_reader.h"
 #include "proxy_host.h"
+#include "table_session.h"
 
 using namespace kgwas;
 using namespace kgwas::proxy;
@@ -23,17 +23,7 @@ namespace {
 
 static_assert(sizeof(ProxyRecord) == sizeof(kgwas_proxy_record) && sizeof(ProxyRecord) == 32, "the device's record is the header's");
 
-constexpr uint64_t PROXY_MAX_PIECE = 1ull << 18, PROXY_RECORDS = 1ull << 20;
-
-double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-// rows per piece for rows of `stride` words: about 64 MiB of rows, at most 2^18 (KGWAS_PROXY_PIECE_ROWS: the tests' hook)
-uint64_t piece_rows(uint64_t n_rows, uint64_t stride) {
-    uint64_t piece = std::max<uint64_t>(1024, std::min<uint64_t>(PROXY_MAX_PIECE, (64ull << 20) / (8 * stride)));
-    const long long forced = opt_int("KGWAS_PROXY_PIECE_ROWS", 0);
-    if (forced > 0) piece = (uint64_t)std::min<long long>(forced, (long long)PROXY_MAX_PIECE);
-    return std::min(piece, std::max<uint64_t>(n_rows, 1));
-}
+constexpr uint64_t PROXY_MAX_PIECE = 1ull << 18, PROXY_RECORDS = 1ull << 20;  // a piece: about 64 MiB of rows, at most 2^18
 // records of the device buffer (KGWAS_PROXY_RECORDS: the tests' hook)
 uint32_t record_cap() {
     const long long forced = opt_int("KGWAS_PROXY_RECORDS", 0);
@@ -63,12 +53,12 @@ void search(const RowLayout& lay, const uint64_t* lead_rows, uint64_t L, uint64_
     const bool popcount = opt_set("KGWAS_LD_POPCOUNT");  // the ablation: n11 on the vector ALU (the same records)
     const uint32_t cap = (uint32_t)std::min<uint64_t>(record_cap(), piece * L);  // (a piece has at most piece * L <= 2^30 records)
     const uint64_t L_pad = (L + 63) / 64 * 64, pitch_q = L_pad / 64, P_pad = (piece + 127) / 128 * 128, max_blocks = (piece + 255) / 256;
-    const uint32_t n_chunks = (uint32_t)((n + 511) / 512 * 4), W_m = (uint32_t)(2 * ((n + 127) / 128));
     const uint64_t n_pieces = (n_rows + piece - 1) / piece;
 
-    DevBuf<uint64_t> d_leads, d_rows[2], d_tqA, d_tqB, d_bits;
-    DevBuf<uint32_t> d_colmap, d_sqA, d_sqB, d_n1A, d_pqA, d_n1B, d_pqB, d_bcnt, d_boff;
-    DevBuf<uint4> d_PA, d_PB;
+    DevBuf<uint64_t> d_leads, d_rows[2], d_bits;
+    DevBuf<uint32_t> d_sqA, d_sqB, d_bcnt, d_boff;
+    Squeezer sq;
+    LdOperands opsA, opsB;  // the leads', prepared once, and the piece's
     DevBuf<ProxyRecord> d_rec;
     PinBuf<kgwas_proxy_record> h_rec;
     PinBuf<uint32_t> h_boff;
@@ -79,33 +69,29 @@ void search(const RowLayout& lay, const uint64_t* lead_rows, uint64_t L, uint64_
         ev_c0[i].create();
         ev_c1[i].create();
     }
-    d_PA.alloc((size_t)n_chunks * L_pad), d_n1A.alloc(L_pad), d_pqA.alloc(L_pad), d_tqA.alloc(L_pad);
-    d_PB.alloc((size_t)n_chunks * P_pad), d_n1B.alloc(P_pad), d_pqB.alloc(P_pad), d_tqB.alloc(P_pad);
+    opsA.alloc(L_pad, n), opsB.alloc(P_pad, n);
     d_bits.alloc(P_pad * pitch_q);
     d_bcnt.alloc(max_blocks), d_boff.alloc(max_blocks + 1), h_boff.alloc(max_blocks + 1);
     d_rec.alloc(cap), h_rec.alloc(cap);
     ev_k0.create(), ev_k1.create();
     if (lay.col) {
-        std::vector<uint32_t> colmap(64ull * W_m, 0xFFFFFFFFu);
-        for (uint64_t i = 0; i < n; i++) colmap[i] = (uint32_t)lay.col[i];
-        d_colmap.alloc(colmap.size());
-        KGWAS_HIP(hipMemcpy(d_colmap.p, colmap.data(), colmap.size() * 4, hipMemcpyHostToDevice));
-        d_sqA.alloc(L * 2 * W_m), d_sqB.alloc(piece * 2 * W_m);
+        sq.create(lay.col, n, lay.W);
+        d_sqA.alloc(L * sq.words_per_row()), d_sqB.alloc(piece * sq.words_per_row());
     }
     Stream s_run, s_copy;  // (declared after the buffers their work uses: they go first, idle)
     s_run.create(hipStreamNonBlocking);
     s_copy.create(hipStreamNonBlocking);
 
-    // the operands of `count` rows at d (the layout's) -> P, n1, pq, tq with `pad` rows, on s_run
-    auto prepare = [&](const uint64_t* d, uint64_t count, uint64_t pad, uint32_t* sq, uint4* P, uint32_t* n1, uint32_t* pq, uint64_t* tq) {
+    // the operands of ops.count rows at d (the layout's), squeezed into d_sq first under a colmap, on s_run
+    auto prepare = [&](const uint64_t* d, uint32_t* d_sq, const LdView& ops) {
         const uint64_t* bits = d + lay.bit_off;
         uint64_t stride = lay.stride, W = lay.W;
         if (lay.col) {
-            KGWAS_HIP(launch_squeeze(d, lay.stride, count, d_colmap.p, W_m, (uint32_t)lay.W, sq, s_run));
-            bits = reinterpret_cast<const uint64_t*>(sq);
-            stride = W = W_m;
+            sq.run(d, lay.stride, ops.count, d_sq, s_run);
+            bits = reinterpret_cast<const uint64_t*>(d_sq);
+            stride = W = sq.W_m;
         }
-        KGWAS_HIP(launch_ld_prep(bits, stride, W, count, (uint32_t)n, n_chunks, pad, tm, P, n1, pq, tq, s_run));
+        KGWAS_HIP(launch_ld_prep(bits, stride, W, (uint32_t)n, tm, ops, s_run));
     };
     auto elapsed = [](hipEvent_t a, hipEvent_t b) {
         float ms = 0;
@@ -116,9 +102,10 @@ void search(const RowLayout& lay, const uint64_t* lead_rows, uint64_t L, uint64_
     // the leads, once
     KGWAS_HIP(hipMemcpyAsync(d_leads.p, lead_rows, L * lay.stride * 8, hipMemcpyHostToDevice, s_run));
     KGWAS_HIP(hipEventRecord(ev_k0, s_run));
-    prepare(d_leads.p, L, L_pad, d_sqA.p, d_PA.p, d_n1A.p, d_pqA.p, d_tqA.p);
+    const LdView A = opsA.view(L, L_pad);
+    prepare(d_leads.p, d_sqA.p, A);
     KGWAS_HIP(hipEventRecord(ev_k1, s_run));
-    if (n1_leads) KGWAS_HIP(hipMemcpyAsync(n1_leads, d_n1A.p, L * 4, hipMemcpyDeviceToHost, s_run));
+    if (n1_leads) KGWAS_HIP(hipMemcpyAsync(n1_leads, A.n1, L * 4, hipMemcpyDeviceToHost, s_run));
     KGWAS_HIP(hipStreamSynchronize(s_run));
     times.kernel_ms += elapsed(ev_k0, ev_k1);
 
@@ -133,13 +120,13 @@ void search(const RowLayout& lay, const uint64_t* lead_rows, uint64_t L, uint64_
     if (n_pieces) upload(0);
     for (uint64_t k = 0; k < n_pieces; k++) {
         const int b = (int)(k & 1);
-        const uint64_t R = rows_of(k), R_pad = (R + 127) / 128 * 128;
+        const uint64_t R = rows_of(k);
         const uint32_t n_blocks = (uint32_t)((R + 255) / 256);
+        const LdView B = opsB.view(R, (R + 127) / 128 * 128);
         KGWAS_HIP(hipStreamWaitEvent(s_run, ev_c1[b], 0));
         KGWAS_HIP(hipEventRecord(ev_k0, s_run));
-        prepare(d_rows[b].p, R, R_pad, d_sqB.p, d_PB.p, d_n1B.p, d_pqB.p, d_tqB.p);
-        KGWAS_HIP(launch_ld_rect(d_PA.p, d_n1A.p, d_pqA.p, L, L_pad, d_PB.p, d_n1B.p, d_tqB.p, R, R_pad, (uint32_t)n, n_chunks, d_bits.p, pitch_q, popcount,
-                                 s_run));
+        prepare(d_rows[b].p, d_sqB.p, B);
+        KGWAS_HIP(launch_ld_rect(A, B, (uint32_t)n, d_bits.p, pitch_q, popcount, s_run));
         KGWAS_HIP(launch_ld_proxy_count(d_bits.p, pitch_q, R, d_bcnt.p, d_boff.p, s_run));
         KGWAS_HIP(hipEventRecord(ev_k1, s_run));
         KGWAS_HIP(hipMemcpyAsync(h_boff.p, d_boff.p, (n_blocks + 1) * 4, hipMemcpyDeviceToHost, s_run));
@@ -151,8 +138,8 @@ void search(const RowLayout& lay, const uint64_t* lead_rows, uint64_t L, uint64_
         times.copy_ms += elapsed(ev_c0[b], ev_c1[b]);
         for (const Round& r : drain_rounds(h_boff.p, n_blocks, cap)) {
             KGWAS_HIP(hipEventRecord(ev_k0, s_run));
-            KGWAS_HIP(launch_ld_proxy_write(d_bits.p, pitch_q, R, d_boff.p, r.blk0, r.blk1, r.lo, cap, d_PA.p, L_pad, d_PB.p, R_pad, n_chunks, d_n1B.p,
-                                            lay.kmers ? d_rows[b].p : nullptr, lay.stride, k * piece, d_rec.p, s_run));
+            KGWAS_HIP(launch_ld_proxy_write(d_bits.p, pitch_q, d_boff.p, r.blk0, r.blk1, r.lo, cap, A, B, lay.kmers ? d_rows[b].p : nullptr, lay.stride,
+                                            k * piece, d_rec.p, s_run));
             KGWAS_HIP(hipEventRecord(ev_k1, s_run));
             KGWAS_HIP(hipMemcpyAsync(h_rec.p, d_rec.p, (size_t)(r.hi - r.lo) * sizeof(ProxyRecord), hipMemcpyDeviceToHost, s_run));
             KGWAS_HIP(hipStreamSynchronize(s_run));
@@ -174,7 +161,7 @@ void kmers_ld_proxies(const uint64_t* lead_bits, uint64_t L, const uint64_t* bit
     use_device(device);
     RowLayout lay;
     lay.stride = lay.W = W;
-    const uint64_t piece = piece_rows(n_rows, W);
+    const uint64_t piece = piece_rows(n_rows, W, 64ull << 20, PROXY_MAX_PIECE, PROXY_MAX_PIECE, "KGWAS_PROXY_PIECE_ROWS");
     uint64_t total = 0;
     SearchTimes times;
     search(lay, lead_bits, L, n_acc, tm, n_rows, piece, nullptr, [&](uint64_t k) { return bits + k * piece * W; }, [](uint64_t) {},
@@ -189,18 +176,6 @@ void kmers_ld_proxies(const uint64_t* lead_bits, uint64_t L, const uint64_t* bit
                 (unsigned long long)n_rows, (unsigned long long)n_acc, times.kernel_ms, times.copy_ms, (unsigned long long)times.rounds);
 }
 
-struct TableOwner {
-    kgwas_table* t = nullptr;
-    kgwas_pheno* ph = nullptr;
-    ~TableOwner() {
-        if (t) kgwas_table_close(t);
-        if (ph) kgwas_pheno_free(ph);
-    }
-};
-void ck(int rc) {
-    if (rc != KGWAS_OK) throw Error(rc, kgwas_last_error());
-}
-
 void run(const char* table_base, uint32_t kmer_len, const char* pheno_path, const char* leads_path, uint32_t tm, uint64_t max_per_lead, int32_t device,
          const char* out_path, kgwas_proxy_stats* st) {
     const char* who = "kgwas_proxy_kmers_run";
@@ -212,33 +187,12 @@ void run(const char* table_base, uint32_t kmer_len, const char* pheno_path, cons
     const std::vector<Lead> leads = read_leads(leads_path, kmer_len, kgwas_kmer_encode);
     const uint64_t L = leads.size();
     check_proxy_shape("proxy_kmers", L, 1, tm);  // (the leads' number before the table is looked for; the accessions below)
-    TableOwner own;
-    uint64_t n_pheno = 0, S = 0;
-    std::vector<const char*> acc;
-    if (pheno_path) {
-        ck(kgwas_pheno_load(pheno_path, &own.ph));
-        ck(kgwas_pheno_info(own.ph, &n_pheno, &S));
-        acc.resize(S);
-        for (uint64_t i = 0; i < S; i++) ck(kgwas_pheno_accession(own.ph, i, &acc[i]));
-    }
-    ck(kgwas_table_open(table_base, kmer_len, &own.t));
-    uint64_t S_f = 0, n_rows = 0, W_f = 0;
-    uint32_t klen = 0;
-    ck(kgwas_table_info(own.t, &S_f, &n_rows, &W_f, &klen));
-    std::vector<uint64_t> col;
-    if (pheno_path) {
-        col.resize(S);
-        std::vector<uint64_t> mask(W_f, 0);
-        ck(kgwas_table_column_map(own.t, acc.data(), S, col.data()));
-        for (uint64_t i = 0; i < S; i++) {
-            if (mask[col[i] / 64] >> (col[i] % 64) & 1) throw Error(KGWAS_ERR_FORMAT, std::string(pheno_path) + " lists the accession " + acc[i] + " twice");
-            mask[col[i] / 64] |= 1ull << (col[i] % 64);
-        }
-        check_squeeze_fits("proxy_kmers", S_f, S);
-    } else {
-        S = S_f;
-    }
-    const uint64_t n = S, stride = 1 + W_f;
+    TableSession ts;
+    if (pheno_path) ts.load_pheno(pheno_path);
+    ts.open_table(table_base, kmer_len);
+    ts.refuse_duplicate_accessions();
+    ts.check_squeeze_fits("proxy_kmers");
+    const uint64_t n = ts.S, n_rows = ts.n_rows, stride = ts.stride();
     check_proxy_shape("proxy_kmers", L, n, tm);
 
     kgwas_proxy_stats s{};
@@ -246,35 +200,25 @@ void run(const char* table_base, uint32_t kmer_len, const char* pheno_path, cons
     s.leads = L;
     // the leads' rows, by the table's own search
     double t = now_ms();
-    std::vector<uint64_t> codes(L), found(L * stride), lead_rows(L * stride);
+    std::vector<uint64_t> codes(L);
     for (uint64_t i = 0; i < L; i++) codes[i] = leads[i].code;
-    uint64_t n_found = 0;
-    ck(kgwas_filter_kmers(own.t, codes.data(), L, device, nullptr, found.data(), &n_found));
-    std::unordered_map<uint64_t, uint64_t> at;  // code -> place among the leads
-    for (uint64_t i = 0; i < L; i++) at.emplace(codes[i], i);
-    std::vector<uint8_t> have(L, 0);
-    for (uint64_t i = 0; i < n_found; i++) {
-        const auto it = at.find(found[i * stride]);
-        if (it == at.end() || have[it->second]) continue;  // (a key the table holds twice: its first row)
-        have[it->second] = 1;
-        memcpy(&lead_rows[it->second * stride], &found[i * stride], stride * 8);
-    }
-    for (uint64_t i = 0; i < L; i++)
-        if (!have[i]) throw Error(KGWAS_ERR_FORMAT, "the k-mer " + leads[i].text + " of " + leads_path + " is not in the table " + table_base);
+    const PlacedRows placed = ts.rows_of_codes(codes, device);
+    if (placed.missing != PlacedRows::NONE)
+        throw Error(KGWAS_ERR_FORMAT, "the k-mer " + leads[placed.missing].text + " of " + leads_path + " is not in the table " + table_base);
     s.search_ms = now_ms() - t;
 
     // one pass over the table
     use_device(device);
     RowLayout lay;
-    lay.stride = stride, lay.bit_off = 1, lay.W = W_f, lay.kmers = true;
-    lay.col = pheno_path ? col.data() : nullptr;
-    const uint64_t piece = piece_rows(n_rows, stride);
+    lay.stride = stride, lay.bit_off = 1, lay.W = ts.W_f, lay.kmers = true;
+    lay.col = pheno_path ? ts.col.data() : nullptr;
+    const uint64_t piece = piece_rows(n_rows, stride, 64ull << 20, PROXY_MAX_PIECE, PROXY_MAX_PIECE, "KGWAS_PROXY_PIECE_ROWS");
     std::vector<uint32_t> n1_leads(L, 0);
     Buckets buckets(L, max_per_lead);
     SearchTimes times;
     if (n_rows) {
-        PieceReader reader(own.t, n_rows, piece, stride);
-        search(lay, lead_rows.data(), L, n, tm, n_rows, piece, n1_leads.data(), [&](uint64_t k) { return reader.wait(k); },
+        PieceReader reader(ts.t, n_rows, piece, stride);
+        search(lay, placed.rows.data(), L, n, tm, n_rows, piece, n1_leads.data(), [&](uint64_t k) { return reader.wait(k); },
                [&](uint64_t k) { reader.release(k); }, [&](const kgwas_proxy_record* rec, uint64_t count) { buckets.add(rec, count); }, times);
     }
     s.rows_read = n_rows;
@@ -290,19 +234,13 @@ void run(const char* table_base, uint32_t kmer_len, const char* pheno_path, cons
         s.proxies_kept += buckets.kept[i].size();
         per_lead += "lead\t" + leads[i].text + "\t" + std::to_string(buckets.kept[i].size()) + "\t" + std::to_string(buckets.found[i]) + "\n";
     }
-    auto write_text = [](const std::string& path, const std::string& body) {
-        FILE* fo = fopen(path.c_str(), "wb");
-        const bool ok = fo && fwrite(body.data(), 1, body.size(), fo) == body.size();
-        if ((fo && fclose(fo) != 0) || !ok) throw Error(KGWAS_ERR_IO, "can't write " + path);
-    };
     write_text(out_path, text);
     s.total_ms = now_ms() - t_start;
-    char r2_text[16], log[4096];
-    snprintf(r2_text, sizeof(r2_text), "%u.%06u", tm / 1000000u, tm % 1000000u);
+    char log[4096];
     int ll = snprintf(log, sizeof(log),
                       "proxy_kmers: the k-mers of the table in LD with a lead (a proxy iff r2 >= the threshold)\nkmers_table\t%s\nkmers_len\t%u\n"
                       "phenotypes\t%s\nleads_file\t%s\nr2\t%s\nmax_per_lead\t%llu\naccessions\t%llu\nleads\t%llu\n",
-                      table_base, kmer_len, pheno_path ? pheno_path : "(none: every accession of the table)", leads_path, r2_text,
+                      table_base, kmer_len, pheno_path ? pheno_path : "(none: every accession of the table)", leads_path, r2_text(tm).c_str(),
                       (unsigned long long)max_per_lead, (unsigned long long)s.accessions, (unsigned long long)s.leads);
     if (ll < 0) throw Error(KGWAS_ERR_IO, std::string("can't write ") + out_path + ".log.txt");
     std::string log_text(log, std::min((size_t)ll, sizeof(log) - 1));

@@ -1,23 +1,19 @@
 // proxy_host.h — the host side of proxy_kmers that needs no device (proxy.cpp; tools/proxy_host_check.cpp runs it under the
 // sanitizers): the limits, the leads file in its two formats, the drain rounds of a piece's records, the per-lead buckets and the
-// output's bytes.
+// output's bytes, over ld_host.h's text helpers; of clump_host.h it needs a clump_kmers output's header line (a leads format).
 #pragma once
 #include "clump_host.h"
 
 namespace kgwas {
 namespace proxy {
 
-constexpr uint64_t MAX_ACC = 8192, MAX_LEADS = 4096;
+constexpr uint64_t MAX_LEADS = 4096;
 
-// checked before any device call, as clump.cpp's check_ld_shape does
+// checked before any device call
 inline void check_proxy_shape(const char* who, uint64_t n_leads, uint64_t n_acc, uint32_t tm) {
-    const std::string w(who);
-    if (n_acc == 0 || n_acc > MAX_ACC)
-        throw Error(KGWAS_ERR_ARG, w + ": " + std::to_string(n_acc) + " accessions: the exact r2 test is built for 1 to " + std::to_string(MAX_ACC) +
-                                       " (its integers are sized for them)");
-    if (tm == 0 || tm > 1000000) throw Error(KGWAS_ERR_ARG, w + ": r2_millionths must be within 1..1000000");
+    check_ld_shape(who, n_acc, tm);
     if (n_leads == 0 || n_leads > MAX_LEADS)
-        throw Error(KGWAS_ERR_ARG, w + ": " + std::to_string(n_leads) + " leads: 1 to " + std::to_string(MAX_LEADS) + " are searched at once");
+        throw Error(KGWAS_ERR_ARG, std::string(who) + ": " + std::to_string(n_leads) + " leads: 1 to " + std::to_string(MAX_LEADS) + " are searched at once");
 }
 
 struct Lead {
@@ -29,19 +25,19 @@ struct Lead {
 // output, known by its header: then the distinct values of its column `lead`, in clump order (by its column `clump`; the file's
 // lines are in the assoc file's order). A k-mer of another length, with a letter other than A, C, G, T, or given twice is refused
 // with its line.
-inline std::vector<Lead> read_leads(const std::string& path, uint32_t kmer_len, clump::EncodeFn encode) {
+inline std::vector<Lead> read_leads(const std::string& path, uint32_t kmer_len, EncodeFn encode) {
     std::ifstream f(path);
     if (!f.is_open()) throw Error(KGWAS_ERR_IO, "can't open leads file: " + path);
     std::string head_text = clump::header_line();
     head_text.pop_back();  // (its newline)
-    const std::vector<std::string> clump_head = clump::fields_of(head_text);
+    const std::vector<std::string> clump_head = fields_of(head_text);
     std::vector<Lead> leads;
     std::vector<uint64_t> clump_no;               // per lead of a clump_kmers output
     std::unordered_map<uint64_t, uint64_t> seen;  // code -> file line
     std::string line;
     bool clumps = false, first = true;
     for (uint64_t ln = 1; std::getline(f, line); ln++) {
-        const std::vector<std::string> fl = clump::fields_of(line);
+        const std::vector<std::string> fl = fields_of(line);
         if (fl.empty()) continue;
         const std::string at = path + " line " + std::to_string(ln) + ": ";
         if (first) {
@@ -56,10 +52,7 @@ inline std::vector<Lead> read_leads(const std::string& path, uint32_t kmer_len, 
         if (!clumps && fl.size() != 1) throw Error(KGWAS_ERR_FORMAT, at + std::to_string(fl.size()) + " fields: a list of leads has one k-mer per line");
         Lead l;
         l.text = clumps ? fl[3] : fl[0];
-        if (l.text.size() != kmer_len)
-            throw Error(KGWAS_ERR_FORMAT, at + "k-mer '" + l.text + "' has length " + std::to_string(l.text.size()) + ", not " + std::to_string(kmer_len));
-        if (encode(l.text.c_str(), l.text.size(), &l.code) != KGWAS_OK)
-            throw Error(KGWAS_ERR_FORMAT, at + "k-mer '" + l.text + "' has a letter other than A, C, G, T");
+        l.code = parse_kmer_field(l.text, kmer_len, encode, at);
         const auto ins = seen.emplace(l.code, ln);
         if (!ins.second) {
             if (clumps) continue;  // (a clump's members all name its lead)
@@ -129,19 +122,13 @@ struct Buckets {
     }
 };
 
-inline std::string kmer_letters(uint64_t word, uint32_t kmer_len) {  // bits2kmer31: the most significant base first
-    std::string s(kmer_len, 'A');
-    for (uint32_t i = 0; i < kmer_len; i++) s[i] = "ACGT"[(word >> (2 * (kmer_len - 1 - i))) & 3];
-    return s;
-}
-
 inline const char* header_line() { return "lead\tkmer\tr2\tphase\tn1\tn11\trow\n"; }
 
 // One output line: the lead as its file spells it, the proxy's k-mer, r2 (%.6f of num / den), the sign of n n11 - ca cb, the proxy's
 // n1, n11 with the lead, the proxy's table row.
 inline void append_line(std::string& text, const std::string& lead, uint32_t kmer_len, uint64_t n, uint64_t n1_lead, const kgwas_proxy_record& r) {
     char buf[64];
-    snprintf(buf, sizeof(buf), "%.6f", clump::r2_of(n, r.n1, n1_lead, r.n11));
+    snprintf(buf, sizeof(buf), "%.6f", r2_of(n, r.n1, n1_lead, r.n11));
     const bool minus = n * r.n11 < n1_lead * (uint64_t)r.n1;
     text += lead + "\t" + kmer_letters(r.kmer, kmer_len) + "\t" + buf + "\t" + (minus ? "-" : "+") + "\t" + std::to_string(r.n1) + "\t" +
             std::to_string(r.n11) + "\t" + std::to_string(r.row) + "\n";

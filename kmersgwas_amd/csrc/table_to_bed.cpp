@@ -47,16 +47,13 @@ extern "C" int kgwas_table_to_bed(kgwas_table* t, const uint64_t* col, uint64_t 
         for (uint64_t i = 0; i < S; i++)
             if (col[i] >= S_f) throw Error(KGWAS_ERR_ARG, "kgwas_table_to_bed: column index out of range");
         check_squeeze_fits("kgwas_table_to_bed", S_f, S);  // (before any allocation or output file)
-        const uint32_t W_m = (uint32_t)(2 * ((S + 127) / 128));  // m_hash_words rounded to the 128-bit unit (:51)
-        const uint32_t bpr = (uint32_t)((S + 3) / 4);            // write_PA: one byte per 4 accessions
+        const uint32_t bpr = (uint32_t)((S + 3) / 4);  // write_PA: one byte per 4 accessions
         const uint64_t stride = 1 + W_f;
-        uint64_t piece = std::max<uint64_t>(1024, std::min<uint64_t>(1u << 20, (256ull << 20) / (8 * stride)));
-        const long long forced = opt_int("KGWAS_BED_PIECE_ROWS", 0);
-        if (forced > 0) piece = (uint64_t)std::min<long long>(forced, 1 << 20);
+        // about 256 MiB of rows, at most 2^20 and (since the rule is common.h's) never more than the table has: smaller buffers for a small table
+        const uint64_t piece = piece_rows(n_rows, stride, 256ull << 20, 1u << 20, 1u << 20, "KGWAS_BED_PIECE_ROWS");
 
-        std::vector<uint32_t> colmap(64ull * W_m, 0xFFFFFFFFu);
-        for (uint64_t i = 0; i < S; i++) colmap[i] = (uint32_t)col[i];
-        DevBuf<uint32_t> d_colmap, d_sq, d_n1;
+        Squeezer sq;  // (its W_m: m_hash_words rounded to the 128-bit unit, src/kmers_table_to_bed.cpp:51)
+        DevBuf<uint32_t> d_sq, d_n1;
         DevBuf<uint64_t> d_rows, d_hash;
         DevBuf<uint8_t> d_bed;
         // Two sets of host buffers: piece k + 1 is read, copied and processed on the GPU (this thread) while piece k's kept rows
@@ -66,10 +63,9 @@ extern "C" int kgwas_table_to_bed(kgwas_table* t, const uint64_t* col, uint64_t 
             PinBuf<uint32_t> n1;
             PinBuf<uint8_t> bed;
         } hs[2];
-        d_colmap.alloc(std::max<size_t>(colmap.size(), 1));  // (no accession at all: still something to point at)
-        KGWAS_HIP(hipMemcpy(d_colmap.p, colmap.data(), colmap.size() * 4, hipMemcpyHostToDevice));
+        sq.create(col, S, W_f);
         d_rows.alloc(piece * stride);
-        d_sq.alloc(std::max<uint64_t>(piece * 2 * W_m, 1));
+        d_sq.alloc(std::max<uint64_t>(piece * sq.words_per_row(), 1));  // (no accession at all: still something to point at)
         d_n1.alloc(piece);
         d_hash.alloc(piece);
         d_bed.alloc(std::max<uint64_t>(piece * bpr, 1));
@@ -145,12 +141,9 @@ extern "C" int kgwas_table_to_bed(kgwas_table* t, const uint64_t* col, uint64_t 
                         if (!run_n) run0 = r;
                         run_n++;
                         bim_buf += "0\t";
-                        {
-                            const uint64_t w = h.rows.p[r * stride];
-                            char km[32];
-                            for (size_t i = 0; i < klen; i++) km[i] = "ACGT"[(w >> (2 * (klen - 1 - i))) & 3];  // bits2kmer31, src/kmer_general.cpp:77-87
-                            bim_buf.append(km, klen);
-                        }
+                        char km[32];
+                        kmer_letters(h.rows.p[r * stride], klen, km);
+                        bim_buf.append(km, klen);
                         bim_buf += "\t0\t0\t0\t1\n";
                         written++;
                         if (bim_buf.size() > (8u << 20)) flush_run();
@@ -218,9 +211,9 @@ extern "C" int kgwas_table_to_bed(kgwas_table* t, const uint64_t* col, uint64_t 
             }
             if (kgwas_table_read_rows(t, pos, c, h.rows.p) != KGWAS_OK) throw Error(KGWAS_ERR_IO, kgwas_last_error());
             KGWAS_HIP(hipMemcpyAsync(d_rows.p, h.rows.p, c * stride * 8, hipMemcpyHostToDevice, st));
-            KGWAS_HIP(launch_squeeze(d_rows.p, stride, c, d_colmap.p, W_m, (uint32_t)W_f, d_sq.p, st));
-            KGWAS_HIP(launch_bed_rowinfo(d_sq.p, c, W_m, d_n1.p, d_hash.p, st));
-            KGWAS_HIP(launch_bed_bytes(d_sq.p, c, W_m, bpr, d_bed.p, st));
+            sq.run(d_rows.p, stride, c, d_sq.p, st);
+            KGWAS_HIP(launch_bed_rowinfo(d_sq.p, c, sq.W_m, d_n1.p, d_hash.p, st));
+            KGWAS_HIP(launch_bed_bytes(d_sq.p, c, sq.W_m, bpr, d_bed.p, st));
             KGWAS_HIP(hipMemcpyAsync(h.n1.p, d_n1.p, c * 4, hipMemcpyDeviceToHost, st));
             KGWAS_HIP(hipMemcpyAsync(h.hash.p, d_hash.p, c * 8, hipMemcpyDeviceToHost, st));
             KGWAS_HIP(hipMemcpyAsync(h.bed.p, d_bed.p, c * bpr, hipMemcpyDeviceToHost, st));

@@ -11,6 +11,9 @@ import pytest
 import kmersgwas_amd as kg
 from kmersgwas_amd import capi
 from kmersgwas_amd.capi import lib
+from oracle import oracle_np as onp
+
+import lmm_table_np as T
 
 BIN = os.path.join(os.path.dirname(os.path.abspath(capi.__file__)), "bin", "clump_kmers")
 K = 31
@@ -89,6 +92,21 @@ def test_a_good_file_gets_as_far_as_the_table(tmp_path):
     r = subprocess.run([BIN, "-o", str(out), "--assoc", str(tmp_path / "in.assoc.txt"), "--kmers_table", "absent_table", "--kmers_len", "31",
                         "--r2", "0.5", "--p_max", "1e-3"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 1 and "absent_table" in r.stderr and not out.exists(), r.stderr
+
+
+def test_an_accession_listed_twice(tmp_path):
+    """a real table of three rows and a phenotype file that names one of its accessions twice: refused before any device call"""
+    rows = T.table_from_bits(T.random_bits(3, 5, 1, 0.2, 0.8), 6, np.arange(5), 1)
+    base = str(tmp_path / "tab")
+    onp.write_table(base, ["acc%d" % i for i in range(6)], K, rows[:, 0], rows[:, 1:])
+    ph = tmp_path / "twice.tsv"
+    ph.write_text("accession_id\tv\n" + "".join("acc%d\t%d\n" % (c, i) for i, c in enumerate((4, 1, 3, 1, 0))))
+    (tmp_path / "in.assoc.txt").write_text(HEAD9 + line9(T.kmer_text(rows[1, 0])) + line9(T.kmer_text(rows[0, 0]), "3e-9"))
+    out = tmp_path / "clumps.txt"
+    r = subprocess.run([BIN, "-o", str(out), "--assoc", str(tmp_path / "in.assoc.txt"), "--kmers_table", base, "--kmers_len", str(K), "-p", str(ph)],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 1 and "%s lists the accession acc1 twice" % ph in r.stderr, r.stderr
+    assert not out.exists() and not os.path.exists(str(out) + ".log.txt"), "an output file was written"
 
 
 def test_entry_points_and_argument_checks():

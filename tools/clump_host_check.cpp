@@ -1,7 +1,8 @@
-// clump_host_check.cpp - the host side of clump_kmers (csrc/clump_host.h: the threshold's text, the assoc parser, the p order, the
-// streaming clump pass, the output lines) on fixed inputs, under the sanitizers. The link matrix the clump pass consumes is made
-// here with a literal restatement of the predicate and handed over in blocks of several sizes, pitches wider than the rows
-// included, as the device hands it over; the result is compared with a whole-matrix greedy pass.
+// clump_host_check.cpp - the host side of clump_kmers (csrc/clump_host.h and what it takes from csrc/ld_host.h: the threshold's text,
+// the assoc parser, the p order, the placement of the hits' rows, the streaming clump pass, the output lines) on fixed inputs, under
+// the sanitizers. The link matrix the clump pass consumes is made here with a literal restatement of the predicate and handed over
+// in blocks of several sizes, pitches wider than the rows included, as the device hands it over; the result is compared with a
+// whole-matrix greedy pass.
 // build: g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include
 //        -I kmersgwas_amd/csrc tools/clump_host_check.cpp -o tools/bin/clump_host_check
 // (a host-only program: run it on the CPU, on its own)
@@ -171,9 +172,36 @@ static void check_clumper(uint64_t N, uint64_t n, uint64_t tm, uint64_t seed) {
     CHECK(r2_of(8192, 4096, 4096, 3072) == 0.25 && std::isnan(r2_of(8, 8, 4, 4)));
 }
 
+// the rows of a list of codes from what the table's search found (ld_host.h, place_rows): the list in shuffled order, a key the
+// table holds twice (its first row is taken), a code the table lacks (its place comes back)
+static void check_placement() {
+    const uint64_t stride = 3;
+    std::vector<uint64_t> found;  // table order: keys 10, 20, 20, 30, 40, 50; words 1 and 2 of a row say which row it is
+    const uint64_t keys[] = {10, 20, 20, 30, 40, 50};
+    for (uint64_t i = 0; i < 6; i++) found.insert(found.end(), {keys[i], 100 + i, 200 + i});
+    const std::vector<uint64_t> codes = {40, 10, 50, 20, 30};
+    const PlacedRows all = place_rows(codes.data(), codes.size(), found.data(), 6, stride);
+    CHECK(all.missing == PlacedRows::NONE && all.rows.size() == codes.size() * stride);
+    const uint64_t from[] = {4, 0, 5, 1, 3};  // (key 20: row 1, not row 2)
+    for (size_t i = 0; i < codes.size(); i++)
+        CHECK(all.rows[i * stride] == codes[i] && all.rows[i * stride + 1] == 100 + from[i] && all.rows[i * stride + 2] == 200 + from[i]);
+    // a list with two codes the table lacks: the first one's place; a found row of a key nobody asked for is passed over
+    const std::vector<uint64_t> some = {30, 7, 10, 8};
+    const PlacedRows part = place_rows(some.data(), some.size(), found.data(), 6, stride);
+    CHECK(part.missing == 1 && part.rows.size() == some.size() * stride && part.rows[0] == 30 && part.rows[2 * stride + 1] == 100);
+    // nothing found, nothing asked for
+    CHECK(place_rows(some.data(), some.size(), nullptr, 0, stride).missing == 0);
+    const PlacedRows none = place_rows(nullptr, 0, found.data(), 6, stride);
+    CHECK(none.missing == PlacedRows::NONE && none.rows.empty());
+    // exactly the arrays: a read past them is a read past the allocation
+    const std::vector<uint64_t> one_found = {10, 1, 2}, one_code = {10};
+    CHECK(place_rows(one_code.data(), 1, one_found.data(), 1, stride).rows == one_found);
+}
+
 int main() {
     check_threshold();
     check_parser();
+    check_placement();
     check_clumper(1, 5, 800000, 1);
     check_clumper(33, 67, 800000, 2);
     check_clumper(130, 128, 250000, 3);
