@@ -240,6 +240,7 @@ typedef struct kgwas_scan_stats {
  * and struct kgwas_lmm_unique_stats, kgwas_lmm_test_table_unique, kgwas_lmm_run_table_unique (lmm_lrt --pattern_cache),
  * and struct kgwas_lmm_skip_stats, kgwas_lmm_test_table_multi_skip, kgwas_lmm_run_table_multi_skip (lmm_lrt --pattern_skip),
  * and structs kgwas_proxy_record, kgwas_proxy_stats, kgwas_kmers_ld_proxies, kgwas_proxy_kmers_run (proxy_kmers).
+ * and structs kgwas_locate_record, kgwas_locate_stats, kgwas_locate_kmers_bases, kgwas_locate_kmers_run (locate_kmers).
  * Those came after version 15 without a bump: a caller that may meet an older version-15 library probes for them by symbol
  * (dlsym, or hasattr on a ctypes handle). */
 #define KGWAS_ABI_VERSION 15
@@ -864,7 +865,7 @@ int kgwas_clump_kmers_run(const char* table_base, uint32_t kmer_len, const char*
 
 /* ------------------------------------------------------------------------------------
  * proxy_kmers: every k-mer of the table in LD with a lead k-mer - the step after clump_kmers, which ends with one lead per
- * signal: the k-mers that travel with a lead are the ones to assemble or map. A tool of this project's own. A row of the table
+ * signal: the k-mers that travel with a lead are the ones to assemble or map (locate_kmers, below). A tool of this project's own. A row of the table
  * is a PROXY of a lead iff the pair is linked by clump_kmers' predicate (above: num * 1000000 >= r2_millionths * den, den > 0,
  * in 128-bit integers on the device). Every (lead, row) pair is tested, the lead's own row included: a non-constant lead finds
  * itself, a constant lead finds nothing, a complement is a proxy (phase -).
@@ -902,6 +903,64 @@ int kgwas_kmers_ld_proxies(const uint64_t* lead_bits, uint64_t n_leads, const ui
                            uint64_t* n_out);
 int kgwas_proxy_kmers_run(const char* table_base, uint32_t kmer_len, const char* pheno_path, const char* leads_path, uint32_t r2_millionths,
                           uint64_t max_per_lead, int32_t device, const char* out_path, kgwas_proxy_stats* st);
+
+/* ------------------------------------------------------------------------------------
+ * locate_kmers: the genome positions of k-mers, exact or with one mismatch - the step after proxy_kmers: a k-mer with a p-value
+ * becomes a point on a Manhattan plot once it has a contig and a position. A tool of this project's own. An associated k-mer
+ * usually carries the non-reference allele and does not occur in the reference; with one mismatch allowed it lands on its locus
+ * and the mismatching base is the variant.
+ *
+ * Definitions. The BASE STREAM is kgwas_count_kmers_bases': bytes, A C G T in either case are bases, every other byte separates.
+ * A WINDOW at offset p is k consecutive base bytes; its code a has A=0, C=1, G=2, T=3, two bits per base, first base most
+ * significant. QUERY i is k letters: f_i the code of the letters as spelled, r_i the code of their reverse complement. Its
+ * PATTERNS are (f_i, strand 0 = +) and, unless r_i == f_i, (r_i, strand 1 = -). Two queries are the same k-mer when their
+ * canonical codes (kgwas_kmer_encode) are equal. With d = mismatches in {0, 1} a HIT is a (window, pattern) pair whose codes
+ * differ in h <= d base positions; its record is {pos = p, kmer = i, strand, mismatches = h, offset, pad = 0}, offset 0 for h = 0,
+ * else the 1-based index, in the window as the reference spells it, of the differing base. One window can hit several queries and,
+ * with d = 1, both patterns of one query: each pair is one record. Records come in ascending pos, then kmer, then strand: the same
+ * bytes in every run.
+ *
+ * kgwas_locate_kmers_bases: the array level. bases[n_bytes] is host memory, or device memory of `device` when on_device != 0;
+ * codes[n_kmers] the f_i. The patterns are sorted once and stay on the device (d = 1: by their first ceil(k / 2) and by their last
+ * floor(k / 2) bases; a window looks both halves up, and a pair within one mismatch is found exactly once); the stream passes in
+ * pieces that overlap by k - 1 bytes (the next piece's copy beside this piece's kernels), and the hits are compacted on the device
+ * into records. *n_out gets the count of all records; the first min(cap, *n_out) are written to records_out. Checked before any
+ * device call (KGWAS_ERR_ARG): null codes or n_out, null bases with n_bytes > 0, null records_out with cap > 0, kmer_len outside
+ * 1..31, mismatches > 1, mismatches == 1 with kmer_len < 2, n_kmers of 0 or above 2^20, a code with bits at or above
+ * 2 * kmer_len, two queries that are the same k-mer. No HIP device -> KGWAS_ERR_DEVICE. KGWAS_LOCATE_PIECE_BYTES (window positions
+ * per piece, at most 2^25) and KGWAS_LOCATE_RECORDS (records of the device buffer, default 2^20; a piece with more is drained in
+ * rounds) are the tests' hooks.
+ * kgwas_locate_kmers_run: the tool. reference_path is FASTA in plain text: the first byte must be '>' (else KGWAS_ERR_FORMAT
+ * "<path>: not FASTA"; an empty file or one without a sequence byte is KGWAS_ERR_FORMAT too); a trailing '\r' is dropped from every
+ * line and a missing final newline is fine; a contig's name is its header line after '>' up to the first blank or tab (an empty
+ * name or one given twice is refused by name); its sequence is the concatenation of its lines, every byte of which has a position,
+ * and one separator byte goes between contigs in the stream. A file that cannot be opened -> KGWAS_ERR_IO "can't open file:
+ * <path>". kmers_path is, by its first line: a tab-separated file whose header has a column `rs` (an lmm_lrt / GEMMA .assoc.txt,
+ * a clump_kmers output), one whose header has a column `kmer` and no `rs` (a proxy_kmers output: its distinct values in order of
+ * first appearance), or a plain list, one k-mer per line; a column `p_lrt` is carried along as text. Refused by name with the line
+ * (KGWAS_ERR_FORMAT) before the reference is opened: a k-mer of another length than kmer_len, with a letter other than A, C, G, T,
+ * given twice in a list or an `rs` column, a line with too few fields, no k-mer at all.
+ * out_path gets the header "kmer contig pos strand mismatches offset ref alt" (tabs; a last column p_lrt when the input had one)
+ * and one line per kept hit, grouped by k-mer in the input's order and within a k-mer by contig in the file's order, then
+ * position, then + before -: pos is the 1-based position of the window's first base in its contig, ref the reference's letter at
+ * the mismatch (upper case), alt the k-mer's base there in the reference's orientation (on strand - the complement of the query's
+ * letter at k - offset, 0-based); both are '.' for an exact hit. Per k-mer the first max_per_kmer hits in that order are kept, the
+ * rest only counted (0: no limit). out_path + ".log.txt": the inputs, one line "kmer <text> <kept> <found>" per query, the counters
+ * and the times. No output file exists after a refusal. *st (may be NULL) is written when the call succeeds.
+ * ---------------------------------------------------------------------------------- */
+typedef struct kgwas_locate_record {
+    uint64_t pos;
+    uint32_t kmer;
+    uint8_t strand, mismatches, offset, pad;
+} kgwas_locate_record;
+typedef struct kgwas_locate_stats {
+    uint64_t contigs, bases, windows_tested, kmers, hits_found, hits_kept, kmers_without_hit, kmers_with_one_hit, drain_rounds;
+    double parse_ms, copy_ms, kernel_ms, total_ms; /* the reader thread's parsing, the pieces' copies and the kernels (events), all */
+} kgwas_locate_stats;
+int kgwas_locate_kmers_bases(const void* bases, uint64_t n_bytes, int on_device, const uint64_t* codes, uint64_t n_kmers, uint32_t kmer_len,
+                             uint32_t mismatches, int32_t device, kgwas_locate_record* records_out, uint64_t cap, uint64_t* n_out);
+int kgwas_locate_kmers_run(const char* reference_path, const char* kmers_path, uint32_t kmer_len, uint32_t mismatches, uint64_t max_per_kmer,
+                           int32_t device, const char* out_path, kgwas_locate_stats* st);
 
 /* ------------------------------------------------------------------------------------
  * Seeded synthetic table rows: kmer = row + 1, per-row frequency q/256 with

@@ -52,6 +52,7 @@ SYMBOLS = [
     "kgwas_lmm_test_table_multi_skip", "kgwas_lmm_run_table_multi_skip",
     "kgwas_r2_millionths", "kgwas_kmers_ld", "kgwas_clump_kmers_run",
     "kgwas_kmers_ld_proxies", "kgwas_proxy_kmers_run",
+    "kgwas_locate_kmers_bases", "kgwas_locate_kmers_run",
     "kgwas_synth_rows_device", "kgwas_synth_rows_host",
 ]
 
@@ -80,6 +81,20 @@ class ProxyStats(C.Structure):
     _fields_ = [("accessions", C.c_uint64), ("leads", C.c_uint64), ("rows_read", C.c_uint64), ("pairs_tested", C.c_uint64),
                 ("proxies_found", C.c_uint64), ("proxies_kept", C.c_uint64), ("drain_rounds", C.c_uint64), ("search_ms", C.c_double),
                 ("kernel_ms", C.c_double), ("copy_ms", C.c_double), ("total_ms", C.c_double)]
+
+
+class LocateRecord(C.Structure):
+    """kgwas_locate_record"""
+    _fields_ = [("pos", C.c_uint64), ("kmer", C.c_uint32), ("strand", C.c_uint8), ("mismatches", C.c_uint8), ("offset", C.c_uint8), ("pad", C.c_uint8)]
+
+
+class LocateStats(C.Structure):
+    """kgwas_locate_stats"""
+    _fields_ = [(k, C.c_uint64) for k in ("contigs", "bases", "windows_tested", "kmers", "hits_found", "hits_kept", "kmers_without_hit",
+                                          "kmers_with_one_hit", "drain_rounds")] + [(k, C.c_double) for k in ("parse_ms", "copy_ms", "kernel_ms", "total_ms")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class ScanParams(C.Structure):
@@ -305,6 +320,9 @@ lib.kgwas_kmers_ld.argtypes = [_vp, _u64, _u64, _u64, _u32, _i32, _u64, _vp, _vp
 lib.kgwas_clump_kmers_run.argtypes = [C.c_char_p, _u32, C.c_char_p, C.c_char_p, _u32, C.c_double, _i32, _u64, C.c_char_p, C.POINTER(ClumpStats)]
 lib.kgwas_kmers_ld_proxies.argtypes = [_vp, _u64, _vp, _u64, _u64, _u64, _u32, _i32, _vp, _u64, C.POINTER(C.c_uint64)]
 lib.kgwas_proxy_kmers_run.argtypes = [C.c_char_p, _u32, C.c_char_p, C.c_char_p, _u32, _u64, _i32, C.c_char_p, C.POINTER(ProxyStats)]
+# locate_kmers: added after ABI version 15 without a bump
+lib.kgwas_locate_kmers_bases.argtypes = [_vp, _u64, C.c_int, _vp, _u64, _u32, _u32, _i32, _vp, _u64, C.POINTER(C.c_uint64)]
+lib.kgwas_locate_kmers_run.argtypes = [C.c_char_p, C.c_char_p, _u32, _u32, _u64, _i32, C.c_char_p, C.POINTER(LocateStats)]
 lib.kgwas_build_table.argtypes = [C.c_char_p, _pstr, _pstr, _u64, _u32, _i32, C.c_char_p, _pu64]
 lib.kgwas_list_kmers.argtypes = [_pstr, _u64, _u32, _u64, C.c_double, _i32, C.c_char_p, _pu64]
 lib.kgwas_count_kmers_files.argtypes = [_pstr, _u64, _u32, _u64, _u64, _i32, C.c_char_p, _pu64]

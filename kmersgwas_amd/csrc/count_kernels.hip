@@ -7,59 +7,22 @@
 // the run heads, ck_reduce turns a run into count (distance to the next head) and flags (orient of its first and of its last
 // word) and decides, ck_compact writes the kept key | flags words in order. No lane walks along a run.
 //
-// ck_encode: a workgroup of 256 lanes takes a tile of 4096 positions. Each lane loads its 16 bases with one 16-byte load and
-// packs them into 32 bits of 2-bit codes (first base in the top bits) and 16 validity bits; the packed tile and a halo of 32
-// positions go to LDS (1.5 KiB), from where a lane takes the two entries behind its own: 48 positions in registers cover its
-// 16 windows of up to 31 bases. The first window's code is a funnel shift, its reverse complement a bit reversal; the other
+// ck_encode: a workgroup of 256 lanes takes a tile of 4096 positions (kmer_windows.h: the tile, the packing and the codes, which
+// locate_kernels.hip shares). The first window's code is a funnel shift, its reverse complement a bit reversal; the other
 // 15 follow by rolling both codes one base on. The words of the tile are compacted in LDS (32 KiB) and written with ONE slot
 // claim per workgroup (per-wave device-scope atomics on one address: DESIGN.md §0 row f-2, §4.1b) and coalesced stores.
 #include <hipcub/hipcub.hpp>
 
 #include "kernels.h"
+#include "kmer_windows.h"
 
 namespace kgwas {
 
 namespace {
 
-constexpr uint32_t CK_BLOCK = 256;
-constexpr uint32_t CK_RUN = 16;                    // positions per lane
-constexpr uint32_t CK_TILE = CK_BLOCK * CK_RUN;    // positions per workgroup and step
-constexpr uint32_t CK_PACKS = CK_BLOCK + 2;        // packed entries per tile: its own and a halo of 32 positions >= k - 1
 constexpr uint32_t CK_ITEMS = 8;                   // words per lane of the heads / reduce / compact kernels
 constexpr uint32_t CK_RTILE = CK_BLOCK * CK_ITEMS;
 constexpr uint64_t CK_FLAG_CANON = 0x4000000000000000ull, CK_FLAG_NON = 0x8000000000000000ull;
-
-// 2-bit code of a base, 4 for a separator
-__device__ __forceinline__ uint32_t ck_code(uint32_t c) {
-    c &= 0xDFu;  // (lower case)
-    return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u;
-}
-
-// 16 positions from p on: codes (position i in bits 31-2i, 30-2i) and validity (bit i); positions at or behind n are separators
-__device__ __forceinline__ void ck_pack(const uint8_t* bases, uint64_t n, uint64_t p, bool aligned, uint32_t& codes, uint32_t& valid) {
-    uint32_t w[4] = {0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au};
-    if (p + 16 <= n && aligned) {
-        const uint4 v = *reinterpret_cast<const uint4*>(bases + p);
-        w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
-    } else if (p < n) {
-        const uint32_t m = (uint32_t)min((uint64_t)16, n - p);
-        for (uint32_t i = 0; i < m; i++) w[i >> 2] = (w[i >> 2] & ~(0xFFu << (8 * (i & 3)))) | ((uint32_t)bases[p + i] << (8 * (i & 3)));
-    }
-    codes = 0, valid = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < 16; i++) {
-        const uint32_t c = ck_code((w[i >> 2] >> (8 * (i & 3))) & 0xFFu);
-        codes |= (c & 3u) << (30 - 2 * i);
-        valid |= (uint32_t)(c < 4u) << i;
-    }
-}
-
-// the reverse complement of a k-base code (kmer_reverse_complement, src/kmer_general.h:102-109)
-__device__ __forceinline__ uint64_t ck_revcomp(uint64_t a, uint32_t k) {
-    uint64_t x = ((uint64_t)__brev((uint32_t)a) << 32) | __brev((uint32_t)(a >> 32));  // all 64 bits reversed
-    x = ((x & 0xAAAAAAAAAAAAAAAAull) >> 1) | ((x & 0x5555555555555555ull) << 1);       // and each pair set right again
-    return (~x) >> (64 - 2 * k);
-}
 
 __global__ void __launch_bounds__(CK_BLOCK) ck_encode_kernel(const uint8_t* __restrict__ bases, uint64_t n, uint32_t k, uint64_t lo, uint64_t hi,
                                                              uint64_t* __restrict__ words, uint64_t cap, unsigned long long* ctr, int aligned) {
@@ -100,8 +63,7 @@ __global__ void __launch_bounds__(CK_BLOCK) ck_encode_kernel(const uint8_t* __re
             w[j] = (key << 1) | (canon ? 0u : 1u);
             if (ok && key >= lo && key < hi) emit |= 1u << j, n1 += !canon;
             // the base at position j + k comes in
-            const uint32_t q = j + k;
-            const uint64_t c = q < 32 ? (X_hi >> (62 - 2 * q)) & 3 : (X_lo >> (62 - 2 * (q - 32))) & 3;
+            const uint64_t c = ck_base_at(X_hi, X_lo, j + k);
             a = ((a << 2) | c) & cmask;
             b = (b >> 2) | ((3 - c) << (2 * k - 2));
         }

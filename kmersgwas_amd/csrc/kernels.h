@@ -435,4 +435,38 @@ hipError_t launch_ld_proxy_write(const uint64_t* bits, uint64_t pitch_q, const u
                                  uint32_t cap, const LdView& A, const LdView& B, const uint64_t* kmers, uint64_t kmer_stride, uint64_t row_base,
                                  ProxyRecord* rec, hipStream_t st);
 
+// The scan of the count / scan / write scheme, shared by proxy_kmers and locate_kmers: boff[b] = bcnt[0] + .. + bcnt[b - 1] for
+// b <= n_blocks (boff[n_blocks]: the total), by one workgroup.
+hipError_t launch_block_offsets(const uint32_t* bcnt, uint32_t n_blocks, uint32_t* boff, hipStream_t st);
+
+// locate_kmers (locate_kernels.hip). A LocateList is the queries' patterns sorted by (key, id): keys[n] the sort
+// key (d = 0: the code itself, and codes == keys; d = 1: the first ceil(k / 2) bases for H, the last floor(k / 2) for L), codes[n]
+// the pattern's whole code, ids[n] = kmer << 1 | strand, and spl[ns] = keys[j * B] the splitters, ns = ceil(n / B) <=
+// LOCATE_SPLITTERS. An empty list has n = ns = 0.
+//  count: the windows at positions [0, n_win) of bases[0, n_buf), n_win <= n_buf, n_win <= LOCATE_MAX_PIECE (a window has at most
+//         3 k + 1 <= 94 hits - the codes within one mismatch of it, and no two patterns share a code -, so a piece's records are
+//         below 2^32); bcnt[tile] the records of a tile of 4096 positions, boff[.. + 1] the records before a tile and, last, the
+//         total; *windows += the windows of k bases.
+//  write: the records numbered [win_lo, win_lo + cap) in (pos, kmer, strand) order, from the tiles [tile0, tile1), to
+//         rec[number - win_lo]; pos = pos0 + the window's position. The record's layout is kgwas_locate_record's.
+constexpr uint32_t LOCATE_SPLITTERS = 2048;
+constexpr uint64_t LOCATE_MAX_PIECE = 1ull << 25;
+struct LocateList {
+    const uint64_t *spl, *keys, *codes;
+    const uint32_t* ids;
+    uint64_t n, B;
+    uint32_t ns;
+};
+struct LocateRecord {
+    uint64_t pos;
+    uint32_t kmer;
+    uint8_t strand, mismatches, offset, pad;
+};
+uint32_t locate_tiles(uint64_t n_win);
+hipError_t launch_locate_count(const uint8_t* bases, uint64_t n_buf, uint64_t n_win, uint32_t kmer_len, uint32_t mismatches, const LocateList& H,
+                               const LocateList& L, uint32_t* bcnt, uint32_t* boff, unsigned long long* windows, hipStream_t st);
+hipError_t launch_locate_write(const uint8_t* bases, uint64_t n_buf, uint64_t n_win, uint32_t kmer_len, uint32_t mismatches, const LocateList& H,
+                               const LocateList& L, const uint32_t* boff, uint32_t tile0, uint32_t tile1, uint32_t win_lo, uint32_t cap, uint64_t pos0,
+                               LocateRecord* rec, hipStream_t st);
+
 }  // namespace kgwas

@@ -326,7 +326,11 @@ hipError_t launch_ld_proxy_count(const uint64_t* bits, uint64_t pitch_q, uint64_
     if (R > (1ull << 20)) return hipErrorInvalidValue;
     const uint32_t n_blocks = (uint32_t)((R + 255u) / 256u);
     hipLaunchKernelGGL(ld_proxy_count_kernel, dim3(n_blocks), dim3(256), 0, st, bits, pitch_q, (uint32_t)R, bcnt);
-    hipLaunchKernelGGL(ld_proxy_scan_kernel, dim3(1), dim3(256), 0, st, (const uint32_t*)bcnt, n_blocks, boff);
+    return launch_block_offsets(bcnt, n_blocks, boff, st);
+}
+
+hipError_t launch_block_offsets(const uint32_t* bcnt, uint32_t n_blocks, uint32_t* boff, hipStream_t st) {
+    hipLaunchKernelGGL(ld_proxy_scan_kernel, dim3(1), dim3(256), 0, st, bcnt, n_blocks, boff);
     return hipGetLastError();
 }
 

@@ -12,6 +12,7 @@ Names follow the reference's classes (src/kmers_multiple_databases.h, src/best_a
   build_kmers_table     <- build_kmers_table (the table from sorted k-mer files)      (f-7)
   kmers_ld              -- this project's own: exact r^2 links between k-mers (clump_kmers)
   kmers_ld_proxies      -- this project's own: the rows in LD with a few lead rows, as records (proxy_kmers)
+  locate_kmers_bases    -- this project's own: where in a base stream k-mers occur, exactly or with one mismatch (locate_kmers)
 
 Everything numeric happens inside libkgwas (HIP kernels on the GPU + the std::priority_queue
 replay); this module only moves buffers.
@@ -824,6 +825,61 @@ def kmers_ld_proxies(lead_bits, bits, n_acc: int, r2, cap: int | None = None, de
         rec = np.zeros(room, PROXY_RECORD)
         check(lib.kgwas_kmers_ld_proxies(ptr(lead_bits), len(lead_bits), ptr(bits), len(bits), bits.shape[1], n_acc, tm, device,
                                          ptr(rec) if room else None, room, C.byref(n)))
+        if cap is not None or n.value <= room:
+            return rec[:min(n.value, room)], n.value
+        room = n.value
+
+
+LOCATE_RECORD = np.dtype([("pos", np.uint64), ("kmer", np.uint32), ("strand", np.uint8), ("mismatches", np.uint8), ("offset", np.uint8), ("pad", np.uint8)])
+
+
+def kmer_codes(kmers, kmer_len: int) -> np.ndarray:
+    """The codes of k-mers as spelled (A=0, C=1, G=2, T=3, first base most significant; not the canonical form): what
+    locate_kmers_bases takes."""
+    out = np.zeros(len(kmers), np.uint64)
+    for i, w in enumerate(kmers):
+        if len(w) != kmer_len or set(w) - set("ACGT"):
+            raise ValueError("kmer_codes: %r is not %d letters of A, C, G, T" % (w, kmer_len))
+        c = 0
+        for ch in w:
+            c = c << 2 | "ACGT".index(ch)
+        out[i] = c
+    return out
+
+
+def locate_kmers_bases(bases, codes, kmer_len: int, mismatches: int = 1, cap: int | None = None, device: int = 0):
+    """Where in a base stream the k-mers `codes` (uint64, the letters as spelled: kmer_codes), or their reverse complements, occur
+    with at most `mismatches` (0 or 1) differing bases (kgwas_locate_kmers_bases: the sorted patterns stay on the device, the stream
+    passes in pieces, the hits come back as records). `bases` is bytes, a uint8 NumPy array, or a uint8 torch tensor on the host or
+    on `device`: every byte other than A, C, G, T (either case) separates. Returns (records, n): records is a structured array of
+    dtype LOCATE_RECORD (pos, kmer, strand, mismatches, offset, pad = 0) in (pos, kmer, strand) order and n the count of all hits.
+    cap=None: every record is returned (a second call where the first guess was too small); otherwise the first min(cap, n)."""
+    codes = np.ascontiguousarray(codes, np.uint64).reshape(-1)
+    on_device = 0
+    if hasattr(bases, "data_ptr"):  # a torch tensor
+        import torch
+        if bases.dtype != torch.uint8:
+            raise TypeError("locate_kmers_bases: the bases must be uint8")
+        keep = bases.contiguous()
+        if keep.is_cuda:
+            if keep.device.index != device:
+                raise ValueError("locate_kmers_bases: the tensor is on device %s, the search runs on device %d" % (keep.device.index, device))
+            torch.cuda.synchronize(keep.device)
+            on_device = 1
+        p, size = C.c_void_p(keep.data_ptr()), keep.numel()
+    elif isinstance(bases, (bytes, bytearray, memoryview, np.ndarray)):
+        keep = np.ascontiguousarray(np.frombuffer(bases, np.uint8) if not isinstance(bases, np.ndarray) else bases)
+        if keep.dtype != np.uint8:
+            raise TypeError("locate_kmers_bases: the bases must be uint8")
+        p, size = ptr(keep), keep.size
+    else:
+        raise TypeError("locate_kmers_bases: bytes, a uint8 array or a uint8 tensor, not %s" % type(bases).__name__)
+    n = C.c_uint64(0)
+    room = 4096 if cap is None else cap
+    while True:
+        rec = np.zeros(room, LOCATE_RECORD)
+        check(lib.kgwas_locate_kmers_bases(p if size else None, size, on_device, ptr(codes), len(codes), kmer_len, mismatches, device,
+                                           ptr(rec) if room else None, room, C.byref(n)))
         if cap is not None or n.value <= room:
             return rec[:min(n.value, room)], n.value
         room = n.value
