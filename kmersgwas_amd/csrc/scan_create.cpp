@@ -133,7 +133,7 @@ static std::vector<float> upload_exact_layouts(kgwas_scan* s, const ScanShape& s
     return std::move(ex.sums);
 }
 
-// The filter's operand sets (cmode) or the narrow filter's operands, built on the host and uploaded
+// The narrow filter's operands, or the planner's operand sets (fset), built on the host and uploaded
 static void upload_filters(kgwas_scan* s, const ScanPlan& pl, const ScanShape& sh, const std::vector<float>& sums) {
     if (pl.narrow) {
         const NarrowOperands op = narrow_operands(sh, pl, s->Y, sums, s->dbg_keep_resid ? s->dbg_resid[2].data() : nullptr);
@@ -143,42 +143,30 @@ static void upload_filters(kgwas_scan* s, const ScanPlan& pl, const ScanShape& s
         KGWAS_HIP(hipMemcpy(s->d_ncols.p, op.ncols.data(), sh.P * sizeof(NarrowCol), hipMemcpyHostToDevice));
     }
     for (int mi = 0; mi < 2; mi++) {
-        const FilterSet& fs = pl.set[mi];
-        if (!fs.slices) continue;
-        kgwas_scan::CoarseMode& M = s->cmode[mi];
-        M.mx = fs.mx;
-        M.mx_full = fs.n_full;
-        M.mx_quarter = fs.n_quarter;
-        M.mx_s1_fp6 = fs.s1_fp6;
-        if (fs.mx) M.mx_scale0 = 0x01010101u * (uint32_t)(0x7F + (fs.slices == 1 ? 0 : 5));
-        M.slices = fs.slices;
-        M.n_parts = (uint32_t)fs.parts.size();
-        M.tile_slices = fs.tile_slices;
-        M.tile_slices_eq = fs.tile_slices_eq;
+        if (!pl.set[mi].slices) continue;
+        kgwas_scan::DeviceFilterSet& M = s->fset[mi];
+        M.plan = pl.set[mi];
+        const FilterSet& fs = M.plan;
+        if (fs.mx) M.scale0 = 0x01010101u * (uint32_t)(0x7F + (fs.slices == 1 ? 0 : 5));
         uint32_t groups_all = 0;
         for (size_t pi = 0; pi < fs.parts.size(); pi++) {
             const FilterPart& fp = fs.parts[pi];
-            kgwas_scan::CoarsePart& Pt = M.part[pi];
-            Pt.T = fp.T;
-            Pt.n_lgroups = (uint32_t)(fp.groups / fp.ng);  // (streaming form: operand groups = grid blocks per row block)
-            Pt.stream = fp.stream;
-            Pt.ng = fp.ng;
             if (fp.stream) s->st.coarse_mx_stream = fp.stream;
-            groups_all += Pt.n_lgroups;
+            groups_all += fp.launch_groups();
             double* resid = s->dbg_keep_resid ? s->dbg_resid[mi].data() : nullptr;
             const PartOperands op = fs.mx ? block_scaled_operands(sh, fs, fp, s->Y, sums, resid)
                                           : int8_operands(sh, pl.n_kgroups, fs, fp, s->Y, sums, resid);
             M.eg_max = std::max(M.eg_max, op.eg_max);
             M.rall_max = std::max(M.rall_max, op.rall_max);
             M.rmax_max = std::max(M.rmax_max, op.rmax_max);
-            Pt.d_Bq.alloc(op.Bq.size());
-            Pt.d_cols.alloc(op.cols.size());
-            KGWAS_HIP(hipMemcpy(Pt.d_Bq.p, op.Bq.data(), op.Bq.size(), hipMemcpyHostToDevice));
-            KGWAS_HIP(hipMemcpy(Pt.d_cols.p, op.cols.data(), op.cols.size() * sizeof(CoarseCol), hipMemcpyHostToDevice));
+            M.dev[pi].d_Bq.alloc(op.Bq.size());
+            M.dev[pi].d_cols.alloc(op.cols.size());
+            KGWAS_HIP(hipMemcpy(M.dev[pi].d_Bq.p, op.Bq.data(), op.Bq.size(), hipMemcpyHostToDevice));
+            KGWAS_HIP(hipMemcpy(M.dev[pi].d_cols.p, op.cols.data(), op.cols.size() * sizeof(CoarseCol), hipMemcpyHostToDevice));
         }
-        s->st.coarse_mode_tiles[mi] = M.part[0].T;
+        s->st.coarse_mode_tiles[mi] = fs.parts.empty() ? 0 : fs.parts[0].T;
         s->st.coarse_mode_lgroups[mi] = groups_all;
-        s->st.coarse_mode_tile_slices[mi] = M.tile_slices;
+        s->st.coarse_mode_tile_slices[mi] = fs.tile_slices;
         if (fs.mx) {
             if (pl.use_mx) s->st.coarse_mx = 1;
             s->st.coarse_mx_s1_fp6 = fs.s1_fp6;
@@ -224,19 +212,10 @@ static void alloc_slots(kgwas_scan* s, const CreateTrace& tcreate) {
         // device side: 20 B x key_slots of HBM per slot, up to 4 GiB in all; host side: the record ring
         const uint64_t slot_bytes = (uint64_t)s->key_slots * 20;
         s->n_slots = (int)std::min<uint64_t>(MAX_SLOTS, std::max<uint64_t>(4, (4ull << 30) / std::max<uint64_t>(slot_bytes, 1)));
-        // Pinning memory is slow - 1 GiB takes 0.21-0.25 s, two thirds of a session's creation (KGWAS_TRACE), and every
-        // other allocation of the process queues behind it, so a thread of its own does not hide it: the ring is sized
-        // for what the scan plans to have in flight instead of the cap. A chunk is planned to fill 40 % of the key list
-        // (next_sparse_chunk) and the GPU runs up to ~16 chunks ahead of the replay: 20 planned chunks' records
-        // (8 x a slot's worst case), at least 64 MiB and two worst-case chunks, at most 1 GiB - 390 MB at 101 columns
-        // (top-10001), 775 MB at 201. A ring that fills up only makes the GPU wait for the replay (fetch_records).
-        s->ring_size = (size_t)std::max<uint64_t>(std::min<uint64_t>(1ull << 30, std::min<uint64_t>((uint64_t)s->n_slots * slot_bytes, std::max<uint64_t>(64ull << 20, 8 * slot_bytes))),
-                                                  2 * slot_bytes + 4096);
-        // (tests: a ring barely larger than one chunk's worst case, so that it wraps and fills up)
-        if (opt_str("KGWAS_RING_BYTES"))
-            s->ring_size = (size_t)std::max<uint64_t>(strtoull(opt_str("KGWAS_RING_BYTES"), nullptr, 10), slot_bytes + 4096);
+        const char* forced = opt_str("KGWAS_RING_BYTES");  // (tests)
+        s->rr.set_size(record_ring_bytes((uint64_t)s->n_slots, slot_bytes, forced ? std::max<uint64_t>(strtoull(forced, nullptr, 10), 1) : 0));
         tcreate("device buffers and slots allocated");
-        s->ring.alloc(s->ring_size);
+        s->ring.alloc(s->rr.size());
         s->ring_dev = s->ring.dev();
         tcreate("pinned record ring allocated");
     } else {

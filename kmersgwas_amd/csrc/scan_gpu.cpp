@@ -165,8 +165,7 @@ void run_dense(kgwas_scan* s, const uint64_t* d_rows, uint64_t n_rows, uint64_t 
     // A dense START's scores (9.5 MB at 101 columns: 0.17 ms of PCIe) travel on the copy stream, behind the scorer and beside the
     // selection and the first sparse chunk, which the caller submits before it waits for them (wait_dense_copy): the stream's
     // first sparse launch does not queue up behind a kernel that is parked on PCIe stores.
-    static const bool dcopy_side = !exp_set("KGWAS_DENSE_COPY_INLINE");  // experiments: the copy on the scan's stream, as before
-    if (select && dcopy_side && s->copy_stream) {
+    if (select && s->copy_stream) {
         // (an SDMA transfer, not the copying kernel: its waves, parked on PCIe stores, doubled the selection's time beside them -
         // 199 against 101 us under the profiler, profiles/r06_chunk_timeline.txt of the first version; tools/probe_d2h.hip: a
         // transfer costs the kernels beside it nothing)
@@ -291,11 +290,11 @@ void dense_fill(kgwas_scan* s, uint64_t n_rows, uint64_t first_row, std::chrono:
 // i.e. early in a scan (low thresholds, many candidates per row) the chunks take two slices, later one. infl[] are the
 // survivors per candidate the finished chunks of each mode reported (fetch_records).
 int pick_coarse_mode(const kgwas_scan* s) {
-    if (!s->cmode[0].ready) return 1;
-    if (!s->cmode[1].ready) return 0;
+    if (!s->fset[0].ready) return 1;
+    if (!s->fset[1].ready) return 0;
     const double cand_row = (double)s->sum_topn / (double)std::max<uint64_t>(s->rows_submitted, 1);
-    auto eq = [](const kgwas_scan::CoarseMode& M) { return M.tile_slices_eq > 0 ? M.tile_slices_eq : (double)M.tile_slices; };
-    const double tiles0 = eq(s->cmode[0]), tiles1 = eq(s->cmode[1]);
+    auto eq = [](const FilterSet& M) { return M.tile_slices_eq > 0 ? M.tile_slices_eq : (double)M.tile_slices; };
+    const double tiles0 = eq(s->fset[0].plan), tiles1 = eq(s->fset[1].plan);
     return cand_row * std::max(0.0, s->infl_obs[0] - s->infl_obs[1]) < s->mode_k * (tiles1 - tiles0) ? 0 : 1;
 }
 
@@ -338,10 +337,37 @@ static void dbg_log_survivors(kgwas_scan* s) {
     }
 }
 
-// count_hist: first (and only) scoring of these rows in the sparse phase -> their candidates feed the
-// device-side threshold histograms. Overflow re-runs must not count the same rows twice.
-void submit_sparse(kgwas_scan* s, Slot& sl, const uint64_t* d_rows, uint64_t n_rows, uint64_t first_row,
-                   bool count_hist) {
+// ---- a sparse chunk's launches, stage by stage (submit_sparse) -----------------------------------------------------------
+// The chunk's four events - start (ev_k0), filter done (ev_mid), kernels done (ev_k1), counts on the host (ev_counts) - are bound
+// to the prep launch, the last filter launch, the compaction and the tail launch (launch.h: a recorded event costs the stream
+// 2.9 us, a bound one nothing); ev_k0 is the END of the prep launch, i.e. the kernel statistics no longer count its 2-3 us.
+struct ChunkGeom {  // computed once per chunk
+    uint64_t n_words;  // 64-row words of the survivors' bitmap per column
+    uint32_t n_segs;   // 65 536-row segments (the narrow filter's per-segment counts)
+    uint32_t rpb;      // rows per block of the filter's launches
+};
+
+static ChunkGeom chunk_geom(const kgwas_scan* s, uint64_t n_rows) {
+    static const uint32_t rpb_env = (uint64_t)exp_int("KGWAS_COARSE_RPB", 0u);  // experiments
+    ChunkGeom g;
+    g.n_words = (n_rows + 63) / 64;
+    g.n_segs = (uint32_t)((g.n_words + 1023) / 1024);
+    if (s->narrow)
+        // (short blocks: three 4-wave blocks share a CU and a launch's block count is rarely a multiple of the
+        // 768 block slots, so long blocks leave CUs idle at the end of every launch: 4096 rows per block measured
+        // 3.4 ms per 100 M rows, 768 rows 3.0; the large chunks of a table that fills the HBM - 48-128 M rows - take
+        // 1280: 26.3 ms per 1.2 G rows against 27.1 with 768, 26.5 with 1024 or 1536)
+        g.rpb = n_rows >= (1u << 24) ? 1280u : n_rows >= (1u << 18) ? 768u : 256u;
+    else
+        // the operand tiles (up to 128 KB) are loaded into LDS once per block, so blocks are long where the launch still
+        // fills the chip four times over
+        g.rpb = n_rows >= (1u << 22) ? 4096u : n_rows >= (1u << 20) ? 2048u : 512u;
+    if (rpb_env) g.rpb = rpb_env;
+    return g;
+}
+
+// Stage 1: the chunk's arguments and the thresholds it is scored against (count_hist: see submit_sparse)
+static ScoreArgs chunk_args(kgwas_scan* s, Slot& sl, const uint64_t* d_rows, uint64_t n_rows, uint64_t first_row, bool count_hist) {
     ScoreArgs a;
     fill_args(s, a, d_rows, n_rows, first_row, !s->direct);
     a.cand = sl.d_cand;
@@ -363,213 +389,196 @@ void submit_sparse(kgwas_scan* s, Slot& sl, const uint64_t* d_rows, uint64_t n_r
                                  s->stream));
         a.thr = s->d_thr_redo.p;
     }
-    const bool use_coarse = s->coarse && count_hist;
-    // The chunk's four events - start (ev_k0), filter done (ev_mid), kernels done (ev_k1), counts on the host (ev_counts) - are bound
-    // to the prep launch, the last filter launch, the compaction and the tail launch (launch.h: a recorded event costs the stream
-    // 2.9 us, a bound one nothing); ev_k0 is the END of the prep launch, i.e. the kernel statistics no longer count its 2-3 us.
+    return a;
+}
+
+// Stage 2: the squeeze (if the rows are not read in place) and ONE launch for the chunk's counters, its survivors' bitmap
+// ([column][64-row word], which a popcount scan turns into row-ordered keys per column: no key list, no sort) and the narrow
+// filter's per-segment counts - inside the interval the statistics count as kernel time.
+static void launch_prep(kgwas_scan* s, Slot& sl, const ScoreArgs& a, const ChunkGeom& g, bool filtered) {
     if (!s->direct) {
         KGWAS_HIP(hipEventRecord(sl.ev_sq0, s->stream));  // (only read when rows are squeezed)
-        maybe_squeeze(s, d_rows, n_rows);
+        maybe_squeeze(s, a.file_rows, a.n_rows);
         KGWAS_HIP(hipEventRecord(sl.ev_k0, s->stream));
     }
-    {
-        // One launch for the chunk's counters, its survivors' bitmap ([column][64-row word], which a popcount scan turns
-        // into row-ordered keys per column: no key list, no sort) and the narrow filter's per-segment counts - inside the
-        // interval the statistics count as kernel time.
-        const uint64_t n_words = (n_rows + 63) / 64;
-        const uint32_t n_segs = (uint32_t)((n_words + 1023) / 1024);
-        // (narrow scans: the thresholds are raised here, by the first blocks of this launch, from everything the chunks
-        // before this one counted - not by a launch of its own behind each chunk)
-        PrepThr tu;
-        memset(&tu, 0, sizeof(tu));
-        if (use_coarse && s->narrow && s->hist_ready) {
-            tu.hist = s->d_hist.p;
-            tu.hist_base = s->d_hist_base.p;
-            tu.bins = HIST_BINS;
-            tu.topn = s->d_topn.p;
-            tu.thr_host = s->d_thr_host.p;
-            tu.thr = s->d_thr.p;
-        }
-        // (wide path: the key launches clear the words they list, so the bitmap is zeroed here only before a session's first
-        // chunk or after a chunk whose key launches were never queued - in full, the chunks' geometries differ)
-        const bool zero_bitmap = use_coarse && (s->narrow || !s->bitmap_clean);
-        const uint64_t zero_words = !zero_bitmap ? 0 : (s->narrow ? s->n_pheno * n_words : s->d_bitmap.n);
-        const auto prep = [&] {
-            return launch_chunk_prep(sl.d_cnt.p, (uint32_t)s->n_pheno, sl.d_tested.p, use_coarse ? s->d_key_count.p : nullptr,
-                                     zero_bitmap ? s->d_bitmap.p : nullptr, zero_words,
-                                     (use_coarse && s->narrow) ? s->d_bm_blocks.p : nullptr, (use_coarse && s->narrow) ? (uint32_t)s->n_pheno * n_segs : 0u,
-                                     tu, s->stream);
-        };
-        if (s->direct) KGWAS_HIP(bind_stop(sl.ev_k0, s->stream, prep));
-        else KGWAS_HIP(prep());
+    const bool narrow = filtered && s->narrow;
+    // (narrow scans: the thresholds are raised here, by the first blocks of this launch, from everything the chunks
+    // before this one counted - not by a launch of its own behind each chunk)
+    PrepThr tu;
+    memset(&tu, 0, sizeof(tu));
+    if (narrow && s->hist_ready) {
+        tu.hist = s->d_hist.p;
+        tu.hist_base = s->d_hist_base.p;
+        tu.bins = HIST_BINS;
+        tu.topn = s->d_topn.p;
+        tu.thr_host = s->d_thr_host.p;
+        tu.thr = s->d_thr.p;
     }
-    sl.used_coarse = use_coarse;
-    if (use_coarse) {
-        CoarseArgs c;
-        memset(&c, 0, sizeof(c));
-        c.src = a.src;
-        c.n_rows = n_rows;
-        c.S = a.S;
-        c.n_pheno = a.n_pheno;
-        c.min_count = a.min_count;
-        c.n_kgroups = s->n_kgroups;
-        const int cm = s->narrow ? 0 : pick_coarse_mode(s);
-        if (s->dbg_keep_surv) dbg_log_thresholds(s, a.thr, n_rows, first_row, s->narrow ? 2u : (uint32_t)cm);
-        const kgwas_scan::CoarseMode& M = s->cmode[cm];
-        sl.coarse_mode = cm;
-        sl.cand_est = (double)s->sum_topn * (double)n_rows / (double)std::max<uint64_t>(s->rows_submitted, 1);
-        c.n_slices = M.slices;
-        c.eg_max = M.eg_max;
-        c.rall_max = M.rall_max;
-        c.rmax_max = M.rmax_max;
-        c.thr = a.thr;
-        c.tested = a.tested;
-        static const uint32_t rpb_env = (uint64_t)exp_int("KGWAS_COARSE_RPB", 0u);  // experiments
-        const uint64_t n_words = (n_rows + 63) / 64;
-        if (s->narrow) {
-            NarrowArgs na;
-            memset(&na, 0, sizeof(na));
-            na.src = a.src;
-            na.n_rows = n_rows;
-            na.S = a.S;
-            na.n_pheno = a.n_pheno;
-            na.min_count = a.min_count;
-            na.n_kgroups = s->n_kgroups;
-            na.Bn = s->d_Bn.p;
-            na.cols = s->d_ncols.p;
-            na.thr = a.thr;
-            na.bitmap = s->d_bitmap.p;
-            na.words_per_col = n_words;
-            na.tested = a.tested;
-            na.pack1 = s->narrow_pack1 ? 1u : 0u;
-            na.seg_cnt = s->d_bm_blocks.p;
-            na.n_segs = (uint32_t)((n_words + 1023) / 1024);
-            // (rows of the same device buffer behind this chunk, when the rows are read in place: only a feed's last chunk needs
-            // the narrow filter's second, tiny launch)
-            na.slack_rows = s->direct ? s->slack_rows : 0;
-            // (short blocks: three 4-wave blocks share a CU and a launch's block count is rarely a multiple of the
-            // 768 block slots, so long blocks leave CUs idle at the end of every launch: 4096 rows per block measured
-            // 3.4 ms per 100 M rows, 768 rows 3.0; the large chunks of a table that fills the HBM - 48-128 M rows - take
-            // 1280: 26.3 ms per 1.2 G rows against 27.1 with 768, 26.5 with 1024 or 1536)
-            KGWAS_HIP(bind_stop(sl.ev_mid, s->stream, [&] { return launch_narrow(na, rpb_env ? rpb_env : (n_rows >= (1u << 24) ? 1280u : n_rows >= (1u << 18) ? 768u : 256u), s->stream); }));
+    // (wide path: the key launches clear the words they list, so the bitmap is zeroed here only before a session's first
+    // chunk or after a chunk whose key launches were never queued - in full, the chunks' geometries differ)
+    const bool zero_bitmap = filtered && (s->narrow || !s->bitmap_clean);
+    const uint64_t zero_words = !zero_bitmap ? 0 : (s->narrow ? s->n_pheno * g.n_words : s->d_bitmap.n);
+    const auto prep = [&] {
+        return launch_chunk_prep(sl.d_cnt.p, (uint32_t)s->n_pheno, sl.d_tested.p, filtered ? s->d_key_count.p : nullptr,
+                                 zero_bitmap ? s->d_bitmap.p : nullptr, zero_words, narrow ? s->d_bm_blocks.p : nullptr,
+                                 narrow ? (uint32_t)s->n_pheno * g.n_segs : 0u, tu, s->stream);
+    };
+    if (s->direct) KGWAS_HIP(bind_stop(sl.ev_k0, s->stream, prep));
+    else KGWAS_HIP(prep());
+}
+
+// What CoarseArgs, MxArgs and NarrowArgs have in common
+template <class A>
+static void fill_filter_args(A& x, const kgwas_scan* s, const ScoreArgs& a, const ChunkGeom& g) {
+    memset(&x, 0, sizeof(x));
+    x.src = a.src;
+    x.n_rows = a.n_rows;
+    x.S = a.S;
+    x.n_pheno = a.n_pheno;
+    x.min_count = a.min_count;
+    x.thr = a.thr;
+    x.bitmap = s->d_bitmap.p;
+    x.words_per_col = g.n_words;
+    x.tested = a.tested;
+}
+
+// Stage 3, one to four columns: the narrow filter; it counts its survivors per segment itself
+static void launch_filter_narrow(kgwas_scan* s, Slot& sl, const ScoreArgs& a, const ChunkGeom& g) {
+    NarrowArgs na;
+    fill_filter_args(na, s, a, g);
+    na.n_kgroups = s->n_kgroups;
+    na.Bn = s->d_Bn.p;
+    na.cols = s->d_ncols.p;
+    na.pack1 = s->narrow_pack1 ? 1u : 0u;
+    na.seg_cnt = s->d_bm_blocks.p;
+    na.n_segs = g.n_segs;
+    // (rows of the same device buffer behind this chunk, when the rows are read in place: only a feed's last chunk needs
+    // the narrow filter's second, tiny launch)
+    na.slack_rows = s->direct ? s->slack_rows : 0;
+    KGWAS_HIP(bind_stop(sl.ev_mid, s->stream, [&] { return launch_narrow(na, g.rpb, s->stream); }));
+}
+
+// Stage 3, wide: one launch per part of the operand set M - int8, or block-scaled with its operands resident or streamed
+template <class A>
+static void fill_part_args(A& x, const kgwas_scan::DeviceFilterSet& M, size_t pi) {
+    x.n_lgroups = M.plan.parts[pi].launch_groups();
+    x.n_slices = M.plan.slices;
+    x.Bq = reinterpret_cast<decltype(x.Bq)>(M.dev[pi].d_Bq.p);
+    x.cols = M.dev[pi].d_cols.p;
+    if (pi) x.tested = nullptr;  // every launch sees every row: one of them counts
+    x.eg_max = M.eg_max;
+    x.rall_max = M.rall_max;
+    x.rmax_max = M.rmax_max;
+}
+static void launch_filter_wide(kgwas_scan* s, Slot& sl, const ScoreArgs& a, const ChunkGeom& g, const kgwas_scan::DeviceFilterSet& M) {
+    s->bitmap_clean = false;  // (until the key launches are queued behind the filter)
+    const size_t n_parts = M.plan.parts.size();
+    for (size_t pi = 0; pi < n_parts; pi++) {
+        const FilterPart& fp = M.plan.parts[pi];
+        hipEvent_t stop = pi + 1 == n_parts ? (hipEvent_t)sl.ev_mid : nullptr;  // the last part ends the filter
+        if (M.plan.mx) {
+            MxArgs x;
+            fill_filter_args(x, s, a, g);
+            fill_part_args(x, M, pi);
+            x.n_full = M.plan.n_full;
+            x.n_quarter = M.plan.n_quarter;
+            x.s1_fp6 = M.plan.s1_fp6;
+            x.scale0 = M.scale0;
+            const auto filt = [&] { return fp.stream ? launch_mxs(x, fp.T, fp.ng, fp.stream - 1u, g.rpb, s->stream) : launch_mx(x, fp.T, g.rpb, s->stream); };
+            KGWAS_HIP(stop ? bind_stop(stop, s->stream, filt) : filt());
         } else {
-            s->bitmap_clean = false;  // (until the key launches are queued behind the filter)
-            c.bitmap = s->d_bitmap.p;
-            c.words_per_col = n_words;
-            // rows per block: the operand tiles (up to 128 KB) are loaded into LDS once per block, so blocks are long
-            // where the launch still fills the chip four times over
-            for (uint32_t pi = 0; pi < M.n_parts; pi++) {
-                const kgwas_scan::CoarsePart& Pt = M.part[pi];
-                c.n_lgroups = Pt.n_lgroups;
-                c.Bq = Pt.d_Bq.p;
-                c.cols = Pt.d_cols.p;
-                c.tested = pi == 0 ? a.tested : nullptr;  // every launch sees every row: one of them counts
-                const bool last_part = pi + 1u == M.n_parts;
-                const uint32_t rpb = rpb_env ? rpb_env : (n_rows >= (1u << 22) ? 4096u : n_rows >= (1u << 20) ? 2048u : 512u);
-                if (M.mx) {
-                    MxArgs x;
-                    memset(&x, 0, sizeof(x));
-                    x.src = c.src;
-                    x.n_rows = n_rows;
-                    x.S = c.S;
-                    x.n_pheno = c.n_pheno;
-                    x.min_count = c.min_count;
-                    x.n_full = M.mx_full;
-                    x.n_quarter = M.mx_quarter;
-                    x.n_lgroups = Pt.n_lgroups;
-                    x.n_slices = M.slices;
-                    x.s1_fp6 = M.mx_s1_fp6;
-                    x.scale0 = M.mx_scale0;
-                    x.Bq = reinterpret_cast<const uint8_t*>(Pt.d_Bq.p);
-                    x.cols = Pt.d_cols.p;
-                    x.thr = c.thr;
-                    x.bitmap = c.bitmap;
-                    x.words_per_col = c.words_per_col;
-                    x.tested = c.tested;
-                    x.eg_max = c.eg_max;
-                    x.rall_max = c.rall_max;
-                    x.rmax_max = c.rmax_max;
-                    const auto filt = [&] {
-                        return Pt.stream ? launch_mxs(x, Pt.T, Pt.ng, Pt.stream - 1u, rpb, s->stream) : launch_mx(x, Pt.T, rpb, s->stream);
-                    };
-                    if (last_part) KGWAS_HIP(bind_stop(sl.ev_mid, s->stream, filt));
-                    else KGWAS_HIP(filt());
-                } else {
-                    const auto filt = [&] { return launch_coarse(c, Pt.T, rpb, s->stream); };
-                    if (last_part) KGWAS_HIP(bind_stop(sl.ev_mid, s->stream, filt));
-                    else KGWAS_HIP(filt());
-                }
-            }
-            if (!M.n_parts) KGWAS_HIP(hipEventRecord(sl.ev_mid, s->stream));
+            CoarseArgs c;
+            fill_filter_args(c, s, a, g);
+            fill_part_args(c, M, pi);
+            c.n_kgroups = s->n_kgroups;
+            const auto filt = [&] { return launch_coarse(c, fp.T, g.rpb, s->stream); };
+            KGWAS_HIP(stop ? bind_stop(stop, s->stream, filt) : filt());
         }
-        a.tested = nullptr;  // counted by the filter
-        a.so_score = sl.d_so_score.p;
-        a.so_kmer = sl.d_so_kmer.p;
-        a.so_row = sl.d_so_row.p;
-        if (s->narrow) {
-            // one to four columns: keys in one launch (the filter has counted its survivors per segment), every survivor's
-            // record written in place by the re-score kernel - a chunk is five launches, not thirteen
-            KGWAS_HIP(launch_narrow_keys(s->d_bitmap.p, n_words, n_rows, (uint32_t)s->n_pheno, s->d_bm_blocks.p, s->d_surv_sorted.p, s->key_slots,
-                                         s->row_key_bits, s->d_surv_off.p, s->d_surv_cnt.p, s->d_key_count.p, s->d_tile_pref.p, sl.d_meta.p, sl.d_tested.p, s->stream));
-            if (s->dbg_keep_surv) dbg_log_survivors(s);
-            KGWAS_HIP(bind_stop(sl.ev_k1, s->stream, [&] { return launch_rescore_direct(a, s->d_surv_sorted.p, s->d_surv_off.p, s->d_surv_cnt.p, s->row_key_bits, s->d_tile_pref.p, s->stream); }));
-        } else {
-        KGWAS_HIP(launch_bitmap_keys(s->d_bitmap.p, n_words, n_rows, (uint32_t)s->n_pheno, s->d_bm_blocks.p, s->d_bm_mask.p, s->d_surv_sorted.p, s->key_slots,
+    }
+    if (!n_parts) KGWAS_HIP(hipEventRecord(sl.ev_mid, s->stream));
+}
+
+// Stage 4: the bitmap's bits as row-ordered keys, then the survivors' exact scores and the chunk's records (ev_k1)
+static void launch_keys_rescore(kgwas_scan* s, Slot& sl, ScoreArgs a, const ChunkGeom& g) {
+    a.tested = nullptr;  // counted by the filter
+    a.so_score = sl.d_so_score.p;
+    a.so_kmer = sl.d_so_kmer.p;
+    a.so_row = sl.d_so_row.p;
+    if (s->narrow) {
+        // one to four columns: keys in one launch (the filter has counted its survivors per segment), every survivor's
+        // record written in place by the re-score kernel - a chunk is five launches, not thirteen
+        KGWAS_HIP(launch_narrow_keys(s->d_bitmap.p, g.n_words, a.n_rows, (uint32_t)s->n_pheno, s->d_bm_blocks.p, s->d_surv_sorted.p, s->key_slots,
+                                     s->row_key_bits, s->d_surv_off.p, s->d_surv_cnt.p, s->d_key_count.p, s->d_tile_pref.p, sl.d_meta.p, sl.d_tested.p, s->stream));
+        if (s->dbg_keep_surv) dbg_log_survivors(s);
+        KGWAS_HIP(bind_stop(sl.ev_k1, s->stream, [&] { return launch_rescore_direct(a, s->d_surv_sorted.p, s->d_surv_off.p, s->d_surv_cnt.p, s->row_key_bits, s->d_tile_pref.p, s->stream); }));
+    } else {
+        KGWAS_HIP(launch_bitmap_keys(s->d_bitmap.p, g.n_words, a.n_rows, (uint32_t)s->n_pheno, s->d_bm_blocks.p, s->d_bm_mask.p, s->d_surv_sorted.p, s->key_slots,
                                      s->row_key_bits, s->d_surv_off.p, s->d_surv_cnt.p, s->d_key_count.p, s->d_tile_pref.p, s->stream));
         s->bitmap_clean = true;
         if (s->dbg_keep_surv) dbg_log_survivors(s);
-        a.so_score = sl.d_so_score.p;
-        a.so_kmer = sl.d_so_kmer.p;
-        a.so_row = sl.d_so_row.p;
         KGWAS_HIP(bind_stop(sl.ev_k1, s->stream, [&] {
             return launch_rescore(a, s->d_surv_sorted.p, s->d_surv_off.p, s->d_surv_cnt.p, s->row_key_bits, s->d_tile_pref.p,
                                   s->d_tile_cnt.p, s->d_tmp_score.p, s->d_key_count.p, sl.d_meta.p, s->stream);
         }));
-        }
-        s->st.score_launches++;
-    } else {
-        if (s->direct) KGWAS_HIP(hipEventRecord(sl.ev_k0, s->stream));  // (bound to nothing above: the prep launch of an exact-scorer chunk is not timed)
-        launch_score(s, a);
-        KGWAS_HIP(hipEventRecord(sl.ev_k1, s->stream));
     }
-    const bool fused_tail = use_coarse && s->narrow;  // thresholds: raised by the next chunk's prep launch; the tested count: in meta (launch_narrow_keys)
-    static const bool tail_kernel = !(exp_int("KGWAS_TAIL_KERNEL", 1) == 0);  // experiments: 0 = hipMemcpyAsync calls
-    const bool one_launch = use_coarse && tail_kernel && sl.h_meta_dev;
-    // wide path: the threshold update and the chunk's tail (counts, tested-row shards, thresholds into the mapped buffers) are one launch
-    const bool thr_and_tail = one_launch && s->hist_ready && !fused_tail;
-    if (s->hist_ready && !fused_tail && !thr_and_tail)  // raise the thresholds for whatever is queued next; no host round trip
+    s->st.score_launches++;
+}
+
+// Stage 5 of a filtered chunk: ONE launch (ev_counts) brings its counts and - for the columns in select mode, which bound
+// their pools with them - the device's thresholds as they stand behind it into the slot's mapped buffers; the record copies
+// follow on the copy stream once the control thread has read the counts (fetch_records).
+static void launch_tail(kgwas_scan* s, Slot& sl) {
+    const bool thr_too = s->lazy_any.load(std::memory_order_relaxed);
+    const uint32_t n_meta = (uint32_t)(2 * s->n_pheno + 4);
+    sl.tested_in_meta = s->narrow;
+    KGWAS_HIP(bind_stop(sl.ev_counts, s->stream, [&] {
+        // narrow scans - thresholds: raised by the next chunk's prep launch; the tested count: in meta (launch_narrow_keys)
+        if (s->narrow)
+            return launch_chunk_tail(sl.d_meta.p, n_meta, sl.h_meta_dev, sl.d_tested.p, 0u, sl.h_tested_dev, s->d_thr.p, thr_too ? (uint32_t)s->n_pheno : 0u,
+                                     sl.h_thr_dev, s->stream);
+        // wide path: the same launch also raises the thresholds for whatever is queued next (no host round trip) and brings the
+        // tested-row shards
+        return launch_thr_tail(s->d_hist.p, s->d_hist_base.p, HIST_BINS, s->d_topn.p, s->d_thr_host.p, s->d_thr.p, (uint32_t)s->n_pheno, sl.d_meta.p, n_meta,
+                               sl.h_meta_dev, sl.d_tested.p, (uint32_t)TESTED_SHARDS, sl.h_tested_dev, thr_too ? sl.h_thr_dev : nullptr, s->stream);
+    }));
+}
+
+// A chunk of the exact scorer (sessions without a filter, overflow re-runs): its candidate lists in the slot's mapped buffer,
+// the threshold update, and the counts by plain copies (ev_done: no record copies follow)
+static void launch_exact(kgwas_scan* s, Slot& sl, const ScoreArgs& a) {
+    if (s->direct) KGWAS_HIP(hipEventRecord(sl.ev_k0, s->stream));  // (bound to nothing: the prep launch of an exact-scorer chunk is not timed)
+    launch_score(s, a);
+    KGWAS_HIP(hipEventRecord(sl.ev_k1, s->stream));
+    if (s->hist_ready)  // raise the thresholds for whatever is queued next; no host round trip
         KGWAS_HIP(launch_thr_update(s->d_hist.p, s->d_hist_base.p, HIST_BINS, s->d_topn.p, s->d_thr_host.p, s->d_thr.p,
                                     (uint32_t)s->n_pheno, s->stream));
-    if (!fused_tail && !one_launch)
-        KGWAS_HIP(hipMemcpyAsync(sl.h_tested.p, sl.d_tested.p, TESTED_SHARDS * sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                                 s->stream));
-    sl.tested_in_meta = fused_tail;
-    if (thr_and_tail) {
-        const bool thr_too = s->lazy_any.load(std::memory_order_relaxed);
-        KGWAS_HIP(bind_stop(sl.ev_counts, s->stream, [&] {
-            return launch_thr_tail(s->d_hist.p, s->d_hist_base.p, HIST_BINS, s->d_topn.p, s->d_thr_host.p, s->d_thr.p, (uint32_t)s->n_pheno, sl.d_meta.p,
-                                   (uint32_t)(2 * s->n_pheno + 4), sl.h_meta_dev, sl.d_tested.p, (uint32_t)TESTED_SHARDS, sl.h_tested_dev,
-                                   thr_too ? sl.h_thr_dev : nullptr, s->stream);
-        }));
-    } else if (one_launch) {
-        // counts, tested-row shards and - for the columns in select mode, which bound their pools with them - the device's
-        // thresholds as they stand behind this chunk: one launch into the mapped buffers; the record copies follow on the copy
-        // stream once the control thread has read the counts (fetch_records)
-        const bool thr_too = s->lazy_any.load(std::memory_order_relaxed);
-        KGWAS_HIP(bind_stop(sl.ev_counts, s->stream, [&] {
-            return launch_chunk_tail(sl.d_meta.p, (uint32_t)(2 * s->n_pheno + 4), sl.h_meta_dev, sl.d_tested.p, fused_tail ? 0u : (uint32_t)TESTED_SHARDS,
-                                     sl.h_tested_dev, s->d_thr.p, thr_too ? (uint32_t)s->n_pheno : 0u, sl.h_thr_dev, s->stream);
-        }));
-    } else if (use_coarse) {
-        // the record copies follow on the copy stream once the control thread has read the counts (fetch_records)
-        KGWAS_HIP(hipMemcpyAsync(sl.h_meta.p, sl.d_meta.p, (2 * s->n_pheno + 4) * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-        // (columns in select mode prune their pools with the device's thresholds as they stand behind this chunk)
-        if (s->lazy_any.load(std::memory_order_relaxed))
-            KGWAS_HIP(hipMemcpyAsync(sl.h_thr.p, s->d_thr.p, s->n_pheno * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-        KGWAS_HIP(hipEventRecord(sl.ev_counts, s->stream));
+    KGWAS_HIP(hipMemcpyAsync(sl.h_tested.p, sl.d_tested.p, TESTED_SHARDS * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                             s->stream));
+    sl.tested_in_meta = false;
+    KGWAS_HIP(hipMemcpyAsync(sl.h_cnt.p, sl.d_cnt.p, s->n_pheno * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+    KGWAS_HIP(hipEventRecord(sl.ev_done, s->stream));
+}
+
+// count_hist: first (and only) scoring of these rows in the sparse phase -> their candidates feed the
+// device-side threshold histograms. Overflow re-runs must not count the same rows twice: they go to the exact scorer.
+void submit_sparse(kgwas_scan* s, Slot& sl, const uint64_t* d_rows, uint64_t n_rows, uint64_t first_row,
+                   bool count_hist) {
+    const bool filtered = s->coarse && count_hist;
+    const ChunkGeom g = chunk_geom(s, n_rows);
+    const ScoreArgs a = chunk_args(s, sl, d_rows, n_rows, first_row, count_hist);
+    launch_prep(s, sl, a, g, filtered);
+    sl.used_coarse = filtered;
+    if (filtered) {
+        const int cm = s->narrow ? 0 : pick_coarse_mode(s);
+        if (s->dbg_keep_surv) dbg_log_thresholds(s, a.thr, n_rows, first_row, s->narrow ? 2u : (uint32_t)cm);
+        sl.coarse_mode = cm;
+        sl.cand_est = (double)s->sum_topn * (double)n_rows / (double)std::max<uint64_t>(s->rows_submitted, 1);
+        if (s->narrow) launch_filter_narrow(s, sl, a, g);
+        else launch_filter_wide(s, sl, a, g, s->fset[cm]);
+        launch_keys_rescore(s, sl, a, g);
+        launch_tail(s, sl);
     } else {
-        KGWAS_HIP(hipMemcpyAsync(sl.h_cnt.p, sl.d_cnt.p, s->n_pheno * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-        KGWAS_HIP(hipEventRecord(sl.ev_done, s->stream));
+        launch_exact(s, sl, a);
     }
     sl.rows = d_rows;
     sl.first_row = first_row;
@@ -672,17 +681,13 @@ void wait_event(kgwas_scan* s, hipEvent_t ev) {
     s->st.gpu_wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
 }
 
-// The ring has run full while the columns' logs refer to its records (ring_keep). Called by the control thread when every
-// published chunk is replayed (no worker is inside a column): the logs take copies, and the ring is recycled from here on -
-// free up to the end of the last replayed chunk; chunks that are fetched but not yet published keep their records where
-// they are and are copied into the logs when their turn comes.
+// The ring has run full while the columns' logs refer to its records (RecordRing::keep). Called by the control thread when
+// every published chunk is replayed (no worker is inside a column): the logs take copies, and the ring recycles from here on.
 void ring_to_recycling(kgwas_scan* s, uint64_t replayed) {
     for (uint64_t j = 0; j < s->n_pheno; j++)
         if (s->lazy[j].on) s->lazy[j].detach();
-    s->ring_keep.store(false, std::memory_order_release);
-    s->ring_tail = replayed ? s->slot[(size_t)((replayed - 1) % (uint64_t)s->n_slots)].ring_end : s->ring_feed_start;
-    s->ring_freed = replayed;
-    if (s->trace) fprintf(stderr, "[kgwas t=%.3f] record ring full: logs detached, ring recycles from %zu (head %zu of %zu)\n", s->t_ms(), s->ring_tail, s->ring_head, s->ring_size);
+    s->rr.to_recycling(replayed, replayed ? s->slot_of(replayed - 1).ring_end : 0);
+    if (s->trace) fprintf(stderr, "[kgwas t=%.3f] record ring full: logs detached, ring recycles from %zu (head %zu of %zu)\n", s->t_ms(), s->rr.tail(), s->rr.head(), s->rr.size());
 }
 
 // Coarse chunk: wait for its counts, then order the copy of exactly that many candidate records (three arrays) from
@@ -694,45 +699,12 @@ bool fetch_records(kgwas_scan* s, Slot& sl, uint64_t seq) {
     const uint32_t n = sl.h_meta.p[2 * s->n_pheno];
     const uint32_t n_surv = sl.h_meta.p[2 * s->n_pheno + 1];
     const bool copy = n && n_surv <= s->key_slots;
-    {
-        // give back what the replay has finished with (chunks are replayed, hence freed, in order); before this slot's
-        // ring_end is overwritten below: its previous chunk is among them
-        const uint64_t rep = s->seq_replayed.load(std::memory_order_acquire);
-        if (s->ring_keep.load(std::memory_order_relaxed)) s->ring_freed = rep;  // (the logs refer to the records: nothing is given back)
-        while (s->ring_freed < rep) {
-            s->ring_tail = s->slot[(size_t)(s->ring_freed % (uint64_t)s->n_slots)].ring_end;
-            s->ring_freed++;
-        }
-        // empty: start over at the bottom - but only when every chunk fetched before this one has been freed: a fetched,
-        // not yet replayed chunk without records (or one that overflowed) carries a ring_end taken from the old head,
-        // and freeing it later would move the tail back over records placed at the bottom in the meantime
-        if (!s->ring_keep.load(std::memory_order_relaxed) && s->ring_tail == s->ring_head && s->ring_freed == seq) s->ring_head = s->ring_tail = 0;
-    }
-    if (copy) {
-        const size_t need = ((size_t)n * 20 + 63) / 64 * 64;
-        size_t at;
-        if (s->ring_keep.load(std::memory_order_relaxed)) {  // linear: [0, head) is referred to by the columns' logs
-            if (s->ring_size - s->ring_head < need) return false;  // (the caller lets the replay catch up, then ring_to_recycling)
-            at = s->ring_head;
-        } else if (s->ring_head >= s->ring_tail) {  // used part does not wrap (or the ring is empty)
-            if (s->ring_size - s->ring_head >= need)
-                at = s->ring_head;
-            else if (s->ring_tail > need)  // wrap: the bytes up to the end stay unused until this chunk is freed
-                at = 0;
-            else
-                return false;
-        } else {
-            if (s->ring_tail - s->ring_head > need)
-                at = s->ring_head;
-            else
-                return false;
-        }
-        sl.so_score = reinterpret_cast<double*>(s->ring.p + at);
-        sl.so_kmer = reinterpret_cast<uint64_t*>(s->ring.p + at + (size_t)n * 8);
-        sl.so_row = reinterpret_cast<uint32_t*>(s->ring.p + at + (size_t)n * 16);
-        s->ring_head = at + need;
-    }
-    sl.ring_end = s->ring_head;
+    // (before this slot's ring_end is overwritten below: its previous chunk is among those given back)
+    s->rr.give_back(s->seq_replayed.load(std::memory_order_acquire), [s](uint64_t q) { return s->slot_of(q).ring_end; });
+    const size_t at = s->rr.place(copy ? n : 0, seq);
+    if (at == RecordRing::NO_ROOM) return false;
+    if (copy) sl.so = record_ptrs(s->ring.p, at, n);
+    sl.ring_end = s->rr.head();
     if (!s->narrow && n_surv > s->key_slots)  // the list overflowed (the chunk is redone by the exact scorer): plan the next chunks for what it saw
         s->infl_obs[sl.coarse_mode] = std::min(256.0, std::max(s->infl_obs[sl.coarse_mode], 1.25 * (double)n_surv / std::max(sl.cand_est, 1.0)));
     else if (!s->narrow && n >= 1024)
@@ -745,13 +717,12 @@ bool fetch_records(kgwas_scan* s, Slot& sl, uint64_t seq) {
     static const char* rc_env = opt_str("KGWAS_RECORD_COPY");
     const bool by_memcpy = rc_env ? strcmp(rc_env, "memcpy") == 0 : !s->streamed_feed;
     if (copy && !by_memcpy) {
-        uint8_t* dev_at = s->ring_dev + (reinterpret_cast<uint8_t*>(sl.so_score) - s->ring.p);
-        KGWAS_HIP(launch_records_to_host(sl.d_so_score.p, sl.d_so_kmer.p, sl.d_so_row.p, n, reinterpret_cast<double*>(dev_at),
-                                         reinterpret_cast<uint64_t*>(dev_at + (size_t)n * 8), reinterpret_cast<uint32_t*>(dev_at + (size_t)n * 16), s->copy_stream));
+        const RecordPtrs d = record_ptrs(s->ring_dev, at, n);
+        KGWAS_HIP(launch_records_to_host(sl.d_so_score.p, sl.d_so_kmer.p, sl.d_so_row.p, n, d.score, d.kmer, d.row, s->copy_stream));
     } else if (copy) {
-        KGWAS_HIP(hipMemcpyAsync(sl.so_score, sl.d_so_score.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s->copy_stream));
-        KGWAS_HIP(hipMemcpyAsync(sl.so_row, sl.d_so_row.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, s->copy_stream));
-        KGWAS_HIP(hipMemcpyAsync(sl.so_kmer, sl.d_so_kmer.p, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, s->copy_stream));
+        KGWAS_HIP(hipMemcpyAsync(sl.so.score, sl.d_so_score.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s->copy_stream));
+        KGWAS_HIP(hipMemcpyAsync(sl.so.row, sl.d_so_row.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, s->copy_stream));
+        KGWAS_HIP(hipMemcpyAsync(sl.so.kmer, sl.d_so_kmer.p, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, s->copy_stream));
     }
     KGWAS_HIP(hipEventRecord(sl.ev_done, s->copy_stream));
     return true;

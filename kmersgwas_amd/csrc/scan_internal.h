@@ -1,7 +1,8 @@
 // scan_internal.h — the association-scan session's internals shared by scan_host.cpp (CPU topology, heaps), scan_gpu.cpp
 // (chunk submission: kernels, thresholds, record copies), scan_replay.cpp (streaming replay + the feed loop),
 // scan_plan.cpp (a session's plan and the operand sets of its filters, on the host), scan_create.cpp (session set-up) and
-// scan_api.cpp (the C ABI). Not a public header: the boundary is include/kgwas.h.
+// scan_api.cpp (the C ABI); the replay pool is pool.h, the record ring's offsets and policy record_ring.h. Not a public header: the
+// boundary is include/kgwas.h.
 //
 // The association-scan session: pass 1 of associate_kmers (src/associate_kmers.cpp:99-148)
 // re-designed around the GPU.
@@ -49,166 +50,10 @@
 #include "device.h"
 #include "ingest.h"
 #include "kernels.h"
+#include "pool.h"
+#include "record_ring.h"
 
 namespace kgwas {
-
-// Minimal persistent worker pool: parallel_for over phenotype columns. The caller does not take part: it
-// sleeps until the workers are done, so exactly size() threads are busy (sized to the CPU quota).
-class Pool {
-   public:
-    // cpus: optional CPU to pin worker i to (empty = leave placement to the scheduler).
-    explicit Pool(unsigned n, const std::vector<std::vector<int>>& cpus = {})
-        : stop_(false), gen_(0), n_items_(0) {
-        if (n < 1) n = 1;
-        for (unsigned i = 0; i < n; i++) {
-            const std::vector<int> mine = i < cpus.size() ? cpus[i] : std::vector<int>();
-            try {
-                th_.emplace_back([this, i, mine] {
-                    kgwas_name_this_thread("kgwas-replay");
-                    if (!mine.empty()) {
-                        cpu_set_t set;
-                        CPU_ZERO(&set);
-                        for (int c : mine)
-                            if (c >= 0 && c < CPU_SETSIZE) CPU_SET(c, &set);
-                        (void)pthread_setaffinity_np(pthread_self(), sizeof(set), &set);
-                    }
-                    loop(i);
-                });
-            } catch (const std::system_error&) {
-                // no more threads to be had: the pool is the workers that exist (items are claimed, not assigned, so any
-                // number of workers runs them all); with none at all the session cannot be built
-                if (th_.empty()) throw;
-                break;
-            }
-        }
-    }
-    ~Pool() {
-        {
-            std::unique_lock<std::mutex> lk(mu_);
-            stop_ = true;
-            gen_++;
-        }
-        cv_.notify_all();
-        for (auto& t : th_) t.join();
-    }
-    // Static assignment: item i always runs on worker i % size(), so a phenotype column's heap
-    // (~320 KB at N = 10001) stays in one core's cache from chunk to chunk.
-    void parallel_for(size_t n, const std::function<void(size_t)>& fn) {
-        if (n == 0) return;
-        start(n, fn);
-        wait();
-        rethrow();
-    }
-    // An item that throws (an allocation that fails) ends its worker's turn; the first such exception is kept until the next
-    // start() and rethrown here: by parallel_for itself, and by callers of start()/wait() once they are on their normal path.
-    void rethrow() {
-        std::exception_ptr e;
-        {
-            std::unique_lock<std::mutex> lk(mu_);
-            e = err_;
-            err_ = nullptr;
-        }
-        if (e) std::rethrow_exception(e);
-    }
-    // The two halves of parallel_for: start() hands the items out and returns, wait() blocks until every ITEM is done - not
-    // until every worker has looked in: on a shared host a worker that was asleep may get its CPU milliseconds late, and its
-    // items are long done by the others (they are claimed, not assigned) - the dense fill of a headline step, 1.4 ms of work,
-    // took 6-9 ms in one step of twenty on such boxes while wait() counted workers. Between the two the workers run on their own
-    // (the streaming replay: items are worker loops that end when told to). fn must stay alive until wait() returns; one start
-    // at a time.
-    void start(size_t n, const std::function<void(size_t)>& fn) {
-        std::unique_lock<std::mutex> lk(mu_);
-        // (a worker of the previous start that woke late may still be walking the claim flags - it finds nothing - before they
-        // are reset: workers enter run() under mu_, so none slips in behind this check)
-        while (in_run_.load(std::memory_order_acquire) != 0) {
-            lk.unlock();
-            __builtin_ia32_pause();
-            lk.lock();
-        }
-        fn_ = &fn;
-        n_items_ = n;
-        if (claimed_.size() < n) claimed_ = std::vector<std::atomic<uint8_t>>(n);
-        for (size_t i = 0; i < n; i++) claimed_[i].store(0, std::memory_order_relaxed);
-        left_.store(n, std::memory_order_relaxed);
-        err_ = nullptr;
-        done_.store(n == 0 ? 1 : 0, std::memory_order_relaxed);
-        gen_.fetch_add(1, std::memory_order_release);
-        lk.unlock();
-        cv_.notify_all();
-    }
-    void wait(bool spin = true) {
-        for (int sp = 0; spin && sp < 20000; sp++) {  // replays take a few ms at most: spin before sleeping
-            if (done_.load(std::memory_order_acquire)) break;
-            __builtin_ia32_pause();
-        }
-        std::unique_lock<std::mutex> lk(mu_);
-        done_cv_.wait(lk, [this] { return done_.load(std::memory_order_acquire) != 0; });
-    }
-    size_t size() const { return th_.size(); }
-    bool finished() const { return done_.load(std::memory_order_acquire) != 0; }  // every started item has run
-
-   private:
-    // Own items first, in increasing order; then take whatever nobody has started yet, from the far end
-    // (with 101 columns on 16 workers the five workers that own a seventh column give it away to a worker
-    // that is done with its six). An item runs exactly once, on one thread; one that throws (an allocation that fails) is
-    // done all the same, and the first such exception is kept for rethrow().
-    void item(size_t i) {
-        try {
-            (*fn_)(i);
-        } catch (...) {
-            std::unique_lock<std::mutex> lk(mu_);
-            if (!err_) err_ = std::current_exception();
-        }
-        if (left_.fetch_sub(1, std::memory_order_acq_rel) == 1) {
-            std::unique_lock<std::mutex> lk(mu_);
-            done_.store(1, std::memory_order_release);
-            done_cv_.notify_all();
-        }
-    }
-    void run(size_t me) {
-        const size_t T = th_.size();
-        for (size_t i = me; i < n_items_; i += T)
-            if (!claimed_[i].exchange(1, std::memory_order_acq_rel)) item(i);
-        for (size_t i = n_items_; i-- > 0;)
-            if (!claimed_[i].load(std::memory_order_relaxed) && !claimed_[i].exchange(1, std::memory_order_acq_rel)) item(i);
-    }
-    void loop(size_t me) {
-        uint64_t seen = 0;
-        for (;;) {
-            // Chunks arrive every few milliseconds while a scan is running: spin briefly before
-            // sleeping so the wake-up does not cost a futex round trip per worker per chunk.
-            bool got = false;
-            for (int spin = 0; spin < 4000; spin++) {
-                if (gen_.load(std::memory_order_acquire) != seen) {
-                    got = true;
-                    break;
-                }
-                __builtin_ia32_pause();
-            }
-            {
-                std::unique_lock<std::mutex> lk(mu_);
-                if (!got) cv_.wait(lk, [&] { return gen_.load(std::memory_order_acquire) != seen; });
-                seen = gen_.load(std::memory_order_acquire);
-                if (stop_) return;
-                in_run_.fetch_add(1, std::memory_order_acq_rel);  // (under mu_: start() looks at it there)
-            }
-            run(me);
-            in_run_.fetch_sub(1, std::memory_order_acq_rel);
-        }
-    }
-    std::vector<std::thread> th_;
-    std::mutex mu_;
-    std::condition_variable cv_, done_cv_;
-    bool stop_;
-    std::atomic<uint64_t> gen_;
-    std::atomic<int> done_{0};
-    std::atomic<int> in_run_{0};      // workers between the claim of their first item and their last look at the flags
-    std::atomic<size_t> left_{0};     // items of the current start that have not finished
-    std::vector<std::atomic<uint8_t>> claimed_;
-    const std::function<void(size_t)>* fn_ = nullptr;
-    size_t n_items_;
-    std::exception_ptr err_;  // the first exception an item of the current start() threw (guarded by mu_)
-};
 
 // scan_host.cpp: one CPU per replay worker near the GPU; the CPUs the process may really use (cgroup quota)
 std::vector<std::vector<int>> pick_replay_cpus(unsigned n, int device);
@@ -272,7 +117,7 @@ struct LazyCol {
     bool have_bound = false;
     uint32_t n_prunes = 0;
     // the LOG: segments in row order. A sparse chunk's records stay where the GPU put them - in the session's pinned record
-    // ring, which is not recycled while columns refer to it (fetch_records) - and the log holds a reference (sc != null);
+    // ring, which is not recycled while columns refer to it (fetch_records, record_ring.h) - and the log holds a reference (sc != null);
     // single records (dense chunks' rows, absorbed shards, exact-scorer candidates) and, once the ring has run full and gone
     // back to recycling, the chunks' records as well are copied into the three owned arrays (sc == null: [off, off + n) there).
     struct Seg {
@@ -400,9 +245,7 @@ struct Slot {
     // control thread orders on the copy stream once the counts are known (exactly `total` records per array);
     // h_meta: [0, P) candidates per column, [P, 2P) their offsets, [2P] total, [2P + 1] survivor keys emitted,
     // [2P + 2, 2P + 3] narrow scans: the chunk's MAC-passing rows (64 bits; instead of a copy of h_tested)
-    double* so_score = nullptr;   // host copies: a piece of the session's pinned record ring (fetch_records)
-    uint64_t* so_kmer = nullptr;
-    uint32_t* so_row = nullptr;
+    RecordPtrs so{};              // host copies: a piece of the session's pinned record ring (fetch_records)
     size_t ring_end = 0;          // ring offset behind this chunk's records (where the ring is free again once it is replayed)
     DevBuf<double> d_so_score;
     DevBuf<uint64_t> d_so_kmer;
@@ -425,6 +268,58 @@ struct Slot {
     const uint64_t* rows = nullptr;
     uint64_t first_row = 0, n_rows = 0;
     bool squeezed = false, busy = false;
+};
+
+// ---- scan_plan.cpp: a session's plan (no device calls); the session keeps the filter sets it made (kgwas_scan::fset)
+struct FilterOpts {  // every switch the plan reads (env.h), read once per session
+    int coarse_mx = -1;            // KGWAS_COARSE_MX: 0 int8, 1 block-scaled, -1 by plan (unset or set but empty)
+    int coarse_slices = -1;        // KGWAS_COARSE_SLICES: 1 | 2 that set alone, 0 set to another value, -1 unset
+    bool mx_s1_fp6 = false;        // KGWAS_MX_S1=6
+    int mxs = 1, mxs_form = 0;     // KGWAS_MXS, KGWAS_MXS_FORM
+    bool narrow = true;            // KGWAS_NARROW (0: false)
+    bool debug_residuals = false;  // KGWAS_DEBUG_RESIDUALS
+    bool debug_survivors = false;  // KGWAS_DEBUG_SURVIVORS
+    // experiments: KGWAS_COARSE_MIXED, KGWAS_COARSE_NOSPLIT (split = false), KGWAS_NARROW_PACK, KGWAS_CAP_MULT (-1: by
+    // filter), KGWAS_CAP_BUDGET, KGWAS_MODE_K (pick_coarse_mode)
+    bool mixed = true, split = true, narrow_pack = true;
+    long long cap_mult = -1, cap_budget = 4ll << 20;
+    double mode_k = 0.09;
+};
+struct ScanShape {
+    uint64_t S, L, W_m, W_f, P, max_topn;
+    bool direct, finite, chain_safe;
+};
+// One launch of an operand set: `groups` LDS groups of T operand tiles over the columns [j0, j0 + n), cper per group. The
+// streaming form (stream = 1 + launch_mxs's form): `groups` column groups of T column tiles, ng of them per grid block.
+struct FilterPart {
+    uint64_t j0, n, cper;
+    uint32_t T;
+    uint64_t groups;
+    uint32_t stream = 0, ng = 1;
+    uint32_t launch_groups() const { return (uint32_t)(groups / ng); }  // a launch's n_lgroups (streaming form: operand groups = grid blocks per row block)
+};
+// An operand set of the filter: set[0] = one slice per column (half the matrix work, ~2.5 survivors per candidate), set[1] = two
+// slices (~1). Both may be resident; each chunk picks one (pick_coarse_mode).
+struct FilterSet {  // ScanPlan::set[slices - 1], then kgwas_scan::fset[slices - 1].plan; slices = 0: not built
+    bool mx = false;  // block-scaled (score_mx.hip: FP6 (+ FP4 / FP6) slices; parts[].T = column tiles), else int8
+    uint32_t slices = 0, s1_fp6 = 0;
+    uint32_t n_full = 0, n_quarter = 0, n_steps = 0;  // block-scaled: 512-sample groups, 128-sample quarters, K = 128 steps
+    // Full LDS groups first; columns that would only fill part of another full-size group go into a second launch
+    // with as few tiles as they need (201 columns at 2048 samples: 3 groups x 4 tiles + 1 tile instead of 4 x 4).
+    std::vector<FilterPart> parts;  // one or two
+    uint32_t tile_slices = 0;     // operand tiles a row is multiplied with, all parts and groups
+    double tile_slices_eq = 0;    // block-scaled: the same in int8 tile-slice equivalents (0: tile_slices as it is): what pick_coarse_mode compares
+};
+struct ScanPlan {
+    uint32_t kernel = 0;  // the exact scorer
+    bool coarse = false, narrow = false, narrow_pack1 = false;
+    bool use_mx = false;      // the block-scaled family (else int8, perhaps with a block-scaled two-slice set: mixed)
+    bool keep_resid = false;  // KGWAS_DEBUG_RESIDUALS on a filter session
+    bool keep_surv = false;   // KGWAS_DEBUG_SURVIVORS on a filter session
+    uint32_t n_kgroups = 0;
+    uint64_t chunk_max = 0, dense_rows = 0, dense_chunk = 0;
+    uint32_t cap = 0;
+    FilterSet set[2];
 };
 
 }  // namespace kgwas
@@ -462,28 +357,18 @@ struct kgwas_scan {
     // coarse int8 filter (sparse phase)
     bool coarse = false;
     uint32_t n_kgroups = 0;  // 512-sample groups
-    // Operand sets of the filter: mode[0] = one int8 slice per column (half the matrix work, ~2.5 survivors per
-    // candidate), mode[1] = two slices (~1). Both may be resident; each chunk picks one (pick_coarse_mode).
-    struct CoarsePart {  // one launch of the filter: n_lgroups LDS groups of T operand tiles over a range of columns
-        uint32_t T = 0, n_lgroups = 0;
-        uint32_t stream = 0;          // operand-streaming form (score_mxs.hip): 1 + launch_mxs's `form`; T = column tiles per column group
-        uint32_t ng = 1;              // ... column groups per block (n_lgroups then counts operand groups of ng column groups)
-        DevBuf<int8_t> d_Bq;
-        DevBuf<CoarseCol> d_cols;
-    };
-    struct CoarseMode {
+    // The planner's operand sets (scan_plan.cpp) and what upload_filters adds to each: its parts' operands on the device, the
+    // block scale of slice 0 and the row error term's maxima over the columns (kernels.h)
+    struct DeviceFilterSet {
+        FilterSet plan;
         bool ready = false;
-        // block-scaled filter (score_mx.hip): FP6 (+ FP4 / FP6) slices instead of int8 ones; part[].T = column tiles
-        bool mx = false;
-        uint32_t mx_full = 0, mx_quarter = 0, mx_s1_fp6 = 0, mx_scale0 = 0;
-        uint32_t slices = 0, n_parts = 0;
-        uint32_t tile_slices = 0;  // operand tiles a row is multiplied with, all parts and groups
-        double tile_slices_eq = 0;  // the same in int8 tile-slice equivalents (0: tile_slices as it is): what pick_coarse_mode compares
-        float eg_max = 0, rall_max = 0, rmax_max = 0;  // row error term, maxima over the columns (kernels.h)
-        // Full LDS groups first; columns that would only fill part of another full-size group go into a second launch
-        // with as few tiles as they need (201 columns at 2048 samples: 3 groups x 4 tiles + 1 tile instead of 4 x 4).
-        CoarsePart part[2];
-    } cmode[2];
+        uint32_t scale0 = 0;
+        float eg_max = 0, rall_max = 0, rmax_max = 0;
+        struct {
+            DevBuf<int8_t> d_Bq;
+            DevBuf<CoarseCol> d_cols;
+        } dev[2];  // of plan.parts[i]
+    } fset[2];
     // dense start overlapped with the first sparse chunks: thresholds selected on the device (launch_dense_select)
     DevBuf<double> d_sel;
     PinBuf<double> h_sel;
@@ -519,24 +404,15 @@ struct kgwas_scan {
     DevBuf<unsigned long long> d_pat_cnt;  // how many
     uint64_t pat_upper = 0;                // host-side upper bound of that count (rows fed)
     Slot slot[MAX_SLOTS];
-    // Host copies of the coarse chunks' candidate records: ONE pinned ring, a chunk takes exactly its 20 B x candidates
-    // when its counts are known and gives them back when it is replayed (FIFO). Slots used to own worst-case buffers
-    // (cap x P records each), which capped the chunks in flight at 12 for 201 columns: with host and GPU level the GPU
-    // then idled while the host digested the ramp.
+    Slot& slot_of(uint64_t seq) { return slot[(size_t)(seq % (uint64_t)n_slots)]; }  // its previous chunk was replayed n_slots chunks ago
+    // Host copies of the coarse chunks' candidate records: ONE pinned ring; its offsets and policy: record_ring.h
     PinBuf<uint8_t> ring;
     uint8_t* ring_dev = nullptr;  // the ring's address on the device (mapped)
     bool streamed_feed = false;   // the rows of the current feed arrive over PCIe while it runs (ingest_run): fetch_records
     double* h_dense_dev = nullptr;  // device addresses of h_dense / h_n1 / h_kmer (mapped)
     uint32_t* h_n1_dev = nullptr;
     uint64_t* h_kmer_dev = nullptr;
-    size_t ring_size = 0, ring_head = 0, ring_tail = 0;  // used: [tail, head) circularly; head == tail: empty
-    // Columns in select mode keep their sparse chunks' records where the GPU wrote them (LazyCol::Seg): while this is set the
-    // ring is filled linearly and nothing is given back - from one kgwas_scan_reset to the next, across feeds. Should it run full
-    // (ring_to_recycling, scan_gpu.cpp), the logs take copies of what they refer to and the ring recycles as it does for
-    // sessions that replay every column; from then on the workers copy each chunk's records into the logs.
-    std::atomic<bool> ring_keep{false};
-    size_t ring_feed_start = 0;  // ring_head when the current feed began
-    uint64_t ring_freed = 0;                              // chunks (of this feed) whose records have been given back
+    RecordRing rr;
     Slot redo;  // coarse mode: the only slot with exact-scorer candidate records (synchronous overflow re-runs)
     int n_slots = MAX_SLOTS;  // as many as fit 1 GiB of mapped pinned candidate memory (at least 4)
     // dense mode
@@ -682,52 +558,7 @@ void add_replay_stats(kgwas_scan* s, const ReplayAcc& a);
 void replay_worker(kgwas_scan* s, size_t w);
 void feed_device_impl(kgwas_scan* s, const uint64_t* d_rows, uint64_t n_rows, uint64_t first_row);
 // ---- scan_plan.cpp: a session's plan and the host side of its operands (no device calls)
-struct FilterOpts {  // every switch the plan reads (env.h), read once per session
-    int coarse_mx = -1;            // KGWAS_COARSE_MX: 0 int8, 1 block-scaled, -1 by plan (unset or set but empty)
-    int coarse_slices = -1;        // KGWAS_COARSE_SLICES: 1 | 2 that set alone, 0 set to another value, -1 unset
-    bool mx_s1_fp6 = false;        // KGWAS_MX_S1=6
-    int mxs = 1, mxs_form = 0;     // KGWAS_MXS, KGWAS_MXS_FORM
-    bool narrow = true;            // KGWAS_NARROW (0: false)
-    bool debug_residuals = false;  // KGWAS_DEBUG_RESIDUALS
-    bool debug_survivors = false;  // KGWAS_DEBUG_SURVIVORS
-    // experiments: KGWAS_COARSE_MIXED, KGWAS_COARSE_NOSPLIT (split = false), KGWAS_NARROW_PACK, KGWAS_CAP_MULT (-1: by
-    // filter), KGWAS_CAP_BUDGET, KGWAS_MODE_K (pick_coarse_mode)
-    bool mixed = true, split = true, narrow_pack = true;
-    long long cap_mult = -1, cap_budget = 4ll << 20;
-    double mode_k = 0.09;
-};
 FilterOpts read_filter_opts();
-struct ScanShape {
-    uint64_t S, L, W_m, W_f, P, max_topn;
-    bool direct, finite, chain_safe;
-};
-// One launch of an operand set: `groups` LDS groups of T operand tiles over the columns [j0, j0 + n), cper per group. The
-// streaming form (stream = 1 + launch_mxs's form): `groups` column groups of T column tiles, ng of them per grid block.
-struct FilterPart {
-    uint64_t j0, n, cper;
-    uint32_t T;
-    uint64_t groups;
-    uint32_t stream = 0, ng = 1;
-};
-struct FilterSet {  // kgwas_scan::cmode[slices - 1]; slices = 0: not built
-    bool mx = false;  // block-scaled (else int8)
-    uint32_t slices = 0, s1_fp6 = 0;
-    uint32_t n_full = 0, n_quarter = 0, n_steps = 0;  // block-scaled: 512-sample groups, 128-sample quarters, K = 128 steps
-    std::vector<FilterPart> parts;  // one or two
-    uint32_t tile_slices = 0;     // operand tiles a row is multiplied with, all parts and groups
-    double tile_slices_eq = 0;    // block-scaled: the same in int8 tile-slice equivalents
-};
-struct ScanPlan {
-    uint32_t kernel = 0;  // the exact scorer
-    bool coarse = false, narrow = false, narrow_pack1 = false;
-    bool use_mx = false;      // the block-scaled family (else int8, perhaps with a block-scaled two-slice set: mixed)
-    bool keep_resid = false;  // KGWAS_DEBUG_RESIDUALS on a filter session
-    bool keep_surv = false;   // KGWAS_DEBUG_SURVIVORS on a filter session
-    uint32_t n_kgroups = 0;
-    uint64_t chunk_max = 0, dense_rows = 0, dense_chunk = 0;
-    uint32_t cap = 0;
-    FilterSet set[2];
-};
 // Every plan decision; throws the plan's argument errors. resid: the session's dbg_resid, sized here when kept (the
 // one-slice test fills form 0).
 ScanPlan plan_scan(const kgwas_scan_params& p, const ScanShape& sh, const FilterOpts& o, const std::vector<float>& Y,

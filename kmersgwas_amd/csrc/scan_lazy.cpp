@@ -12,7 +12,7 @@
 //   * its LOG: every record the column was shipped (the dense chunks' MAC-passing rows, then the sparse chunks' candidates)
 //     in row order; what an exact replay would need, should it come to that. A sparse chunk's records are not copied: they
 //     stay where the GPU wrote them, in the session's pinned record ring, and the log holds a reference (LazyCol::Seg) - the
-//     ring is filled linearly and not recycled while logs refer to it (scan_internal.h, ring_keep; sized for a pass's records:
+//     ring is filled linearly and not recycled while logs refer to it (record_ring.h, keep; sized for a pass's records:
 //     390 MB at 101 columns, 775 MB at 201). If it runs full after all, the logs take copies (detach) and the ring recycles;
 //     from then on every chunk's records are copied into the logs (three memcpys), as all of them were before.
 //   * its POOL: (score bits, k-mer, row) of the records that can still be among the N largest. It is DERIVED from the log:
@@ -336,9 +336,8 @@ void lazy_reset(kgwas_scan* s) {
     s->n_unselected.store(0);
     s->lazy_pushes.store(0);
     s->tie_check_rows = 4ull << 20;
-    // nothing refers to the record ring any more; a session in select mode fills it linearly (scan_internal.h, ring_keep)
-    s->ring_head = s->ring_tail = 0;
-    s->ring_keep.store(s->lazy_enabled && s->coarse && !(opt_int("KGWAS_LOG_BY_REF", 1) == 0), std::memory_order_release);
+    // nothing refers to the record ring any more; a session in select mode fills it linearly (record_ring.h, keep)
+    s->rr.reset(s->lazy_enabled && s->coarse && !(opt_int("KGWAS_LOG_BY_REF", 1) == 0));
 }
 
 // BestHeap::lowest() / full() of a column in select mode without giving it a heap: a full heap's minimum is the N-th largest
@@ -378,7 +377,7 @@ void lazy_materialize_all(kgwas_scan* s) {
     s->pool->parallel_for(s->n_pheno, [&](size_t j) { pushes += lazy_materialize(s, j); });
     s->st.heap_pushes += pushes.load();
     s->lazy_any.store(false, std::memory_order_relaxed);
-    s->ring_keep.store(false, std::memory_order_release);  // (no log is left: the next feed recycles the ring)
+    s->rr.logs_released();  // (the next feed recycles the ring)
     refresh_full(s);
 }
 

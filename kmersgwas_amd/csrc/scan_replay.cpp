@@ -41,7 +41,7 @@ void replay_group(kgwas_scan* s, Slot& sl, size_t g, ReplayAcc& acc) {
         constexpr int MK = BestHeap::MAX_LOCKSTEP;
         Cur cols[MK];
         size_t n_cols = 0;
-        const bool by_ref = s->ring_keep.load(std::memory_order_acquire);  // (constant while chunks are being replayed)
+        const bool by_ref = s->rr.keep(std::memory_order_acquire);  // (constant while chunks are being replayed)
         // A look at a column's pool costs ~0.1 ms, and the replay it may set off ~4 ms x the share of the feed that is over. A
         // worker with nothing else waiting has that time beside the GPU; one that has fallen behind - few threads for many
         // columns: the host is the scan's bottleneck whenever its replays happen - would only add the looks to its backlog
@@ -58,7 +58,7 @@ void replay_group(kgwas_scan* s, Slot& sl, size_t g, ReplayAcc& acc) {
                 LazyCol& L = s->lazy[j];
                 uint64_t tb;
                 memcpy(&tb, &sl.h_thr.p[j], 8);
-                L.take_chunk(sl.so_score + o, sl.so_kmer + o, sl.so_row + o, n, row0, tb, by_ref);
+                L.take_chunk(sl.so.score + o, sl.so.kmer + o, sl.so.row + o, n, row0, tb, by_ref);
                 nc += n;
                 // behind chunks the control thread picked (flag_tie_check) the pool is looked at for a tie: a column whose N
                 // largest scores are not distinct will need the exact replay, and that costs less now, beside the GPU, than at
@@ -66,7 +66,7 @@ void replay_group(kgwas_scan* s, Slot& sl, size_t g, ReplayAcc& acc) {
                 if (look && L.full() && L.ties_now()) local += lazy_materialize(s, j);
                 continue;
             }
-            cols[n_cols++] = Cur{sl.so_score + o, sl.so_kmer + o, sl.so_row + o, 0, n, &s->heaps[j], j};
+            cols[n_cols++] = Cur{sl.so.score + o, sl.so.kmer + o, sl.so.row + o, 0, n, &s->heaps[j], j};
         }
         // The records were just written by the GPU (no CPU cache holds them) and the replay walks several short
         // streams at once, more than the hardware prefetchers track: pull them in up front, a line at a time.
@@ -536,12 +536,7 @@ void feed_device_impl(kgwas_scan* s, const uint64_t* d_rows, uint64_t n_rows, ui
     s->seq_submitted.store(0);
     s->seq_published.store(0);
     s->seq_replayed.store(0);
-    if (s->ring_keep.load(std::memory_order_relaxed))
-        s->ring_tail = 0;  // (the records of earlier feeds stay: the columns' logs refer to them)
-    else
-        s->ring_head = s->ring_tail = 0;
-    s->ring_feed_start = s->ring_head;
-    s->ring_freed = 0;
+    s->rr.begin_feed();
     // the session's own column groups (a feed may have split some, split_group)
     for (size_t g = 0; g < s->n_groups0 + (size_t)s->n_pheno; g++) {
         if (g < s->n_groups0)
@@ -559,6 +554,22 @@ void feed_device_impl(kgwas_scan* s, const uint64_t* d_rows, uint64_t n_rows, ui
     for (uint64_t j = 0; j < s->n_pheno; j++) s->col_popped[j].store(0, std::memory_order_relaxed);
     s->final_feed.store(s->final_feed_next, std::memory_order_release);
     s->final_feed_next = false;
+    // The next sparse chunk goes to the GPU (the dense fill's pre-submission and the main loop)
+    const auto submit_next = [&](bool during_fill) {
+        const uint64_t c = std::min<uint64_t>(next_sparse_chunk(s), n_rows - pos);
+        Slot& sl = s->slot_of(sub);
+        s->slot_left[(size_t)(&sl - s->slot)].store((uint32_t)s->n_pheno, std::memory_order_release);  // (columns: groups may be split)
+        s->slack_rows = n_rows - pos - c;
+        flag_tie_check(sl, pos, c);
+        submit_sparse(s, sl, d_rows + pos * stride, c, first_row + pos, /*count_hist=*/true);
+        s->slack_rows = 0;
+        s->rows_submitted += c;
+        sub++;
+        s->seq_submitted.store(sub, std::memory_order_release);
+        pos += c;
+        if (s->trace && during_fill) fprintf(stderr, "[kgwas t=%.3f] presubmitted chunk %llu (%llu rows), fill %s\n", s->t_ms(), (unsigned long long)(sub - 1), (unsigned long long)c, s->pool->finished() ? "done" : "running");
+        if (s->trace && !during_fill) fprintf(stderr, "[kgwas t=%.3f] submit chunk %llu (%llu rows)\n", s->t_ms(), (unsigned long long)(sub - 1), (unsigned long long)c);
+    };
     try {
         for (;;) {
             if (pos < n_rows && !s->all_full) {  // dense phase: until every heap is full
@@ -581,25 +592,11 @@ void feed_device_impl(kgwas_scan* s, const uint64_t* d_rows, uint64_t n_rows, ui
                     // every heap will be full after these rows, and no score is a NaN (the heap's order with NaNs in it is
                     // not a total one: plain path)
                     const bool early = s->h_sel_info.p[0] >= s->max_topn && s->h_sel_info.p[1] == 0;
-                    const auto submit_one = [&]() {
-                            const uint64_t cs = std::min<uint64_t>(next_sparse_chunk(s), n_rows - pos);
-                            const size_t si = (size_t)(sub % (uint64_t)s->n_slots);
-                            s->slot_left[si].store((uint32_t)s->n_pheno, std::memory_order_release);  // (columns: groups may be split)
-                            s->slack_rows = n_rows - pos - cs;
-                            flag_tie_check(s->slot[si], pos, cs);
-                            submit_sparse(s, s->slot[si], d_rows + pos * stride, cs, first_row + pos, /*count_hist=*/true);
-                            s->slack_rows = 0;
-                            s->rows_submitted += cs;
-                            sub++;
-                            s->seq_submitted.store(sub, std::memory_order_release);
-                            pos += cs;
-                            if (s->trace) fprintf(stderr, "[kgwas t=%.3f] presubmitted chunk %llu (%llu rows), fill %s\n", s->t_ms(), (unsigned long long)(sub - 1), (unsigned long long)cs, s->pool->finished() ? "done" : "running");
-                    };
                     if (early && pos < n_rows) {
                         // the first sparse chunk goes out before the dense scores are in host memory (their copy runs beside it)
                         s->sel_valid = true;
                         s->rows_submitted = std::max(s->rows_submitted, s->rows_done + c);
-                        submit_one();
+                        submit_next(/*during_fill=*/true);
                         s->sel_valid = false;
                     }
                     wait_dense_copy(s);
@@ -608,13 +605,13 @@ void feed_device_impl(kgwas_scan* s, const uint64_t* d_rows, uint64_t n_rows, ui
                         s->rows_submitted = std::max(s->rows_submitted, s->rows_done + c);
                         // GPU work for the duration of the fill: at least two chunks, more only while the workers are
                         // still pushing (a submission costs this thread 0.1-0.2 ms; the replay starts when both are done)
-                        while (pos < n_rows && sub < std::min<uint64_t>(depth, 12) && (sub < 2 || !s->pool->finished())) submit_one();
+                        while (pos < n_rows && sub < std::min<uint64_t>(depth, 12) && (sub < 2 || !s->pool->finished())) submit_next(/*during_fill=*/true);
                         s->sel_valid = false;
                         // While the workers go on pushing: order the record copies of the chunks whose counts have come in,
                         // so the first chunks' records are in host memory when the fill ends (the copy of chunk 0 - 28 MB
                         // at 101 columns - used to start only then: 0.7 ms in which sixteen workers had nothing to replay).
                         while (!s->pool->finished() && cpy < sub) {
-                            Slot& sl = s->slot[(size_t)(cpy % (uint64_t)s->n_slots)];
+                            Slot& sl = s->slot_of(cpy);
                             if (sl.used_coarse && hipEventQuery(sl.ev_counts) != hipSuccess) {
                                 // (sleeping, not spinning: this thread is not pinned and may share a CPU with a pinned worker)
                                 std::this_thread::sleep_for(std::chrono::microseconds(20));
@@ -644,18 +641,7 @@ void feed_device_impl(kgwas_scan* s, const uint64_t* d_rows, uint64_t n_rows, ui
             const uint64_t rep_now = replayed();
             if (pos < n_rows && sub - rep_now < depth) {
                 start_async();
-                const uint64_t c = std::min<uint64_t>(next_sparse_chunk(s), n_rows - pos);
-                const size_t si = (size_t)(sub % (uint64_t)s->n_slots);  // its previous chunk was replayed n_slots chunks ago
-                s->slot_left[si].store((uint32_t)s->n_pheno, std::memory_order_release);  // (columns: groups may be split)
-                s->slack_rows = n_rows - pos - c;
-                flag_tie_check(s->slot[si], pos, c);
-                submit_sparse(s, s->slot[si], d_rows + pos * stride, c, first_row + pos, /*count_hist=*/true);
-                s->slack_rows = 0;
-                if (s->trace) fprintf(stderr, "[kgwas t=%.3f] submit chunk %llu (%llu rows)\n", s->t_ms(), (unsigned long long)sub, (unsigned long long)c);
-                s->rows_submitted += c;
-                sub++;
-                s->seq_submitted.store(sub, std::memory_order_release);
-                pos += c;
+                submit_next(/*during_fill=*/false);
             }
             // Coarse chunks hand their records over in two steps: counts first (compute stream), then exactly that many
             // records on the copy stream, ordered here as soon as the counts are in - before waiting for an older
@@ -663,15 +649,14 @@ void feed_device_impl(kgwas_scan* s, const uint64_t* d_rows, uint64_t n_rows, ui
             const bool can_submit = pos < n_rows && sub - rep_now < depth;
             // (exact-scorer chunks have no counts step and no ev_counts: querying a null event fails AND leaves the error
             // for the next hipGetLastError - the next kernel launch then reports "invalid resource handle")
-            if (cpy < sub && ((cpy == pub && !can_submit) || !s->slot[(size_t)(cpy % (uint64_t)s->n_slots)].used_coarse ||
-                              hipEventQuery(s->slot[(size_t)(cpy % (uint64_t)s->n_slots)].ev_counts) == hipSuccess)) {
-                if (fetch_records(s, s->slot[(size_t)(cpy % (uint64_t)s->n_slots)], cpy)) {
+            if (cpy < sub && ((cpy == pub && !can_submit) || !s->slot_of(cpy).used_coarse || hipEventQuery(s->slot_of(cpy).ev_counts) == hipSuccess)) {
+                if (fetch_records(s, s->slot_of(cpy), cpy)) {
                     if (s->trace) fprintf(stderr, "[kgwas t=%.3f] counts of chunk %llu in, record copy ordered\n", s->t_ms(), (unsigned long long)cpy);
                     cpy++;
                     continue;
                 }
                 // the record ring is full: publish what is fetched; if all of that is published, wait for the replay
-                if (pub == cpy && s->ring_keep.load(std::memory_order_relaxed)) {
+                if (pub == cpy && s->rr.keep()) {
                     wait_replayed(pub);
                     if (s->rp_failed.load(std::memory_order_acquire)) break;
                     ring_to_recycling(s, pub);
@@ -683,9 +668,9 @@ void feed_device_impl(kgwas_scan* s, const uint64_t* d_rows, uint64_t n_rows, ui
                     continue;
                 }
             }
-            if (pub < cpy && (!can_submit || hipEventQuery(s->slot[(size_t)(pub % (uint64_t)s->n_slots)].ev_done) == hipSuccess)) {
+            if (pub < cpy && (!can_submit || hipEventQuery(s->slot_of(pub).ev_done) == hipSuccess)) {
                 // publish the oldest chunk the GPU still owes
-                Slot& sl = s->slot[(size_t)(pub % (uint64_t)s->n_slots)];
+                Slot& sl = s->slot_of(pub);
                 wait_event(s, sl.ev_done);  // records and counts are in host memory
                 if (chunk_complete(s, sl)) {
                     if (s->trace) fprintf(stderr, "[kgwas t=%.3f] publish chunk %llu\n", s->t_ms(), (unsigned long long)pub);

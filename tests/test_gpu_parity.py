@@ -929,6 +929,44 @@ def test_record_ring_wraps_and_fills(monkeypatch, by_ref):
     scan.close()
 
 
+def test_record_ring_across_reset(monkeypatch):
+    """The ring's state across reset(): a session whose one-chunk ring ran full in a scan of two feeds (logs detached, ring
+    recycling) is reset and scans the same rows again in one feed - the ring is empty again and refers-to-records mode is
+    restored, so the second scan is a fresh session's."""
+    S, P, topn = 128, 8, 500
+    rows = random_table(200_000, S, seed=78)
+    col = np.arange(S, dtype=np.uint64)
+    Y = phenotypes(S, P - 1, seed=6)  # P columns
+    mac = onp.min_count(S, 0.05, 5)
+    exp = ob.associate(rows, S, col, Y, topn, mac)
+    monkeypatch.setenv("KGWAS_RING_BYTES", "1")  # clamped to one chunk's worst case + 4 KB
+    scan = kg.AssociationScan(S, col, Y, topn, mac, chunk_rows=8192)
+    fresh = kg.AssociationScan(S, col, Y, topn, mac, chunk_rows=8192)
+    monkeypatch.delenv("KGWAS_RING_BYTES")
+    scan.feed_host(rows[:80_000], 0)
+    scan.feed_host(rows[80_000:], 80_000)
+    scan.finish()
+    _check_topn(scan, exp, P)
+    st = scan.stats()
+    print("first scan: candidates", st["candidates"], "ring bytes", (2 * topn + 4096) * P * 20 + 4096)
+    assert st["rows_tested"] == exp["tested"]
+    # more record bytes than the ring holds went through it
+    assert st["candidates"] * 20 > (2 * topn + 4096) * P * 20 + 4096
+    fresh.feed_host(rows, 0)
+    fresh.finish()
+    _check_topn(fresh, exp, P)
+    scan.reset()
+    scan.feed_host(rows, 0)
+    scan.finish()
+    _check_topn(scan, exp, P)
+    st2 = scan.stats()
+    print("after reset: columns_selected", st2["columns_selected"], "fresh", fresh.stats()["columns_selected"])
+    assert st2["rows_tested"] == exp["tested"]
+    assert st2["columns_selected"] == fresh.stats()["columns_selected"] > 0  # (all 8 on this table: its scores have no ties)
+    fresh.close()
+    scan.close()
+
+
 @pytest.mark.parametrize("S_f,S,reorder", [(241, 241, False), (300, 257, True), (64, 64, False), (1030, 1030, False)])
 def test_pattern_counter(S_f, S, reorder):
     """--pattern_counter: distinct hash_presence_absence_pattern values over the tested rows, with many
