@@ -241,6 +241,7 @@ typedef struct kgwas_scan_stats {
  * and struct kgwas_lmm_skip_stats, kgwas_lmm_test_table_multi_skip, kgwas_lmm_run_table_multi_skip (lmm_lrt --pattern_skip),
  * and structs kgwas_proxy_record, kgwas_proxy_stats, kgwas_kmers_ld_proxies, kgwas_proxy_kmers_run (proxy_kmers).
  * and structs kgwas_locate_record, kgwas_locate_stats, kgwas_locate_kmers_bases, kgwas_locate_kmers_run (locate_kmers).
+ * and structs kgwas_fetch_record, kgwas_fetch_stats, kgwas_fetch_reads_bases, kgwas_fetch_reads_run (fetch_reads).
  * Those came after version 15 without a bump: a caller that may meet an older version-15 library probes for them by symbol
  * (dlsym, or hasattr on a ctypes handle). */
 #define KGWAS_ABI_VERSION 15
@@ -865,7 +866,7 @@ int kgwas_clump_kmers_run(const char* table_base, uint32_t kmer_len, const char*
 
 /* ------------------------------------------------------------------------------------
  * proxy_kmers: every k-mer of the table in LD with a lead k-mer - the step after clump_kmers, which ends with one lead per
- * signal: the k-mers that travel with a lead are the ones to assemble or map (locate_kmers, below). A tool of this project's own. A row of the table
+ * signal: the k-mers that travel with a lead are the ones to assemble (fetch_reads, below) or map (locate_kmers, below). A tool of this project's own. A row of the table
  * is a PROXY of a lead iff the pair is linked by clump_kmers' predicate (above: num * 1000000 >= r2_millionths * den, den > 0,
  * in 128-bit integers on the device). Every (lead, row) pair is tested, the lead's own row included: a non-constant lead finds
  * itself, a constant lead finds nothing, a complement is a proxy (phase -).
@@ -961,6 +962,67 @@ int kgwas_locate_kmers_bases(const void* bases, uint64_t n_bytes, int on_device,
                              uint32_t mismatches, int32_t device, kgwas_locate_record* records_out, uint64_t cap, uint64_t* n_out);
 int kgwas_locate_kmers_run(const char* reference_path, const char* kmers_path, uint32_t kmer_len, uint32_t mismatches, uint64_t max_per_kmer,
                            int32_t device, const char* out_path, kgwas_locate_stats* st);
+
+/* ------------------------------------------------------------------------------------
+ * fetch_reads: the reads of an accession that contain listed k-mers - the other step after proxy_kmers: an associated k-mer that
+ * lands nowhere in the reference (an insertion, a gene the reference lacks) is followed up by pulling the reads that hold it and
+ * its proxies out of an accession's read set and assembling them locally. A tool of this project's own.
+ *
+ * Definitions. The BASE STREAM is bytes; A C G T in either case are bases. A READ is the bytes between one '\n' and the next: read
+ * r ends at the r-th newline; reads are numbered from 0 over the whole stream, and an empty run is a read with no window. Any byte
+ * other than a base or a newline ('N', '\r', ...) lies inside its read and breaks windows; it does not end the read. A WINDOW at
+ * offset p of a read is k consecutive base bytes of that read; its code is locate_kmers': A=0, C=1, G=2, T=3, two bits per base,
+ * first base most significant. QUERY i has the code f_i as spelled and r_i reverse-complemented; two queries with the same
+ * canonical code (kgwas_kmer_encode) are the same k-mer and are refused, so a window hits at most one query. STRAND 0: the window
+ * equals f_i (a palindrome counts as strand 0); strand 1: it equals r_i. Per read: n_hits is the number of its windows that hit,
+ * first_pos the 0-based byte offset in the read of the first hit window, kmer and strand those of that window. A read is KEPT iff
+ * n_hits >= min_hits (min_hits >= 1). Its record is {read, n_hits, first_pos, kmer, strand, pad = 0}, 24 bytes; records come in
+ * ascending read, the same bytes in every run. kmer_windows[i] is the number of hit windows of query i over all reads, kept or not.
+ *
+ * kgwas_fetch_reads_bases: the array level. bases[n_bytes] is host memory (there is no on-device form: the pieces are cut at
+ * newlines, which the host finds); codes[n_kmers] the f_i. The queries' canonical codes are sorted once and stay on the device; the
+ * stream passes in pieces of at most P bytes that each end behind a newline (a last run without a newline gets one in the pinned
+ * copy; the next piece's copy runs beside this piece's kernels), the hits are reduced per read on the device, and the kept reads'
+ * records come back in rounds of the record buffer's size. *n_out gets the count of all records; the first min(cap, *n_out) are
+ * written to records_out. kmer_windows_out[n_kmers] may be NULL. Checked before any device call (KGWAS_ERR_ARG): null codes or
+ * n_out, null bases with n_bytes > 0, null records_out with cap > 0, kmer_len outside 1..31, min_hits == 0, n_kmers of 0 or above
+ * 2^20, a code with bits at or above 2 * kmer_len, two queries that are the same k-mer. No HIP device -> KGWAS_ERR_DEVICE. A read
+ * that does not fit a piece (its bytes and its newline) is KGWAS_ERR_ARG and names its length. KGWAS_FETCH_PIECE_BYTES (P, default
+ * and at most 2^25), KGWAS_FETCH_RECORDS (records of the device buffer, default 2^20) and KGWAS_FETCH_PREFILTER (0: no presence
+ * bitmap ahead of the list search; records and counts are the same either way) are the tests' hooks.
+ * kgwas_fetch_reads_run: the tool. reads_path (and mates_path, may be NULL) are FASTQ or FASTA in plain text, "-" for standard
+ * input, by kgwas_count_kmers_run's rules and texts: the first byte is '@' or '>' (else KGWAS_ERR_FORMAT "<path>: neither FASTA nor
+ * FASTQ"); a FASTQ record is four lines with '@' and '+' at the head of its first and third line; a FASTA record's sequence is the
+ * concatenation of its lines; a trailing '\r' is dropped for the stream; a missing final newline is fine; a file that cannot be
+ * opened -> KGWAS_ERR_IO "can't open file: <path>". Reads enter the stream in file order. With mates, record i of the two files is
+ * a pair: mate 1 is read 2 i of the stream, mate 2 read 2 i + 1; the files must have the same format, unequal record counts are
+ * KGWAS_ERR_FORMAT naming the longer file, and a pair is kept iff either mate is kept. kmers_path is read as kgwas_locate_kmers_run
+ * reads it (a plain list, an .assoc.txt, a clump_kmers or a proxy_kmers output), with the same refusals, before the reads are
+ * opened. A UNIT is a read or, with mates, a pair; it belongs to the k-mer of its first kept read. Per k-mer the first
+ * max_reads_per_kmer units in input order are written, the rest only counted (0: no limit). Outputs: out_prefix + ".fastq" or
+ * ".fasta" (with mates "_1." and "_2."): the written units' records, their bytes exactly as the input has them, in input order, a
+ * final newline added if the last record lacked one. out_prefix + ".reads.tsv": the header "read mate n_hits first_pos kmer strand"
+ * (tabs) and one line per kept read of a written unit: the record's name up to the first blank, mate 1 or 2 (0 without mates),
+ * n_hits, the 1-based first_pos, the query's text, + or -. out_prefix + ".log.txt": the inputs, one line "kmer <text> <units
+ * written> <windows>" per query, the counters and the times. No output file exists after a refusal. *st (may be NULL) is written
+ * when the call succeeds: reads and bases of the stream, windows_tested, kmers, windows_hit (the sum of kmer_windows), reads_kept,
+ * reads_written (the kept reads of written units), pairs_written (0 without mates), kmers_without_read (queries with no unit
+ * written), drain_rounds.
+ * ---------------------------------------------------------------------------------- */
+typedef struct kgwas_fetch_record {
+    uint64_t read;
+    uint32_t n_hits, first_pos, kmer;
+    uint8_t strand, pad[3];
+} kgwas_fetch_record;
+typedef struct kgwas_fetch_stats {
+    uint64_t reads, bases, windows_tested, kmers, windows_hit, reads_kept, reads_written, pairs_written, kmers_without_read, drain_rounds;
+    double parse_ms, copy_ms, kernel_ms, total_ms; /* the reader thread's parsing, the pieces' copies and the kernels (events), all */
+} kgwas_fetch_stats;
+int kgwas_fetch_reads_bases(const void* bases, uint64_t n_bytes, const uint64_t* codes, uint64_t n_kmers, uint32_t kmer_len, uint32_t min_hits,
+                            int32_t device, kgwas_fetch_record* records_out, uint64_t cap, uint64_t* n_out,
+                            uint64_t* kmer_windows_out /* [n_kmers], may be NULL */);
+int kgwas_fetch_reads_run(const char* reads_path, const char* mates_path /* may be NULL */, const char* kmers_path, uint32_t kmer_len,
+                          uint32_t min_hits, uint64_t max_reads_per_kmer, int32_t device, const char* out_prefix, kgwas_fetch_stats* st);
 
 /* ------------------------------------------------------------------------------------
  * Seeded synthetic table rows: kmer = row + 1, per-row frequency q/256 with

@@ -53,6 +53,7 @@ SYMBOLS = [
     "kgwas_r2_millionths", "kgwas_kmers_ld", "kgwas_clump_kmers_run",
     "kgwas_kmers_ld_proxies", "kgwas_proxy_kmers_run",
     "kgwas_locate_kmers_bases", "kgwas_locate_kmers_run",
+    "kgwas_fetch_reads_bases", "kgwas_fetch_reads_run",
     "kgwas_synth_rows_device", "kgwas_synth_rows_host",
 ]
 
@@ -92,6 +93,20 @@ class LocateStats(C.Structure):
     """kgwas_locate_stats"""
     _fields_ = [(k, C.c_uint64) for k in ("contigs", "bases", "windows_tested", "kmers", "hits_found", "hits_kept", "kmers_without_hit",
                                           "kmers_with_one_hit", "drain_rounds")] + [(k, C.c_double) for k in ("parse_ms", "copy_ms", "kernel_ms", "total_ms")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class FetchRecord(C.Structure):
+    """kgwas_fetch_record"""
+    _fields_ = [("read", C.c_uint64), ("n_hits", C.c_uint32), ("first_pos", C.c_uint32), ("kmer", C.c_uint32), ("strand", C.c_uint8), ("pad", C.c_uint8 * 3)]
+
+
+class FetchStats(C.Structure):
+    """kgwas_fetch_stats"""
+    _fields_ = [(k, C.c_uint64) for k in ("reads", "bases", "windows_tested", "kmers", "windows_hit", "reads_kept", "reads_written", "pairs_written",
+                                          "kmers_without_read", "drain_rounds")] + [(k, C.c_double) for k in ("parse_ms", "copy_ms", "kernel_ms", "total_ms")]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -323,6 +338,9 @@ lib.kgwas_proxy_kmers_run.argtypes = [C.c_char_p, _u32, C.c_char_p, C.c_char_p, 
 # locate_kmers: added after ABI version 15 without a bump
 lib.kgwas_locate_kmers_bases.argtypes = [_vp, _u64, C.c_int, _vp, _u64, _u32, _u32, _i32, _vp, _u64, C.POINTER(C.c_uint64)]
 lib.kgwas_locate_kmers_run.argtypes = [C.c_char_p, C.c_char_p, _u32, _u32, _u64, _i32, C.c_char_p, C.POINTER(LocateStats)]
+# fetch_reads: added after ABI version 15 without a bump
+lib.kgwas_fetch_reads_bases.argtypes = [_vp, _u64, _vp, _u64, _u32, _u32, _i32, _vp, _u64, C.POINTER(C.c_uint64), _vp]
+lib.kgwas_fetch_reads_run.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, _u32, _u32, _u64, _i32, C.c_char_p, C.POINTER(FetchStats)]
 lib.kgwas_build_table.argtypes = [C.c_char_p, _pstr, _pstr, _u64, _u32, _i32, C.c_char_p, _pu64]
 lib.kgwas_list_kmers.argtypes = [_pstr, _u64, _u32, _u64, C.c_double, _i32, C.c_char_p, _pu64]
 lib.kgwas_count_kmers_files.argtypes = [_pstr, _u64, _u32, _u64, _u64, _i32, C.c_char_p, _pu64]

@@ -27,6 +27,7 @@
 #include "common.h"
 #include "device.h"
 #include "kernels.h"
+#include "reads_source.h"
 #include "sorted_file_io.h"
 
 using namespace kgwas;
@@ -134,45 +135,11 @@ struct Uploader {
 };
 
 // ---- the files --------------------------------------------------------------------------------------------------------------------
-struct Source {
-    std::string path;
-    Fd fd;
-    char fmt = 0;  // '>' FASTA, '@' FASTQ, 0: an empty file
-};
-
-size_t read_some(int fd, char* dst, size_t n, const std::string& path) {
-    for (;;) {
-        const ssize_t r = ::read(fd, dst, n);
-        if (r < 0 && errno == EINTR) continue;
-        if (r < 0) throw Error(KGWAS_ERR_IO, "read error on " + path + ": " + std::strerror(errno));
-        return (size_t)r;
-    }
-}
-
-void open_source(Source& s, const char* path) {
-    s.path = path;
-    if (s.path == "-") {
-        s.fd.fd = ::dup(0);
-        s.path = "standard input";
-    } else
-        s.fd.fd = ::open(path, O_RDONLY);
-    if (s.fd.fd < 0) throw Error(KGWAS_ERR_IO, "can't open file: " + s.path);
-    char c;
-    if (read_some(s.fd.fd, &c, 1, s.path) == 0) return;
-    if (c != '>' && c != '@') throw Error(KGWAS_ERR_FORMAT, s.path + ": neither FASTA nor FASTQ");
-    s.fmt = c;
-}
-
 struct Chunk {
     std::vector<char> data;  // whole records
     const Source* src = nullptr;
     bool last = false;  // the file ends with it
 };
-
-inline size_t line_end(const char* d, size_t from, size_t n) {
-    const void* e = memchr(d + from, '\n', n - from);
-    return e ? (size_t)(static_cast<const char*>(e) - d) : n;
-}
 
 void convert(Chunk& c, Uploader& up) {
     char* d = c.data.data();

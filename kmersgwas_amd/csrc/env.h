@@ -52,6 +52,10 @@
 //   KGWAS_LD_TIMING=1          kgwas_kmers_ld and kgwas_kmers_ld_proxies print their kernels' time (events around them alone) on stderr
 //   KGWAS_PROXY_PIECE_ROWS=n   (test hook) rows per piece of kgwas_kmers_ld_proxies / proxy_kmers (default: up to 2^18, about 64 MiB of rows)
 //   KGWAS_PROXY_RECORDS=n      (test hook) records of their device record buffer (default 2^20); a piece with more is drained in rounds
+//   KGWAS_FETCH_PIECE_BYTES=n  (test hook) bytes per piece of kgwas_fetch_reads_* (default and at most 2^25); a piece is whole reads
+//   KGWAS_FETCH_RECORDS=n      (test hook) records of their device record buffer (default 2^20); a piece with more is drained in rounds
+//   KGWAS_FETCH_PREFILTER=0|1  (test hook) without / with the presence bitmap ahead of the list search; the results are the same
+//   KGWAS_FETCH_TIMING=1       kgwas_fetch_reads_bases prints its kernels' and copies' time (events) on stderr
 //   KGWAS_DEBUG_SLOW_WORKER=w:pct:min_us   (test hook) slows one replay worker down
 //   KGWAS_DEBUG_RESIDUALS=1    (test hook) sessions keep their filters' quantisation residuals (kgwas_scan_debug_residuals)
 //   KGWAS_DEBUG_SURVIVORS=1    (test hook) filter sessions log every filtered chunk's thresholds and survivors, synchronously

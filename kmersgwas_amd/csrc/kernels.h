@@ -469,4 +469,31 @@ hipError_t launch_locate_write(const uint8_t* bases, uint64_t n_buf, uint64_t n_
                                const LocateList& L, const uint32_t* boff, uint32_t tile0, uint32_t tile1, uint32_t win_lo, uint32_t cap, uint64_t pos0,
                                LocateRecord* rec, hipStream_t st);
 
+// fetch_reads (fetch_kernels.hip). A piece is bases[0, n), n <= LOCATE_MAX_PIECE, whole reads that each end with
+// '\n'; n_reads is the count of its newlines, which the host knows. Q is ONE LocateList of the queries' canonical codes (codes ==
+// keys), ids[i] = query << 1 | (the canonical code is the reverse complement of the query as spelled).
+//  filter: filter[FETCH_FILTER_WORDS] = the presence bitmap of Q's keys.
+//  mark:   marks[tiles * 256] (16 bits per lane: a plain bitmap over the piece's positions) = the windows that spell a query;
+//          kmer_windows[query] += its hit windows, *windows += the windows of k bases; nlcnt[tiles] / nloff[tiles + 1] the tiles'
+//          newline counts and their scan. filter == nullptr: no prefilter.
+//  count:  starts[n_reads + 1] from nloff; bcnt[block] the kept reads among a block of 256 reads, boff[.. + 1] their scan.
+//  write:  the records numbered [win_lo, win_lo + cap) in read order, from the read blocks [blk0, blk1), to rec[number - win_lo];
+//          read = read0 + the read's number in the piece. The record's layout is kgwas_fetch_record's.
+constexpr uint32_t FETCH_FILTER_BITS = 18;
+constexpr uint32_t FETCH_FILTER_WORDS = 1u << (FETCH_FILTER_BITS - 5);
+struct FetchRecord {
+    uint64_t read;
+    uint32_t n_hits, first_pos, kmer;
+    uint8_t strand, pad[3];
+};
+inline uint32_t fetch_read_blocks(uint32_t n_reads) { return (n_reads + 255u) / 256u; }
+hipError_t launch_fetch_filter(const LocateList& Q, uint32_t* filter, hipStream_t st);
+hipError_t launch_fetch_mark(const uint8_t* bases, uint64_t n, uint32_t kmer_len, const LocateList& Q, const uint32_t* filter, uint16_t* marks,
+                             uint32_t* nlcnt, uint32_t* nloff, unsigned long long* kmer_windows, unsigned long long* windows, hipStream_t st);
+hipError_t launch_fetch_count(const uint8_t* bases, uint64_t n, uint32_t kmer_len, uint32_t min_hits, const uint16_t* marks, const uint32_t* nloff,
+                              uint32_t n_reads, uint32_t* starts, uint32_t* bcnt, uint32_t* boff, hipStream_t st);
+hipError_t launch_fetch_write(const uint8_t* bases, uint64_t n, uint32_t kmer_len, uint32_t min_hits, const LocateList& Q, const uint16_t* marks,
+                              const uint32_t* starts, uint32_t n_reads, const uint32_t* boff, uint32_t blk0, uint32_t blk1, uint32_t win_lo, uint32_t cap,
+                              uint64_t read0, FetchRecord* rec, hipStream_t st);
+
 }  // namespace kgwas

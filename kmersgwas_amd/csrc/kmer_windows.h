@@ -1,5 +1,5 @@
-// kmer_windows.h — the k-base windows of a resident base stream, shared by count_kernels.hip (count_kmers_with_strand) and
-// locate_kernels.hip (locate_kmers): the tile both walk, a base's 2-bit code, sixteen positions packed from one 16-byte load, and
+// kmer_windows.h — the k-base windows of a resident base stream, shared by count_kernels.hip (count_kmers_with_strand),
+// locate_kernels.hip (locate_kmers) and fetch_kernels.hip (fetch_reads): the tile they walk, a base's 2-bit code, sixteen positions packed from one 16-byte load, and
 // the reverse complement of a code. The base stream is bytes; A C G T (either case) are bases, every other byte separates.
 //
 // The tile: a workgroup of 256 lanes takes 4096 positions, 16 per lane. Each lane packs its 16 bases into 32 bits of 2-bit codes
@@ -52,6 +52,38 @@ __device__ __forceinline__ uint64_t ck_revcomp(uint64_t a, uint32_t k) {
 // in the top half of X_lo.
 __device__ __forceinline__ uint64_t ck_base_at(uint64_t X_hi, uint64_t X_lo, uint32_t q) {
     return q < 32 ? (X_hi >> (62 - 2 * q)) & 3 : (X_lo >> (62 - 2 * (q - 32))) & 3;
+}
+
+// A lane's windows of the tile at t0: per_window(j, a) for window j (position t0 + 16 tid + j < n_win, all k bases valid) with
+// code a. Returns their number. The tile's packed positions go through s_codes / s_valid; the caller's barrier ends the tile.
+template <class F>
+__device__ __forceinline__ uint32_t ck_lane_windows(const uint8_t* bases, uint64_t n_buf, uint64_t n_win, uint64_t t0, int aligned, uint32_t k,
+                                                    uint32_t* s_codes, uint32_t* s_valid, F&& per_window) {
+    const uint32_t tid = threadIdx.x;
+    uint32_t c0, v0;
+    ck_pack(bases, n_buf, t0 + (uint64_t)tid * CK_RUN, aligned, c0, v0);
+    s_codes[tid] = c0, s_valid[tid] = v0;
+    if (tid < 2) {
+        uint32_t ch, vh;
+        ck_pack(bases, n_buf, t0 + CK_TILE + (uint64_t)tid * CK_RUN, aligned, ch, vh);
+        s_codes[CK_BLOCK + tid] = ch, s_valid[CK_BLOCK + tid] = vh;
+    }
+    __syncthreads();
+    const uint64_t X_hi = ((uint64_t)c0 << 32) | s_codes[tid + 1], X_lo = (uint64_t)s_codes[tid + 2] << 32;
+    const uint64_t V = (uint64_t)v0 | ((uint64_t)s_valid[tid + 1] << 16) | ((uint64_t)s_valid[tid + 2] << 32);
+    const uint64_t kmask = (1ull << k) - 1, cmask = (1ull << (2 * k)) - 1;
+    const uint64_t p0 = t0 + (uint64_t)tid * CK_RUN;
+    uint64_t a = X_hi >> (64 - 2 * k);
+    uint32_t n_valid = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < CK_RUN; j++) {
+        if (((V >> j) & kmask) == kmask && p0 + j < n_win) {
+            n_valid++;
+            per_window(j, a);
+        }
+        a = ((a << 2) | ck_base_at(X_hi, X_lo, j + k)) & cmask;  // the base at position j + k comes in
+    }
+    return n_valid;
 }
 
 }  // namespace kgwas

@@ -81,38 +81,6 @@ __device__ __forceinline__ void lk_window_hits(uint64_t a, const LkShape& s, con
     }
 }
 
-// A lane's windows of the tile at t0: per_window(j, a) for window j (position t0 + 16 tid + j < n_win, all k bases valid) with
-// code a. Returns their number. The tile's packed positions go through s_codes / s_valid; the caller's barrier ends the tile.
-template <class F>
-__device__ __forceinline__ uint32_t lk_lane_windows(const uint8_t* bases, uint64_t n_buf, uint64_t n_win, uint64_t t0, int aligned, uint32_t k,
-                                                    uint32_t* s_codes, uint32_t* s_valid, F&& per_window) {
-    const uint32_t tid = threadIdx.x;
-    uint32_t c0, v0;
-    ck_pack(bases, n_buf, t0 + (uint64_t)tid * CK_RUN, aligned, c0, v0);
-    s_codes[tid] = c0, s_valid[tid] = v0;
-    if (tid < 2) {
-        uint32_t ch, vh;
-        ck_pack(bases, n_buf, t0 + CK_TILE + (uint64_t)tid * CK_RUN, aligned, ch, vh);
-        s_codes[CK_BLOCK + tid] = ch, s_valid[CK_BLOCK + tid] = vh;
-    }
-    __syncthreads();
-    const uint64_t X_hi = ((uint64_t)c0 << 32) | s_codes[tid + 1], X_lo = (uint64_t)s_codes[tid + 2] << 32;
-    const uint64_t V = (uint64_t)v0 | ((uint64_t)s_valid[tid + 1] << 16) | ((uint64_t)s_valid[tid + 2] << 32);
-    const uint64_t kmask = (1ull << k) - 1, cmask = (1ull << (2 * k)) - 1;
-    const uint64_t p0 = t0 + (uint64_t)tid * CK_RUN;
-    uint64_t a = X_hi >> (64 - 2 * k);
-    uint32_t n_valid = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < CK_RUN; j++) {
-        if (((V >> j) & kmask) == kmask && p0 + j < n_win) {
-            n_valid++;
-            per_window(j, a);
-        }
-        a = ((a << 2) | ck_base_at(X_hi, X_lo, j + k)) & cmask;  // the base at position j + k comes in
-    }
-    return n_valid;
-}
-
 __device__ __forceinline__ void lk_load_splitters(const LocateList& H, const LocateList& L, uint64_t* s_splH, uint64_t* s_splL) {
     for (uint32_t i = threadIdx.x; i < H.ns; i += CK_BLOCK) s_splH[i] = H.spl[i];
     for (uint32_t i = threadIdx.x; i < L.ns; i += CK_BLOCK) s_splL[i] = L.spl[i];
@@ -128,7 +96,7 @@ __global__ void __launch_bounds__(CK_BLOCK) lk_count_kernel(const uint8_t* __res
     lk_load_splitters(H, L, s_splH, s_splL);
     for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         uint32_t v[2] = {0u, 0u};
-        v[1] = lk_lane_windows(bases, n_buf, n_win, (uint64_t)tile * CK_TILE, aligned, s.k, s_codes, s_valid, [&](uint32_t, uint64_t a) {
+        v[1] = ck_lane_windows(bases, n_buf, n_win, (uint64_t)tile * CK_TILE, aligned, s.k, s_codes, s_valid, [&](uint32_t, uint64_t a) {
             lk_window_hits(a, s, H, s_splH, L, s_splL, [&](uint32_t, uint32_t, uint32_t) { v[0]++; });
         });
         block_sum(v, red);
@@ -153,7 +121,7 @@ __global__ void __launch_bounds__(CK_BLOCK) lk_write_kernel(const uint8_t* __res
         const uint64_t t0 = (uint64_t)tile * CK_TILE;
         uint64_t codes[CK_RUN];
         uint32_t cnt = 0, mask = 0;
-        lk_lane_windows(bases, n_buf, n_win, t0, aligned, s.k, s_codes, s_valid, [&](uint32_t j, uint64_t a) {
+        ck_lane_windows(bases, n_buf, n_win, t0, aligned, s.k, s_codes, s_valid, [&](uint32_t j, uint64_t a) {
             const uint32_t before = cnt;
             lk_window_hits(a, s, H, s_splH, L, s_splL, [&](uint32_t, uint32_t, uint32_t) { cnt++; });
             codes[j] = a;

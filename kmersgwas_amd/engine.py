@@ -13,6 +13,8 @@ Names follow the reference's classes (src/kmers_multiple_databases.h, src/best_a
   kmers_ld              -- this project's own: exact r^2 links between k-mers (clump_kmers)
   kmers_ld_proxies      -- this project's own: the rows in LD with a few lead rows, as records (proxy_kmers)
   locate_kmers_bases    -- this project's own: where in a base stream k-mers occur, exactly or with one mismatch (locate_kmers)
+  fetch_reads_bases     -- this project's own: the reads of a newline-separated stream that contain listed k-mers (fetch_reads)
+  fetch_reads           -- the tool's run: reads files in, the kept reads, their table and the log out
 
 Everything numeric happens inside libkgwas (HIP kernels on the GPU + the std::priority_queue
 replay); this module only moves buffers.
@@ -883,6 +885,45 @@ def locate_kmers_bases(bases, codes, kmer_len: int, mismatches: int = 1, cap: in
         if cap is not None or n.value <= room:
             return rec[:min(n.value, room)], n.value
         room = n.value
+
+
+FETCH_RECORD = np.dtype([("read", np.uint64), ("n_hits", np.uint32), ("first_pos", np.uint32), ("kmer", np.uint32), ("strand", np.uint8), ("pad", np.uint8, (3,))])
+
+
+def fetch_reads_bases(bases, codes, kmer_len: int, min_hits: int = 1, cap: int | None = None, device: int = 0):
+    """The reads of a stream that contain the k-mers `codes` (uint64, the letters as spelled: kmer_codes) or their reverse
+    complements (kgwas_fetch_reads_bases). `bases` is bytes or a uint8 NumPy array on the host: a read is the bytes between one
+    newline and the next, A C G T (either case) are bases, every other byte breaks windows. Returns (records, n, kmer_windows):
+    records is a structured array of dtype FETCH_RECORD (read, n_hits, first_pos, kmer, strand, pad = 0), one per read with at least
+    `min_hits` hit windows, in ascending read; n the count of all records; kmer_windows[i] the hit windows of query i over all reads.
+    cap=None: every record is returned (a second call where the first guess was too small); otherwise the first min(cap, n)."""
+    codes = np.ascontiguousarray(codes, np.uint64).reshape(-1)
+    if not isinstance(bases, (bytes, bytearray, memoryview, np.ndarray)):
+        raise TypeError("fetch_reads_bases: bytes or a uint8 array, not %s" % type(bases).__name__)
+    keep = np.ascontiguousarray(np.frombuffer(bases, np.uint8) if not isinstance(bases, np.ndarray) else bases)
+    if keep.dtype != np.uint8:
+        raise TypeError("fetch_reads_bases: the bases must be uint8")
+    n = C.c_uint64(0)
+    room = 4096 if cap is None else cap
+    while True:
+        rec = np.zeros(room, FETCH_RECORD)
+        windows = np.zeros(len(codes), np.uint64)
+        check(lib.kgwas_fetch_reads_bases(ptr(keep) if keep.size else None, keep.size, ptr(codes), len(codes), kmer_len, min_hits, device,
+                                          ptr(rec) if room else None, room, C.byref(n), ptr(windows) if len(codes) else None))
+        if cap is not None or n.value <= room:
+            return rec[:min(n.value, room)], n.value, windows
+        room = n.value
+
+
+def fetch_reads(reads_path: str, kmers_path: str, kmer_len: int, out_prefix: str, mates_path: str | None = None, min_hits: int = 1,
+                max_reads_per_kmer: int = 0, device: int = 0) -> dict:
+    """fetch_reads, the tool (kgwas_fetch_reads_run): the reads of `reads_path` (FASTQ or FASTA; with `mates_path` pairs) that hold
+    at least `min_hits` windows spelling a k-mer of `kmers_path` go to out_prefix.fastq / .fasta (out_prefix_1.*, _2.* with mates),
+    out_prefix.reads.tsv and out_prefix.log.txt. Returns kgwas_fetch_stats as a dict."""
+    st = capi.FetchStats()
+    check(lib.kgwas_fetch_reads_run(os.fsencode(reads_path), None if mates_path is None else os.fsencode(mates_path), os.fsencode(kmers_path), kmer_len,
+                                    min_hits, max_reads_per_kmer, device, os.fsencode(out_prefix), C.byref(st)))
+    return st.as_dict()
 
 
 def filter_kmers_write(path: str, table: KmersTable, codes, device: int = 0) -> int:
